@@ -12,14 +12,22 @@ N > 1: either under torch.distributed.run (one rank per GPU), or bare (`python b
 rank processes before touching a GPU (self_launch) and forwards rank 0's line.  Clips shard across ranks with no data-path
 collective (weak scaling); rank 0 converts the weights once and broadcasts the bf16 arenas device-to-device over RCCL before timing.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set up, warm up, time --steps clips, print.
+SparseCtrl is evaluated several (50 steps: 5) DDIM steps at a time (pipeline.controlnet_group_size): all 50 evaluations per clip are
+computed inside the timed region.
+
+    --dump-outputs DIR   after the timed steps, the arrays the timed path returned in its last step go to DIR/<name>.npy (float32, at most
+                         64 MB in all; a larger output is written as a fixed seeded sample).  Inputs and weights are seeded: the same
+                         arguments give the same inputs on every run, so two builds can be compared output for output.
+    --full               everything else the benchmark measures, each leg after the timed region (--no-op-profile, --no-psnr,
+                         --no-cpu-baseline, --no-end-to-end leave single legs out).  Extra objects:
   roofline     dominant kernel class = the MFMA implicit-GEMM (conv/Linear): algorithmic FLOPs / summed launch
-               time, measured with one HIP event pair per launch on the launch stream (nr_net_profile_last).
+               time, measured with one HIP event pair per launch on the launch stream (nr_net_profile_last, a replay of its own).
   cpu_baseline the oracle (fp32 torch restatement of the reference graph, eager, math attention) timed on the host
                cores for a bounded sample and scaled to the clip.  The same oracle leg also CHECKS the clip just timed
                (config.psnr_c2_vs_fp32_oracle_db: final latents vs the oracle run in fp32 on the GPU, outside the timed region);
-               --no-cpu-baseline skips the whole leg.  SparseCtrl is evaluated several (50 steps: 5) DDIM steps at a time (pipeline.controlnet_group_size):
-               all 50 evaluations per clip are computed inside the timed region.
+               --no-cpu-baseline skips the whole leg.
+  end_to_end   the same clips through the whole __call__ (native CLIP -> loop -> native VAE decode -> .videos).
 """
 import argparse
 import json
@@ -56,18 +64,23 @@ def parse():
     ap.add_argument("--latent", type=int, default=32, help="latent side (pixels/8)")
     ap.add_argument("--batch", type=int, default=1, help="clips per pipeline call (BASELINE config 4 runs 8 clips/GPU; headline = 1); "
                                                          "--workload keyframe: keyframes per Euler loop (utils.unclip_recon's num_samples)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need, after the timed region: the per-launch event pass (roofline), the PSNR legs, "
+                         "the CPU baseline and the end-to-end leg (the --no-* switches below leave single legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path returned in its last step to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="skip the end-to-end leg of the headline run (native CLIP _encode_prompt -> loop -> native VAE decode -> .videos, SURVEY 8d)")
+                    help="with --full: skip the end-to-end leg of the headline run (native CLIP _encode_prompt -> loop -> native VAE decode -> .videos, SURVEY 8d)")
     ap.add_argument("--attn-fp8", action="store_true", help="BASELINE config 5: spatial/cross attention on OCP e4m3 MFMA operands (bf16 is the default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-psnr", action="store_true", help="skip the reference-fixture PSNR run (profiling passes: keeps tiny-network launches out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (and the oracle check of the timed clip)")
+    ap.add_argument("--no-psnr", action="store_true", help="with --full: skip the PSNR runs (profiling passes: keeps tiny-network launches out)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-controlnet", action="store_true",
                     help="DIAGNOSTIC (not BASELINE config 2): the loop without SparseCtrl, to read what the second stream costs the U-Net's chain; "
                          "the line says so in config.workload")
     ap.add_argument("--no-op-profile", action="store_true",
-                    help="skip the per-launch HIP-event pass (rocprofv3 runs: keeps the launch counts of the trace at exactly the timed steps); "
-                         "the roofline object is then omitted")
+                    help="with --full: skip the per-launch HIP-event pass and every other leg after the timed region, as a plain run does "
+                         "(rocprofv3 runs: keeps the launch counts of the trace at exactly the timed steps); the roofline object is then omitted")
     ap.add_argument("--workload", choices=["video", "keyframe", "vae", "enhance"], default="video",
                     help="video = BASELINE config 2 (headline); keyframe = config 3: sgm unCLIP U-Net, Euler-EDM + CFG 5.0; "
                          "vae = the first-stage round trip of one clip (SURVEY 8f rank 1): encode 16 frames + decode 16 frames; "
@@ -81,6 +94,25 @@ def parse():
                          "rank logic without a GPU (tests/test_bench_launch.py)")
     ap.add_argument("--launch-timeout", type=float, default=3600.0, help="self-launch: seconds before the rank processes are stopped")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy in float32.  Every array gets an equal share of
+    `limit` bytes; one larger than its share is written as a sample of its flattened elements at fixed seeded positions (the same
+    positions on every run), so two builds compare the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            print(f"bench.py: {name} {list(a.shape)} written as a seeded sample of {idx.size} of its {a.size} elements", file=sys.stderr)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def count_gpus_without_runtime(topology="/sys/class/kfd/kfd/topology/nodes"):
@@ -236,19 +268,22 @@ def vae_main(args):
         z, vid = step(*it)
     torch.cuda.synchronize()
     el = time.perf_counter() - t1
-    pd, pe = dec.profile_last(), enc.profile_last()
-    ig_ms = pd["igemm"]["ms"] + pe["igemm"]["ms"]
-    ig_fl = pd["igemm"]["flops"] + pe["igemm"]["flops"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"latents": z, "decoded": vid})
     res = {
         "metric": "first-stage VAE frames/sec (encode + decode of a 16f x 256^2 clip)", "value": round(args.steps * F / el, 3), "unit": "frames/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * el / args.steps, 3), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
         "config": {"workload": f"SURVEY 8f rank 1: encode {F} x 3x{L * 8}x{L * 8} images + decode ({F},4,{L},{L}) latents, SD-1.5 VAE "
-                               f"(ch 128, mult 1,2,4,4), random-init weights", "output_finite": bool(torch.isfinite(vid).all() and torch.isfinite(z).all())},
-        "roofline": {"bound": "mfma", "kernel": "igemm_bf16_kernel (3x3 conv)", "achieved": round(ig_fl / (ig_ms * 1e-3) / 1e12, 2),
-                     "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(ig_fl / (ig_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4), "traffic": None,
-                     "per_class_ms": {"decode": {k: round(v["ms"], 3) for k, v in pd.items()}, "encode": {k: round(v["ms"], 3) for k, v in pe.items()}}}}
-    if not args.no_cpu_baseline:
+                               f"(ch 128, mult 1,2,4,4), random-init weights", "output_finite": bool(torch.isfinite(vid).all() and torch.isfinite(z).all())}}
+    if args.full:
+        pd, pe = dec.profile_last(), enc.profile_last()
+        ig_ms = pd["igemm"]["ms"] + pe["igemm"]["ms"]
+        ig_fl = pd["igemm"]["flops"] + pe["igemm"]["flops"]
+        res["roofline"] = {"bound": "mfma", "kernel": "igemm_bf16_kernel (3x3 conv)", "achieved": round(ig_fl / (ig_ms * 1e-3) / 1e12, 2),
+                           "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(ig_fl / (ig_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4), "traffic": None,
+                           "per_class_ms": {"decode": {k: round(v["ms"], 3) for k, v in pd.items()}, "encode": {k: round(v["ms"], 3) for k, v in pe.items()}}}
+    if args.full and not args.no_cpu_baseline:
         from oracle import vae_oracle as V
         hd = {k: v.cpu() for k, v in dsd.items()}
         he = {k: v.cpu() for k, v in esd.items()}
@@ -283,7 +318,8 @@ def keyframe_main(args):
         sd[k] = z.cpu()
     net = NativeSGMUNet(cfg).to(dev)
     net.load_state_dict(sd)
-    if args.no_cpu_baseline:
+    cpu_leg = args.full and not args.no_cpu_baseline
+    if not cpu_leg:
         del sd
     L = args.keyframe_latent
     B = args.batch          # keyframes per Euler loop = CFG batch 2B (utils.unclip_recon's num_samples, utils.py:302-303,316-321)
@@ -301,10 +337,10 @@ def keyframe_main(args):
         out = sampler(net, it["z"], cond=it["c"], uc=it["uc"])
     torch.cuda.synchronize()
     el = time.perf_counter() - t1
-    p = net.profile_last()
-    ig = p["igemm"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"samples": out})
     cpu = None
-    if not args.no_cpu_baseline:
+    if cpu_leg:
         # the oracle's UNetModel forward (fp32, eager) on the host cores: ONE full Euler step of this configuration (CFG batch of 2),
         # scaled by the step count only
         from oracle import sgm_oracle as S
@@ -329,20 +365,23 @@ def keyframe_main(args):
                                f"context 256x1664, 2 501 M-parameter UNetModel, random-init weights",
                    "keyframes_per_call": B, "ms_per_euler_step": round(1e3 * el / args.steps / args.keyframe_steps, 3),
                    "ms_per_keyframe_step": round(1e3 * el / args.steps / args.keyframe_steps / B, 3), "output_finite": bool(torch.isfinite(out).all()),
-                   "resident_weight_gb": round(net.weight_bytes() / 1e9, 2)},
-        "roofline": {"bound": "mfma", "kernel": "igemm_bf16_kernel", "achieved": round(ig["flops"] / (ig["ms"] * 1e-3) / 1e12, 2),
-                     "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(ig["flops"] / (ig["ms"] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
-                     # the event pass launches eagerly (one HIP event pair per launch): with ~730 launches of ~10 us the HOST can be the slower side,
-                     # and the intervals then contain idle time (their sum exceeds the replayed graph's step).  Second reading: the class keeps its
-                     # share of the event pass, applied to the step as the timed region ran it.
-                     "event_pass_ms_per_step": round(sum(v["ms"] for v in p.values()), 3),
-                     "replayed_graph_ms_per_step": round(1e3 * el / args.steps / args.keyframe_steps, 3),
-                     "frac_of_replayed_step_share": round(ig["flops"] / (1e-3 * (1e3 * el / args.steps / args.keyframe_steps) * ig["ms"] /
-                                                                         max(sum(v["ms"] for v in p.values()), 1e-9)) / 1e12 / PEAK_BF16_TFLOPS, 4),
-                     "traffic": keyframe_traffic(B, L), "per_class_ms_per_step": {k: round(v["ms"], 3) for k, v in p.items()},
-                     "launches_per_step": int(sum(v["launches"] for v in p.values())),
-                     "algorithmic_gbytes_per_step": round(sum(v["bytes"] for v in p.values()) / 1e9, 2),
-                     "algorithmic_tflop_per_step": round(sum(v["flops"] for v in p.values()) / 1e12, 3)}}
+                   "resident_weight_gb": round(net.weight_bytes() / 1e9, 2)}}
+    if args.full:
+        p = net.profile_last()
+        ig = p["igemm"]
+        res["roofline"] = {"bound": "mfma", "kernel": "igemm_bf16_kernel", "achieved": round(ig["flops"] / (ig["ms"] * 1e-3) / 1e12, 2),
+                           "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(ig["flops"] / (ig["ms"] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
+                           # the event pass launches eagerly (one HIP event pair per launch): with ~730 launches of ~10 us the HOST can be the slower side,
+                           # and the intervals then contain idle time (their sum exceeds the replayed graph's step).  Second reading: the class keeps its
+                           # share of the event pass, applied to the step as the timed region ran it.
+                           "event_pass_ms_per_step": round(sum(v["ms"] for v in p.values()), 3),
+                           "replayed_graph_ms_per_step": round(1e3 * el / args.steps / args.keyframe_steps, 3),
+                           "frac_of_replayed_step_share": round(ig["flops"] / (1e-3 * (1e3 * el / args.steps / args.keyframe_steps) * ig["ms"] /
+                                                                               max(sum(v["ms"] for v in p.values()), 1e-9)) / 1e12 / PEAK_BF16_TFLOPS, 4),
+                           "traffic": keyframe_traffic(B, L), "per_class_ms_per_step": {k: round(v["ms"], 3) for k, v in p.items()},
+                           "launches_per_step": int(sum(v["launches"] for v in p.values())),
+                           "algorithmic_gbytes_per_step": round(sum(v["bytes"] for v in p.values()) / 1e9, 2),
+                           "algorithmic_tflop_per_step": round(sum(v["flops"] for v in p.values()) / 1e12, 3)}
     if cpu:
         res["cpu_baseline"] = cpu
     print(json.dumps(res))
@@ -493,6 +532,8 @@ def enhance_main(args):
         ts, kimg, vid = chain()
         tot += ts[-1] - ts[0]
         stages += np.diff(ts)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"keyframes": kimg, "videos": vid})
     tot /= args.steps
     stages /= args.steps
     print(json.dumps({
@@ -571,7 +612,8 @@ def main():
         if rank == 0:
             sd = {k: v.cpu() for k, v in gpu_random_state_dict(state_dict_schema(cfg, kind), seed, dev).items()}
             net.load_state_dict(sd)
-            host_sd[kind] = sd
+            if args.full:               # the oracle legs after the timed region read the host weights
+                host_sd[kind] = sd
             if use_dist:
                 # converts the weights for the shape every rank will run: SparseCtrl is evaluated `grp` DDIM steps at a time (pipeline.py)
                 from neurons_amd.pipeline import controlnet_group_size
@@ -641,33 +683,15 @@ def main():
         print("per-step ms of the last clip (first entry: call start -> end of step 0): " + " ".join(f"{m:.2f}" for m in ms) +
               f" | sum {sum(ms):.1f} ms, wall per clip {1e3 * elapsed / args.steps:.1f} ms", file=sys.stderr)
     finite = bool(torch.isfinite(out).all().item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"videos": out})
 
     result = None
     if rank == 0:
         total_frames = world * args.steps * F * Bc
         value = total_frames / elapsed
-        # ---- roofline of the dominant kernel class (MFMA implicit GEMM), HIP events per launch ----
         # SparseCtrl is evaluated `grp` DDIM steps at a time (pipeline.controlnet_group): its per-launch profile covers grp steps
         grp = getattr(pipe, "last_controlnet_group", 1)
-        if args.no_op_profile:
-            print(json.dumps({"metric": "denoising frames/sec, 16f x 256^2 clip, 50 DDIM steps", "value": round(value, 4), "unit": "frames/s",
-                              "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 2),
-                              "config": {"workload": "profiler pass (no per-launch event pass)", "ddim_steps": args.ddim_steps,
-                                         "sparsectrl_steps_per_evaluation": grp}}))
-            if dist is not None:
-                dist.barrier()
-                dist.destroy_process_group()
-            return
-        pu = unet.profile_last()
-        pc = ctrl.profile_last() if not args.no_controlnet else {k: {f: 0.0 for f in v} for k, v in pu.items()}
-        pc = {k: {f: v[f] / grp for f in v} for k, v in pc.items()}
-        ig_ms = pu["igemm"]["ms"] + pc["igemm"]["ms"]
-        ig_fl = pu["igemm"]["flops"] + pc["igemm"]["flops"]
-        ig_n = pu["igemm"]["launches"] + pc["igemm"]["launches"]
-        achieved = ig_fl / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
-        breakdown = {k: round(pu[k]["ms"] + pc[k]["ms"], 3) for k in pu}
-        step_flops = sum(pu[k]["flops"] + pc[k]["flops"] for k in pu)
-        step_bytes = sum(pu[k]["bytes"] + pc[k]["bytes"] for k in pu)
         result = {
             "metric": "denoising frames/sec, 16f x 256^2 clip, 50 DDIM steps",
             "value": round(value, 4), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -678,48 +702,67 @@ def main():
                                    f"(batch {2 * Bc}), SparseCtrl + temporal U-Net per step, random-init weights" +
                                    (" -- DIAGNOSTIC RUN WITHOUT SparseCtrl (--no-controlnet): not the configured workload" if args.no_controlnet else ""),
                        "clips_per_gpu": args.steps * Bc, "frame_steps_per_s": round(value * args.ddim_steps, 2),
-                       "ms_per_ddim_step": round(1e3 * elapsed / args.steps / args.ddim_steps, 3),
+                       "ddim_steps": args.ddim_steps, "ms_per_ddim_step": round(1e3 * elapsed / args.steps / args.ddim_steps, 3),
+                       "sparsectrl_steps_per_evaluation": grp,
                        "hip_graph": not args.no_graph, "output_finite": finite, "setup_s": round(setup_s, 1),
                        "resident_weight_gb": round((unet.weight_bytes() + ctrl.weight_bytes()) / 1e9, 2),
-                       # whole-step algorithmic HBM bytes (every kernel's operands counted once) / measured wall time of a DDIM step
-                       "achieved_hbm_gbs": round(step_bytes / (elapsed / args.steps / args.ddim_steps) / 1e9, 1),
-                       "achieved_tflops": round(step_flops / (elapsed / args.steps / args.ddim_steps) / 1e12, 1),
                        "attention": "e4m3 spatial/cross (fp32 softmax/accumulate), bf16 temporal" if args.attn_fp8 else "bf16"},
-            "roofline": {"bound": "mfma", "kernel": "igemm_bf16_kernel (3x3/1x1 conv + Linear)", "achieved": round(achieved, 2),
-                         "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                         # HBM bytes of the igemm class per DDIM step (GB) from the committed rocprofv3 PMC passes, next to the
-                         # class's algorithmic bytes: traffic >> algorithmic = operand re-reads / split-K slabs
-                         "traffic": (pmc_traffic() or {}).get("igemm_hbm_gbytes_per_ddim_step") if headline else None,
-                         "traffic_unit": "GB per DDIM step (igemm class, PMC FETCH_SIZE x2 + WRITE_SIZE)",
-                         "traffic_detail": pmc_traffic() if headline else None,
-                         "algorithmic_gbytes_per_ddim_step": round((pu["igemm"]["bytes"] + pc["igemm"]["bytes"]) / 1e9, 2),
-                         "launches_per_ddim_step": round(ig_n, 1), "ms_per_ddim_step": round(ig_ms, 3),
-                         # kernels enqueued per DDIM step, both networks (split-K reduces, multi-pass norms and the time-embedding MLP counted
-                         # per kernel; + set_timesteps and the CFG/DDIM update; SparseCtrl's share is 1/grp of an evaluation)
-                         "whole_step_launches_sparsectrl_counted_at_1_over_group": round(sum(pu[k]["launches"] + pc[k]["launches"] for k in pu) + 2 + 1.0 / grp, 1),
-                         "sparsectrl_steps_per_evaluation": grp,
-                         "algorithmic_tflop_per_ddim_step": round(ig_fl / 1e12, 3),
-                         "per_class_ms_per_ddim_step": breakdown,
-                         "whole_step_algorithmic": {"tflop": round(step_flops / 1e12, 3), "gbytes": round(step_bytes / 1e9, 2)}},
         }
-        # "PSNR vs ref" half of the metric: (a) the reference-generated C1 fixture (tiny networks, 10 steps) and (b) THIS configuration:
-        # the clip just timed, final latents against the fp32 oracle run on the same GPU, same weights and inputs (outside the timed region)
-        result["config"]["psnr_c1_fixture_db"] = None if args.no_psnr else psnr_vs_reference(dev)
-        # The oracle leg (rank 0, N = 1, headline configuration only; `--no-cpu-baseline` skips all of it): oracle/ is used here as
-        # the CHECKER of the clip just timed (b) and as the timed CPU baseline -- never as anything measured in `value` or shipped.
-        # Larger configurations (4 / 5) take their parity from tests/test_fullsize_gpu.py and tests/test_engine_gpu.py.
-        oracle_leg = (not args.no_cpu_baseline) and world == 1 and headline
-        result["config"]["psnr_c2_vs_fp32_oracle_db"] = psnr_headline(dev, host_sd, ucfg, ccfg, pipe, clips[-1], args) if (oracle_leg and not args.no_psnr) else None
-        if oracle_leg:
-            result["cpu_baseline"] = cpu_baseline(host_sd, ucfg, ccfg, args)
-        # end-to-end __call__ (CLIP -> loop -> VAE decode -> .videos) beside the loop-only headline; N = 1 only
-        if world == 1 and not args.no_end_to_end and not args.attn_fp8:
-            result["end_to_end"] = end_to_end_leg(args, dev, unet, ctrl, sched, clips)
+        if args.full and not args.no_op_profile:
+            full_legs(args, result, dev, world, headline, elapsed, grp, host_sd, ucfg, ccfg, unet, ctrl, sched, pipe, clips)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(result))
+
+
+def full_legs(args, result, dev, world, headline, elapsed, grp, host_sd, ucfg, ccfg, unet, ctrl, sched, pipe, clips):
+    """--full on rank 0, after the timed region: the per-launch event pass (roofline), the PSNR legs, the CPU baseline and the
+    end-to-end leg, added to `result`."""
+    # ---- roofline of the dominant kernel class (MFMA implicit GEMM), HIP events per launch ----
+    pu = unet.profile_last()
+    pc = ctrl.profile_last() if not args.no_controlnet else {k: {f: 0.0 for f in v} for k, v in pu.items()}
+    pc = {k: {f: v[f] / grp for f in v} for k, v in pc.items()}
+    ig_ms = pu["igemm"]["ms"] + pc["igemm"]["ms"]
+    ig_fl = pu["igemm"]["flops"] + pc["igemm"]["flops"]
+    ig_n = pu["igemm"]["launches"] + pc["igemm"]["launches"]
+    achieved = ig_fl / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
+    breakdown = {k: round(pu[k]["ms"] + pc[k]["ms"], 3) for k in pu}
+    step_flops = sum(pu[k]["flops"] + pc[k]["flops"] for k in pu)
+    step_bytes = sum(pu[k]["bytes"] + pc[k]["bytes"] for k in pu)
+    # whole-step algorithmic HBM bytes (every kernel's operands counted once) / measured wall time of a DDIM step
+    result["config"]["achieved_hbm_gbs"] = round(step_bytes / (elapsed / args.steps / args.ddim_steps) / 1e9, 1)
+    result["config"]["achieved_tflops"] = round(step_flops / (elapsed / args.steps / args.ddim_steps) / 1e12, 1)
+    result["roofline"] = {"bound": "mfma", "kernel": "igemm_bf16_kernel (3x3/1x1 conv + Linear)", "achieved": round(achieved, 2),
+                          "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                          # HBM bytes of the igemm class per DDIM step (GB) from the committed rocprofv3 PMC passes, next to the
+                          # class's algorithmic bytes: traffic >> algorithmic = operand re-reads / split-K slabs
+                          "traffic": (pmc_traffic() or {}).get("igemm_hbm_gbytes_per_ddim_step") if headline else None,
+                          "traffic_unit": "GB per DDIM step (igemm class, PMC FETCH_SIZE x2 + WRITE_SIZE)",
+                          "traffic_detail": pmc_traffic() if headline else None,
+                          "algorithmic_gbytes_per_ddim_step": round((pu["igemm"]["bytes"] + pc["igemm"]["bytes"]) / 1e9, 2),
+                          "launches_per_ddim_step": round(ig_n, 1), "ms_per_ddim_step": round(ig_ms, 3),
+                          # kernels enqueued per DDIM step, both networks (split-K reduces, multi-pass norms and the time-embedding MLP counted
+                          # per kernel; + set_timesteps and the CFG/DDIM update; SparseCtrl's share is 1/grp of an evaluation)
+                          "whole_step_launches_sparsectrl_counted_at_1_over_group": round(sum(pu[k]["launches"] + pc[k]["launches"] for k in pu) + 2 + 1.0 / grp, 1),
+                          "sparsectrl_steps_per_evaluation": grp,
+                          "algorithmic_tflop_per_ddim_step": round(ig_fl / 1e12, 3),
+                          "per_class_ms_per_ddim_step": breakdown,
+                          "whole_step_algorithmic": {"tflop": round(step_flops / 1e12, 3), "gbytes": round(step_bytes / 1e9, 2)}}
+    # "PSNR vs ref" half of the metric: (a) the reference-generated C1 fixture (tiny networks, 10 steps) and (b) THIS configuration:
+    # the clip just timed, final latents against the fp32 oracle run on the same GPU, same weights and inputs (outside the timed region)
+    result["config"]["psnr_c1_fixture_db"] = None if args.no_psnr else psnr_vs_reference(dev)
+    # The oracle leg (rank 0, N = 1, headline configuration only; `--no-cpu-baseline` skips all of it): oracle/ is used here as
+    # the CHECKER of the clip just timed (b) and as the timed CPU baseline -- never as anything measured in `value` or shipped.
+    # Larger configurations (4 / 5) take their parity from tests/test_fullsize_gpu.py and tests/test_engine_gpu.py.
+    oracle_leg = (not args.no_cpu_baseline) and world == 1 and headline
+    result["config"]["psnr_c2_vs_fp32_oracle_db"] = psnr_headline(dev, host_sd, ucfg, ccfg, pipe, clips[-1], args) if (oracle_leg and not args.no_psnr) else None
+    if oracle_leg:
+        result["cpu_baseline"] = cpu_baseline(host_sd, ucfg, ccfg, args)
+    # end-to-end __call__ (CLIP -> loop -> VAE decode -> .videos) beside the loop-only headline (SURVEY 8d); N = 1 only
+    if world == 1 and not args.no_end_to_end and not args.attn_fp8:
+        result["end_to_end"] = end_to_end_leg(args, dev, unet, ctrl, sched, clips)
 
 
 def psnr_headline(dev, host_sd, ucfg, ccfg, pipe, clip, args):

@@ -13,20 +13,20 @@ done
 for rep in 1 2; do
   for arm in base new; do
     v=""; [ $arm = base ] && v=base
-    NR_LIB_VARIANT=$v python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-psnr --no-end-to-end 2>/dev/null | tail -1 | python -c "
+    NR_LIB_VARIANT=$v python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-psnr --no-end-to-end 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('headline  $arm rep $rep:', d['value'], 'frames/s', d['config']['ms_per_ddim_step'], 'ms/DDIM step; class frac', d['roofline']['frac'])" >> $out
   done
 done
 for arm in base new; do
   v=""; [ $arm = base ] && v=base
-  NR_LIB_VARIANT=$v python bench.py --workload keyframe --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  NR_LIB_VARIANT=$v python bench.py --full --workload keyframe --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('keyframe  $arm:', d['value'], 'keyframes/s', d['config']['ms_per_euler_step'], 'ms/Euler step; class frac', d['roofline']['frac'])" >> $out
 done
 for arm in base new; do
   v=""; [ $arm = base ] && v=base
-  NR_LIB_VARIANT=$v python bench.py --workload video --batch 8 --steps 1 --warmup 1 --no-cpu-baseline --no-psnr --no-end-to-end 2>/dev/null | tail -1 | python -c "
+  NR_LIB_VARIANT=$v python bench.py --full --workload video --batch 8 --steps 1 --warmup 1 --no-cpu-baseline --no-psnr --no-end-to-end 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('config 4 (8 clips)  $arm:', d['value'], 'frames/s; class frac', d['roofline']['frac'])" >> $out
 done

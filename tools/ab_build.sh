@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 run() {  # $1 = label, $2 = EXTRA, $3 = NOPK override ("default" keeps the Makefile's)
   make -C neurons_amd/csrc clean > /dev/null 2>&1
   if [ "$3" = "default" ]; then make -C neurons_amd/csrc -j16 EXTRA="$2" > /dev/null 2>&1; else make -C neurons_amd/csrc -j16 EXTRA="$2" NOPK="$3" > /dev/null 2>&1; fi
-  python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-psnr 2>&1 | tail -1 | python -c "
+  python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-psnr 2>&1 | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$1', d['value'], 'fps', d['config']['ms_per_ddim_step'], 'ms/step igemm', d['roofline']['ms_per_ddim_step'], d['roofline']['per_class_ms_per_ddim_step'])"
 }

@@ -1,5 +1,5 @@
 # in-situ A/B of igemm overrides under hipGraph (no per-launch host overhead): bash tools/igemm_ab.sh
-run() { python bench.py --no-cpu-baseline --no-psnr --steps 2 --warmup 1 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-44s %.3f fps %.3f ms/step igemm %.0f TF/s' % ('$1', d['value'], d['config']['ms_per_ddim_step'], d['roofline']['achieved']))"; }
+run() { python bench.py --full --no-cpu-baseline --no-psnr --steps 2 --warmup 1 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-44s %.3f fps %.3f ms/step igemm %.0f TF/s' % ('$1', d['value'], d['config']['ms_per_ddim_step'], d['roofline']['achieved']))"; }
 run base
 export NR_IGEMM_FORCE_KS=3 NR_IGEMM_FORCE_MAXM=8192 NR_IGEMM_FORCE_MINM=8192
 NR_IGEMM_FORCE="128,160,1,2,-1,4" run "3x3 M=8192 128x160 split1"
