@@ -8,8 +8,9 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# NR_LIB_VARIANT=pk loads libneurons_amd_pk.so: the SAME sources built WITH packed fp32 VALU ops (make -C neurons_amd/csrc pk), the
-# other arm of the two-stream determinism A/B (tools/race_gn.py, profiles/r03_race_*); never the product library
+# NR_LIB_VARIANT=<name> loads libneurons_amd_<name>.so instead of the product library: pk (the same sources WITH packed fp32 VALU ops,
+# make -C neurons_amd/csrc pk: the other arm of the two-stream determinism A/B, tools/race_gn.py), stamp (in-kernel shader-clock stamps for the
+# timeline tools, make -C neurons_amd/csrc stamp) or base (another commit's library for a same-box A/B, tools/ab_lib.sh)
 LIB_PATH = os.path.join(_HERE, "libneurons_amd" + ("_" + os.environ["NR_LIB_VARIANT"] if os.environ.get("NR_LIB_VARIANT") else "") + ".so")
 
 NR_KIND_UNET3D = 0

@@ -59,48 +59,17 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // ----------------------------------------------------------------------------------------------
-// Output stores.  The eight XCD L2s are not coherent with each other, so the release at the end of every kernel writes the L2's dirty lines
-// back before the next kernel of the stream may start: with plain stores that write-back sits on the critical path between two launches
-// (MI355X_MICROARCH.md price list, row "boundary": + B / 6 TB/s for B dirty bytes, 1.7 us behind a 10 MB activation).  NR_STORE_WT builds
-// store activations write-through (`sc1`: agent scope, the bytes leave the L2 while the kernel still computes; same instruction rate as a
-// plain 16-byte store), so the end-of-kernel release finds nothing to write.  The consumer kernel reads them from the Infinity Cache, where
-// 7 of its 8 XCDs had to look anyway.  Data registers: the hardware needs them for two wait states only (s_nop 1), as in rowpanel.hip.
-#ifndef NR_STORE_WT
-#define NR_STORE_WT 0
-#endif
-__device__ __forceinline__ void nr_store16(bf16* ptr, const bf16x8& v) {
-#if NR_STORE_WT
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(ptr), "v"(v) : "memory");
-#else
-  *(bf16x8*)ptr = v;
-#endif
-}
-__device__ __forceinline__ void nr_store16f(float* ptr, const f32x4& v) {      // split-K slabs: written by one kernel, read by the reduce
-#if NR_STORE_WT
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(ptr), "v"(v) : "memory");
-#else
-  *(f32x4*)ptr = v;
-#endif
-}
-__device__ __forceinline__ void nr_store8(bf16* ptr, const bf16x4& v) {
-#if NR_STORE_WT
-  asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" : : "v"(ptr), "v"(v) : "memory");
-#else
-  *(bf16x4*)ptr = v;
-#endif
-}
+// Output stores (plain stores: write-through `sc1` stores made the step 4 % slower, profiles/r05_store_wt_ab.txt)
+__device__ __forceinline__ void nr_store16(bf16* ptr, const bf16x8& v) { *(bf16x8*)ptr = v; }
+__device__ __forceinline__ void nr_store16f(float* ptr, const f32x4& v) { *(f32x4*)ptr = v; }      // split-K slabs: written by one kernel, read by the reduce
+__device__ __forceinline__ void nr_store8(bf16* ptr, const bf16x4& v) { *(bf16x4*)ptr = v; }
 
 // Kernel arguments pinned in SGPRs at entry.  Left alone, hipcc loads the argument block lazily: one s_load + s_waitcnt lgkmcnt(0) in front of
 // every first use (the tiled igemm had 16 such round trips, scalar-cache misses among them, between its entry and its first LDS-DMA: 3,500 of the
 // ~20,000 cycles of a short-K workgroup, profiles/r05_igemm_timeline.txt).  An empty asm that takes the value as an "s" operand makes it opaque
 // (no rematerialisation from the argument segment), so every pinned field is fetched by the loads the compiler batches at the top of the kernel.
-#ifndef NR_PIN_ARGS
-#define NR_PIN_ARGS 1     // 0: the lazy loads again (A/B arm: make variant NAME=nopin VFLAGS=-DNR_PIN_ARGS=0)
-#endif
 template <class T> __device__ __forceinline__ T nr_pin(T v) {
-#if NR_PIN_ARGS
   asm volatile("" : "+s"(v));
-#endif
   return v;
 }
 
@@ -147,9 +116,6 @@ struct NrGemmParams {
   int tap_inner;       // 3x3, stride 1, single source: K walks (64-channel chunk, tap) with the TAP fastest; weights [N][Cin/64][9][64].
                        // The 9 re-reads of an activation row segment then fall into 9 consecutive k-tiles (L2 hits) instead of being
                        // spread over the whole K loop (tap-major order: the working set of the tiles in flight exceeds the 4 MiB L2)
-  int* sk_ctr;         // non-null: a split-K launch of this description reduces IN the launch (gemm.hip, l2red): one int per output tile, zero before
-                       // the first launch and left zero by every launch; owned by this launch description (concurrent streams never share one).
-                       // null: fp32 slabs + splitk_reduce_kernel.  Ask nr_igemm_splitk_l2_tiles() how many ints a description needs (0 = not eligible)
   const bf16* w_fm;    // non-null: the same weights in FRAGMENT-MAJOR order for smallm.hip: [N/16][K/32][64 lanes][8], lane (fr, fg) of block
                        // (T, ks) holds W[16 T + fr][32 ks + 8 fg .. + 7], so a wave's MFMA A-operand load is one contiguous KiB (nr_launch_smallm_w_pack)
 };
@@ -161,7 +127,7 @@ __device__ __forceinline__ NrGemmParams nr_pin_params(NrGemmParams p) {
   p.rowvec = nr_pin(p.rowvec); p.rowvec_div = nr_pin(p.rowvec_div); p.rowvec_mod = nr_pin(p.rowvec_mod); p.rowvec_ld = nr_pin(p.rowvec_ld);
   p.res = nr_pin(p.res); p.ldr = nr_pin(p.ldr); p.out = nr_pin(p.out); p.ldo = nr_pin(p.ldo); p.out_scale = nr_pin(p.out_scale);
   p.geglu = nr_pin(p.geglu); p.ln_c = nr_pin(p.ln_c); p.ln_eps = nr_pin(p.ln_eps); p.act = nr_pin(p.act); p.pad_tl0 = nr_pin(p.pad_tl0);
-  p.out_f32 = nr_pin(p.out_f32); p.tap_inner = nr_pin(p.tap_inner); p.w_fm = nr_pin(p.w_fm); p.sk_ctr = nr_pin(p.sk_ctr);
+  p.out_f32 = nr_pin(p.out_f32); p.tap_inner = nr_pin(p.tap_inner); p.w_fm = nr_pin(p.w_fm);
   return p;
 }
 
@@ -177,7 +143,6 @@ struct NrRowPanelParams {
   bf16* out; int ldo;
   float out_scale; int geglu; int act;
   int nsplit;                        // workgroups per 256-row panel (each takes a contiguous range of 64-column chunks)
-  int dbg;                           // timing experiments only (NR_RP_DBG): 1 no stores, 2 no DMA after the prologue, 4 no barrier wait
 };
 
 struct NrAttnParams {

@@ -30,7 +30,6 @@
 extern "C" {
 int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStream_t stream);
 size_t nr_igemm_workspace_bytes(const NrGemmParams* pp);
-int nr_igemm_splitk_l2_tiles(const NrGemmParams* pp);
 // lin160.hip: short-K Linears (K = 640 / 1280, N % 160 == 0, >= 2048 rows) on fragment-major weights
 size_t nr_lin160_stream_bytes(int N, int K);
 int nr_lin160_eligible(const NrGemmParams* pp);
@@ -801,20 +800,13 @@ struct nr_net {
       const double bytes = 2.0 * (in_elems + (double)p.N * p.K + (double)p.M * outC + (o.res ? (double)p.M * outC : 0.0));
       char d[160];
       snprintf(d, sizeof(d), "igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0);
-      // in-launch split-K reduction (experiment NR_SPLITK_L2=1, gemm.hip l2red): one zeroed, self-cleaning counter per output tile, owned by
-      // this launch description for the lifetime of the plan (the two streams never share counters)
-      if (const int sk_tiles = nr_igemm_splitk_l2_tiles(&p)) {
-        Act ctr = new_act_persistent(1, 1, 1, 2 * ((sk_tiles + 3) & ~3));
-        ctx_persist.push_back(ctr);
-        if (!dry) { HIP_OK(hipMemset(ctr.ptr, 0, (size_t)sk_tiles * sizeof(int))); p.sk_ctr = reinterpret_cast<int*>(ctr.ptr); }
-      }
       // split-K slabs (small-M / huge-K layers): scratch with the lifetime of this launch
       const size_t wsb = nr_igemm_workspace_bytes(&p);
       float* ws = nullptr;
       std::shared_ptr<Buf> wsbuf;
       if (wsb) { wsbuf = new_tmp(wsb); ws = at<float>(wsbuf->off); }
       emit([p, ws](hipStream_t s) { LAUNCH_OK(nr_launch_igemm(&p, ws, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
-      if (wsb) last_op_launches(p.sk_ctr ? 1 : 2);          // split-K: the igemm + its reduce kernel (one launch with the in-launch reduction)
+      if (wsb) last_op_launches(2);          // split-K: the igemm + its reduce kernel
       op_tap(ksize == 3 ? "conv3" : (p.ln_c ? "lngemm" : "gemm"), out);
     }
     return out;
@@ -2986,16 +2978,9 @@ extern "C" nr_status nr_net_read_tap(nr_net* h, int32_t i, float* host_out, int6
 }
 
 // ---- single-op entry points ---------------------------------------------------------------------
-static float* op_workspace(NrGemmParams& p) {
+static float* op_workspace(const NrGemmParams& p) {
   static float* ws = nullptr;
   static size_t cap = 0;
-  static int* ctr = nullptr;                     // tile counters of the in-launch split-K reduction (NR_SPLITK_L2=1): zeroed once, self-cleaning
-  const int tiles = nr_igemm_splitk_l2_tiles(&p);
-  if (tiles > 0) {
-    if (tiles > 65536) throw NrError(NR_ERR_UNSUPPORTED, "op hook: too many split-K tiles");
-    if (!ctr) { HIP_OK(hipMalloc((void**)&ctr, 65536 * sizeof(int))); HIP_OK(hipMemset(ctr, 0, 65536 * sizeof(int))); }
-    p.sk_ctr = ctr;
-  }
   const size_t need = nr_igemm_workspace_bytes(&p);
   if (need > cap) {
     HIP_OK(hipDeviceSynchronize());

@@ -60,7 +60,6 @@ struct NrFFParams {
   const float* b1;               // [8C] net.0 bias in the value/gate-interleaved row order of the weight
   const float* bc;               // [C]  bpo + Wpo bff2
   float ln_eps;
-  int dbg;               // timing experiments only (NR_FUSED_DBG): 1 no DMA waits, 2 no stage barriers, 4 no DMA issue (results are wrong)
 };
 
 // exact-erf GELU gate times the value, two outputs at a time (Abramowitz-Stegun 7.1.25 as gelu_erf_fast of common.h)
@@ -137,8 +136,8 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
   auto stage_begin = [&]() -> const bf16* {
     // stage s must have landed: this wave's 10 DMA pieces of stage s + 1 (issued during stage s - 1) may stay outstanding.  No other
     // vector-memory operation is issued inside the loop, so the count is exact.
-    if (!(p.dbg & 1)) { if (s + 1 < FF_NSTAGES) wait_vmcnt<FF_DMA>(); else wait_vmcnt<0>(); }
-    if (!(p.dbg & 2)) __builtin_amdgcn_s_barrier();            // everyone's pieces of stage s landed; everyone is done reading stage s - 1
+    if (s + 1 < FF_NSTAGES) wait_vmcnt<FF_DMA>(); else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();            // everyone's pieces of stage s landed; everyone is done reading stage s - 1
     // where the pieces of stage s + 2 come from / go to (the slot stage s - 1 occupied).  The last two stages re-fetch the final stage into
     // that free slot, so the piece issue stays unconditional (a branch per piece would cut the MFMA groups into separate scheduling regions)
     const int s2 = s + 2 < FF_NSTAGES ? s + 2 : FF_NSTAGES - 1;
@@ -150,7 +149,7 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
   };
   // piece i of stage s + 2 goes out behind MFMA group i of stage s: spreads the ~100-cycle issue cost of an LDS-DMA piece over the stage
   // instead of stalling its head
-  auto prefetch_piece = [&](int i) { if (i < FF_DMA && !(p.dbg & 4)) glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
+  auto prefetch_piece = [&](int i) { if (i < FF_DMA) glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
   auto stage_end = [&]() { ++s; ring = ring + 1 == FF_NS ? 0 : ring + 1; };
 
   auto frag_n320 = [&](const bf16* sW, int nt, int ks2) {
@@ -366,10 +365,6 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
   }
 
   wait_vmcnt<0>();      // the tail's dummy pieces
-#ifndef NR_FF_EPI16
-#define NR_FF_EPI16 1
-#endif
-#if NR_FF_EPI16
   // ---- epilogue: out = x + bc + acc.  In the accumulator layout a lane holds rows (16 mt + fr), columns 16 nt + 4 fg .. +3: 8-byte accesses in 32-byte
   // row segments.  Round 5 (as xattn.hip / tattn.hip): v_permlane16_swap between the column tiles (2 k, 2 k + 1) hands every lane 8 CONSECUTIVE columns
   // (even lane rows: tile 2 k, columns 4 fg .. 4 fg + 7; odd: tile 2 k + 1, columns 4 (fg - 1) ..), so residual loads and stores are 16 bytes per lane in
@@ -401,26 +396,6 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
     }
   }
 }
-#else
-  // ---- epilogue: out = x + bc + acc, lane holds rows (16 mt + fr), columns 16 nt + 4 fg .. +3 (A/B arm: -DNR_FF_EPI16=0) ----
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int m = mrow0 + 16 * mt + fr;
-    if (m >= p.M) continue;
-    const bf16* xr = p.x + (size_t)m * p.ldx + 4 * fg;
-    bf16* orow = p.out + (size_t)m * p.ldo + 4 * fg;
-#pragma unroll
-    for (int nt = 0; nt < NT2; ++nt) {
-      const bf16x4 xv = *(const bf16x4*)(xr + 16 * nt);
-      const f32x4 b = *(const f32x4*)(p.bc + 16 * nt + 4 * fg);
-      bf16x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (bf16)(oacc[nt][mt][e] + b[e] + (float)xv[e]);
-      nr_store8(orow + 16 * nt, o);
-    }
-  }
-}
-#endif
 
 // Builds the 65-stage weight stream from W1 ([8C][C] bf16, value/gate-interleaved rows: engine w_geglu) and
 // Wc ([C][5C] bf16 = [Wpo | Wpo Wff2], engine w_fold_ff_proj).  One thread per 16-byte chunk of the stream.
@@ -475,8 +450,6 @@ extern "C" int nr_launch_ff_fused(const bf16* t, int ldt, const bf16* x, int ldx
   NrFFParams p;
   p.t = t; p.ldt = ldt; p.x = x; p.ldx = ldx; p.out = out; p.ldo = ldo; p.M = M; p.stream = stream; p.gamma = gamma; p.beta = beta; p.b1 = b1; p.bc = bc;
   p.ln_eps = ln_eps; p.norot = norot;
-  static const int dbg = getenv("NR_FUSED_DBG") ? atoi(getenv("NR_FUSED_DBG")) : 0;
-  p.dbg = dbg;
   constexpr size_t shm = (size_t)FF_NS * FF_STAGE * sizeof(bf16) + (size_t)8 * FF_C * sizeof(float);
   int dev = 0;
   (void)hipGetDevice(&dev);

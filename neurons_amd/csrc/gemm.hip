@@ -73,9 +73,6 @@ __device__ __forceinline__ int fdiv_small(int a, int d) {
   return q;
 }
 
-#ifndef NR_ABLATE
-#define NR_ABLATE 0      // timing ablations of the k-loop (experiments build only, results wrong): 2 no LDS-DMA in the loop, 4 fragment reads in the
-#endif                   // first iteration only, 8 no MFMAs (tools/conv_halo_potential.py)
 #ifdef NR_STAMP
 // Diagnostic build only (make stamp -> libneurons_amd_stamp.so, tools/igemm_timeline.py): shader-clock stamps of wave 0 of the first
 // 512 workgroups.  The stamps go to a buffer of their own; no output value depends on them.
@@ -123,21 +120,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, local = orig >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
   }
-  // splitk < 0: |splitk| K-slices with the IN-LAUNCH reduction (round 6, experiment NR_SPLITK_L2=1): the slices of one output tile are
-  // consecutive logical ids, i.e. (the XCD ranges above being contiguous and a multiple of |splitk| long: the launcher checks) they run on ONE
-  // XCD, their fp32 slabs meet in that XCD's L2 and the last arriver sums them and runs the epilogue -- no second launch, no cache-wide fence
-  // MEASURED SLOWER (0.43-1.00 x, profiles/r06_splitk_xcd_ab.txt: the last arriver reads its tile's slabs alone): experiments library only.
-#ifdef NR_EXPERIMENTS
-  const bool l2red = splitk < 0;
-  if (l2red) splitk = -splitk;
-  int slice;
-  if (l2red) { const int t = fdiv_small(bid, splitk); slice = bid - t * splitk; bid = t; }
-  else { slice = splitk > 1 ? fdiv_small(bid, ntn * ntm) : 0; bid -= slice * ntn * ntm; }
-  const int tile_id = bid;
-#else
   const int slice = splitk > 1 ? fdiv_small(bid, ntn * ntm) : 0;
   bid -= slice * ntn * ntm;
-#endif
   // tile order inside an XCD's range: the operand that is re-used by neighbouring tiles should be the BIG
   // one.  m_fast: neighbours share a weight panel (weight-heavy 4x4 / 8x8 levels); else an activation panel.
   int bm, bn;
@@ -272,12 +256,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     bf16* sB = sA + BM * BK;
     if constexpr (ADMA) {
       const unsigned la = lds_addr(sA + wave * GA * 8 * BK), lb = lds_addr(sB + wave * GB * 8 * BK);
-#ifdef NR_ABLATE_A
-      // timing ablation (wrong results): the activation tile is fetched for one tap in nine only -- what a halo tile held in LDS would
-      // leave of the A traffic of a tap-inner 3x3 conv (tools/conv_halo_potential.py; 2-stage instantiations wait with vmcnt(0), so the
-      // barrier protocol stays valid)
-      if (!tap_inner || st_tap == 0)
-#endif
 #pragma unroll
       for (int j = 0; j < GA; ++j) glds16_asm(ap[j], la + (unsigned)(j * 8 * BK * (int)sizeof(bf16)));
 #pragma unroll
@@ -330,9 +308,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     if (kt_begin + s0 < kt_end) stage(s0);
   int cur = 0;
   NR_STAMP_AT(1);
-#if NR_ABLATE & 4
-  bf16x8 wf[2][NT], xf[2][MT];
-#endif
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     // tile kt must have landed; the younger (NS-2) tiles may stay outstanding (vmcnt counts in issue order)
     if (kt + (NS - 2) < kt_end) wait_vmcnt<(NS - 2) * G>(); else wait_vmcnt<0>();
@@ -342,11 +317,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     const bf16* sB = sA + BM * BK;
     // fragment reads of k-step 0 go out FIRST, so their LDS latency is covered by the staging code below
     // (pointer bumps + LDS-DMA issue for tile kt+NS-1) instead of sitting exposed in front of the MFMAs
-#if !(NR_ABLATE & 4)
     bf16x8 wf[2][NT], xf[2][MT];
-#else
-    if (kt == kt_begin) {
-#endif
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       const int row = wn * WN + i * 16 + fr;
@@ -357,19 +328,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
       const int row = wm * WM + j * 16 + fr;
       xf[0][j] = *(const bf16x8*)(sA + row * BK + ((fg ^ (row & 7)) << 3));
     }
-#if NR_ABLATE & 4
-    }
-#endif
     __builtin_amdgcn_sched_barrier(0);
     {
       const int nxt = kt + NS - 1;           // refill the buffer tile kt-1 occupied
       int nb = cur + NS - 1; if (nb >= NS) nb -= NS;
-      if (nxt < kt_end && !(NR_ABLATE & 2)) stage(nb);
+      if (nxt < kt_end) stage(nb);
     }
     __builtin_amdgcn_sched_barrier(0);
-#if NR_ABLATE & 4
-    if (kt == kt_begin) {
-#endif
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       const int row = wn * WN + i * 16 + fr;
@@ -380,20 +345,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
       const int row = wm * WM + j * 16 + fr;
       xf[1][j] = *(const bf16x8*)(sA + row * BK + (((4 + fg) ^ (row & 7)) << 3));
     }
-#if NR_ABLATE & 4
-    }
-#endif
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j)
-#if NR_ABLATE & 8
-          asm volatile("" : : "v"(wf[ks][i]), "v"(xf[ks][j]));
-#else
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][i], xf[ks][j], acc[i][j], 0, 0, 0);
-#endif
     if constexpr (LNF) {
       const bf16x2 one2 = {(bf16)1.0f, (bf16)1.0f};
 #pragma unroll
@@ -464,45 +422,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
         nr_store16f(slab + (size_t)m * p.N + n, acc[i][j]);
       }
     }
-#ifndef NR_EXPERIMENTS
     return;
-#else
-    if (!l2red) return;
-    // ---- in-launch reduction.  Every thread's slab stores are complete (acknowledged by the L2: the vector L1 is write-through) before the
-    // workgroup's arrival is counted; the counter lives in the XCD's L2 (workgroup-scope atomic: executed there, not at the memory side), and so
-    // do the sibling slabs the last arriver then reads (first touch by this CU in this launch: its L1, invalidated at kernel start, cannot hold
-    // them).  Slices are summed in slice order whoever arrives last: bit-identical to splitk_reduce_kernel. ----
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* ctr = p.sk_ctr + tile_id;
-    int* flag = reinterpret_cast<int*>(smem);
-    if (tid == 0) {
-      const int old = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int last = old == splitk - 1;
-      if (last) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // self-cleaning: the next launch finds zeros
-      *flag = last;
-    }
-    __syncthreads();
-    const int last = *flag;
-    __syncthreads();                       // (the staged epilogue below re-uses the LDS)
-    if (!last) return;
-    asm volatile("" ::: "memory");
-    const size_t slab_elems = (size_t)p.M * p.N;
-#pragma unroll
-    for (int j = 0; j < MT; ++j) {
-      const int m = m0 + wm * WM + j * 16 + fr;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        const int n = n0 + wn * WN + i * 16 + 4 * fg;
-        if (n >= p.N) continue;
-        const float* src = partial + (size_t)m * p.N + n;
-        f32x4 v = *(const f32x4*)src;
-        for (int sl = 1; sl < splitk; ++sl) v += *(const f32x4*)(src + sl * slab_elems);
-        acc[i][j] = v;
-      }
-    }
-#endif
   }
   // Staged epilogue (whenever the fp32 C tile fits in the LDS ring): accumulators -> LDS (16-byte chunks
   // XOR-swizzled with row&7: conflict-free both ways) -> each thread handles 8 consecutive output channels of one
@@ -789,7 +709,7 @@ int launch_cfg(const NrGemmParams& p, unsigned grid, int splitk, float* partial,
     (void)hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   }
   static const int adma_min = getenv("NR_IGEMM_ADMA_MINK") ? atoi(getenv("NR_IGEMM_ADMA_MINK")) : 24;   // k-tiles per slice; A/B switch
-  const int nk_slice = (p.K / 64) / (splitk > 0 ? splitk : (splitk < 0 ? -splitk : 1));
+  const int nk_slice = (p.K / 64) / (splitk > 1 ? splitk : 1);
   // plain Linears (1x1, one source) on the instantiation without the conv paths (rings up to 4 deep: the ones Linears are planned with)
   static const bool lin_on = !(getenv("NR_IGEMM_LIN") && getenv("NR_IGEMM_LIN")[0] == '0');            // A/B switch
   if constexpr (NS <= 4) {
@@ -862,18 +782,6 @@ extern "C" int nr_launch_g8p(const NrGemmParams* pp, int m_fast, hipStream_t str
 // smallm.hip: panel-resident kernel for the M <= 512 Linears; needs the fragment-major copy of the weights (NrGemmParams::w_fm)
 extern "C" int nr_smallm_eligible(const NrGemmParams* pp);
 extern "C" int nr_launch_smallm(const NrGemmParams* pp, hipStream_t stream);
-#ifdef NR_EXPERIMENTS
-// Rejected experiments (csrc/experiments/, built only by `make experiments` into libneurons_amd_exp.so for the A/B tools; never the product):
-// gemm256.hip: 256-row tiles with role-alternating wave groups for the long-K convs / Linears (NR_IGEMM256=2)
-extern "C" int nr_igemm256_plan(const NrGemmParams* pp, int* bn_out, int* splitk_out);
-extern "C" size_t nr_igemm256_workspace_bytes(const NrGemmParams* pp);
-extern "C" int nr_launch_igemm256(const NrGemmParams* pp, float* workspace, int m_fast, int* splitk_used, hipStream_t stream);
-
-// gemmws.hip: four MFMA waves + one LDS-DMA wave per 128 x 128 tile (NR_IGEMM_WS=1|2)
-extern "C" int nr_igemm_ws_plan(const NrGemmParams* pp, int* splitk_out);
-extern "C" size_t nr_igemm_ws_workspace_bytes(const NrGemmParams* pp);
-extern "C" int nr_launch_igemm_ws(const NrGemmParams* pp, float* workspace, int m_fast, int* splitk_used, hipStream_t stream);
-#endif
 
 // fp32 scratch (bytes) a launch of this shape needs for split-K slabs (0 if none)
 extern "C" size_t nr_igemm_workspace_bytes(const NrGemmParams* pp) {
@@ -881,31 +789,10 @@ extern "C" size_t nr_igemm_workspace_bytes(const NrGemmParams* pp) {
   if (nr_rowpanel_eligible(pp)) return 0;
   if (pp->w_fm) return 0;                      // the caller chose smallm.hip when it built this description (nr_smallm_eligible)
   if (nr_g8p_plan(pp)) return 0;
-#ifdef NR_EXPERIMENTS
-  if (nr_igemm_ws_plan(pp, nullptr)) return nr_igemm_ws_workspace_bytes(pp);
-  if (nr_igemm256_plan(pp, nullptr, nullptr)) return nr_igemm256_workspace_bytes(pp);
-#endif
   Plan pl = choose_plan(plan_view(*pp));
   int mf = 0;
   apply_override(*pp, pl, mf);
   return pl.splitk > 1 ? (size_t)pl.splitk * pp->M * pp->N * sizeof(float) : 0;
-}
-
-// Tile counters an in-launch split-K reduction of this description needs (NrGemmParams::sk_ctr), 0 when the launch is not a split-K launch of
-// the tiled igemm, its tile count is not a multiple of 8 (whole tiles per XCD), or the experiment is off (experiments library + NR_SPLITK_L2=1)
-extern "C" int nr_igemm_splitk_l2_tiles(const NrGemmParams* pp) {
-#ifndef NR_EXPERIMENTS
-  (void)pp;
-  return 0;             // product library: slabs + splitk_reduce_kernel (the in-launch form lost its A/B)
-#endif
-  static const bool on = getenv("NR_SPLITK_L2") && getenv("NR_SPLITK_L2")[0] == '1';
-  if (!on || nr_igemm_workspace_bytes(pp) == 0 || pp->out_f32) return 0;
-  Plan pl = choose_plan(plan_view(*pp));
-  int mf = 0;
-  apply_override(*pp, pl, mf);
-  if (pl.splitk <= 1) return 0;
-  const int tiles = ((pp->M + pl.bm - 1) / pl.bm) * ((pp->N + pl.bn - 1) / pl.bn);
-  return tiles % 8 == 0 ? tiles : 0;
 }
 
 // Host launcher.  Returns 0 on success, nonzero on unsupported shape.  `workspace` must hold
@@ -927,40 +814,6 @@ extern "C" int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStre
     if (ntm_ >= 8 && ntn_ >= 4 && w_e >= 3.0e6) mf = 8;
     return nr_launch_g8p(pp, mf, stream);
   }
-#ifdef NR_EXPERIMENTS
-  if (!getenv("NR_IGEMM_FORCE") && nr_igemm_ws_plan(pp, nullptr)) {
-    const double w_e = (double)p.N * p.K, a_e = (double)p.M * Cin;
-    int mf = w_e > a_e ? 1 : 0;
-    const int ntm_ = (p.M + 127) / 128, ntn_ = (p.N + 127) / 128;
-    if (ntm_ >= 8 && ntn_ >= 4 && w_e >= 3.0e6) mf = 8;
-    int used = 1;
-    const int rc = nr_launch_igemm_ws(pp, workspace, mf, &used, stream);
-    if (rc) return rc;
-    if (used > 1) {
-      const long long total = (long long)p.M * (p.N / 4);
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, used, (const float*)workspace);
-    }
-    return 0;
-  }
-  {
-    int bn256 = 0, sk256 = 1;
-    if (nr_igemm256_plan(pp, &bn256, &sk256)) {
-      const double w_e = (double)p.N * p.K;
-      const double a_e = (double)p.M * Cin * (p.ksize == 3 ? (p.stride == 2 ? 4.0 : (p.ups ? 0.25 : 1.0)) : 1.0);
-      int mf = w_e > a_e ? 1 : 0;
-      const int ntm_ = (p.M + 255) / 256, ntn_ = (p.N + bn256 - 1) / bn256;
-      if (ntm_ >= 8 && ntn_ >= 4 && w_e >= 3.0e6) mf = 8;
-      int used = 1;
-      const int rc = nr_launch_igemm256(pp, workspace, mf, &used, stream);
-      if (rc) return rc;
-      if (used > 1) {
-        const long long total = (long long)p.M * (p.N / 4);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, used, (const float*)workspace);
-      }
-      return 0;
-    }
-  }
-#endif
   if (p.K % 64 != 0 || Cin % 64 != 0 || p.N % 32 != 0) return 1;
   if (p.a1 && (p.c0 % 64 != 0)) return 2;
   if (p.K != p.ksize * p.ksize * Cin) return 3;
@@ -996,10 +849,6 @@ extern "C" int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStre
   if (pl.splitk > 1 && !workspace) return 6;
   float* partial = p.out_f32 ? p.out_f32 : (pl.splitk > 1 ? workspace : nullptr);
   const unsigned grid = (unsigned)(((p.M + pl.bm - 1) / pl.bm) * ((p.N + pl.bn - 1) / pl.bn) * pl.splitk);
-  // in-launch split-K reduction (the caller provided tile counters): all slices of a tile on one XCD needs whole tiles per XCD range
-  const int sk_slices = pl.splitk;
-  const bool l2red = pl.splitk > 1 && p.sk_ctr && !p.out_f32 && (grid / pl.splitk) % 8 == 0;
-  if (l2red) pl.splitk = -pl.splitk;
   int rc;
   if (pl.bm == 256 && pl.bn == 160) rc = launch_tile<256, 160, 2, 2>(p, grid, pl, partial, m_fast, stream);
   else if (pl.bm == 256 && pl.waves == 4) rc = launch_tile<256, 128, 2, 2>(p, grid, pl, partial, m_fast, stream);
@@ -1017,7 +866,6 @@ extern "C" int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStre
   else if (pl.bm == 64 && pl.bn == 64) rc = launch_tile<64, 64, 2, 2>(p, grid, pl, partial, m_fast, stream);
   else rc = 9;            // no such tile: never launch another one on a grid computed for this one
   if (rc) return rc;      // no instantiation for this (tile, LayerNorm-fused) request: fail loudly, never skip the launch
-  (void)sk_slices;
   if (pl.splitk > 1) {
     const long long total = (long long)p.M * (p.N / 4);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, pl.splitk,

@@ -50,10 +50,6 @@ __device__ __forceinline__ size_t rowvec_row(const NrGemmParams& p, int m) {
   return (size_t)r * p.rowvec_ld;
 }
 
-#ifndef NR_G8P_ABLATE
-#define NR_G8P_ABLATE 0     // timing ablations (experiments build only, results wrong): 1 no LDS-DMA in the loop, 2 no fragment reads in the loop, 4 no MFMAs
-#endif
-
 constexpr int G8_BM = 256, G8_BK = 64;
 
 template <int NT, bool TAPI, int NPH = 4>
@@ -222,30 +218,26 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
 #pragma unroll
     for (int ph = 0; ph < NPH; ++ph) {
       // ---------------- load section ----------------
-      if (!(NR_G8P_ABLATE & 2) || t == 0) {
-        if (ph == 0) {
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < NT; ++i) wf[ks][i] = *(const bf16x8*)(sbase + wrow + i * 16 * 128 + (frag0 ^ (unsigned)(ks * 64)));
-        }
+      if (ph == 0) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-          for (int jj = 0; jj < MPP; ++jj) xf[ks][jj] = *(const bf16x8*)(sbase + xrow + (MPP * ph + jj) * 16 * 128 + (frag0 ^ (unsigned)(ks * 64)));
+          for (int i = 0; i < NT; ++i) wf[ks][i] = *(const bf16x8*)(sbase + wrow + i * 16 * 128 + (frag0 ^ (unsigned)(ks * 64)));
       }
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int jj = 0; jj < MPP; ++jj) xf[ks][jj] = *(const bf16x8*)(sbase + xrow + (MPP * ph + jj) * 16 * 128 + (frag0 ^ (unsigned)(ks * 64)));
       __builtin_amdgcn_sched_barrier(0);
-      if (!(NR_G8P_ABLATE & 1)) {
-        if (ph < NPH / 2) {
-          if (has1) {
+      if (ph < NPH / 2) {
+        if (has1) {
 #pragma unroll
-            for (int j = 0; j < APP; ++j) issue_a(ab1, tap1, st ^ 1, APP * ph + j);
-          }
-        } else {
-          if (has2) {
+          for (int j = 0; j < APP; ++j) issue_a(ab1, tap1, st ^ 1, APP * ph + j);
+        }
+      } else {
+        if (has2) {
 #pragma unroll
-            for (int j = WPP * (ph - NPH / 2); j < (ph == NPH - 1 ? NT : WPP * (ph - NPH / 2 + 1)); ++j) issue_w(t + 2, st, j);
-          }
+          for (int j = WPP * (ph - NPH / 2); j < (ph == NPH - 1 ? NT : WPP * (ph - NPH / 2 + 1)); ++j) issue_w(t + 2, st, j);
         }
       }
       if constexpr (NPH == 2) {
@@ -264,19 +256,13 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
         for (int jj = 0; jj < MPP; ++jj)
 #pragma unroll
           for (int i = 0; i < NT; ++i) {
-#if NR_G8P_ABLATE & 4
-            asm volatile("" : : "v"(wf[ks][i]), "v"(xf[ks][jj]));
-#else
             acc[i][MPP * ph + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][i], xf[ks][jj], acc[i][MPP * ph + jj], 0, 0, 0);
-#endif
           }
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
-      if (!(NR_G8P_ABLATE & 1)) {
-        // counted waits: everything but the N youngest pieces of this wave has landed (vmcnt counts in issue order)
-        if (ph == NPH - 2 && has1) { if (has2) wait_vm<4 + W_BEFORE_LAST>(); else wait_vm<4>(); }   // W(t+1) landed; A(t+1) [+ part of W(t+2)] may fly
-        if (ph == NPH - 1 && has1) { if (has2) wait_vm<NT>(); else wait_vm<0>(); }                  // A(t+1) landed; W(t+2) may fly
-      }
+      // counted waits: everything but the N youngest pieces of this wave has landed (vmcnt counts in issue order)
+      if (ph == NPH - 2 && has1) { if (has2) wait_vm<4 + W_BEFORE_LAST>(); else wait_vm<4>(); }   // W(t+1) landed; A(t+1) [+ part of W(t+2)] may fly
+      if (ph == NPH - 1 && has1) { if (has2) wait_vm<NT>(); else wait_vm<0>(); }                  // A(t+1) landed; W(t+2) may fly
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
     }

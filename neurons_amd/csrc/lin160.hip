@@ -30,9 +30,6 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // 2 + 3 s / 3 + 3 s / 4 + 3 s = stage s (< 40) after its DMA wait / barrier / MFMAs, 125 loop end, 126 kernel end
 __device__ unsigned long long lin160_stamp_buf[512][128];
 #define L1_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512 && (slot) < 128) lin160_stamp_buf[blockIdx.x][(slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-// panel kernel, TIMING-ONLY ablations of its stage loop (results wrong; stamp build only, compile-time template argument chosen by NR_Q_DBG at launch; bits: 1 no stage
-// barrier, 2 no DMA pieces in the loop, 4 no fragment reads in the loop, 8 no MFMAs, 16 no DMA wait, 32 no block epilogue)
-#define Q_DBG(bit) (DBG & (bit))
 // panel kernel, fine stamps of ONE steady-state stage (g = 11) for wave 0 (rows 0 .. 255 of the buffer) and its SIMD-mate wave 4 (rows 256 .. 511): slots 64 + 3 kk = k-step kk
 // begins, 65 + 3 kk = its DMA burst (if any) issued, 66 + 3 kk = its MFMAs issued; 76 / 77 / 78 = in front of the DMA wait / behind it / behind the barrier (inside k-step 3)
 #ifdef NR_STAMP_FINE
@@ -43,7 +40,6 @@ __device__ unsigned long long lin160_stamp_buf[512][128];
 #else
 #define L1_STAMP(slot) do { } while (0)
 #define Q_STAMPW(slot) do { } while (0)
-#define Q_DBG(bit) 0
 #endif
 
 constexpr int L1_BN = 160, L1_NT = 10;
@@ -295,7 +291,7 @@ struct NrLin128QParams {
 // waves accumulate all of them over their half of K), a stage is still 32 KiB (8 k-steps x 4 fragments), the ring has 3 slots, and at the end of a block the pair
 // swaps partial sums through 32 KiB of LDS (each wave hands over the two tiles the other one finishes, one extra barrier per block); the row statistics are
 // combined the same way once.
-template <int KS, bool GEGLU, bool KSPLIT = false, int DBG = 0>
+template <int KS, bool GEGLU, bool KSPLIT = false>
 __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
   constexpr int K = 32 * KS;
   constexpr int KSL = KSPLIT ? KS / 2 : KS;            // k-steps a wave holds
@@ -502,16 +498,16 @@ __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
         const unsigned char* nbase;
         if (kk < 3) nbase = smem + slot * Q_STAGE + (kk + 1) * (NTB * 1024);
         else {
-          if (!Q_DBG(16)) wait_vmcnt<(NS - 2) * 4>();            // stage g + 1 landed: younger pieces of this wave in flight = stages g + 2 .. g + NS - 1 (4 each)
+          wait_vmcnt<(NS - 2) * 4>();            // stage g + 1 landed: younger pieces of this wave in flight = stages g + 2 .. g + NS - 1 (4 each)
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's reads of slot g are in registers: the slot may be refilled behind the barrier
           if (g < 40) L1_STAMP(2 + 3 * g);
-          if (!Q_DBG(1)) __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_s_barrier();
           if (g < 40) L1_STAMP(3 + 3 * g);
           nbase = smem + nslot * Q_STAGE;
         }
         __builtin_amdgcn_sched_barrier(0);
         // the wave's four DMA pieces of stage g + NS - 1 in one burst at the head of the stage (staggering the two waves of a SIMD measured the same)
-        if (kk == 0 && !Q_DBG(2)) {
+        if (kk == 0) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) issue_piece(g + NS - 1, i);
         }
@@ -520,9 +516,9 @@ __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
         for (int n = 0; n < 4; ++n) {
 #pragma unroll
           for (int rt = 0; rt < 2; ++rt)
-            if (!Q_DBG(8)) acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[n], xb[rt][4 * st + kk], (st == 0 && kk == 0) ? zero4 : acc[rt][n], 0, 0, 0);
+            acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[n], xb[rt][4 * st + kk], (st == 0 && kk == 0) ? zero4 : acc[rt][n], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
-          if (!Q_DBG(4)) w[n] = *(const bf16x8*)(nbase + (unsigned)(n * 1024) + wl);
+          w[n] = *(const bf16x8*)(nbase + (unsigned)(n * 1024) + wl);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -530,7 +526,7 @@ __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
       ++g;
       slot = nslot;
     }
-    if (!Q_DBG(32)) epilogue(j);
+    epilogue(j);
     if constexpr (KSPLIT) {
       // the first fragments of the next block are read again BEHIND the epilogue: their registers are free across it (the exchange needs them: with the prefetched
       // set live hipcc spills panel registers and rotates the whole panel by four registers per block, 140 v_mov_b64)
@@ -683,22 +679,6 @@ extern "C" int nr_launch_lin160(const NrGemmParams* pp, const bf16* stream, hipS
       done |= 1ull << (dev & 63);
     }
     const dim3 grid((unsigned)(nrg * q.NCG));
-#ifdef NR_STAMP
-    if (const int bits = (!ksplit && getenv("NR_Q_DBG")) ? atoi(getenv("NR_Q_DBG")) : 0) {      // timing-only ablation arms of the GEGLU form
-      auto go = [&](auto kf) { (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_max); hipLaunchKernelGGL(kf, grid, dim3(512), shm, s, q); };
-      switch (bits) {
-        case 1: go(lin128q_kernel<20, true, false, 1>); break;
-        case 2: go(lin128q_kernel<20, true, false, 2>); break;
-        case 4: go(lin128q_kernel<20, true, false, 4>); break;
-        case 8: go(lin128q_kernel<20, true, false, 8>); break;
-        case 14: go(lin128q_kernel<20, true, false, 14>); break;
-        case 16: go(lin128q_kernel<20, true, false, 16>); break;
-        case 17: go(lin128q_kernel<20, true, false, 17>); break;
-        default: return 1;
-      }
-      return 0;
-    }
-#endif
     if (ksplit) {
       if (g.geglu) hipLaunchKernelGGL((lin128q_kernel<40, true, true>), grid, dim3(512), shm, s, q);
       else hipLaunchKernelGGL((lin128q_kernel<40, false, true>), grid, dim3(512), shm, s, q);

@@ -44,11 +44,7 @@ __device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) 
 // every chunk behind the previous chunk's HBM writes.  The hardware only needs the registers for two wait states (s_nop 1).
 // rsrc: the four descriptor words in SGPRs; off: byte offset per lane (range-checked: out-of-range lanes are dropped).
 __device__ __forceinline__ void buffer_store16(const u32x4& v, const u32x4& rsrc, unsigned off) {
-#if NR_STORE_WT
-  asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen sc1\n\ts_nop 1" : : "v"(v), "v"(off), "s"(rsrc) : "memory");
-#else
   asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" : : "v"(v), "v"(off), "s"(rsrc) : "memory");
-#endif
 }
 
 // s_waitcnt vmcnt(n) for a wave-uniform runtime n in [0, 15]
@@ -243,7 +239,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(NrRowPanelParams p) {
         // [NSTORE stores][KT DMA of chunk i+1] (plus epilogue loads): waiting until at most that many operations are
         // outstanding retires chunk i without draining chunk i+1 or the latest output stores.
         const int i = ph >> 1;
-        if (i == 0 || (p.dbg & 4)) wait_vmcnt_dyn(0);
+        if (i == 0) wait_vmcnt_dyn(0);
         else wait_vmcnt_dyn(i + 1 < nc ? KT + NSTORE : NSTORE);
       }
       __builtin_amdgcn_s_barrier();
@@ -255,7 +251,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(NrRowPanelParams p) {
       const int cur = i % RP_NS;
       const int cg = c_begin + i;
       const int nw0 = cg * 64;                              // first W row / bias index of the chunk
-      if (i + 2 < nc && !(p.dbg & 2)) issue((i + 2) % RP_NS);
+      if (i + 2 < nc) issue((i + 2) % RP_NS);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt)
@@ -373,9 +369,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(NrRowPanelParams p) {
 #pragma unroll
       for (int j = 0; j < NSTORE; ++j) {
         const u32x4 v = *(const u32x4*)sc_rd[j];
-        unsigned off = out_off[j] + no0b;
-        if (p.dbg & 1) off = RP_OOB;
-        buffer_store16(v, rs_out, off);
+        buffer_store16(v, rs_out, out_off[j] + no0b);
       }
     }
   }
@@ -415,9 +409,6 @@ extern "C" int nr_launch_rowpanel(const NrGemmParams* pp, hipStream_t stream) {
   if (ns > NC) ns = NC;
   if (ns < 1) ns = 1;
   p.nsplit = ns;
-  static const int dbg = getenv("NR_RP_DBG") ? atoi(getenv("NR_RP_DBG")) : 0;
-  p.dbg = dbg;
-  if (getenv("NR_RP_NSPLIT")) { p.nsplit = ns = atoi(getenv("NR_RP_NSPLIT")); }
   constexpr size_t shm = (size_t)(RP_NS * 5 * 64 * 64 + 8 * 2048) * sizeof(bf16);
   int dev = 0;
   (void)hipGetDevice(&dev);

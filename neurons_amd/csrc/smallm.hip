@@ -215,11 +215,7 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
     for (int ks = 0; ks < SM_KSW; ++ks) {
       bf16x8 (&xc)[2] = (ks & 1) ? xc2 : xa;
       bf16x8 (&xn)[2] = (ks & 1) ? xa : xc2;
-#ifdef SM_ABLATE_X        // timing experiment (WRONG results): a quarter of the LDS fragment reads
-      if (ks + 1 < SM_KSW && ((ks + 1) & 3) == 0) read_x(xn, ks + 1); else { xn[0] = xc[0]; xn[1] = xc[1]; }
-#else
       if (ks + 1 < SM_KSW) read_x(xn, ks + 1);
-#endif
       acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wcur[ks], xc[0], acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wcur[ks], xc[1], acc[1], 0, 0, 0);
       if (refill) wcur[ks] = *(const bf16x8*)(wref + ks * 512);

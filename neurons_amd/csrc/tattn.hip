@@ -61,7 +61,6 @@ struct NrTAttnParams {
   const float* bo;         // [C] to_out bias
   float ln_eps;
   float scale_log2e;       // d^-0.5 * log2(e)
-  int dbg;                 // timing experiments only (NR_FUSED_DBG): 1 no DMA waits, 2 no stage barriers, 4 no DMA issue (results are wrong)
 };
 
 // out-tile accumulation with the accumulator PINNED in the AGPR half of the register file (round 5, as xattn.hip: "+a": vDst = SrcC = an AGPR quad).
@@ -70,15 +69,8 @@ struct NrTAttnParams {
 // LDS (s_waitcnt placed for the asm input), its B operand (ob_prev*) is written by the attention's last phase, which never sits directly in front
 // of one of these MFMAs (phase 6 runs behind the last group), and the accumulator is next touched one head later or by the epilogue behind an
 // explicit s_nop.  tattn.o is compiled with -amdgpu-mfma-vgpr-form so the short-lived projection / attention accumulators stay in VGPRs.
-#ifndef NR_ACC_AGPR
-#define NR_ACC_AGPR 1      // 0: the compiler-allocated form again (A/B arm: make variant NAME=noagpr VFLAGS=-DNR_ACC_AGPR=0)
-#endif
 __device__ __forceinline__ void mfma_acc_agpr(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-#if NR_ACC_AGPR
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-#else
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-#endif
 }
 
 // own and partner value across 16-lane rows on the VALU (round 5): v_permlane16_swap / v_permlane32_swap with both operands = v give every lane
@@ -140,7 +132,7 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
     pf_src = wsrc + (size_t)head * TA_HEAD_BYTES + (size_t)part * TA_QKV_BYTES + (size_t)(wave * pf_n) * 1024;
     pf_dst = lds0 + (unsigned)(slot * TA_SLOT) + (unsigned)(wave * pf_n * 1024);
   };
-  auto prefetch_piece = [&](int i) { if (!(p.dbg & 4)) glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
+  auto prefetch_piece = [&](int i) { glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
   set_prefetch(0, 0, 0);
 #pragma unroll
   for (int i = 0; i < 8; ++i) prefetch_piece(i);
@@ -211,8 +203,8 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
   int slot = 0;
   // stage start: this wave's pieces of the stage (landed) vs the FOLLOWING stage's pieces (next_dma of them may stay in flight)
   auto stage_wait = [&](int next_dma) {
-    if (!(p.dbg & 1)) { if (next_dma == 10) wait_vmcnt<10>(); else wait_vmcnt<8>(); }
-    if (!(p.dbg & 2)) __builtin_amdgcn_s_barrier();
+    if (next_dma == 10) wait_vmcnt<10>(); else wait_vmcnt<8>();
+    __builtin_amdgcn_s_barrier();
   };
   auto next_slot = [&]() { slot = slot + 1 == TA_NS ? 0 : slot + 1; };
   auto slot_plus2 = [&]() { int x = slot + 2; return x >= TA_NS ? x - TA_NS : x; };
@@ -252,11 +244,16 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
                              : __builtin_amdgcn_mfma_f32_16x16x32_bf16(wc[nt], xb[mt][ks], acc[nt][mt], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    // the attention consumes these tiles as bf16 MFMA operands: keep them packed (12 VGPRs per tensor instead of 24)
+    // the attention consumes these tiles as bf16 MFMA operands: keep them packed (12 VGPRs per tensor instead of 24).  The empty asm pins every
+    // accumulator quad in front of its packing: without it hipcc 7.2 gave the last k-step's MFMA a destination partially overlapping the SrcC
+    // the previous MFMA wrote (the chain tools/check_mfma_overlap.py rejects, see xattnw.hip)
 #pragma unroll
     for (int nt = 0; nt < 3; ++nt)
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) outp[nt][mt] = pack4(acc[nt][mt]);
+      for (int mt = 0; mt < 2; ++mt) {
+        asm volatile("" : "+v"(acc[nt][mt]));
+        outp[nt][mt] = pack4(acc[nt][mt]);
+      }
   };
   auto frag_o = [&](const bf16* sW, int nt, int ks2) {
     const int row = (nt & 3) * 16 + fr;
@@ -490,8 +487,6 @@ extern "C" int nr_launch_tattn_fused(bf16* t, int nbatch, int frames, int hw, co
   NrTAttnParams p;
   p.t = t; p.hw = hw; p.nbatch = nbatch; p.stream = stream; p.gamma = gamma; p.gb = gb; p.bo = bo; p.ln_eps = ln_eps; p.norot = norot;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)TA_D);
-  static const int dbg = getenv("NR_FUSED_DBG") ? atoi(getenv("NR_FUSED_DBG")) : 0;
-  p.dbg = dbg;
   constexpr size_t shm = (size_t)TA_NS * TA_SLOT;
   int dev = 0;
   (void)hipGetDevice(&dev);

@@ -96,15 +96,8 @@ __device__ __forceinline__ float rows_sum(float v) {
 // the asm input), its B operand was converted many instructions earlier, and the accumulator is next touched one head later or by the epilogue
 // behind an explicit s_nop (below).  No VALU-written operand ever sits directly in front of these MFMAs (the VALU -> MFMA-operand hazard
 // attention.hip's mfma_bf16_tied pays an s_nop for): the weight fragments come from ds_read, O^T was packed before the stage's barrier.
-#ifndef NR_ACC_AGPR
-#define NR_ACC_AGPR 1      // 0: the compiler-allocated form again (A/B arm: make variant NAME=noagpr VFLAGS=-DNR_ACC_AGPR=0)
-#endif
 __device__ __forceinline__ void mfma_acc_agpr(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-#if NR_ACC_AGPR
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-#else
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-#endif
 }
 
 __device__ __forceinline__ s16x4 pack4(const f32x4& v) {
