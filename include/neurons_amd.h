@@ -74,7 +74,7 @@ typedef struct nr_net_config {
   int32_t motion_num_attention_blocks;       /* 2 (UNet v3) / 1 (SparseCtrl)                      */
   int32_t motion_pe_max_len;                 /* 24 (UNet default) / 32 (SparseCtrl)               */
   int32_t motion_module_mid_block;           /* 0                                                 */
-  int32_t conditioning_channels;             /* SparseCtrl: 4 (+1 mask channel is implied)        */
+  int32_t conditioning_channels;             /* SparseCtrl: 4 latent / 3 RGB (+1 mask channel is implied) */
   int32_t set_noisy_sample_input_to_zero;    /* SparseCtrl: 1                                     */
   /* sgm UNetModel only (generative_models/configs/unclip6.yaml:47-63); for that kind block_out_channels[i] =
    * channel_mult[i]*model_channels, layers_per_block = num_res_blocks, down_block_has_attn[i] = (2^i in
@@ -82,6 +82,12 @@ typedef struct nr_net_config {
   int32_t transformer_depth[NR_MAX_LEVELS];  /* 1,2,10 (0 for the other kinds = depth 1)          */
   int32_t num_head_channels;                 /* 64: heads = C / 64 (0 for the other kinds)        */
   int32_t adm_in_channels;                   /* 1024: width of the `y` vector                     */
+  /* SparseCtrl condition embedding (sparse_controlnet.py:176-190).  0 = the simplified single 3x3 conv at the latent resolution
+   * (latent_condition.yaml); L > 0 = SparseControlNetConditioningEmbedding with conditioning_embedding_out_channels =
+   * cond_embedding_channels[0..L) (image_condition.yaml: 4 levels, 16,32,96,256).  The condition and mask passed to
+   * nr_sparsectrl_forward* are then at 2^(L-1) x the latent resolution (8 x for four levels).                              */
+  int32_t cond_embedding_levels;
+  int32_t cond_embedding_channels[NR_MAX_LEVELS];
 } nr_net_config;
 
 #define NR_DTYPE_F32 0
@@ -138,8 +144,8 @@ nr_status nr_unet3d_forward(nr_net* h, nr_stream stream, const float* sample_dev
 
 /* replaces SparseControlNetModel.forward (sparse_controlnet.py:450-581)
  *   sample_dev   fp32 [batch][4][F][h][w]; may be NULL when set_noisy_sample_input_to_zero
- *   cond_dev     fp32 [cond_batch][cond_ch][F][h][w]  controlnet_cond
- *   mask_dev     fp32 [cond_batch][1][F][h][w]        conditioning_mask
+ *   cond_dev     fp32 [cond_batch][cond_ch][F][h][w]  controlnet_cond (h, w: latent size; x 2^(L-1) with cond_embedding_levels = L > 0)
+ *   mask_dev     fp32 [cond_batch][1][F][h][w]        conditioning_mask (same size as cond_dev)
  *   cond_batch   batch of cond/mask; broadcast over the CFG halves as b % cond_batch
  *   scale        conditioning_scale
  *   out_down_dev num_residuals pointers, bf16 channels-last, written
@@ -375,6 +381,15 @@ nr_status nr_op_gemm_ex(nr_stream stream, const void* a_dev, int32_t lda, const 
 nr_status nr_op_conv3x3(nr_stream stream, const void* x0_dev, int32_t c0, const void* x1_dev, int32_t c1, int32_t nimg,
                         int32_t H, int32_t W, int32_t stride, int32_t ups, const void* w_dev, const float* bias_dev,
                         const float* rowvec_dev, int32_t rowvec_div, const void* res_dev, void* out_dev, int32_t Cout);
+/* SparseCtrl image-condition embedding layers (condembed_* in elementwise.hip).  nr_op_condembed_in: the first 3x3 conv + SiLU from fp32 NCFHW
+ * cond [nsrc][c0][F][H][W] and mask [nsrc][1][F][H][W] (frames fmap[0..nframes), host array) to bf16 [nsrc * nframes][H][W][Cout],
+ * weight fp32 [(c0 + 1) * 9][Cout], Cout 16 / 32.  nr_op_condembed_conv: 3x3 pad-1 conv (stride 1 / 2) bf16 [nimg][H][W][Cin] ->
+ * [nimg][OH][OW][Cout] + bias (+ SiLU), weight fragment-major [Cout/16][ceil(9 Cin / 32)][64][8] bf16 (ops.condembed_conv packs it). */
+nr_status nr_op_condembed_in(nr_stream stream, const float* cond_dev, const float* mask_dev, int32_t c0, int32_t nsrc, int32_t F, int32_t H,
+                             int32_t W, const int32_t* fmap, int32_t nframes, const float* w_dev, const float* bias_dev, int32_t Cout,
+                             void* out_dev);
+nr_status nr_op_condembed_conv(nr_stream stream, const void* x_dev, int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t stride,
+                               const void* wfm_dev, const float* bias_dev, int32_t Cout, int32_t silu, void* out_dev);
 /* nr_op_conv3x3 for stride 1 / no upsample / one source, weight pre-arranged as [Cout][Cin/64][3][3][64] (the engine's layout for the
  * ResnetBlock convs: the K loop walks 64-channel chunks with the 9 taps innermost) */
 nr_status nr_op_conv3x3_tap_inner(nr_stream stream, const void* x0, int32_t c0, int32_t nimg, int32_t H, int32_t W, const void* w,

@@ -48,6 +48,8 @@ class NrNetConfig(C.Structure):
         ("transformer_depth", C.c_int32 * NR_MAX_LEVELS),
         ("num_head_channels", C.c_int32),
         ("adm_in_channels", C.c_int32),
+        ("cond_embedding_levels", C.c_int32),
+        ("cond_embedding_channels", C.c_int32 * NR_MAX_LEVELS),
     ]
 
 
@@ -118,6 +120,8 @@ SYMBOLS = {
     "nr_op_gemm_ex": (_I32, [_VP, _VP, _I32, _VP, _VP, _VP, C.c_float, _VP, _I32, _I32, _I32, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _I32, _I32,
                              C.c_float]),
     "nr_op_conv3x3": (_I32, [_VP, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _VP, _I32]),
+    "nr_op_condembed_in": (_I32, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, C.POINTER(_I32), _I32, _VP, _VP, _I32, _VP]),
+    "nr_op_condembed_conv": (_I32, [_VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP]),
     "nr_op_conv3x3_tap_inner": (_I32, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _VP, _I32]),
     "nr_op_groupnorm": (_I32, [_VP, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _VP, _VP, C.c_float, _I32, _VP, _VP]),
     "nr_op_layernorm": (_I32, [_VP, _VP, _VP, _I32, _I32, _VP, _VP, C.c_float, _VP, _I32, _I32]),

@@ -7,6 +7,8 @@
 //   linear_small    : y = W act(x) + b for the handful-of-rows time-embedding MLPs (unet.py:392; resnet.py:191)
 //   cfg_ddim_step   : classifier-free guidance + DDIM eta=0 update           (pipeline_neuroclips.py:478-483)
 //   add_bf16        : out = a + b (ControlNet residual adds, unet.py:425-428,436-439)
+//   condembed_*     : the SparseCtrl image-condition embedding (end of this file): a first conv from the fp32 condition planes, the
+//                     small-channel 3x3 convs on MFMA (implicit GEMM, K = 9 Cin <= 864) and the batch / frame broadcast
 #include "common.h"
 
 namespace {
@@ -584,3 +586,233 @@ extern "C" int nr_launch_f32_to_bf16(const float* a, bf16* out, long long n, hip
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a, out, n);
   return 0;
 }
+
+// =============================================================================================
+// SparseCtrl image-condition embedding (condembed_*) (SparseControlNetConditioningEmbedding, animatediff/models/sparse_controlnet.py:49-82):
+// eight 3x3 pad-1 convolutions from the RGB condition + mask at 8x the latent resolution down to the latent grid, SiLU after every
+// conv but the last.  Three kernels:
+//   condembed_in    : the first conv (Cin = conditioning_channels + 1 <= 8, Cout = 16 / 32) straight from the fp32 NCFHW condition and
+//                     mask planes (concatenated on the fly, as conv_in_small in elementwise.hip), plain FMA, one thread per output pixel.
+//                     The frames it runs on come from a map: with the identical-frame evaluation only the conditioned frames + one
+//                     representative of the rest are embedded (the engine's n_cond_frames).
+//   condembed_conv  : the small-channel convs (Cin 16 .. 256, stride 1 / 2) as an implicit GEMM on v_mfma_f32_16x16x32_bf16.  K runs
+//                     (tap, channel) with the channel fastest; Cin % 8 == 0, so the 8 bf16 of a lane's B fragment are one 16-byte load
+//                     of one input pixel, and a 32-deep k-step covers two taps at Cin = 16 (the K = 9 Cin tail is zero-padded).
+//                     Weights are fragment-major [Cout/16][KS][64 lanes][8] (KS = ceil(9 Cin / 32)): a wave's A operand of one k-step
+//                     is one contiguous KiB, read through L2 (the largest layer, 96 -> 256, is 442 KiB).  The activations are
+//                     read straight from global memory into the B fragments; a tap re-reads its neighbours' pixels from L1/L2.
+//                     Each wave computes 32 output pixels x 16 NT output channels.
+//   condembed_bcast : x[b][f] = emb[b % cond_batch][emap[f]] (+ addend[b][f]): the per-condition-image embedding broadcast over the
+//                     CFG / grouped batch and over the frames that share one embedding.
+// =============================================================================================
+
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) short i16x8;
+
+constexpr int CE_MAX_FRAMES = 64;
+struct CeFrameMap { int f[CE_MAX_FRAMES]; };
+
+// ---------------------------------------------------------------------------------------------
+// first conv: out[n][y][x][co] = silu(bias[co] + sum_{ci,ky,kx} wT[ci*9+ky*3+kx][co] * in(ci, y+ky-1, x+kx-1))
+// in(ci < c0) = cond[b][ci][f][..], in(c0) = mask[b][0][f][..]; n = b * Fe + e, f = fmap[e].  grid (ceil(H*W / 256), nimg)
+// ---------------------------------------------------------------------------------------------
+template <int COUT>
+__global__ __launch_bounds__(256) void condembed_in_kernel(const float* __restrict__ cond, const float* __restrict__ mask, int c0,
+                                                           int F, int H, int W, CeFrameMap fmap, int Fe,
+                                                           const float* __restrict__ wT, const float* __restrict__ bias,
+                                                           bf16* __restrict__ out) {
+  __shared__ float sw[8 * 9 * COUT];
+  __shared__ float sb[COUT];
+  const int cin = c0 + 1;
+  for (int i = threadIdx.x; i < cin * 9 * COUT; i += 256) sw[i] = wT[i];
+  if (threadIdx.x < COUT) sb[threadIdx.x] = bias[threadIdx.x];
+  __syncthreads();
+  const int n = blockIdx.y;
+  const int b = n / Fe, f = fmap.f[n - b * Fe];
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= H * W) return;
+  const int y = pix / W, x = pix - y * W;
+  float acc[COUT];
+#pragma unroll
+  for (int o = 0; o < COUT; ++o) acc[o] = sb[o];
+  for (int ci = 0; ci < cin; ++ci) {
+    const float* src = ci < c0 ? cond + (((size_t)b * c0 + ci) * F + f) * H * W : mask + ((size_t)b * F + f) * H * W;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int iy = y + t / 3 - 1, ix = x + t % 3 - 1;
+      const float v = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? src[(size_t)iy * W + ix] : 0.f;
+      const float* wr = sw + (ci * 9 + t) * COUT;
+#pragma unroll
+      for (int o = 0; o < COUT; ++o) acc[o] += v * wr[o];
+    }
+  }
+  bf16* op = out + ((size_t)n * H * W + pix) * COUT;
+#pragma unroll
+  for (int o8 = 0; o8 < COUT; o8 += 8) {
+    bf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (bf16)silu_f(acc[o8 + e]);
+    nr_store16(op + o8, v);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// small-channel 3x3 conv, pad 1, stride S: out[p][co] = act(bias[co] + sum_k W[co][k] * im2col(x)[p][k]), k = tap * CIN + c.
+// Transposed MFMA as in gemm.hip (weights = A operand, pixels = B operand): lane (fr = l & 15, g = l >> 4) holds output channels
+// 16 T + 4 g .. + 3 of pixel 16 j + fr, stored as one 8-byte vector.  Block = 4 waves x 32 pixels; grid (ceil(M / 128), Cout / (16 NT)).
+// ---------------------------------------------------------------------------------------------
+template <int CIN, int S, int NT>
+__global__ __launch_bounds__(256) void condembed_conv_kernel(const bf16* __restrict__ x, int H, int W, int OH, int OW, int M,
+                                                             const bf16* __restrict__ wfm, const float* __restrict__ bias, int Cout,
+                                                             int silu, bf16* __restrict__ out) {
+  constexpr int K = 9 * CIN;
+  constexpr int KS = (K + 31) / 32;
+  constexpr int MT = 2;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int fr = lane & 15, g = lane >> 4;
+  const int p0 = (blockIdx.x * 4 + wave) * (16 * MT);
+  const int T0 = blockIdx.y * NT;
+  if (p0 >= M) return;
+  // per lane: the pixel of its B-fragment column in each of the MT pixel tiles
+  int pn[MT], py[MT], px[MT];
+  bool pv[MT];
+#pragma unroll
+  for (int j = 0; j < MT; ++j) {
+    const int p = p0 + 16 * j + fr;
+    pv[j] = p < M;
+    const int pp = pv[j] ? p : 0;
+    const int n = pp / (OH * OW), r = pp - n * OH * OW;
+    const int oy = r / OW, ox = r - oy * OW;
+    pn[j] = n; py[j] = oy * S - 1; px[j] = ox * S - 1;
+  }
+  f32x4 acc[NT][MT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const i16x8* wl = (const i16x8*)wfm + (size_t)T0 * KS * 64 + lane;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int k0 = 32 * ks + 8 * g;
+    const int tap = k0 / CIN, c = k0 - tap * CIN;
+    const int ky = tap / 3, kx = tap - ky * 3;
+    i16x8 bfr[MT];
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+      const int iy = py[j] + ky, ix = px[j] + kx;
+      const bool ok = pv[j] && k0 < K && iy >= 0 && iy < H && ix >= 0 && ix < W;
+      bfr[j] = ok ? *(const i16x8*)(x + (((size_t)pn[j] * H + iy) * W + ix) * CIN + c) : i16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      const i16x8 a = wl[((size_t)i * KS + ks) * 64];
+#pragma unroll
+      for (int j = 0; j < MT; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bfr[j]), acc[i][j], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int co = (T0 + i) * 16 + 4 * g;
+    const f32x4 bv = *(const f32x4*)(bias + co);
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+      if (!pv[j]) continue;
+      f32x4 v = acc[i][j] + bv;
+      bf16x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = (bf16)(silu ? silu_f(v[e]) : v[e]);
+      nr_store8(out + (size_t)(p0 + 16 * j + fr) * Cout + co, o);
+    }
+  }
+}
+
+// x[n = b * F + f] = emb[(b % cb) * Fe + emap[f]] (+ add[n]), img8 = 16-byte words per image
+__global__ __launch_bounds__(256) void condembed_bcast_kernel(const bf16x8* __restrict__ emb, int cb, int Fe, CeFrameMap emap, int F,
+                                                              long long img8, const bf16x8* __restrict__ add, bf16x8* __restrict__ out,
+                                                              long long total8) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total8) return;
+  const long long n = i / img8, r = i - n * img8;
+  const int b = (int)(n / F), f = (int)(n - (long long)b * F);
+  bf16x8 v = emb[((long long)(b % cb) * Fe + emap.f[f]) * img8 + r];
+  if (add) {
+    const bf16x8 a = add[i];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (bf16)((float)v[e] + (float)a[e]);
+  }
+  out[i] = v;
+}
+
+template <int CIN, int S>
+int launch_conv(int NT, dim3 grid, hipStream_t s, const bf16* x, int H, int W, int OH, int OW, int M, const bf16* w, const float* b,
+                int Cout, int silu, bf16* out) {
+  if (NT == 1) hipLaunchKernelGGL((condembed_conv_kernel<CIN, S, 1>), grid, dim3(256), 0, s, x, H, W, OH, OW, M, w, b, Cout, silu, out);
+  else if (NT == 2) hipLaunchKernelGGL((condembed_conv_kernel<CIN, S, 2>), grid, dim3(256), 0, s, x, H, W, OH, OW, M, w, b, Cout, silu, out);
+  else return 3;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nr_condembed_in_supported(int cin, int Cout) { return cin >= 1 && cin <= 8 && (Cout == 16 || Cout == 32); }
+
+// nsrc condition images x Fe frames (frames fmap[0..Fe) of the F-frame condition) -> [nsrc * Fe][H][W][Cout] bf16
+int nr_launch_condembed_in(const float* cond, const float* mask, int c0, int nsrc, int F, int H, int W, const int* fmap, int Fe,
+                           const float* wT, const float* bias, int Cout, bf16* out, hipStream_t s) {
+  if (!nr_condembed_in_supported(c0 + 1, Cout) || Fe < 1 || Fe > CE_MAX_FRAMES || nsrc < 1) return 1;
+  CeFrameMap m;
+  for (int e = 0; e < Fe; ++e) {
+    if (fmap[e] < 0 || fmap[e] >= F) return 2;
+    m.f[e] = fmap[e];
+  }
+  const dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)(nsrc * Fe));
+  if (Cout == 16) hipLaunchKernelGGL(condembed_in_kernel<16>, grid, dim3(256), 0, s, cond, mask, c0, F, H, W, m, Fe, wT, bias, out);
+  else hipLaunchKernelGGL(condembed_in_kernel<32>, grid, dim3(256), 0, s, cond, mask, c0, F, H, W, m, Fe, wT, bias, out);
+  return 0;
+}
+
+int nr_condembed_conv_supported(int Cin, int stride, int Cout) {
+  const bool cin_ok = Cin == 16 || Cin == 32 || Cin == 64 || Cin == 96 || Cin == 128 || Cin == 256;
+  return cin_ok && (stride == 1 || stride == 2) && Cout % 16 == 0 && Cout > 0;
+}
+
+// bf16 elements of the fragment-major weight [Cout/16][ceil(9 Cin / 32)][64][8]
+long long nr_condembed_wfm_elems(int Cin, int Cout) { return (long long)Cout * ((9 * Cin + 31) / 32) * 32; }
+
+int nr_launch_condembed_conv(const bf16* x, int nimg, int H, int W, int Cin, int stride, const bf16* wfm, const float* bias, int Cout,
+                             int silu, bf16* out, hipStream_t s) {
+  if (!nr_condembed_conv_supported(Cin, stride, Cout) || nimg < 1) return 1;
+  const int OH = stride == 2 ? (H - 1) / 2 + 1 : H, OW = stride == 2 ? (W - 1) / 2 + 1 : W;
+  const long long M = (long long)nimg * OH * OW;
+  if (M >= (1ll << 31) / 256) return 2;     // pixel * Cout (Cout <= 256) stays below 2^31
+  const int NT = Cout % 32 == 0 ? 2 : 1;
+  const dim3 grid((unsigned)((M + 127) / 128), (unsigned)(Cout / (16 * NT)));
+  const int m = (int)M;
+#define CE_CASE(C)                                                                                                  \
+  if (Cin == C)                                                                                                     \
+    return stride == 1 ? launch_conv<C, 1>(NT, grid, s, x, H, W, OH, OW, m, wfm, bias, Cout, silu, out)            \
+                       : launch_conv<C, 2>(NT, grid, s, x, H, W, OH, OW, m, wfm, bias, Cout, silu, out);
+  CE_CASE(16) CE_CASE(32) CE_CASE(64) CE_CASE(96) CE_CASE(128) CE_CASE(256)
+#undef CE_CASE
+  return 1;
+}
+
+int nr_launch_condembed_bcast(const bf16* emb, int cb, int Fe, const int* emap, int B, int F, long long img_elems, const bf16* add,
+                              bf16* out, hipStream_t s) {
+  if (img_elems % 8 != 0 || cb < 1 || B % cb != 0 || F > CE_MAX_FRAMES) return 1;
+  CeFrameMap m;
+  for (int f = 0; f < F; ++f) {
+    if (emap[f] < 0 || emap[f] >= Fe) return 2;
+    m.f[f] = emap[f];
+  }
+  const long long img8 = img_elems / 8, total8 = (long long)B * F * img8;
+  hipLaunchKernelGGL(condembed_bcast_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, s, (const bf16x8*)emb, cb, Fe, m, F,
+                     img8, (const bf16x8*)add, (bf16x8*)out, total8);
+  return 0;
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "../../include/neurons_amd.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -115,6 +116,16 @@ int nr_ff_fused_eligible(int C, long long M);
 int nr_launch_ff_stream_pack(const bf16* w1, const bf16* wc, bf16* stream, hipStream_t s);
 int nr_launch_ff_fused(const bf16* t, int ldt, const bf16* x, int ldx, bf16* out, int ldo, int M, const bf16* stream, const float* gamma,
                        const float* beta, const float* b1, const float* bc, float ln_eps, int norot, hipStream_t s);
+// elementwise.hip condembed_*: SparseCtrl image-condition embedding (first conv from the fp32 planes, small-channel MFMA convs, batch / frame broadcast)
+int nr_condembed_in_supported(int cin, int Cout);
+int nr_launch_condembed_in(const float* cond, const float* mask, int c0, int nsrc, int F, int H, int W, const int* fmap, int Fe,
+                           const float* wT, const float* bias, int Cout, bf16* out, hipStream_t s);
+int nr_condembed_conv_supported(int Cin, int stride, int Cout);
+long long nr_condembed_wfm_elems(int Cin, int Cout);
+int nr_launch_condembed_conv(const bf16* x, int nimg, int H, int W, int Cin, int stride, const bf16* wfm, const float* bias, int Cout,
+                             int silu, bf16* out, hipStream_t s);
+int nr_launch_condembed_bcast(const bf16* emb, int cb, int Fe, const int* emap, int B, int F, long long img_elems, const bf16* add,
+                              bf16* out, hipStream_t s);
 }
 
 namespace {
@@ -672,6 +683,40 @@ struct nr_net {
       for (int o = 0; o < Cout; ++o)
         for (int k = 0; k < Cin * 9; ++k) h[(size_t)k * Cout + o] = t.data[(size_t)o * Cin * 9 + k];
       return upload("convin:" + key, h.data(), h.size() * 4);
+    });
+  }
+  // 3x3 conv weight [Cout][Cin][3][3] -> the fragment-major bf16 layout of condembed_conv: [Cout/16][KS][64 lanes][8], KS = ceil(9 Cin / 32);
+  // lane (fr, g) of block (T, ks) holds W[16 T + fr][k], k = 32 ks + 8 g .. + 7 = tap * Cin + c (zero beyond K = 9 Cin)
+  const bf16* w_condembed(const std::string& key, int Cout, int Cin) {
+    const HostTensor& t = need(key);
+    check_shape(key, t, {Cout, Cin, 3, 3});
+    return (const bf16*)cached("cefm:" + key, [&]() {
+      (void)data_of(key);
+      const int K = 9 * Cin, KS = (K + 31) / 32;
+      std::vector<uint16_t> h((size_t)nr_condembed_wfm_elems(Cin, Cout), 0);
+      for (int T = 0; T < Cout / 16; ++T)
+        for (int ks = 0; ks < KS; ++ks)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int j = 0; j < 8; ++j) {
+              const int o = 16 * T + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + j;
+              if (k >= K) continue;
+              const int tap = k / Cin, c = k % Cin;
+              h[(((size_t)T * KS + ks) * 64 + lane) * 8 + j] = f2bf_host(t.data[((size_t)o * Cin + c) * 9 + tap]);
+            }
+      return upload("cefm:" + key, h.data(), h.size() * 2);
+    });
+  }
+  // elementwise sum of two fp32 vectors (the embedding's conv_out bias with conv_in.bias folded in)
+  const float* w_f32_sum(const std::string& a, const std::string& b, int64_t n) {
+    check_shape(a, need(a), {n});
+    check_shape(b, need(b), {n});
+    const std::string name = "f32sum:" + a + "|" + b;
+    return (const float*)cached(name, [&]() {
+      const HostTensor& ta = data_of(a);
+      const HostTensor& tb = data_of(b);
+      std::vector<float> h((size_t)n);
+      for (int64_t i = 0; i < n; ++i) h[i] = ta.data[i] + tb.data[i];
+      return upload(name, h.data(), h.size() * 4);
     });
   }
   const float* w_f32(const std::string& key, int64_t n) {
@@ -1812,6 +1857,100 @@ struct nr_net {
     res_shapes.clear();
   }
 
+  // ---- SparseCtrl image-condition variant: SparseControlNetConditioningEmbedding (sparse_controlnet.py:49-82) added to conv_in (:513-521) ----
+  // x[b][f] = emb(cat[cond, mask])[b % cond_batch][f] + conv_in.bias (+ conv_in(sample) when the noisy sample is not zeroed).  The embedding
+  // depends on the condition and mask only: it runs once per condition image (cond_batch of them, read from io at launch; the buffers are
+  // sized for cond_batch = B2), never per CFG / grouped sample, and with the identical-frame evaluation active (nd > 0) only on the distinct
+  // frames (a zero condition with a zero mask embeds to the same constant on every other frame), then is broadcast into x.
+  Act embed_conv(const Act& in, int Fe, const std::string& key, int Cout, int stride, int silu, const float* bias) {
+    const int Cin = in.C, Hi = in.H, Wi = in.W;
+    const int OH = stride == 2 ? (Hi - 1) / 2 + 1 : Hi, OW = stride == 2 ? (Wi - 1) / 2 + 1 : Wi;
+    Act o = new_act(in.nimg, OH, OW, Cout);
+    const bf16* w = w_condembed(key + ".weight", Cout, Cin);
+    const float* b = bias ? bias : w_f32(key + ".bias", Cout);
+    const bf16* ip = in.ptr; bf16* op = o.ptr;
+    char d[160];
+    snprintf(d, sizeof(d), "condembed_conv Cin=%d Cout=%d s=%d H=%d W=%d frames=%d", Cin, Cout, stride, OH, OW, Fe);
+    emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_condembed_conv(ip, io.cond_batch * Fe, Hi, Wi, Cin, stride, w, b, Cout, silu, op, s)); },
+         NR_PROF_IGEMM, 2.0 * Fe * OH * OW * Cout * 9.0 * Cin, 2.0 * Fe * ((double)Hi * Wi * Cin + (double)OH * OW * Cout) + 2.0 * Cout * 9.0 * Cin, d);
+    return o;
+  }
+  void cond_embedding(Act& x, int nd, const int* fmap_reduce, const int* fmap_expand) {
+    const int L = cfg.cond_embedding_levels, C0 = cfg.block_out_channels[0], cc = cfg.conditioning_channels;
+    const int* ch = cfg.cond_embedding_channels;
+    const int Hc = H << (L - 1), Wc = W << (L - 1), Fn = F, Hn = H, Wn = W;
+    const int Fe = nd > 0 ? nd : F;
+    std::vector<int> fsel(Fe), emap(F);
+    for (int e = 0; e < Fe; ++e) fsel[e] = nd > 0 ? fmap_reduce[e] : e;
+    for (int f = 0; f < F; ++f) emap[f] = nd > 0 ? fmap_expand[f] : f;
+    const std::string pre = "controlnet_cond_embedding.";
+    // flops / bytes of the op descriptions are per condition image
+    Act e = new_act(B2 * Fe, Hc, Wc, ch[0]);
+    {
+      const float* w = w_conv_in(pre + "conv_in.weight", ch[0], cc + 1);
+      const float* b = w_f32(pre + "conv_in.bias", ch[0]);
+      bf16* op = e.ptr; const int C = ch[0];
+      char d[160];
+      snprintf(d, sizeof(d), "condembed_in Cin=%d Cout=%d H=%d W=%d frames=%d", cc + 1, C, Hc, Wc, Fe);
+      emit([=, this](hipStream_t s) {
+        LAUNCH_OK(nr_launch_condembed_in(io.cond, io.mask, cc, io.cond_batch, Fn, Hc, Wc, fsel.data(), Fe, w, b, C, op, s));
+      }, NR_PROF_OTHER, 2.0 * Fe * Hc * Wc * C * 9.0 * (cc + 1), 4.0 * Fe * Hc * Wc * (cc + 1) + 2.0 * Fe * Hc * Wc * C, d);
+    }
+    for (int i = 0; i + 1 < L; ++i) {
+      e = embed_conv(e, Fe, pre + "blocks." + std::to_string(2 * i), ch[i], 1, 1, nullptr);
+      e = embed_conv(e, Fe, pre + "blocks." + std::to_string(2 * i + 1), ch[i + 1], 2, 1, nullptr);
+    }
+    if (e.H != H || e.W != W) throw NrError(NR_ERR_STATE, "condition embedding: output size differs from the latent size");
+    const bool zero_sample = cfg.set_noisy_sample_input_to_zero;
+    const std::string bo_key = pre + "conv_out.bias";
+    const float* bo = zero_sample ? w_f32_sum(bo_key, "conv_in.bias", C0) : w_f32(bo_key, C0);    // conv_in(0) = conv_in.bias folded in
+    const int cl = ch[L - 1];
+    Act eo;
+    if (cl % 64 == 0) {
+      // conv_out (Cin = 256 at the latent grid) on the implicit-GEMM conv kernel; M follows the condition batch at launch
+      eo = new_act(B2 * Fe, H, W, C0);
+      NrGemmParams p;
+      std::memset(&p, 0, sizeof(p));
+      p.a0 = e.ptr; p.c0 = cl; p.lda0 = cl; p.H = H; p.W = W; p.OH = H; p.OW = W; p.ksize = 3; p.stride = 1;
+      p.w = w_conv3(pre + "conv_out.weight", C0, cl); p.N = C0; p.K = 9 * cl; p.bias = bo; p.out = eo.ptr; p.ldo = C0; p.out_scale = 1.f;
+      size_t wsb = 0;                                  // split-K scratch for the largest need of any cond_batch dividing B2
+      for (int cb = 1; cb <= B2; ++cb)
+        if (B2 % cb == 0) { p.M = cb * Fe * H * W; wsb = std::max(wsb, nr_igemm_workspace_bytes(&p)); }
+      float* ws = nullptr;
+      std::shared_ptr<Buf> wsbuf;
+      if (wsb) { wsbuf = new_tmp(wsb); ws = at<float>(wsbuf->off); }
+      p.M = Fe * H * W;
+      char d[160];
+      snprintf(d, sizeof(d), "igemm ks=3 s=1 ups=0 M=%d N=%d K=%d condembed conv_out frames=%d", p.M, p.N, p.K, Fe);
+      const int hw = H * W;
+      emit([this, p, ws, Fe, hw](hipStream_t s) {
+        NrGemmParams q = p;
+        q.M = io.cond_batch * Fe * hw;
+        LAUNCH_OK(nr_launch_igemm(&q, ws, s));
+      }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, 2.0 * ((double)p.M * cl + (double)p.N * p.K + (double)p.M * C0), d);
+    } else {
+      eo = embed_conv(e, Fe, pre + "conv_out", C0, 1, 0, bo);
+    }
+    e = Act();
+    const long long img = (long long)H * W * C0;
+    bf16* xp = x.ptr; const bf16* ep = eo.ptr; const int b2n = B2;
+    const std::string d = "condembed_bcast frames=" + std::to_string(Fe) + " -> " + std::to_string(F);
+    if (zero_sample) {
+      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_condembed_bcast(ep, io.cond_batch, Fe, emap.data(), b2n, Fn, img, nullptr, xp, s)); },
+           NR_PROF_OTHER, 0.0, 4.0 * B2 * F * img, d);
+    } else {
+      const float* wT = w_conv_in("conv_in.weight", C0, cfg.in_channels);
+      const float* bi = w_f32("conv_in.bias", C0);
+      Act x2 = new_act(B2 * F, H, W, C0);
+      bf16* x2p = x2.ptr; const int ic = cfg.in_channels, nimg = B2 * F;
+      emit([=, this](hipStream_t s) {
+        LAUNCH_OK(nr_launch_conv_in_small(io.sample, nullptr, ic, 0, b2n, nimg, Fn, Hn, Wn, wT, bi, nullptr, C0, x2p, 1.f, 0.f, s));
+        LAUNCH_OK(nr_launch_condembed_bcast(ep, io.cond_batch, Fe, emap.data(), b2n, Fn, img, x2p, xp, s));
+      }, NR_PROF_OTHER, 2.0 * nimg * H * W * C0 * 9.0 * ic, 6.0 * B2 * F * img, d);
+      last_op_launches(2);
+    }
+  }
+
   void build() {
     if (cfg.kind == NR_KIND_LEAF_TRANSFORMER3D || cfg.kind == NR_KIND_LEAF_TEMPORAL) { build_leaf(); return; }
     if (cfg.kind == NR_KIND_CLIP_TEXT) { build_clip(); return; }
@@ -1883,6 +2022,27 @@ struct nr_net {
       ctx_persist.push_back(ctx_bf);
     }
 
+    // SparseCtrl identical-frame evaluation (see n_cond_frames): distinct frames = the conditioned ones + one representative of the rest
+    int nd = 0, fmap_reduce[64], fmap_expand[64];
+    if (cfg.kind == NR_KIND_SPARSECTRL && cfg.set_noisy_sample_input_to_zero && cfg.use_motion_module && n_cond_frames >= 0 && !keep_all && F <= 64) {
+      int rep = -1;
+      for (int f = 0; f < F && rep < 0; ++f) {
+        bool is_c = false;
+        for (int k = 0; k < n_cond_frames; ++k) is_c = is_c || cond_frames[k] == f;
+        if (!is_c) rep = f;
+      }
+      int nc = 0;
+      for (int k = 0; k < n_cond_frames; ++k) if (cond_frames[k] < F) fmap_reduce[nc++] = cond_frames[k];
+      if (rep >= 0 && nc + 1 < F) {
+        fmap_reduce[nc] = rep;
+        nd = nc + 1;
+        for (int f = 0; f < F; ++f) {
+          fmap_expand[f] = nc;
+          for (int k = 0; k < nc; ++k) if (fmap_reduce[k] == f) fmap_expand[f] = k;
+        }
+      }
+    }
+
     // ---- conv_in ----
     const bool cfg_half = cfg_dedup_active();      // conv_in .. attn1 of the first transformer on the first half of the batch only
     Act x = new_act(cfg_half ? nimg / 2 : nimg, H, W, C0);
@@ -1893,6 +2053,8 @@ struct nr_net {
       emit([=, this](hipStream_t s) {
         LAUNCH_OK(nr_launch_conv_in_small(io.sample, nullptr, ic, 0, b2n, ni, Fn, Hn, Wn, wT, bi, nullptr, C0, xp, 1.f, 0.f, s));
       });
+    } else if (cfg.cond_embedding_levels > 0) {
+      cond_embedding(x, nd, fmap_reduce, fmap_expand);
     } else {
       // sparse_controlnet.py:467-521: sample := 0 -> conv_in(0) = bias; + cond_embedding(cat[cond, mask])
       const int cc = cfg.conditioning_channels;
@@ -1921,26 +2083,6 @@ struct nr_net {
     // ---- down blocks ----
     std::vector<Act> skips;
     skips.push_back(cfg_half ? expand_cfg(x) : x);          // skip connections are full-batch (the ControlNet residuals added to them differ per half)
-    // SparseCtrl identical-frame evaluation (see n_cond_frames): distinct frames = the conditioned ones + one representative of the rest
-    int nd = 0, fmap_reduce[64], fmap_expand[64];
-    if (cfg.kind == NR_KIND_SPARSECTRL && cfg.set_noisy_sample_input_to_zero && cfg.use_motion_module && n_cond_frames >= 0 && !keep_all && F <= 64) {
-      int rep = -1;
-      for (int f = 0; f < F && rep < 0; ++f) {
-        bool is_c = false;
-        for (int k = 0; k < n_cond_frames; ++k) is_c = is_c || cond_frames[k] == f;
-        if (!is_c) rep = f;
-      }
-      int nc = 0;
-      for (int k = 0; k < n_cond_frames; ++k) if (cond_frames[k] < F) fmap_reduce[nc++] = cond_frames[k];
-      if (rep >= 0 && nc + 1 < F) {
-        fmap_reduce[nc] = rep;
-        nd = nc + 1;
-        for (int f = 0; f < F; ++f) {
-          fmap_expand[f] = nc;
-          for (int k = 0; k < nc; ++k) if (fmap_reduce[k] == f) fmap_expand[f] = k;
-        }
-      }
-    }
     for (int i = 0; i < L; ++i) {
       const int Cout = cfg.block_out_channels[i];
       const std::string bp = "down_blocks." + std::to_string(i);
@@ -2314,6 +2456,16 @@ extern "C" nr_status nr_net_create(const nr_net_config* cfg, nr_net** out) {
   }
   if (!vae && cfg->cross_attention_dim % 64 != 0) throw NrError(NR_ERR_UNSUPPORTED, "cross_attention_dim must be a multiple of 64");
   if (cfg->norm_num_groups > 64) throw NrError(NR_ERR_UNSUPPORTED, "norm_num_groups > 64");
+  if (cfg->kind == NR_KIND_SPARSECTRL && cfg->cond_embedding_levels != 0) {
+    const int L = cfg->cond_embedding_levels;
+    const int* ch = cfg->cond_embedding_channels;
+    bool ok = L >= 1 && L <= NR_MAX_LEVELS && nr_condembed_in_supported(cfg->conditioning_channels + 1, ch[0]);
+    for (int i = 0; ok && i + 1 < L; ++i) ok = nr_condembed_conv_supported(ch[i], 1, ch[i]) && nr_condembed_conv_supported(ch[i], 2, ch[i + 1]);
+    if (ok && ch[L - 1] % 64 != 0) ok = nr_condembed_conv_supported(ch[L - 1], 1, cfg->block_out_channels[0]);
+    if (!ok)
+      throw NrError(NR_ERR_UNSUPPORTED, "SparseCtrl condition embedding: 1..4 levels, conditioning_channels + 1 <= 8, first level 16 or 32 "
+                                        "channels, the others 16 / 32 / 64 / 96 / 128 / 256");
+  }
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) throw NrError(NR_ERR_HIP, "no HIP device available: libneurons_amd requires an MI355X (gfx950) GPU");
   nr_net* h = new nr_net();
@@ -3124,6 +3276,23 @@ extern "C" nr_status nr_op_conv3x3(nr_stream stream, const void* x0, int32_t c0,
   p.bias = bias; p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
   p.res = (const bf16*)res; p.ldr = Cout; p.out = (bf16*)out; p.ldo = Cout; p.out_scale = 1.f;
   LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_condembed_in(nr_stream stream, const float* cond, const float* mask, int32_t c0, int32_t nsrc, int32_t F, int32_t H,
+                                        int32_t W, const int32_t* fmap, int32_t nframes, const float* w, const float* bias, int32_t Cout,
+                                        void* out) {
+  NR_TRY
+  if (!fmap) throw NrError(NR_ERR_ARG, "fmap is null");
+  LAUNCH_OK(nr_launch_condembed_in(cond, mask, c0, nsrc, F, H, W, fmap, nframes, w, bias, Cout, (bf16*)out, (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_condembed_conv(nr_stream stream, const void* x, int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t stride,
+                                          const void* wfm, const float* bias, int32_t Cout, int32_t silu, void* out) {
+  NR_TRY
+  LAUNCH_OK(nr_launch_condembed_conv((const bf16*)x, nimg, H, W, Cin, stride, (const bf16*)wfm, bias, Cout, silu, (bf16*)out,
+                                     (hipStream_t)stream));
   NR_CATCH
 }
 

@@ -157,6 +157,48 @@ def conv3x3(x0, w, bias=None, x1=None, stride=1, ups=False, rowvec=None, rowvec_
     return out
 
 
+def condembed_pack(w):
+    """3x3 conv weight [Cout, Cin, 3, 3] -> the fragment-major bf16 layout of condembed_conv: [Cout/16][KS][64][8], KS = ceil(9 Cin / 32),
+    lane (fr, g) of block (T, ks) holding W[16 T + fr][32 ks + 8 g .. + 7], K index = tap * Cin + c, zero-padded beyond 9 Cin."""
+    Cout, Cin = w.shape[:2]
+    K = 9 * Cin
+    KS = (K + 31) // 32
+    wk = torch.zeros(Cout, KS * 32, dtype=torch.float32, device=w.device)
+    wk[:, :K] = w.float().permute(0, 2, 3, 1).reshape(Cout, K)
+    return wk.reshape(Cout // 16, 16, KS, 4, 8).permute(0, 2, 3, 1, 4).contiguous().to(torch.bfloat16)
+
+
+def condembed_conv(x, w, bias, stride=1, silu=True):
+    """SparseCtrl image-condition embedding conv (condembed_conv in elementwise.hip): x [nimg, H, W, Cin] bf16, w [Cout, Cin, 3, 3], bias fp32 [Cout];
+    3x3 pad 1, stride 1 / 2, optional SiLU -> [nimg, OH, OW, Cout] bf16."""
+    _chk_bf16(x)
+    _chk_f32(bias)
+    nimg, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    OH, OW = ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if stride == 2 else (H, W)
+    wfm = condembed_pack(w)
+    out = torch.empty(nimg, OH, OW, Cout, dtype=torch.bfloat16, device=x.device)
+    _lib.check(_lib.load().nr_op_condembed_conv(_stream(), _ptr(x), nimg, H, W, Cin, stride, _ptr(wfm), _ptr(bias), Cout, 1 if silu else 0,
+                                                _ptr(out)))
+    return out
+
+
+def condembed_in(cond, mask, w, bias, frames=None):
+    """First conv + SiLU of the embedding from fp32 planes: cond [b, c0, F, H, W], mask [b, 1, F, H, W], w [Cout, c0 + 1, 3, 3] ->
+    [b * len(frames), H, W, Cout] bf16 (frames: the frame indices embedded, default all)."""
+    import ctypes as C
+    _chk_f32(cond, mask, bias)
+    b, c0, F, H, W = cond.shape
+    Cout = w.shape[0]
+    frames = list(range(F)) if frames is None else [int(f) for f in frames]
+    wT = w.float().reshape(Cout, -1).t().contiguous()
+    fm = (C.c_int32 * len(frames))(*frames)
+    out = torch.empty(b * len(frames), H, W, Cout, dtype=torch.bfloat16, device=cond.device)
+    _lib.check(_lib.load().nr_op_condembed_in(_stream(), _ptr(cond), _ptr(mask), c0, b, F, H, W, fm, len(frames), _ptr(wT), _ptr(bias), Cout,
+                                              _ptr(out)))
+    return out
+
+
 def groupnorm(x0, gamma, beta, groups=32, eps=1e-5, silu=False, x1=None):
     _chk_bf16(x0, x1)
     _chk_f32(gamma, beta)

@@ -13,7 +13,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .unet3d import _on_device, UNet3DConfig, _NativeNet, tensor_version
+from .unet3d import _on_device, UNet3DConfig, _NativeNet, condition_upscale, tensor_version
 
 
 @dataclass
@@ -24,7 +24,7 @@ class SparseControlNetOutput:
 
 def controlnet_config_from_unet(unet_config: UNet3DConfig, controlnet_additional_kwargs: Optional[dict] = None) -> UNet3DConfig:
     """``SparseControlNetModel.from_unet`` (sparse_controlnet.py:316-345): copies the U-Net geometry, then applies
-    ``controlnet_additional_kwargs`` (configs/inference/sparsectrl/latent_condition.yaml)."""
+    ``controlnet_additional_kwargs`` (configs/inference/sparsectrl/latent_condition.yaml or image_condition.yaml)."""
     kw = dict(controlnet_additional_kwargs or {})
     mm = dict(num_attention_heads=8, num_transformer_block=1, attention_block_types=("Temporal_Self",),
               temporal_position_encoding=True, temporal_position_encoding_max_len=32, temporal_attention_dim_div=1)
@@ -38,7 +38,8 @@ def controlnet_config_from_unet(unet_config: UNet3DConfig, controlnet_additional
                   conditioning_channels=kw.pop("conditioning_channels", 3),
                   set_noisy_sample_input_to_zero=kw.pop("set_noisy_sample_input_to_zero", False),
                   use_simplified_condition_embedding=kw.pop("use_simplified_condition_embedding", False),
-                  concate_conditioning_mask=kw.pop("concate_conditioning_mask", True))
+                  concate_conditioning_mask=kw.pop("concate_conditioning_mask", True),
+                  conditioning_embedding_out_channels=tuple(kw.pop("conditioning_embedding_out_channels", (16, 32, 96, 256))))
     if kw:
         raise TypeError(f"unexpected controlnet kwargs: {sorted(kw)}")
     return cfg
@@ -96,6 +97,31 @@ class NativeSparseCtrl(_NativeNet):
             self._cframes = frames
             self._plan_key = None           # the launch plan depends on the frame list
 
+    def _check_condition(self, controlnet_cond, conditioning_mask, f, h, w):
+        """The condition and mask are (cb, c, f, h, w) at the latent size (latent-condition variant) or at 2^(levels-1) x it (image-condition
+        variant: RGB pixels, no VAE encode, neuroclips_video.py:278-283)."""
+        if controlnet_cond.dim() != 5 or conditioning_mask.dim() != 5:
+            raise ValueError("controlnet_cond / conditioning_mask must be (b, c, f, h, w)")
+        up = condition_upscale(self.config)
+        want = (f, h * up, w * up)
+        if controlnet_cond.shape[1] != self.config.conditioning_channels or tuple(controlnet_cond.shape[2:]) != want:
+            raise ValueError(f"controlnet_cond shape {tuple(controlnet_cond.shape)} does not match the latent (f, h, w) = {(f, h, w)}: expected "
+                             f"(b, {self.config.conditioning_channels}, {want[0]}, {want[1]}, {want[2]})"
+                             + (f" (the image-condition embedding takes the condition at {up}x the latent resolution)" if up > 1 else ""))
+        if conditioning_mask.shape[1] != 1 or tuple(conditioning_mask.shape[2:]) != want:
+            raise ValueError(f"conditioning_mask shape {tuple(conditioning_mask.shape)} does not match the condition: expected (b, 1, "
+                             f"{want[0]}, {want[1]}, {want[2]})")
+
+    def _stage_buffers(self, cb, f, h, w, device):
+        """Fixed staging buffers of the condition and mask (stable pointers for the captured graphs); True when (re)allocated."""
+        up = condition_upscale(self.config)
+        shape = (cb, self.config.conditioning_channels, f, h * up, w * up)
+        if self._io_cond is not None and tuple(self._io_cond.shape) == shape:
+            return False
+        self._io_cond = torch.empty(shape, dtype=torch.float32, device=device)
+        self._io_mask = torch.empty(cb, 1, f, h * up, w * up, dtype=torch.float32, device=device)
+        return True
+
     def invalidate_condition_frames(self):
         """Forget the cached scan (after an out-of-band write into a condition tensor that is passed again)."""
         self._cframes_key = None
@@ -140,19 +166,14 @@ class NativeSparseCtrl(_NativeNet):
         if ctx.shape[0] != b:     # sparse_controlnet.py:491
             ctx = ctx.repeat(b // ctx.shape[0], 1, 1)
         cb = controlnet_cond.shape[0]
-        if controlnet_cond.dim() != 5 or conditioning_mask.dim() != 5:
-            raise ValueError("controlnet_cond / conditioning_mask must be (b, c, f, h, w)")
-        if controlnet_cond.shape[1] != self.config.conditioning_channels or tuple(controlnet_cond.shape[2:]) != (f, h, w):
-            raise ValueError(f"controlnet_cond shape {tuple(controlnet_cond.shape)} does not match sample {tuple(sample.shape)}")
+        self._check_condition(controlnet_cond, conditioning_mask, f, h, w)
         if b % cb != 0 or conditioning_mask.shape[0] != cb:
             raise ValueError("controlnet_cond batch must divide the sample batch (it is broadcast over the CFG halves)")
         self._sync_condition_frames(controlnet_cond, conditioning_mask)
         self._ensure_plan(b, f, h, w, ctx.shape[1])
         lib = _lib.load()
         self._set_context(ctx)
-        if self._io_cond is None or self._io_cond.shape[0] != cb:
-            self._io_cond = torch.empty(cb, self.config.conditioning_channels, f, h, w, dtype=torch.float32, device=sample.device)
-            self._io_mask = torch.empty(cb, 1, f, h, w, dtype=torch.float32, device=sample.device)
+        self._stage_buffers(cb, f, h, w, sample.device)
         self._cond_key = None       # the fused step (unet3d.forward_with_controlnet) must re-stage its condition
         self._io_cond.copy_(controlnet_cond)
         self._io_mask.copy_(conditioning_mask)
@@ -199,14 +220,17 @@ class NativeSparseCtrl(_NativeNet):
         ctx = encoder_hidden_states
         b = len(timesteps)
         cb, _, f, h, w = controlnet_cond.shape
+        up = condition_upscale(self.config)            # no latent here: its size follows from the condition's
+        if h % up or w % up:
+            raise ValueError(f"forward_async: condition {h}x{w} is not a multiple of the embedding's {up}x downscale")
+        h, w = h // up, w // up
         if ctx.shape[0] != b or b % cb != 0 or conditioning_mask.shape[0] != cb:
             raise ValueError("forward_async: context batch must equal len(timesteps); the condition batch must divide it")
+        self._check_condition(controlnet_cond, conditioning_mask, f, h, w)
         self._sync_condition_frames(controlnet_cond, conditioning_mask)
         self._ensure_plan(b, f, h, w, ctx.shape[1])
         self._set_context(ctx)
-        if self._io_cond is None or self._io_cond.shape[0] != cb:
-            self._io_cond = torch.empty(cb, self.config.conditioning_channels, f, h, w, dtype=torch.float32, device=ctx.device)
-            self._io_mask = torch.empty(cb, 1, f, h, w, dtype=torch.float32, device=ctx.device)
+        if self._stage_buffers(cb, f, h, w, ctx.device):
             self._cond_key = None
         ckey = (controlnet_cond.data_ptr(), tensor_version(controlnet_cond), conditioning_mask.data_ptr(), tensor_version(conditioning_mask),
                 tuple(controlnet_cond.shape), self._plan_key)

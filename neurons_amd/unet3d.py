@@ -44,6 +44,9 @@ class UNet3DConfig:
     set_noisy_sample_input_to_zero: bool = True
     use_simplified_condition_embedding: bool = True
     concate_conditioning_mask: bool = True
+    # image-condition variant (use_simplified_condition_embedding=False): SparseControlNetConditioningEmbedding widths
+    # (sparse_controlnet.py:52-56,186-190); the condition is then at 2^(len - 1) x the latent resolution
+    conditioning_embedding_out_channels: Tuple[int, ...] = (16, 32, 96, 256)
 
 
 @dataclass
@@ -76,8 +79,23 @@ def _check_supported(cfg: UNet3DConfig, kind: int):
             raise NotImplementedError("Temporal_Self attention blocks only")
         if not mm.get("temporal_position_encoding", False):
             raise NotImplementedError("temporal_position_encoding=True only")
-    if kind == _lib.NR_KIND_SPARSECTRL and not (cfg.use_simplified_condition_embedding and cfg.concate_conditioning_mask):
-        raise NotImplementedError("SparseCtrl latent-condition variant only (latent_condition.yaml:2-4)")
+    if kind == _lib.NR_KIND_SPARSECTRL:
+        if not cfg.concate_conditioning_mask:
+            raise NotImplementedError("SparseCtrl needs concate_conditioning_mask=True (latent_condition.yaml / image_condition.yaml)")
+        if not cfg.use_simplified_condition_embedding:
+            ch = tuple(cfg.conditioning_embedding_out_channels)
+            ok = 1 <= len(ch) <= _lib.NR_MAX_LEVELS and ch[0] in (16, 32) and cfg.conditioning_channels + 1 <= 8 and \
+                all(c in (16, 32, 64, 96, 128, 256) for c in ch)
+            if not ok:
+                raise NotImplementedError(f"SparseCtrl condition embedding {ch} with conditioning_channels={cfg.conditioning_channels}: "
+                                          "1-4 levels, the first 16 or 32 channels, the others 16/32/64/96/128/256, at most 7 condition channels")
+
+
+def condition_upscale(cfg: UNet3DConfig) -> int:
+    """Condition resolution over the latent resolution: 1 for the latent-condition variant, 2 per stride-2 embedding block otherwise."""
+    if cfg.use_simplified_condition_embedding:
+        return 1
+    return 2 ** (len(cfg.conditioning_embedding_out_channels) - 1)
 
 
 def make_c_config(cfg: UNet3DConfig, kind: int) -> _lib.NrNetConfig:
@@ -106,6 +124,11 @@ def make_c_config(cfg: UNet3DConfig, kind: int) -> _lib.NrNetConfig:
     c.motion_module_mid_block = 1 if cfg.motion_module_mid_block else 0
     c.conditioning_channels = cfg.conditioning_channels
     c.set_noisy_sample_input_to_zero = 1 if cfg.set_noisy_sample_input_to_zero else 0
+    if kind == _lib.NR_KIND_SPARSECTRL and not cfg.use_simplified_condition_embedding:
+        ch = tuple(cfg.conditioning_embedding_out_channels)
+        c.cond_embedding_levels = len(ch)
+        for i, v in enumerate(ch):
+            c.cond_embedding_channels[i] = v
     return c
 
 
@@ -188,8 +211,21 @@ def state_dict_schema(cfg: UNet3DConfig, kind: int = _lib.NR_KIND_UNET3D) -> dic
         k.update(_motion_keys("mid_block.motion_modules.0", cm, nmm))
     k.update(_resnet_keys("mid_block.resnets.1", cm, cm, temb))
     if kind == _lib.NR_KIND_SPARSECTRL:
-        k["controlnet_cond_embedding.weight"] = (boc[0], cfg.conditioning_channels + 1, 3, 3)
-        k["controlnet_cond_embedding.bias"] = (boc[0],)
+        if cfg.use_simplified_condition_embedding:
+            k["controlnet_cond_embedding.weight"] = (boc[0], cfg.conditioning_channels + 1, 3, 3)
+            k["controlnet_cond_embedding.bias"] = (boc[0],)
+        else:                                                   # SparseControlNetConditioningEmbedding (sparse_controlnet.py:49-70)
+            ch = list(cfg.conditioning_embedding_out_channels)
+            p = "controlnet_cond_embedding"
+            k[f"{p}.conv_in.weight"] = (ch[0], cfg.conditioning_channels + 1, 3, 3)
+            k[f"{p}.conv_in.bias"] = (ch[0],)
+            for i in range(len(ch) - 1):
+                k[f"{p}.blocks.{2 * i}.weight"] = (ch[i], ch[i], 3, 3)
+                k[f"{p}.blocks.{2 * i}.bias"] = (ch[i],)
+                k[f"{p}.blocks.{2 * i + 1}.weight"] = (ch[i + 1], ch[i], 3, 3)
+                k[f"{p}.blocks.{2 * i + 1}.bias"] = (ch[i + 1],)
+            k[f"{p}.conv_out.weight"] = (boc[0], ch[-1], 3, 3)
+            k[f"{p}.conv_out.bias"] = (boc[0],)
         chans = [boc[0]]
         for i in range(L):
             chans += [boc[i]] * cfg.layers_per_block
@@ -230,12 +266,21 @@ def random_state_dict(cfg: UNet3DConfig, kind: int = _lib.NR_KIND_UNET3D, seed: 
     Linear/conv weights ~ N(0, 1/fan_in); norm gains ~ 1 + 0.1 N(0,1); biases ~ 0.02 N(0,1).  The layers
     the reference zero-initialises (motion ``proj_out`` motion_module.py:74-75, ControlNet zero-convs
     sparse_controlnet.py:244-246,281-295) are random too unless ``zero_init_heads`` — otherwise the temporal
-    and control paths would be numerically invisible."""
+    and control paths would be numerically invisible.  Of the image-condition embedding only ``conv_out`` (weight and
+    bias) is zero-initialised, as the reference's ``zero_module`` (sparse_controlnet.py:66-68)."""
     from .synth import randn
+    image_embed = kind == _lib.NR_KIND_SPARSECTRL and not cfg.use_simplified_condition_embedding
     sd = {}
     for name, shape in state_dict_schema(cfg, kind).items():
         z = randn(name, shape, seed)
-        if name.endswith(".bias"):
+        if image_embed and name.startswith("controlnet_cond_embedding."):
+            if name.endswith(".bias"):
+                t = 0.02 * z
+            else:
+                t = z / (int(np.prod(shape[1:])) ** 0.5)
+            if zero_init_heads and name.startswith("controlnet_cond_embedding.conv_out."):
+                t = torch.zeros(shape)
+        elif name.endswith(".bias"):
             is_norm = ".norm" in name or "norms." in name or "conv_norm_out" in name or "ff_norm" in name
             t = (0.1 if is_norm else 0.02) * z
         elif len(shape) == 1:
@@ -697,6 +742,7 @@ class NativeUNet3D(_NativeNet):
         cb = controlnet_cond.shape[0]
         if b % cb != 0 or conditioning_mask.shape[0] != cb:
             raise ValueError("controlnet_cond batch must divide the sample batch")
+        controlnet._check_condition(controlnet_cond, conditioning_mask, f, h, w)
         L = ctx.shape[1]
         if controlnet.device.type == "cuda" and controlnet.device != self.device:
             raise RuntimeError(f"U-Net on {self.device} but SparseCtrl on {controlnet.device}")
@@ -708,9 +754,7 @@ class NativeUNet3D(_NativeNet):
         self._io_sample.copy_(sample)
         self._set_context(ctx)
         controlnet._set_context(ctx)
-        if controlnet._io_cond is None or controlnet._io_cond.shape[0] != cb:
-            controlnet._io_cond = torch.empty(cb, controlnet.config.conditioning_channels, f, h, w, dtype=torch.float32, device=sample.device)
-            controlnet._io_mask = torch.empty(cb, 1, f, h, w, dtype=torch.float32, device=sample.device)
+        controlnet._stage_buffers(cb, f, h, w, sample.device)
         # copy the (step-invariant) condition only when it changed: a prefetched SparseCtrl evaluation may be reading it
         ckey = (controlnet_cond.data_ptr(), tensor_version(controlnet_cond), conditioning_mask.data_ptr(), tensor_version(conditioning_mask),
                 tuple(controlnet_cond.shape), controlnet._plan_key)
