@@ -446,6 +446,11 @@ nr_status nr_op_tattn_fused_frames(nr_stream stream, void* t_dev, int32_t nbatch
  * C = 640 (hw a multiple of 8) or 1280 (hw a multiple of 4), 8 heads.  w_folded == NULL re-uses the weight stream packed by the previous call at this C. */
 nr_status nr_op_tattn_head(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t hw, int32_t C, const void* w_folded_dev,
                            const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps);
+/* The same for sequences of `frames` = 16 or 32 frames (32: BASELINE config 5; a pixel is two 16-row tiles, softmax over 32 keys):
+ * t, a [nbatch * frames * hw][C], rowvec fp32 [frames][3C].  w_folded == NULL re-uses what the previous call at this C packed, which must
+ * have had the same frame count (the epilogue table holds one row per frame). */
+nr_status nr_op_tattn_head_frames(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t frames, int32_t hw, int32_t C,
+                                  const void* w_folded_dev, const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps);
 
 /* The cross-attention of one BasicTransformerBlock ABOVE the C = 320 level up to (not including) to_out, one launch (xattnw.hip, round 6; engine:
  * spatial_transformer):  a = softmax(q K^T / sqrt(d)) V,  q = LayerNorm(t) Wq^T,  K | V = the context projections of the row's clip (attention.py:281-290,

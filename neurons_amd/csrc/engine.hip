@@ -103,13 +103,13 @@ int nr_launch_xattnw_table_pack(const float* lnc, const float* bias, int C, floa
 int nr_launch_xattnw_kv_pack(const bf16* kv, int ldkv, int Lk, int nctx, int C, bf16* kvs, hipStream_t s);
 int nr_launch_xattnw(const bf16* t, bf16* out, int nimg, int hw, int img_per_ctx, int nctx, int Lk, int C, const bf16* wstream, const bf16* kvstream,
                      const float* table, float ln_eps, hipStream_t s);
-// tattnw.hip: q|k|v projection of one head + F x F attention per (pixel group, head) above the C = 320 level (C = 640 / 1280, F = 16)
+// tattnw.hip: q|k|v projection of one head + F x F attention per (pixel group, head) above the C = 320 level (C = 640 / 1280, F = 16 / 32)
 size_t nr_tattnw_stream_bytes(int C);
 int nr_tattnw_eligible(int C, int heads, int frames, int hw, long long rows);
 int nr_launch_tattnw_stream_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s);
-size_t nr_tattnw_table_bytes(int C);
-int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, const float* rowvec, int C, float* table, hipStream_t s);
-int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s);
+size_t nr_tattnw_table_bytes(int C, int frames);
+int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, const float* rowvec, int C, int frames, float* table, hipStream_t s);
+int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int frames, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s);
 // ffpanel.hip: fused FeedForward(GEGLU) + proj_out of the C = 320 level
 size_t nr_ff_stream_bytes(int C);
 int nr_ff_fused_eligible(int C, long long M);
@@ -1356,7 +1356,7 @@ struct nr_net {
       }
       Act a;
       if (nr_tattnw_eligible(C, heads, F, x.H * x.W, det_rows(t.rows())) && t.ld == C) {
-        // C = 640 / 1280, F = 16: LayerNorm + PE (folded), the q|k|v projection of one head and its 16 x 16 attention per (pixel group, head) in
+        // C = 640 / 1280, F = 16 or 32: LayerNorm + PE (folded), the q|k|v projection of one head and its F x F attention per (pixel group, head) in
         // ONE launch (tattnw.hip); q|k|v never reach HBM.  to_out + residual stays the GEMM below.
         const std::string nrm = b + ".norms." + std::to_string(k);
         const std::vector<std::string> wk = {ab + ".to_q.weight", ab + ".to_k.weight", ab + ".to_v.weight"};
@@ -1376,14 +1376,15 @@ struct nr_net {
           if (!had) drop(lnw_name);
           return d;
         });
-        // the head-major epilogue table (LayerNorm-fold vectors + positional-encoding projections) the kernel stages through LDS
-        const std::string tname = "tawe:" + std::to_string(cfg.motion_pe_max_len) + ":" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
+        // the head-major epilogue table (LayerNorm-fold vectors + positional-encoding projections of the first F positions) the kernel stages
+        // through LDS: one per frame count a handle was planned with
+        const std::string tname = "tawe:" + std::to_string(cfg.motion_pe_max_len) + ":" + std::to_string(F) + ":" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
         const float* table = (const float*)cached(tname, [&]() {
           const LnW lw = w_ln_linear(wk, {}, nrm, C, C, false, false);
           void* d = nullptr;
-          const size_t nb = nr_tattnw_table_bytes(C);
+          const size_t nb = nr_tattnw_table_bytes(C, F);
           HIP_OK(hipMalloc(&d, nb));
-          LAUNCH_OK(nr_launch_tattnw_table_pack(lw.c, lw.b, rv, C, (float*)d, nullptr));
+          LAUNCH_OK(nr_launch_tattnw_table_pack(lw.c, lw.b, rv, C, F, (float*)d, nullptr));
           HIP_OK(hipDeviceSynchronize());
           dev[tname] = d; dev_bytes[tname] = nb; weight_bytes += nb;
           return d;
@@ -1394,7 +1395,8 @@ struct nr_net {
         const double M = (double)t.rows();
         char d[160];
         snprintf(d, sizeof(d), "tattn_head M=%d C=%d F=%d (LN+PE folded, q|k|v of one head, FxF attention)", (int)t.rows(), C, F);
-        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_tattnw(tp, ap, nb2, hw, C, stream, table, 1e-5f, s)); }, NR_PROF_IGEMM,
+        const int Fn = F;
+        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_tattnw(tp, ap, nb2, Fn, hw, C, stream, table, 1e-5f, s)); }, NR_PROF_IGEMM,
              2.0 * M * C * 3.0 * C + 4.0 * (M / F) * heads * (double)F * F * (C / heads), 2.0 * (2.0 * M * C + 3.0 * C * (double)C), d);
         op_tap("tattn_head", a);
       } else {
@@ -3460,28 +3462,37 @@ extern "C" nr_status nr_op_xattn_head(nr_stream stream, const void* t_dev, void*
                              ln_eps, (hipStream_t)stream));
   NR_CATCH
 }
-// ---- q|k|v projection of one head + 16 x 16 attention above the C = 320 level (tattnw.hip), op-level entry for tests.  t: bf16 [nbatch * 16 * hw][C]
-// (C = 640 or 1280); a: bf16, same shape (attention output before to_out); w_folded: bf16 [3C][C] = gamma-scaled rows of to_q | to_k | to_v;
-// lnc / bias fp32 [3C]; rowvec fp32 [16][3C] ----
-extern "C" nr_status nr_op_tattn_head(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t hw, int32_t C, const void* w_folded_dev,
-                                      const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
+// ---- q|k|v projection of one head + F x F attention above the C = 320 level (tattnw.hip), op-level entry for tests.  t: bf16 [nbatch * frames * hw][C]
+// (C = 640 or 1280, frames = 16 or 32); a: bf16, same shape (attention output before to_out); w_folded: bf16 [3C][C] = gamma-scaled rows of
+// to_q | to_k | to_v; lnc / bias fp32 [3C]; rowvec fp32 [frames][3C] ----
+extern "C" nr_status nr_op_tattn_head_frames(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t frames, int32_t hw, int32_t C,
+                                             const void* w_folded_dev, const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
   NR_TRY
   if (!t_dev || !a_dev || !lnc_dev || !bias_dev || !rowvec_dev) throw NrError(NR_ERR_ARG, "null argument");
-  if (!nr_tattnw_stream_bytes(C) || nbatch <= 0 || hw <= 0 || hw % (C == 640 ? 8 : 4) != 0)
-    throw NrError(NR_ERR_UNSUPPORTED, "temporal attention head kernel: C = 640 (hw % 8 == 0) or 1280 (hw % 4 == 0), 8 heads, 16 frames");
+  if (!nr_tattnw_stream_bytes(C) || (frames != 16 && frames != 32) || nbatch <= 0 || hw <= 0 || hw % (C == 640 ? 8 : 4) != 0)
+    throw NrError(NR_ERR_UNSUPPORTED, "temporal attention head kernel: C = 640 (hw % 8 == 0) or 1280 (hw % 4 == 0), 8 heads, 16 or 32 frames");
   static void* ws[2] = {nullptr, nullptr};
-  static void* tbl[2] = {nullptr, nullptr};
-  void*& w = ws[C == 640 ? 0 : 1];
-  void*& tb = tbl[C == 640 ? 0 : 1];
+  static void* tbl[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};     // [C][frames]: a table is packed for one frame count
+  static int ws_frames[2] = {0, 0};                                       // the frame count of the last packing call at this C
+  const int ci = C == 640 ? 0 : 1, fi = frames == 16 ? 0 : 1;
+  void*& w = ws[ci];
+  void*& tb = tbl[ci][fi];
   if (!w) HIP_OK(hipMalloc(&w, nr_tattnw_stream_bytes(C)));
-  if (!tb) HIP_OK(hipMalloc(&tb, nr_tattnw_table_bytes(C)));
-  // w_folded == NULL: reuse the stream and the epilogue table packed by the previous call at this C (timing loops)
+  if (!tb) HIP_OK(hipMalloc(&tb, nr_tattnw_table_bytes(C, frames)));
+  // w_folded == NULL: reuse the stream and the epilogue table packed by the previous call at this C (timing loops): same frame count only
   if (w_folded_dev) {
     LAUNCH_OK(nr_launch_tattnw_stream_pack((const bf16*)w_folded_dev, C, (bf16*)w, (hipStream_t)stream));
-    LAUNCH_OK(nr_launch_tattnw_table_pack(lnc_dev, bias_dev, rowvec_dev, C, (float*)tb, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_tattnw_table_pack(lnc_dev, bias_dev, rowvec_dev, C, frames, (float*)tb, (hipStream_t)stream));
+    ws_frames[ci] = frames;
+  } else if (ws_frames[ci] != frames) {
+    throw NrError(NR_ERR_ARG, "temporal attention head kernel: w_folded == NULL needs a previous call at this C and frame count");
   }
-  LAUNCH_OK(nr_launch_tattnw((const bf16*)t_dev, (bf16*)a_dev, nbatch, hw, C, (const bf16*)w, (const float*)tb, ln_eps, (hipStream_t)stream));
+  LAUNCH_OK(nr_launch_tattnw((const bf16*)t_dev, (bf16*)a_dev, nbatch, frames, hw, C, (const bf16*)w, (const float*)tb, ln_eps, (hipStream_t)stream));
   NR_CATCH
+}
+extern "C" nr_status nr_op_tattn_head(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t hw, int32_t C, const void* w_folded_dev,
+                                      const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
+  return nr_op_tattn_head_frames(stream, t_dev, a_dev, nbatch, 16, hw, C, w_folded_dev, lnc_dev, bias_dev, rowvec_dev, ln_eps);
 }
 extern "C" nr_status nr_op_tattn_fused(nr_stream stream, void* t_dev, int32_t nbatch, int32_t hw, const void* wq_dev, const void* wk_dev,
                                        const void* wv_dev, const void* wo_dev, const float* gamma_dev, const float* gb_dev, const float* bo_dev,

@@ -1,5 +1,5 @@
 // The q|k|v projection and the F x F attention of one temporal-attention block ABOVE the C = 320 level (C = 640: d = 80, C = 1280: d = 160;
-// 8 heads, F = 16 frames) in one launch, one workgroup per (pixel group, head):
+// 8 heads, F = 16 frames; F = 32: the last paragraph) in one launch, one workgroup per (pixel group, head):
 //
 //     a[:, head]  =  softmax( q k^T / sqrt(d) ) v ,   [q | k | v] = ( LayerNorm(t) + pe[frame] ) . [Wq | Wk | Wv][head rows]^T
 //
@@ -28,6 +28,13 @@
 // Workgroup -> (pixel group, head): at C = 640 the 8 heads of a pixel group run on ONE XCD (the 164-KB row panel is fetched into one L2, every XCD
 // streams all 2.4 MB of weights); at C = 1280 head h runs on XCD h (each L2 holds 1.2 MB of weights, the 5-MB activation is fetched by all).
 // Algorithmic work per launch at M = 8192 / C = 640 (= M = 2048 / C = 1280): 20.1 GFLOP GEMM + 0.17 GFLOP attention.
+//
+// F = 32 (BASELINE config 5; second template parameter): a pixel is TWO row tiles (frames 0-15 | 16-31).  The k-loop is the same loop on the same 64 rows
+// per workgroup -- only which rows a wave fetches changes: at d = 80 a wave's two row tiles are the two halves of ONE pixel (4 pixels per workgroup), at
+// d = 160 waves 2 i and 2 i + 1 hold the two halves of pixel i (2 pixels per workgroup) and swap their packed K and V^T tiles through two ring slots the
+// loop has left.  Per query tile: S^T = 2 tiles of 16 keys, softmax over the 32 keys, O^T = V^T P^T in ONE v_mfma_f32_16x16x32_bf16 per 16 channels (the
+// lane's four keys of each half, concatenated, are its eight k-slots of both operands).  The epilogue table has one 17-row part per half (row 0: c again,
+// row 1 + f: frame 16 half + f), DMA'd into the two slots the last two finished stages left.  Registers and LDS: the header of TW.
 #include "common.h"
 #include <cstdlib>
 
@@ -64,7 +71,15 @@ __device__ __forceinline__ s16x4 pack4(const f32x4& v) {
   return __builtin_bit_cast(s16x4, b);
 }
 
-constexpr int TW_HEADS = 8, TW_F = 16;
+// acc += A B (16 x 16 x 16) with the accumulator TIED (vDst = SrcC), as attention.hip's mfma_bf16_tied: in the two interleaved K Q^T chains of the 32-frame
+// epilogue hipcc 7.2 otherwise gives MFMAs of the d = 80 instantiation a destination that partially overlaps the SrcC the previous MFMA wrote (wrong sums on
+// gfx950; tools/check_mfma_overlap.py scans the shipped ISA for that pattern; an empty-asm pin between the steps did not cure it here).  The compiler keeps no
+// hazard bookkeeping for an MFMA it cannot see: the leading s_nop 1 covers VALU write -> MFMA read, the caller waits before the first VALU read of the result.
+__device__ __forceinline__ void mfma16_tied(f32x4& acc, const s16x4& a, const s16x4& b) {
+  asm volatile("s_nop 1\n\tv_mfma_f32_16x16x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+}
+
+constexpr int TW_HEADS = 8;
 
 #ifdef NR_STAMP
 // diagnostic build only (make stamp, tools/tattnw_timeline.py): shader-clock stamps of wave 0 of the first 512 workgroups.  Slots: 0 entry, 1 prologue
@@ -76,7 +91,16 @@ __device__ unsigned long long tattnw_stamp_buf[512][128];
 #define TW_STAMP(slot) do { } while (0)
 #endif
 
-template <int D> struct TW {
+// F = 16 / 32 frames.  F is a template parameter, not a run-time tile count: the k-loop and its 30 accumulator tiles (120 registers) are the same in
+// all four instantiations, only the epilogue differs, and a run-time branch there would keep both epilogues' registers live in one kernel.
+// Registers, with the product's flags (csrc/Makefile: CXXFLAGS + NOPK; ROCm 7.2 hipcc), from
+//   hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Wall -Wno-unused-function -I../../include -Xclang -target-feature -Xclang -packed-fp32-ops
+//         --cuda-device-only -Rpass-analysis=kernel-resource-usage -c tattnw.hip         (--save-temps gives the same .num_vgpr values)
+// VGPRs <80, 16> 224, <160, 16> 183, <80, 32> 220, <160, 32> 185 (the kernel before F became a parameter: 210 / 183); no AGPRs, no scratch, 2 waves per
+// SIMD in all four; dynamic LDS 72 / 144 KiB whatever F is.  WITHOUT the NOPK pair the allocator lands elsewhere (228 / 183 / 216 / 185; 244 / 183
+// before); every variant stays below the 256 registers that two workgroups per CU at d = 80 need.
+template <int D, int F = 16> struct TW {
+  static_assert((D == 80 || D == 160) && (F == 16 || F == 32), "d = 80 / 160, 16 or 32 frames");
   static constexpr int C = TW_HEADS * D;
   static constexpr int DT = D / 16;                           // 16-channel tiles of one of q / k / v: 5 / 10
   static constexpr int MT = D == 80 ? 2 : 1;                  // row tiles (pixels) per wave
@@ -84,7 +108,9 @@ template <int D> struct TW {
   static constexpr int GS = D == 80 ? 5 : 6;                  // fragments per MFMA group (one LDS read batch)
   static constexpr int NG = NT / GS;                          // groups per k-step: 3 / 5
   static constexpr int ROWS_W = 16 * MT;                      // rows of t per wave: 32 / 16
-  static constexpr int PIX_WG = 4 * MT;                       // pixels per workgroup: 8 / 4
+  static constexpr int RT = F / 16;                           // row tiles of one pixel: 1 (F = 16) / 2 (F = 32)
+  static constexpr int PIX_WG = 4 * MT / RT;                  // pixels per workgroup: 8 / 4 (F = 16), 4 / 2 (F = 32)
+  static constexpr bool PAIR = RT > MT;                       // d = 160, F = 32: the two row tiles of a pixel sit in two waves (K, V^T swapped through LDS)
   // one stage = ONE k-step (32 channels): NT weight fragments of 1 KiB, padded to whole pieces per wave, + 64 bytes of each of the workgroup's rows
   static constexpr int W_STAGE = D == 80 ? 16 * 1024 : 32 * 1024;
   static constexpr int W_PIECES = W_STAGE / 4096;             // 1-KiB DMA pieces per wave: 4 / 8
@@ -103,8 +129,13 @@ template <int D> struct TW {
   static constexpr bool SPLIT = D == 160;
   static constexpr int THREADS = SPLIT ? 512 : 256;
   static constexpr int TBL_HEAD = D == 80 ? 16 * 1024 : 32 * 1024;   // epilogue table of one head: 17 x 3 d floats (16 320 / 32 640 B) padded to whole pieces
-  static constexpr int TBL_PIECES = TBL_HEAD / 4096;          // per wave: 4 / 8
+  static constexpr int TBL_PIECES = TBL_HEAD / 4096;          // per wave and part: 4 / 8
+  static constexpr int TBL_ALL = RT * TBL_PIECES;             // F = 32: one table part per 16 frames, each in a ring slot of its own
+  static constexpr int TPS = RT == 1 ? PPS : (TBL_ALL + NG - 1) / NG;   // table pieces issued behind each MFMA group of the last stage (d = 80)
+  static constexpr int XCH_PAIR = 2 * 2 * DT * 512;           // PAIR: packed K | V^T tiles (2 DT tiles of 512 B) of the two halves of one pixel: 20 KiB
   static_assert(17 * 3 * D * 4 <= TBL_HEAD && TBL_HEAD <= STAGE, "the epilogue table lands in one free ring slot");
+  static_assert(NS >= RT + 1 && NG * TPS >= TBL_ALL, "one free ring slot per table part at the last stage");
+  static_assert(!PAIR || (NS == 4 && XCH_PAIR <= STAGE), "PAIR: two table slots + two exchange slots");
   static_assert(NT % GS == 0 && NG * PPS >= PPW && NG * PPS >= (D == 80 ? 4 : 8) && NS >= 3 && NS <= 4 && NT * 1024 <= W_STAGE, "piece schedule / wait counts");
 };
 
@@ -114,16 +145,16 @@ struct NrTAttnWParams {
   int hw, nbatch;          // pixels per frame-image, CFG batch
   int xcd_mode;            // 0: the 8 heads of a pixel group share an XCD (needs pixel groups % 8 == 0); 1: head h on XCD h
   const bf16* stream;      // [8 heads][S stages][W_STAGE] fragment-major folded weights (tattnw_stream_pack_kernel)
-  const float* table;      // [8 heads][TBL_HEAD bytes]: per head [17][3 d] fp32 = row 0: c[n] = sum_k W'[n][k]; row 1 + f: b'[n] + pe[f] . W[n]^T
+  const float* table;      // [8 heads][F / 16 parts][TBL_HEAD bytes]: per part [17][3 d] fp32 = row 0: c[n] = sum_k W'[n][k]; row 1 + f: b'[n] + pe[16 part + f] . W[n]^T
                            // (n = the head's q | k | v rows; tattnw_table_pack_kernel), padded to whole DMA pieces
   float ln_eps;
   float scale_log2e;       // d^-0.5 * log2(e)
 };
 
-template <int D>
-__global__ __launch_bounds__(TW<D>::THREADS, TW<D>::WG_PER_CU) void tattn_head_kernel(NrTAttnWParams p) {
-  using T = TW<D>;
-  constexpr int C = T::C, DT = T::DT, MT = T::MT, NT = T::NT, GS = T::GS, NG = T::NG;
+template <int D, int F>
+__global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void tattn_head_kernel(NrTAttnWParams p) {
+  using T = TW<D, F>;
+  constexpr int C = T::C, DT = T::DT, MT = T::MT, NT = T::NT, GS = T::GS, NG = T::NG, RT = T::RT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // T::NS slots of T::STAGE bytes: [weights | rows]
 
   const int tid = threadIdx.x;
@@ -139,7 +170,10 @@ __global__ __launch_bounds__(TW<D>::THREADS, TW<D>::WG_PER_CU) void tattn_head_k
   else { head = (int)(blockIdx.x & 7); pg = blockIdx.x >> 3; }
   const int groups_per_img = p.hw / T::PIX_WG;
   const int b = pg / groups_per_img;
-  const int pix0 = (pg - b * groups_per_img) * T::PIX_WG + wave * MT;      // this wave's first pixel
+  // row tile a of this wave = half tile_half(a) (frames 16 half ..) of pixel tile_pix(a); F = 16: MT pixels from wave MT on
+  const int pix0 = (pg - b * groups_per_img) * T::PIX_WG + wave * MT / RT;      // this wave's first pixel
+  auto tile_pix = [&](int a) { return pix0 + (RT == 1 ? a : 0); };         // F = 32: MT <= RT, every row tile of a wave belongs to one pixel
+  auto tile_half = [&](int a) { return (wave * MT + a) % RT; };
 
   // ---- DMA sources.  Weight piece i of stage s: 1 KiB at head stream + s W_STAGE + (wave W_PIECES + i) KiB.  Row piece a = row tile a of the wave
   // (16 frames of one pixel) x 64 bytes: lane (r = lane >> 2, phys = lane & 3) fetches the 16-byte chunk phys ^ f(r) of row r, f(r) = (-(r >> 2)) & 3:
@@ -151,7 +185,7 @@ __global__ __launch_bounds__(TW<D>::THREADS, TW<D>::WG_PER_CU) void tattn_head_k
 #pragma unroll
   for (int a = 0; a < T::A_PIECES; ++a) {
     const int r = lane >> 2;
-    arow[a] = p.t + ((size_t)(b * TW_F + r) * p.hw + pix0 + a) * C + (((lane & 3) ^ ((-(r >> 2)) & 3)) << 3);
+    arow[a] = p.t + ((size_t)(b * F + 16 * tile_half(a) + r) * p.hw + tile_pix(a)) * C + (((lane & 3) ^ ((-(r >> 2)) & 3)) << 3);
   }
   // Every workgroup walks the k-steps from its own starting point (rot = its pixel group's position in the image, so a row's arithmetic does not
   // depend on the batch it runs in): the 32-64 workgroups of an XCD that stream the SAME head would otherwise request the same KiB of the stream
@@ -164,7 +198,14 @@ __global__ __launch_bounds__(TW<D>::THREADS, TW<D>::WG_PER_CU) void tattn_head_k
     if (i < T::W_PIECES) glds16(wsrc + (size_t)ks * T::W_STAGE + (size_t)i * 1024, dst + (unsigned)((wave * T::W_PIECES + i) * 1024));
     else glds16(arow[i - T::W_PIECES] + 32 * ks, dst + (unsigned)(T::W_STAGE + wave * (T::ROWS_W * 64) + (i - T::W_PIECES) * 1024));
   };
-  const char* tsrc = reinterpret_cast<const char*>(p.table) + (size_t)head * T::TBL_HEAD + (size_t)(wave * T::TBL_PIECES) * 1024 + (size_t)lane * 16;
+  const char* tsrc = reinterpret_cast<const char*>(p.table) + (size_t)head * (RT * T::TBL_HEAD) + (size_t)(wave * T::TBL_PIECES) * 1024 + (size_t)lane * 16;
+  // table piece i (part i / TBL_PIECES) at the last stage: part 0 into the slot stage S - 2 just left (tslot0), part 1 into the one stage S - 3 left
+  auto issue_table = [&](int i, int tslot0) {
+    const int part = i / T::TBL_PIECES, ii = i - part * T::TBL_PIECES;
+    int ts = tslot0;
+    if (part) { ts += T::NS - 1; if (ts >= T::NS) ts -= T::NS; }
+    glds16(tsrc + (size_t)part * T::TBL_HEAD + (size_t)ii * 1024, lds0 + (unsigned)(ts * T::STAGE + (wave * T::TBL_PIECES + ii) * 1024));
+  };
   // prologue: stages 0 .. NS - 2
   if (!T::SPLIT || producer) {
 #pragma unroll
@@ -188,12 +229,13 @@ __global__ __launch_bounds__(TW<D>::THREADS, TW<D>::WG_PER_CU) void tattn_head_k
           for (int i = 0; i < T::PPW; ++i) issue_piece(s_next, pslot, i);
         } else if (s == T::S - 1) {           // the head's epilogue table into the slot stage S - 2 just left
 #pragma unroll
-          for (int i = 0; i < T::TBL_PIECES; ++i) glds16(tsrc + (size_t)i * 1024, lds0 + (unsigned)(pslot * T::STAGE + (wave * T::TBL_PIECES + i) * 1024));
+          for (int i = 0; i < T::TBL_ALL; ++i) issue_table(i, pslot);
         }
         pslot = pslot + 1 == T::NS ? 0 : pslot + 1;
       }
       wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();           // the table is in LDS: the consumers' epilogue may read it
+      if constexpr (T::PAIR) __builtin_amdgcn_s_barrier();   // the consumers' K | V^T exchange barrier counts every wave of the workgroup
       return;
     }
   }
@@ -261,9 +303,9 @@ __global__ __launch_bounds__(TW<D>::THREADS, TW<D>::WG_PER_CU) void tattn_head_k
         }
       } else if (!T::SPLIT && s == T::S - 1) {             // last stage: the head's epilogue table into the slot stage S - 2 just left
 #pragma unroll
-        for (int q = 0; q < T::PPS; ++q) {
-          const int i = g * T::PPS + q;
-          if (i < T::TBL_PIECES) glds16(tsrc + (size_t)i * 1024, lds0 + (unsigned)(pslot * T::STAGE + (wave * T::TBL_PIECES + i) * 1024));
+        for (int q = 0; q < T::TPS; ++q) {
+          const int i = g * T::TPS + q;
+          if (i < T::TBL_ALL) issue_table(i, pslot);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -282,6 +324,7 @@ __global__ __launch_bounds__(TW<D>::THREADS, TW<D>::WG_PER_CU) void tattn_head_k
   }
   TW_STAMP(125);
   // the epilogue table sits in the slot "before" the last stage's: slot now = (last + 1) % NS, table slot = (last + NS - 1) % NS = (slot + NS - 2) % NS
+  // (F = 32: its second part one slot further back)
   int tslot = slot + T::NS - 2; if (tslot >= T::NS) tslot -= T::NS;
   const float* tb = reinterpret_cast<const float*>(smem + tslot * T::STAGE);
   wait_vmcnt<0>();
@@ -297,18 +340,16 @@ __global__ __launch_bounds__(TW<D>::THREADS, TW<D>::WG_PER_CU) void tattn_head_k
     rstd[mt] = rsqrtf(fmaxf(q - a * a, 0.f) + p.ln_eps);
   }
 
-  // ---- fold epilogue + attention per row tile (pixel); the three tensors as packed bf16 MFMA operands ----
+  // ---- fold epilogue of row tile mt with its table part tbh: the three tensors as packed bf16 MFMA operands ----
   // table columns of this lane: q / k tiles nt -> part D + 16 nt + 4 fg .. + 3; v tile nt -> 2 D + 16 nt + fr (its 4 frames 4 fg + r)
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    s16x4 qa[DT], ka[DT], va[DT];
-    const float* te = tb + (1 + fr) * (3 * D);
+  auto fold = [&](int mt, const float* tbh, s16x4 (&qa)[DT], s16x4 (&ka)[DT], s16x4 (&va)[DT]) {
+    const float* te = tbh + (1 + fr) * (3 * D);
 #pragma unroll
     for (int part = 0; part < 2; ++part) {
 #pragma unroll
       for (int nt = 0; nt < DT; ++nt) {
         const int col = part * D + 16 * nt + 4 * fg;
-        const f32x4 c4 = *(const f32x4*)(tb + col), e4 = *(const f32x4*)(te + col);
+        const f32x4 c4 = *(const f32x4*)(tbh + col), e4 = *(const f32x4*)(te + col);
         f32x4 v = acc[part * DT + nt][mt];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (v[e] - mu[mt] * c4[e]) * rstd[mt] + e4[e];
@@ -321,33 +362,106 @@ __global__ __launch_bounds__(TW<D>::THREADS, TW<D>::WG_PER_CU) void tattn_head_k
 #pragma unroll
     for (int nt = 0; nt < DT; ++nt) {
       const int col = 2 * D + 16 * nt + fr;
-      const float cs = tb[col];
+      const float cs = tbh[col];
       f32x4 v = acc[2 * DT + nt][mt];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = (v[r] - muf[r] * cs) * rsf[r] + tb[(1 + 4 * fg + r) * (3 * D) + col];
+      for (int r = 0; r < 4; ++r) v[r] = (v[r] - muf[r] * cs) * rsf[r] + tbh[(1 + 4 * fg + r) * (3 * D) + col];
       va[nt] = pack4(v);
     }
-    // S^T[key 4 fg + r][query fr] = sum_c K[key][c] Q[query][c]
-    f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
+  };
+
+  if constexpr (RT == 1) {
+    // ---- F = 16: fold + attention per row tile (pixel) ----
 #pragma unroll
-    for (int nt = 0; nt < DT; ++nt) s4 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ka[nt], qa[nt], s4, 0, 0, 0);
-    float mx = fmaxf(fmaxf(s4[0], s4[1]), fmaxf(s4[2], s4[3]));
-    mx = xmax32(xmax16(mx));
-    float l = 0.f;
+    for (int mt = 0; mt < MT; ++mt) {
+      s16x4 qa[DT], ka[DT], va[DT];
+      fold(mt, tb, qa, ka, va);
+      // S^T[key 4 fg + r][query fr] = sum_c K[key][c] Q[query][c]
+      f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { s4[r] = __builtin_amdgcn_exp2f((s4[r] - mx) * p.scale_log2e); l += s4[r]; }
-    l = xsum32(xsum16(l));
-    const float inv = __builtin_amdgcn_rcpf(l);
-    const s16x4 pb = pack4(s4);
-    // O^T[channel 16 g + 4 fg + r][query fr] = V^T P^T ; a[row of (frame fr, pixel)][head D + 16 g + 4 fg + r]
-    bf16* orow = p.out + ((size_t)(b * TW_F + fr) * p.hw + pix0 + mt) * C + head * D + 4 * fg;
+      for (int nt = 0; nt < DT; ++nt) s4 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ka[nt], qa[nt], s4, 0, 0, 0);
+      float mx = fmaxf(fmaxf(s4[0], s4[1]), fmaxf(s4[2], s4[3]));
+      mx = xmax32(xmax16(mx));
+      float l = 0.f;
 #pragma unroll
-    for (int g = 0; g < DT; ++g) {
-      const f32x4 o4 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(va[g], pb, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      bf16x4 o;
+      for (int r = 0; r < 4; ++r) { s4[r] = __builtin_amdgcn_exp2f((s4[r] - mx) * p.scale_log2e); l += s4[r]; }
+      l = xsum32(xsum16(l));
+      const float inv = __builtin_amdgcn_rcpf(l);
+      const s16x4 pb = pack4(s4);
+      // O^T[channel 16 g + 4 fg + r][query fr] = V^T P^T ; a[row of (frame fr, pixel)][head D + 16 g + 4 fg + r]
+      bf16* orow = p.out + ((size_t)(b * F + fr) * p.hw + tile_pix(mt)) * C + head * D + 4 * fg;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) o[r] = (bf16)(o4[r] * inv);
-      nr_store8(orow + 16 * g, o);
+      for (int g = 0; g < DT; ++g) {
+        const f32x4 o4 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(va[g], pb, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        bf16x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (bf16)(o4[r] * inv);
+        nr_store8(orow + 16 * g, o);
+      }
+    }
+  } else {
+    // ---- F = 32: the packed tensors of both halves of a pixel first (ka / va indexed by the half = key tile), then the attention per query tile ----
+    int tslot1 = tslot + T::NS - 1; if (tslot1 >= T::NS) tslot1 -= T::NS;
+    const float* tb1 = reinterpret_cast<const float*>(smem + tslot1 * T::STAGE);
+    s16x4 qa[MT][DT], ka[RT][DT], va[RT][DT];
+    if constexpr (!T::PAIR) {
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) fold(mt, mt ? tb1 : tb, qa[mt], ka[mt], va[mt]);      // MT = RT: tile mt is half mt of the wave's pixel
+    } else {
+      // this wave holds half h of pixel wave >> 1, wave ^ 1 the other half: both write their K | V^T tiles ([half][2 DT tiles][64 lanes] x 8 bytes, the
+      // lane's own MFMA operand) into the pair's exchange area and read both halves back.  The areas: the last stage's slot and the one after it
+      // (NS = 4: the two slots that hold neither table part), free since the barrier above
+      const int h = wave & 1;
+      s16x4 ko[DT], vo[DT];
+      fold(0, h ? tb1 : tb, qa[0], ko, vo);
+      int xslot = slot; if (wave >> 1) { xslot += T::NS - 1; if (xslot >= T::NS) xslot -= T::NS; }
+      unsigned char* xb = smem + xslot * T::STAGE + lane * 8;
+#pragma unroll
+      for (int nt = 0; nt < DT; ++nt) {
+        *(s16x4*)(xb + (h * 2 * DT + nt) * 512) = ko[nt];
+        *(s16x4*)(xb + (h * 2 * DT + DT + nt) * 512) = vo[nt];
+      }
+      __syncthreads();                       // with the producer waves' second barrier
+#pragma unroll
+      for (int kt = 0; kt < RT; ++kt)
+#pragma unroll
+        for (int nt = 0; nt < DT; ++nt) {
+          ka[kt][nt] = *(const s16x4*)(xb + (kt * 2 * DT + nt) * 512);
+          va[kt][nt] = *(const s16x4*)(xb + (kt * 2 * DT + DT + nt) * 512);
+        }
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      // S^T[key 16 kt + 4 fg + r][query fr] = sum_c K[key][c] Q[query][c]
+      f32x4 sa = f32x4{0.f, 0.f, 0.f, 0.f}, sb = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int nt = 0; nt < DT; ++nt) {
+        mfma16_tied(sa, ka[0][nt], qa[mt][nt]);
+        mfma16_tied(sb, ka[1][nt], qa[mt][nt]);
+      }
+      asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+v"(sa), "+v"(sb));     // MFMA result -> VALU read: the wait states hipcc would count for its own MFMAs
+      float mx = fmaxf(fmaxf(fmaxf(sa[0], sa[1]), fmaxf(sa[2], sa[3])), fmaxf(fmaxf(sb[0], sb[1]), fmaxf(sb[2], sb[3])));
+      mx = xmax32(xmax16(mx));
+      float l = 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { sa[r] = __builtin_amdgcn_exp2f((sa[r] - mx) * p.scale_log2e); l += sa[r]; }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { sb[r] = __builtin_amdgcn_exp2f((sb[r] - mx) * p.scale_log2e); l += sb[r]; }
+      l = xsum32(xsum16(l));
+      const float inv = __builtin_amdgcn_rcpf(l);
+      // the lane's k-slots 0-3 | 4-7 of the K = 32 product = its keys 4 fg + r of half 0 | half 1, in P^T and in V^T alike
+      const bf16x8 pb = __builtin_shufflevector(__builtin_bit_cast(bf16x4, pack4(sa)), __builtin_bit_cast(bf16x4, pack4(sb)), 0, 1, 2, 3, 4, 5, 6, 7);
+      // O^T[channel 16 g + 4 fg + r][query fr] = V^T P^T ; a[row of (frame 16 half + fr, pixel)][head D + 16 g + 4 fg + r]
+      bf16* orow = p.out + ((size_t)(b * F + 16 * tile_half(mt) + fr) * p.hw + tile_pix(mt)) * C + head * D + 4 * fg;
+#pragma unroll
+      for (int g = 0; g < DT; ++g) {
+        const bf16x8 vb = __builtin_shufflevector(__builtin_bit_cast(bf16x4, va[0][g]), __builtin_bit_cast(bf16x4, va[1][g]), 0, 1, 2, 3, 4, 5, 6, 7);
+        const f32x4 o4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb, pb, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        bf16x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (bf16)(o4[r] * inv);
+        nr_store8(orow + 16 * g, o);
+      }
     }
   }
   TW_STAMP(126);
@@ -382,25 +496,25 @@ __global__ __launch_bounds__(256) void tattnw_stream_pack_kernel(const bf16* __r
   *(bf16x8*)(stream + (size_t)idx * 8) = v;
 }
 
-// epilogue table: per head [17][3 d] fp32 (row 0: c, row 1 + f: b' + pe[f] W^T) from the engine's LayerNorm-fold vectors (rows q | k | v of [3 C])
+// epilogue table: per head and part (16 frames; parts = frames / 16) [17][3 d] fp32 (row 0: c, row 1 + f: b' + pe[16 part + f] W^T) from the engine's
+// LayerNorm-fold vectors (rows q | k | v of [3 C])
 template <int D>
 __global__ __launch_bounds__(256) void tattnw_table_pack_kernel(const float* __restrict__ lnc, const float* __restrict__ bias, const float* __restrict__ rowvec,
-                                                                float* __restrict__ table) {
+                                                                int parts, float* __restrict__ table) {
   using T = TW<D>;
-  constexpr int C = T::C, PER_HEAD = T::TBL_HEAD / 4;
+  constexpr int C = T::C, PER_PART = T::TBL_HEAD / 4;
   const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= TW_HEADS * PER_HEAD) return;
-  const int head = idx / PER_HEAD, e = idx - head * PER_HEAD;
+  if (idx >= TW_HEADS * parts * PER_PART) return;
+  const int hp = idx / PER_PART, e = idx - hp * PER_PART;
+  const int head = hp / parts, part = hp - head * parts;
   float v = 0.f;
   if (e < 17 * 3 * D) {
     const int row = e / (3 * D), j = e - row * (3 * D);
     const int n = (j / D) * C + head * D + (j % D);
-    v = row == 0 ? lnc[n] : bias[n] + rowvec[(size_t)(row - 1) * (3 * C) + n];
+    v = row == 0 ? lnc[n] : bias[n] + rowvec[(size_t)(16 * part + row - 1) * (3 * C) + n];
   }
   table[idx] = v;
 }
-
-unsigned long long g_tw_attr = 0;
 
 }  // namespace
 
@@ -419,10 +533,12 @@ extern "C" size_t nr_tattnw_stream_bytes(int C) {
 }
 
 // rows: the launch's row count (deterministic-batch mode: one clip's).  At C = 1280 a launch needs >= 2048 rows: with 512 (the 4 x 4 level at one
-// clip) only 64 workgroups exist, each streaming a head's 1.2 MB alone: 34 us against 27 us for the q|k|v GEMM + attention core (profiles/r06_tattn_head_ab.txt)
+// clip) only 64 workgroups exist, each streaming a head's 1.2 MB alone: 34 us against 27 us for the q|k|v GEMM + attention core (profiles/r06_tattn_head_ab.txt).
+// frames = 32: a workgroup still owns 64 rows, so the same floor in rows is the same floor in workgroups (profiles/r08_tattn_head_f32_ab.txt)
 extern "C" int nr_tattnw_eligible(int C, int heads, int frames, int hw, long long rows) {
   static const bool off = getenv("NR_TATTN_HEAD") && getenv("NR_TATTN_HEAD")[0] == '0';   // A/B switch
-  if (off || heads != TW_HEADS || frames != TW_F) return 0;
+  if (off || heads != TW_HEADS || (frames != 16 && frames != 32)) return 0;
+  // the same rule at both frame counts (the pixels of a 16-frame workgroup, 8 / 4, are a multiple of those of a 32-frame one, 4 / 2)
   if (C == 640) return hw % TW<80>::PIX_WG == 0;
   if (C == 1280) return hw % TW<160>::PIX_WG == 0 && rows >= 2048;
   return 0;
@@ -437,37 +553,46 @@ extern "C" int nr_launch_tattnw_stream_pack(const bf16* w_folded, int C, bf16* s
   return 0;
 }
 
-extern "C" size_t nr_tattnw_table_bytes(int C) { return C == 640 ? (size_t)TW_HEADS * TW<80>::TBL_HEAD : (C == 1280 ? (size_t)TW_HEADS * TW<160>::TBL_HEAD : 0); }
+extern "C" size_t nr_tattnw_table_bytes(int C, int frames) {
+  if (frames != 16 && frames != 32) return 0;
+  return (size_t)(frames / 16) * (C == 640 ? (size_t)TW_HEADS * TW<80>::TBL_HEAD : (C == 1280 ? (size_t)TW_HEADS * TW<160>::TBL_HEAD : 0));
+}
 
-extern "C" int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, const float* rowvec, int C, float* table, hipStream_t s) {
-  const int total = (int)(nr_tattnw_table_bytes(C) / 4);
+// rowvec: [frames][3 C]
+extern "C" int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, const float* rowvec, int C, int frames, float* table, hipStream_t s) {
+  const int total = (int)(nr_tattnw_table_bytes(C, frames) / 4);
   if (!total) return 1;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (C == 640) hipLaunchKernelGGL(tattnw_table_pack_kernel<80>, grid, dim3(256), 0, s, lnc, bias, rowvec, table);
-  else hipLaunchKernelGGL(tattnw_table_pack_kernel<160>, grid, dim3(256), 0, s, lnc, bias, rowvec, table);
+  if (C == 640) hipLaunchKernelGGL(tattnw_table_pack_kernel<80>, grid, dim3(256), 0, s, lnc, bias, rowvec, frames / 16, table);
+  else hipLaunchKernelGGL(tattnw_table_pack_kernel<160>, grid, dim3(256), 0, s, lnc, bias, rowvec, frames / 16, table);
   return 0;
 }
 
-extern "C" int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s) {
-  if (nbatch <= 0 || hw <= 0 || !nr_tattnw_stream_bytes(C)) return 1;
-  const int pix_wg = C == 640 ? TW<80>::PIX_WG : TW<160>::PIX_WG;
-  if (hw % pix_wg != 0) return 1;
+template <int D, int F>
+static int tattnw_launch(NrTAttnWParams& p, int dev, hipStream_t s) {
+  using T = TW<D, F>;
+  if (p.hw % T::PIX_WG != 0) return 1;
+  const int npg = p.nbatch * (p.hw / T::PIX_WG);
+  p.xcd_mode = (D == 80 && npg % 8 == 0) ? 0 : 1;
+  constexpr size_t shm = (size_t)T::NS * T::STAGE;
+  static unsigned long long attr = 0;        // per instantiation: devices whose dynamic-LDS limit is raised
+  if (!(attr >> (dev & 63) & 1ull)) {
+    if (hipFuncSetAttribute((const void*)tattn_head_kernel<D, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
+    attr |= 1ull << (dev & 63);
+  }
+  hipLaunchKernelGGL((tattn_head_kernel<D, F>), dim3((unsigned)(npg * TW_HEADS)), dim3(T::THREADS), shm, s, p);
+  return 0;
+}
+
+// t, out: [nbatch * frames * hw][C]; table: nr_tattnw_table_bytes(C, frames) packed for the same frame count
+extern "C" int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int frames, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s) {
+  if (nbatch <= 0 || hw <= 0 || !nr_tattnw_stream_bytes(C) || (frames != 16 && frames != 32)) return 1;
   NrTAttnWParams p;
   p.t = t; p.out = out; p.hw = hw; p.nbatch = nbatch; p.stream = stream; p.table = table; p.ln_eps = ln_eps;
   const int d = C / TW_HEADS;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)d);
-  const int npg = nbatch * (hw / pix_wg);
-  p.xcd_mode = (C == 640 && npg % 8 == 0) ? 0 : 1;
-  const size_t shm = C == 640 ? (size_t)TW<80>::NS * TW<80>::STAGE : (size_t)TW<160>::NS * TW<160>::STAGE;
   int dev = 0;
   (void)hipGetDevice(&dev);
-  if (!(g_tw_attr >> (dev & 63) & 1ull)) {
-    if (hipFuncSetAttribute((const void*)tattn_head_kernel<80>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)TW<80>::NS * TW<80>::STAGE)) != hipSuccess) return 2;
-    if (hipFuncSetAttribute((const void*)tattn_head_kernel<160>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)TW<160>::NS * TW<160>::STAGE)) != hipSuccess) return 2;
-    g_tw_attr |= 1ull << (dev & 63);
-  }
-  const unsigned grid = (unsigned)(npg * TW_HEADS);
-  if (C == 640) hipLaunchKernelGGL(tattn_head_kernel<80>, dim3(grid), dim3(TW<80>::THREADS), shm, s, p);
-  else hipLaunchKernelGGL(tattn_head_kernel<160>, dim3(grid), dim3(TW<160>::THREADS), shm, s, p);
-  return 0;
+  if (C == 640) return frames == 16 ? tattnw_launch<80, 16>(p, dev, s) : tattnw_launch<80, 32>(p, dev, s);
+  return frames == 16 ? tattnw_launch<160, 16>(p, dev, s) : tattnw_launch<160, 32>(p, dev, s);
 }
