@@ -3343,7 +3343,9 @@ extern "C" nr_status nr_op_attention(nr_stream stream, int32_t mode, const void*
   std::memset(&p, 0, sizeof(p));
   const bf16* q = (const bf16*)qp; const bf16* kv = (const bf16*)kvp;
   const int fp8_flag = (mode & 8) ? 1 : 0;      // mode | 8: e4m3 MFMA operands (spatial / cross kernels)
+  const int causal_flag = (mode & 16) ? 1 : 0;  // mode | 16: causal mask (mode 0 only; the CLIP text encoder's form)
   mode &= 7;
+  if (causal_flag && (mode != 0 || fp8_flag)) throw NrError(NR_ERR_ARG, "causal attention: mode 0 only");
   p.heads = heads; p.d = C / heads; p.scale = 1.0f / std::sqrt((float)p.d); p.out = (bf16*)outp;
   if (mode == 0) {
     const int ld = 3 * C;
@@ -3361,7 +3363,7 @@ extern "C" nr_status nr_op_attention(nr_stream stream, int32_t mode, const void*
     p.kv_outer = p.q_outer; p.kv_inner_stride = ld; p.kv_seq = p.q_seq;
     p.o_outer = (long long)F * hw * C; p.o_inner_stride = C; p.o_seq = (long long)hw * C;
   } else throw NrError(NR_ERR_ARG, "bad attention mode");
-  p.fp8 = fp8_flag;
+  p.fp8 = fp8_flag; p.causal = causal_flag;
   LAUNCH_OK(nr_launch_attention(&p, (hipStream_t)stream));
   NR_CATCH
 }

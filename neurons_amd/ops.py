@@ -222,34 +222,45 @@ def layernorm(x, gamma, beta, eps=1e-5, pe=None, pe_hw=1, pe_F=1):
     return out
 
 
-def attention_self(qkv, heads, fp8=False):
-    """qkv: [nimg, L, 3C] fused; returns [nimg, L, C].  fp8: OCP e4m3 MFMA operands (L >= 48; BASELINE config 5)."""
-    _chk_bf16(qkv)
-    nimg, L, C3 = qkv.shape
-    Cc = C3 // 3
-    out = torch.empty(nimg, L, Cc, dtype=torch.bfloat16, device=qkv.device)
-    lib = _lib.load()
-    _lib.check(lib.nr_op_attention(_stream(), 8 if fp8 else 0, _ptr(qkv), None, _ptr(out), nimg, L, L, Cc, heads, 1, 1))
+def _attn_out(out, shape, like):
+    """The result tensor of an attention op: a fresh one, or the caller's (contiguous bf16 of the result shape on the inputs' device)."""
+    if out is None:
+        return torch.empty(*shape, dtype=torch.bfloat16, device=like.device)
+    _chk_bf16(out)
+    if tuple(out.shape) != tuple(shape) or out.device != like.device:
+        raise ValueError(f"out: expected a bf16 tensor of shape {tuple(shape)} on {like.device}, got {tuple(out.shape)} on {out.device}")
     return out
 
 
-def attention_cross(q, kv, heads, kv_div, fp8=False):
-    """q: [nimg, L, C]; kv: [nb, Lk, 2C] fused; image n attends to kv[n // kv_div].  fp8 as in attention_self."""
+def attention_self(qkv, heads, fp8=False, causal=False, out=None):
+    """qkv: [nimg, L, 3C] fused; returns [nimg, L, C].  fp8: OCP e4m3 MFMA operands (L >= 48; BASELINE config 5).
+    causal: query i sees keys 0..i (the CLIP text encoder's mask; not with fp8).  out: write the result into this tensor."""
+    _chk_bf16(qkv)
+    nimg, L, C3 = qkv.shape
+    Cc = C3 // 3
+    out = _attn_out(out, (nimg, L, Cc), qkv)
+    lib = _lib.load()
+    _lib.check(lib.nr_op_attention(_stream(), (8 if fp8 else 0) | (16 if causal else 0), _ptr(qkv), None, _ptr(out), nimg, L, L, Cc, heads, 1, 1))
+    return out
+
+
+def attention_cross(q, kv, heads, kv_div, fp8=False, out=None):
+    """q: [nimg, L, C]; kv: [nb, Lk, 2C] fused; image n attends to kv[n // kv_div].  fp8, out as in attention_self."""
     _chk_bf16(q, kv)
     nimg, L, Cc = q.shape
     Lk = kv.shape[1]
-    out = torch.empty_like(q)
+    out = _attn_out(out, (nimg, L, Cc), q)
     lib = _lib.load()
     _lib.check(lib.nr_op_attention(_stream(), 9 if fp8 else 1, _ptr(q), _ptr(kv), _ptr(out), nimg, L, Lk, Cc, heads, 1, kv_div))
     return out
 
 
-def attention_temporal(qkv, heads, frames):
-    """qkv: [(b f), hw, 3C] fused; attention runs over f for every (b, pixel); returns [(b f), hw, C]."""
+def attention_temporal(qkv, heads, frames, out=None):
+    """qkv: [(b f), hw, 3C] fused; attention runs over f for every (b, pixel); returns [(b f), hw, C].  out as in attention_self."""
     _chk_bf16(qkv)
     nimg, hw, C3 = qkv.shape
     Cc = C3 // 3
-    out = torch.empty(nimg, hw, Cc, dtype=torch.bfloat16, device=qkv.device)
+    out = _attn_out(out, (nimg, hw, Cc), qkv)
     lib = _lib.load()
     _lib.check(lib.nr_op_attention(_stream(), 2, _ptr(qkv), None, _ptr(out), nimg, hw, frames, Cc, heads, frames, 1))
     return out
