@@ -238,6 +238,23 @@ nr_status nr_prior_p_sample_step(nr_stream stream, const float* pred_dev, const 
 nr_status nr_cfg_ddim_step(nr_stream stream, const float* eps_dev, const float* x_dev, float* x_out_dev, int64_t n,
                            float guidance_scale, int32_t do_cfg, double alpha_prod_t, double alpha_prod_t_prev);
 
+/* nr_cfg_ddim_step with the rest of diffusers 0.11.1 DDIMScheduler.step (Song et al. 2021 eq. 12 / 16): the arguments the reference's
+ * __call__ hands to scheduler.step (eta, generator: pipeline_neuroclips.py:331-336,483) and the scheduler's config (prediction_type, clip_sample).
+ *   e = e_u + g (e_t - e_u) when do_cfg;   x0 = (x - sqrt(1-a_t) e) / sqrt(a_t) (EPSILON) | e (SAMPLE) | sqrt(a_t) x - sqrt(1-a_t) e (V_PREDICTION);
+ *   SAMPLE / V_PREDICTION re-derive e from x0;  clip_sample clamps x0 to [-1, 1];  use_clipped_model_output re-derives e from the clamped x0;
+ *   x_out = sqrt(a_prev) x0 + dir_coeff e + sigma noise.
+ * The caller forms sigma = eta sqrt((1-a_prev)/(1-a_t) (1 - a_t/a_prev)) and dir_coeff = sqrt(1 - a_prev - sigma^2) in double (both 0 at the last
+ * step, a_prev = 1).  noise_dev fp32 [n] is read only when sigma > 0 (NULL allowed otherwise; sigma > 0 with NULL is NR_ERR_ARG, as is an unknown
+ * prediction type).  x0_out_dev (nullable, fp32 [n], no alias of x) receives x0 = pred_original_sample.  The default rule (EPSILON, no clipping,
+ * sigma = 0, no x0 output) runs the kernel of nr_cfg_ddim_step with the same arguments: results are bit-identical to it. */
+#define NR_DDIM_EPSILON 0
+#define NR_DDIM_SAMPLE 1
+#define NR_DDIM_V_PREDICTION 2
+nr_status nr_cfg_ddim_step_ex(nr_stream stream, const float* eps_dev, const float* x_dev, float* x_out_dev, float* x0_out_dev, int64_t n,
+                              float guidance_scale, int32_t do_cfg, int32_t prediction_type, int32_t clip_sample,
+                              int32_t use_clipped_model_output, double alpha_prod_t, double alpha_prod_t_prev, double sigma, double dir_coeff,
+                              const float* noise_dev);
+
 /* replaces the CFG combine alone (pipeline_neuroclips.py:478-480) for a caller that keeps its own scheduler object
  * (scripts/neuroclips_video.py:219) and calls its .step (pipeline_neuroclips.py:483) on the combined noise:
  *   eps_dev fp32 [2B][...] (uncond half first) -> eps_out_dev fp32 [B][...] = e_u + g (e_t - e_u); n = elements of the output */

@@ -22,6 +22,9 @@ NR_KIND_CLIP_TEXT = 5
 NR_KIND_LEAF_TRANSFORMER3D = 6
 NR_KIND_LEAF_TEMPORAL = 7
 NR_MAX_LEVELS = 4
+NR_DDIM_EPSILON = 0
+NR_DDIM_SAMPLE = 1
+NR_DDIM_V_PREDICTION = 2
 
 
 class NrNetConfig(C.Structure):
@@ -93,6 +96,8 @@ SYMBOLS = {
     "nr_edm_cfg_euler_step": (_I32, [_VP, _VP, _VP, _VP, _I64, C.c_float, C.c_float, C.c_float, C.c_float]),
     "nr_prior_p_sample_step": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, C.c_float, _I32, _I32, C.c_double, C.c_double, C.c_double]),
     "nr_cfg_ddim_step": (_I32, [_VP, _VP, _VP, _VP, _I64, C.c_float, _I32, C.c_double, C.c_double]),
+    "nr_cfg_ddim_step_ex": (_I32, [_VP, _VP, _VP, _VP, _VP, _I64, C.c_float, _I32, _I32, _I32, _I32, C.c_double, C.c_double, C.c_double,
+                                   C.c_double, _VP]),
     "nr_cfg_combine": (_I32, [_VP, _VP, _VP, _I64, C.c_float]),
     "nr_net_export_manifest": (_I64, [_VP, _VP, _I64, C.POINTER(_I64)]),
     "nr_net_export_weights": (_I32, [_VP, _VP, _VP, _I64]),

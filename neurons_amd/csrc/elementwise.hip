@@ -266,6 +266,76 @@ __global__ void cfg_ddim_step_kernel(const float* __restrict__ eps, const float*
   x_out[i] = sqrt_ap * x0 + sqrt_1map * e;
 }
 
+// The full DDIM rule (Song et al. 2021 eq. 12 / 16 in the form of diffusers' DDIMScheduler.step) for everything the kernel above does not
+// cover; each variant is an instantiation of its own, the default (epsilon, no clipping, eta = 0, no x0 output) stays on the kernel above.
+//   PRED 0 epsilon: x0 = (x - sqrt(1-a_t) e) / sqrt(a_t)      1 sample: x0 = e      2 v: x0 = sqrt(a_t) x - sqrt(1-a_t) e
+//   PRED 1 / 2 then re-derive e: (x - sqrt(a_t) x0) / sqrt(1-a_t)  /  sqrt(a_t) v + sqrt(1-a_t) x
+//   CLIP: x0 clamped to [-1, 1];  CLIPPED_OUT: e re-derived from the (clamped) x0;  STOCH: + sigma * noise
+//   x_prev = sqrt(a_prev) x0 + dir e [+ sigma z],  dir = sqrt(1 - a_prev - sigma^2) formed on the host in double (0 at a_prev = 1: no sqrt
+//   of a rounded-negative number here).
+struct DdimCoef { float sqrt_at, sqrt_1mat, sqrt_ap, dir, sigma, guidance; };
+
+template <int PRED, bool CLIP, bool CLIPPED_OUT, bool STOCH>
+__device__ __forceinline__ float ddim_full_one(float e, float xv, float z, const DdimCoef& c, float& x0_out) {
+  float x0;
+  if (PRED == 0) {
+    x0 = (xv - c.sqrt_1mat * e) / c.sqrt_at;
+  } else if (PRED == 1) {
+    x0 = e;
+    e = (xv - c.sqrt_at * x0) / c.sqrt_1mat;
+  } else {
+    x0 = c.sqrt_at * xv - c.sqrt_1mat * e;
+    e = c.sqrt_at * e + c.sqrt_1mat * xv;
+  }
+  if (CLIP) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+  if (CLIPPED_OUT) e = (xv - c.sqrt_at * x0) / c.sqrt_1mat;
+  x0_out = x0;
+  float o = c.sqrt_ap * x0 + c.dir * e;
+  if (STOCH) o += c.sigma * z;
+  return o;
+}
+
+// VEC: thread i owns elements 4i .. 4i+3 with 16-byte loads / stores (every pointer, eps + half_off included, 16-byte aligned: checked by the
+// launcher); the last thread of a total that is no multiple of 4 walks its 1..3 elements one by one.  !VEC: one element per thread.
+template <int PRED, bool CLIP, bool CLIPPED_OUT, bool STOCH, bool VEC>
+__global__ __launch_bounds__(256) void cfg_ddim_full_kernel(const float* __restrict__ eps, const float* __restrict__ x,
+                                                            const float* __restrict__ noise, float* __restrict__ x_out,
+                                                            float* __restrict__ x0_out, long long total, long long half_off, int do_cfg,
+                                                            DdimCoef c) {
+  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * (VEC ? 4 : 1);
+  if (i0 >= total) return;
+  if (VEC && i0 + 4 <= total) {
+    f32x4 e = *(const f32x4*)(eps + i0);
+    if (do_cfg) {
+      const f32x4 et = *(const f32x4*)(eps + i0 + half_off);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) e[k] = e[k] + c.guidance * (et[k] - e[k]);
+    }
+    const f32x4 xv = *(const f32x4*)(x + i0);
+    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    if (STOCH) z = *(const f32x4*)(noise + i0);
+    f32x4 o, p;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float x0;
+      o[k] = ddim_full_one<PRED, CLIP, CLIPPED_OUT, STOCH>(e[k], xv[k], z[k], c, x0);
+      p[k] = x0;
+    }
+    *(f32x4*)(x_out + i0) = o;
+    if (x0_out) *(f32x4*)(x0_out + i0) = p;
+    return;
+  }
+  const long long i1 = VEC ? total : i0 + 1;      // the ragged tail (VEC) or this thread's one element
+  for (long long i = i0; i < i1; ++i) {
+    float e = eps[i];
+    if (do_cfg) e = e + c.guidance * (eps[i + half_off] - e);
+    float x0;
+    const float o = ddim_full_one<PRED, CLIP, CLIPPED_OUT, STOCH>(e, x[i], STOCH ? noise[i] : 0.f, c, x0);
+    x_out[i] = o;
+    if (x0_out) x0_out[i] = x0;
+  }
+}
+
 // classifier-free guidance alone (pipeline_neuroclips.py:478-480): out = eps_uncond + g * (eps_text - eps_uncond).  For callers that keep a
 // scheduler of their own (the combined eps then goes to its .step); the pipeline's own scheduler uses the fused kernel above.
 __global__ void cfg_combine_kernel(const float* __restrict__ eps, float* __restrict__ out, long long total, float guidance) {
@@ -552,6 +622,46 @@ extern "C" int nr_launch_cfg_ddim_step(const float* eps, const float* x, float* 
                                        hipStream_t stream) {
   hipLaunchKernelGGL(cfg_ddim_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, eps, x, x_out,
                      total, total, guidance, do_cfg, sqrt_at, sqrt_1mat, sqrt_ap, sqrt_1map);
+  return 0;
+}
+
+namespace {
+template <int PRED, bool CLIP, bool CLIPPED_OUT, bool STOCH>
+void launch_cfg_ddim_full(const float* eps, const float* x, const float* noise, float* x_out, float* x0_out, long long total, int do_cfg,
+                          const DdimCoef& c, hipStream_t stream) {
+  // 16-byte accesses need every base 16-byte aligned; the text half of eps starts `total` floats in, so with guidance also total % 4 == 0
+  const uintptr_t bases = (uintptr_t)eps | (uintptr_t)x | (uintptr_t)noise | (uintptr_t)x_out | (uintptr_t)x0_out;
+  const bool vec = (bases & 15) == 0 && (!do_cfg || total % 4 == 0);
+  if (vec) {
+    const long long threads = (total + 3) / 4;
+    hipLaunchKernelGGL((cfg_ddim_full_kernel<PRED, CLIP, CLIPPED_OUT, STOCH, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream,
+                       eps, x, noise, x_out, x0_out, total, total, do_cfg, c);
+  } else {
+    hipLaunchKernelGGL((cfg_ddim_full_kernel<PRED, CLIP, CLIPPED_OUT, STOCH, false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                       eps, x, noise, x_out, x0_out, total, total, do_cfg, c);
+  }
+}
+template <int PRED, bool STOCH>
+void launch_cfg_ddim_full_clip(int clip, int clipped_out, const float* eps, const float* x, const float* noise, float* x_out, float* x0_out,
+                               long long total, int do_cfg, const DdimCoef& c, hipStream_t stream) {
+  if (clip && clipped_out) launch_cfg_ddim_full<PRED, true, true, STOCH>(eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);
+  else if (clip) launch_cfg_ddim_full<PRED, true, false, STOCH>(eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);
+  else if (clipped_out) launch_cfg_ddim_full<PRED, false, true, STOCH>(eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);
+  else launch_cfg_ddim_full<PRED, false, false, STOCH>(eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);
+}
+}  // namespace
+
+// pred: 0 epsilon, 1 sample, 2 v_prediction.  noise == nullptr selects the deterministic instantiations (sigma is then not read).
+extern "C" int nr_launch_cfg_ddim_full(const float* eps, const float* x, const float* noise, float* x_out, float* x0_out, long long total,
+                                       float guidance, int do_cfg, int pred, int clip, int clipped_out, float sqrt_at, float sqrt_1mat,
+                                       float sqrt_ap, float dir, float sigma, hipStream_t stream) {
+  if (pred < 0 || pred > 2 || total <= 0) return 1;
+  const DdimCoef c = {sqrt_at, sqrt_1mat, sqrt_ap, dir, sigma, guidance};
+#define NR_DDIM_PRED(P)                                                                                                              \
+  if (noise) launch_cfg_ddim_full_clip<P, true>(clip, clipped_out, eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);          \
+  else launch_cfg_ddim_full_clip<P, false>(clip, clipped_out, eps, x, nullptr, x_out, x0_out, total, do_cfg, c, stream);
+  if (pred == 0) { NR_DDIM_PRED(0) } else if (pred == 1) { NR_DDIM_PRED(1) } else { NR_DDIM_PRED(2) }
+#undef NR_DDIM_PRED
   return 0;
 }
 

@@ -65,6 +65,9 @@ int nr_launch_edm_cfg_euler(const float* net, const float* x, float* x_out, long
 int nr_launch_cfg_combine(const float* eps, float* out, long long total, float guidance, hipStream_t stream);
 int nr_launch_cfg_ddim_step(const float* eps, const float* x, float* x_out, long long total, float guidance, int do_cfg,
                             float sqrt_at, float sqrt_1mat, float sqrt_ap, float sqrt_1map, hipStream_t stream);
+int nr_launch_cfg_ddim_full(const float* eps, const float* x, const float* noise, float* x_out, float* x0_out, long long total, float guidance,
+                            int do_cfg, int pred, int clip, int clipped_out, float sqrt_at, float sqrt_1mat, float sqrt_ap, float dir, float sigma,
+                            hipStream_t stream);
 int nr_launch_add_bf16(const bf16* a, const bf16* b, bf16* out, long long n, hipStream_t stream);
 int nr_launch_prior_p_sample(const float* pred, const float* pred_null, const float* x, const float* noise, float* x_out, float* x_start_out,
                              long long total, float cond_scale, int mode, int clamp, float sqrt_ac, float sqrt_1mac, float sqrt_recip_ac,
@@ -3090,6 +3093,34 @@ extern "C" nr_status nr_cfg_ddim_step(nr_stream stream, const float* eps_dev, co
   LAUNCH_OK(nr_launch_cfg_ddim_step(eps_dev, x_dev, x_out_dev, n, guidance_scale, do_cfg, (float)std::sqrt(a_t),
                                     (float)std::sqrt(1.0 - a_t), (float)std::sqrt(a_prev), (float)std::sqrt(1.0 - a_prev),
                                     (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_cfg_ddim_step_ex(nr_stream stream, const float* eps_dev, const float* x_dev, float* x_out_dev, float* x0_out_dev,
+                                         int64_t n, float guidance_scale, int32_t do_cfg, int32_t prediction_type, int32_t clip_sample,
+                                         int32_t use_clipped_model_output, double a_t, double a_prev, double sigma, double dir_coeff,
+                                         const float* noise_dev) {
+  NR_TRY
+  if (!eps_dev || !x_dev || !x_out_dev || n <= 0) throw NrError(NR_ERR_ARG, "bad argument");
+  if (x0_out_dev && (x0_out_dev == x_out_dev || x0_out_dev == x_dev)) throw NrError(NR_ERR_ARG, "x0_out_dev must not alias x_dev / x_out_dev");
+  if (prediction_type < NR_DDIM_EPSILON || prediction_type > NR_DDIM_V_PREDICTION)
+    throw NrError(NR_ERR_ARG, "unknown prediction type (NR_DDIM_EPSILON / NR_DDIM_SAMPLE / NR_DDIM_V_PREDICTION)");
+  // !(..) forms: a NaN fails them too
+  if (!(a_t > 0.0 && a_t <= 1.0 && a_prev > 0.0 && a_prev <= 1.0)) throw NrError(NR_ERR_ARG, "alpha products out of range (0, 1]");
+  if (!(sigma >= 0.0 && dir_coeff >= 0.0 && sigma * sigma + dir_coeff * dir_coeff <= 1.0 + 1e-9))
+    throw NrError(NR_ERR_ARG, "sigma / direction coefficient out of range");
+  if (sigma > 0.0 && !noise_dev) throw NrError(NR_ERR_ARG, "sigma > 0 needs a noise tensor");
+  const bool rederive = prediction_type == NR_DDIM_SAMPLE || use_clipped_model_output;     // divides by sqrt(1 - a_t)
+  if (rederive && !(a_t < 1.0)) throw NrError(NR_ERR_ARG, "alpha_prod_t = 1: the noise cannot be re-derived from x0");
+  if (prediction_type == NR_DDIM_EPSILON && !clip_sample && !use_clipped_model_output && sigma == 0.0 && !x0_out_dev) {
+    // the default rule: the same kernel with the same arguments as nr_cfg_ddim_step (dir_coeff = sqrt(1 - a_prev) at sigma = 0)
+    LAUNCH_OK(nr_launch_cfg_ddim_step(eps_dev, x_dev, x_out_dev, n, guidance_scale, do_cfg, (float)std::sqrt(a_t), (float)std::sqrt(1.0 - a_t),
+                                      (float)std::sqrt(a_prev), (float)dir_coeff, (hipStream_t)stream));
+  } else {
+    LAUNCH_OK(nr_launch_cfg_ddim_full(eps_dev, x_dev, sigma > 0.0 ? noise_dev : nullptr, x_out_dev, x0_out_dev, n, guidance_scale, do_cfg ? 1 : 0,
+                                      prediction_type, clip_sample ? 1 : 0, use_clipped_model_output ? 1 : 0, (float)std::sqrt(a_t),
+                                      (float)std::sqrt(1.0 - a_t), (float)std::sqrt(a_prev), (float)dir_coeff, (float)sigma, (hipStream_t)stream));
+  }
   NR_CATCH
 }
 

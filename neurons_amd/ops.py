@@ -266,13 +266,30 @@ def attention_temporal(qkv, heads, frames, out=None):
     return out
 
 
-def cfg_ddim_step(eps, x, guidance_scale, alpha_prod_t, alpha_prod_t_prev, do_cfg=True):
-    _chk_f32(eps, x)
+def cfg_ddim_step(eps, x, guidance_scale, alpha_prod_t, alpha_prod_t_prev, do_cfg=True, *, prediction_type="epsilon", clip_sample=False,
+                  use_clipped_model_output=False, eta=0.0, noise=None, return_pred_original=False):
+    """CFG combine + one DDIM update.  Without keywords: nr_cfg_ddim_step (epsilon prediction, eta = 0).  Any keyword goes through
+    nr_cfg_ddim_step_ex: prediction_type "epsilon" / "sample" / "v_prediction", clip_sample (x0 clamped to [-1, 1]), use_clipped_model_output,
+    eta with ``noise`` (fp32, x's shape; required when eta gives sigma > 0), return_pred_original -> (x_prev, x0)."""
+    _chk_f32(eps, x, noise)
     out = torch.empty_like(x)
     lib = _lib.load()
-    _lib.check(lib.nr_cfg_ddim_step(_stream(), _ptr(eps), _ptr(x), _ptr(out), x.numel(), float(guidance_scale),
-                                    1 if do_cfg else 0, float(alpha_prod_t), float(alpha_prod_t_prev)))
-    return out
+    if prediction_type == "epsilon" and not clip_sample and not use_clipped_model_output and eta == 0.0 and noise is None \
+            and not return_pred_original:
+        _lib.check(lib.nr_cfg_ddim_step(_stream(), _ptr(eps), _ptr(x), _ptr(out), x.numel(), float(guidance_scale),
+                                        1 if do_cfg else 0, float(alpha_prod_t), float(alpha_prod_t_prev)))
+        return out
+    from .scheduler import PREDICTION_TYPES, ddim_sigma_dir
+    if prediction_type not in PREDICTION_TYPES:
+        raise ValueError(f"prediction_type given as {prediction_type} must be one of `epsilon`, `sample`, or `v_prediction`")
+    if noise is not None and noise.numel() != x.numel():
+        raise ValueError(f"noise: expected {x.numel()} elements (the latents' shape), got {noise.numel()}")
+    sigma, dir_coeff = ddim_sigma_dir(float(alpha_prod_t), float(alpha_prod_t_prev), float(eta))
+    x0 = torch.empty_like(x) if return_pred_original else None
+    _lib.check(lib.nr_cfg_ddim_step_ex(_stream(), _ptr(eps), _ptr(x), _ptr(out), _ptr(x0), x.numel(), float(guidance_scale), 1 if do_cfg else 0,
+                                       PREDICTION_TYPES[prediction_type], 1 if clip_sample else 0, 1 if use_clipped_model_output else 0,
+                                       float(alpha_prod_t), float(alpha_prod_t_prev), sigma, dir_coeff, _ptr(noise)))
+    return (out, x0) if return_pred_original else out
 
 
 def cfg_combine(eps, guidance_scale):

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .scheduler import PREDICTION_TYPES
 
 
 @dataclass
@@ -253,8 +254,6 @@ class NeuroclipsPipeline:
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
-        if eta != 0.0 and hasattr(self.scheduler, "alpha_pair"):
-            raise NotImplementedError("eta != 0 is not on the NEURONS path")
 
         batch_size = 1
         if latents is not None:
@@ -304,6 +303,19 @@ class NeuroclipsPipeline:
             noise = noise.to(device=device, dtype=latents.dtype)
         latents = self.scheduler.add_noise(latents, noise, latent_timestep)
         latents = latents.to(torch.float32).contiguous()      # DDIM state stays fp32 for the whole loop
+        # eta > 0 (stochastic DDIM) with this package's scheduler: the variance noise of every step is drawn here, before the loop.  The reference
+        # draws it inside scheduler.step (diffusers 0.11.1: randn(model_output.shape, generator=generator, dtype=model_output.dtype), once per
+        # step, after every draw above); with one generator (or one per video) and fixed shapes the stream of values is the same, and the loop
+        # below stays free of host-side work between its launches.  eta = 0 draws nothing
+        full_rule = own_scheduler and (float(eta) != 0.0 or not getattr(self.scheduler, "is_default_rule", True))
+        step_noise = None
+        if full_rule and float(eta) != 0.0:
+            if isinstance(generator, list):
+                one = (1,) + tuple(latents.shape[1:])
+                step_noise = [torch.cat([torch.randn(one, generator=g, device=device, dtype=torch.float32) for g in generator], dim=0)
+                              for _ in timesteps_host]
+            else:
+                step_noise = [torch.randn(latents.shape, generator=generator, device=device, dtype=torch.float32) for _ in timesteps_host]
 
         use_ctrl = (getattr(self, "controlnet", None) is not None) and (controlnet_images is not None)
         if use_ctrl:
@@ -385,7 +397,20 @@ class NeuroclipsPipeline:
                     noise_pred = self.unet(latent_model_input, t, encoder_hidden_states=text_embeddings,
                                            down_block_additional_residuals=down_res,
                                            mid_block_additional_residual=mid_res).sample
-                if own_scheduler:
+                if full_rule:
+                    # the same fusion for the rest of the step contract (eta, prediction_type): one HIP kernel, sigma and the direction
+                    # coefficient from the host tables, this step's pre-drawn noise
+                    a_t, a_prev, sigma, dir_coeff = self.scheduler.step_coefficients(t, eta)
+                    new_latents = torch.empty_like(latents)
+                    z = step_noise[i] if (step_noise is not None and sigma > 0.0) else None
+                    _lib.check(lib.nr_cfg_ddim_step_ex(torch.cuda.current_stream().cuda_stream, noise_pred.data_ptr(), latents.data_ptr(),
+                                                       new_latents.data_ptr(), None, n_lat, float(guidance_scale),
+                                                       1 if do_classifier_free_guidance else 0,
+                                                       PREDICTION_TYPES[self.scheduler.config.prediction_type],
+                                                       1 if self.scheduler.config.clip_sample else 0, 0, a_t, a_prev, sigma, dir_coeff,
+                                                       None if z is None else z.data_ptr()))
+                    latents = new_latents
+                elif own_scheduler:
                     # CFG combine + DDIM step fused in one HIP kernel (reference: :478-483)
                     a_t, a_prev = self.scheduler.alpha_pair(t)
                     new_latents = torch.empty_like(latents)

@@ -8,8 +8,9 @@ as in diffusers' ``step``) — parity for this class is *unpinned* by any refere
 against the in-repo sibling ``animatediff/utils/util.py:211-221`` (``next_step``) in tests/.
 
 Only table construction / coefficient selection happens here (host logic).  The per-element update runs in
-the HIP kernel ``nr_cfg_ddim_step`` (include/neurons_amd.h); ``step`` refuses CPU tensors.
+the HIP kernels behind ``nr_cfg_ddim_step`` / ``nr_cfg_ddim_step_ex`` (include/neurons_amd.h); ``step`` refuses CPU tensors.
 """
+import math
 from dataclasses import dataclass
 from types import SimpleNamespace
 
@@ -21,6 +22,28 @@ import torch
 class DDIMSchedulerOutput:
     prev_sample: torch.Tensor
     pred_original_sample: torch.Tensor = None
+
+
+PREDICTION_TYPES = {"epsilon": 0, "sample": 1, "v_prediction": 2}      # NR_DDIM_* of include/neurons_amd.h
+
+
+def betas_for_alpha_bar(num_diffusion_timesteps, max_beta=0.999):
+    """The cosine schedule ("squaredcos_cap_v2"; Nichol & Dhariwal 2021 eq. 17): alpha_bar(s) = cos((s + 0.008) / 1.008 * pi / 2) ** 2,
+    beta_i = min(1 - alpha_bar((i + 1) / T) / alpha_bar(i / T), max_beta)."""
+    def alpha_bar(s):
+        return math.cos((s + 0.008) / 1.008 * math.pi / 2) ** 2
+    T = num_diffusion_timesteps
+    return torch.tensor([min(1 - alpha_bar((i + 1) / T) / alpha_bar(i / T), max_beta) for i in range(T)], dtype=torch.float32)
+
+
+def ddim_sigma_dir(a_t, a_prev, eta):
+    """(sigma, dir_coeff) of one DDIM step in double: sigma = eta sqrt((1 - a_prev) / (1 - a_t) (1 - a_t / a_prev)) (Song et al. 2021 eq. 16),
+    dir_coeff = sqrt(1 - a_prev - sigma^2).  eta = 0 gives (0, sqrt(1 - a_prev)) exactly; the last step (a_prev = 1) gives (0, 0)."""
+    if eta == 0.0:
+        return 0.0, math.sqrt(1.0 - a_prev)
+    variance = (1.0 - a_prev) / (1.0 - a_t) * (1.0 - a_t / a_prev)
+    sigma = float(eta) * math.sqrt(max(variance, 0.0))
+    return sigma, math.sqrt(max(1.0 - a_prev - sigma * sigma, 0.0))
 
 
 class DDIMScheduler:
@@ -36,10 +59,12 @@ class DDIMScheduler:
             betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
         elif beta_schedule == "scaled_linear":
             betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        elif beta_schedule == "squaredcos_cap_v2":
+            betas = betas_for_alpha_bar(num_train_timesteps)
         else:
             raise NotImplementedError(f"{beta_schedule} does is not implemented for {self.__class__}")
-        if prediction_type != "epsilon":
-            raise NotImplementedError("only epsilon prediction is on the NEURONS path")
+        if prediction_type not in PREDICTION_TYPES:
+            raise ValueError(f"prediction_type given as {prediction_type} must be one of `epsilon`, `sample`, or `v_prediction`")
         self.betas = betas
         self.alphas = 1.0 - betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
@@ -78,6 +103,18 @@ class DDIMScheduler:
         a_prev = float(self.alphas_cumprod[prev_t]) if prev_t >= 0 else float(self.final_alpha_cumprod)
         return a_t, a_prev
 
+    def step_coefficients(self, timestep, eta=0.0):
+        """(alpha_prod_t, alpha_prod_t_prev, sigma, dir_coeff) as python floats for integer ``timestep``: everything the fused CFG + DDIM kernel
+        needs from the host, without a device sync (see ``ddim_sigma_dir``)."""
+        a_t, a_prev = self.alpha_pair(timestep)
+        sigma, dir_coeff = ddim_sigma_dir(a_t, a_prev, eta)
+        return a_t, a_prev, sigma, dir_coeff
+
+    @property
+    def is_default_rule(self):
+        """epsilon prediction without clipping: with eta = 0 the update the pipeline issues as plain ``nr_cfg_ddim_step``."""
+        return self.config.prediction_type == "epsilon" and not self.config.clip_sample
+
     def add_noise(self, original_samples, noise, timesteps):
         ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
         timesteps = timesteps.to(original_samples.device)
@@ -93,17 +130,27 @@ class DDIMScheduler:
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True):
-        if eta != 0.0:
-            raise NotImplementedError("the NEURONS path runs DDIM with eta = 0 (pipeline_neuroclips.py:331)")
-        if self.config.clip_sample:
-            raise NotImplementedError("clip_sample=True is not on the NEURONS path (inference-v3.yaml:21)")
+        """diffusers 0.11.1 ``DDIMScheduler.step``: eta, use_clipped_model_output, generator / variance_noise, config.clip_sample and
+        config.prediction_type are honoured; ``pred_original_sample`` is returned.  The arithmetic runs in HIP (nr_cfg_ddim_step_ex)."""
+        if generator is not None and variance_noise is not None:
+            raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                             " `variance_noise` stays `None`.")
         if not (model_output.is_cuda and sample.is_cuda):
-            raise RuntimeError("DDIMScheduler.step runs in the HIP kernel nr_cfg_ddim_step: CUDA (ROCm) tensors required, "
-                               "there is no CPU fallback")
+            # a RuntimeError by class (callers that catch the library's errors) that also says what it is: not implemented on the CPU
+            raise NotImplementedError("DDIMScheduler.step runs in the HIP kernel nr_cfg_ddim_step: CUDA (ROCm) tensors required, "
+                                      "there is no CPU fallback")
         from . import ops
         a_t, a_prev = self.alpha_pair(timestep)
-        prev = ops.cfg_ddim_step(model_output.float().contiguous(), sample.float().contiguous(), 1.0, a_t, a_prev,
-                                 do_cfg=False).to(sample.dtype)
+        if eta > 0 and variance_noise is None:
+            # drawn as diffusers draws it: once per step whenever eta > 0 (the last step, where sigma = 0, included), in the model output's
+            # shape and dtype on its device
+            variance_noise = torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+        noise = variance_noise.to(device=sample.device, dtype=torch.float32).contiguous() if variance_noise is not None else None
+        prev, x0 = ops.cfg_ddim_step(model_output.float().contiguous(), sample.float().contiguous(), 1.0, a_t, a_prev, do_cfg=False,
+                                     prediction_type=self.config.prediction_type, clip_sample=bool(self.config.clip_sample),
+                                     use_clipped_model_output=bool(use_clipped_model_output), eta=eta, noise=noise,
+                                     return_pred_original=True)
+        prev, x0 = prev.to(sample.dtype), x0.to(sample.dtype)
         if not return_dict:
             return (prev,)
-        return DDIMSchedulerOutput(prev_sample=prev)
+        return DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
