@@ -14,7 +14,7 @@
 // O^T = V^T P^T needs (k-slot permutation applied identically to both operands), i.e. P never leaves
 // registers.  Row max / row sum are two xor-shuffles across the 4 lane groups.  V tiles are staged
 // transposed in a per-wave LDS region.
-#include "common.h"
+#include "launchers.h"
 
 namespace {
 

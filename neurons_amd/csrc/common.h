@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
+#include <cstring>
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -184,3 +186,79 @@ struct NrAddMulti {
   long long n8_end[16];    // exclusive prefix sums of the tensors' sizes in 16-byte units
   int count;
 };
+
+// ----------------------------------------------------------------------------------------------
+// Descriptor builders (host only): the one place each launch struct above is filled.  The engine's planner and the op-level hooks
+// (nr_op_*) both call them; fields a builder does not take stay zero and are set by the caller (rowvec, ln_c, plan_m, ...).
+// ----------------------------------------------------------------------------------------------
+
+// output size of a conv: 1x1 keeps H x W; 3x3 (pad 1) after the optional nearest-2x upsample, then stride
+inline void nr_conv_out_hw(int H, int W, int ksize, int stride, int ups, int* OH, int* OW) {
+  *OH = H; *OW = W;
+  if (ksize == 3) {
+    if (ups) { *OH *= 2; *OW *= 2; }
+    if (stride == 2) { *OH = (*OH - 1) / 2 + 1; *OW = (*OW - 1) / 2 + 1; }
+  }
+}
+
+// 1x1 / 3x3 conv over nimg images of H x W pixels (a plain GEMM of M rows: nimg = M, H = W = 1); out_scale = 1 and rowvec_div = 1
+inline NrGemmParams nr_gemm_params(const bf16* a0, int c0, int lda0, const bf16* a1, int c1, int lda1, int nimg, int H, int W, int ksize, int stride,
+                                   int ups, const bf16* w, int N, const float* bias, const bf16* res, int ldr, bf16* out, int ldo) {
+  NrGemmParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.a0 = a0; p.c0 = c0; p.lda0 = lda0;
+  p.a1 = a1; p.c1 = a1 ? c1 : 0; p.lda1 = lda1;
+  p.H = H; p.W = W;
+  nr_conv_out_hw(H, W, ksize, stride, ups, &p.OH, &p.OW);
+  p.ksize = ksize; p.stride = stride; p.ups = ups;
+  p.w = w;
+  p.M = nimg * p.OH * p.OW; p.N = N; p.K = ksize * ksize * (p.c0 + p.c1);
+  p.bias = bias; p.rowvec_div = 1;
+  p.res = res; p.ldr = ldr;
+  p.out = out; p.ldo = ldo; p.out_scale = 1.f;
+  return p;
+}
+
+// mode 0 spatial self (q|k|v fused, row stride ldq, hw tokens per image); 1 cross (q rows of ldq, k|v rows of ldkv, Lk keys, image n reads
+// context n / kv_div); 2 temporal self (q|k|v fused, `frames` tokens per pixel)
+inline NrAttnParams nr_attn_params(int mode, const bf16* q, const bf16* kv, bf16* out, int ldq, int ldkv, int ldo, int nimg, int hw, int Lk, int C,
+                                   int heads, int frames, int kv_div, int causal, int fp8) {
+  NrAttnParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.heads = heads; p.d = C / heads; p.scale = 1.0f / std::sqrt((float)p.d);
+  p.out = out; p.causal = causal; p.fp8 = fp8;
+  if (mode == 0) {
+    p.q = q; p.k = q + C; p.v = q + 2 * C;
+    p.nbatch = nimg; p.Lq = hw; p.Lk = hw;
+    p.inner = 1; p.q_outer = (long long)hw * ldq; p.q_inner_stride = 0; p.q_seq = ldq;
+    p.kv_inner = 1; p.kv_outer = p.q_outer; p.kv_inner_stride = 0; p.kv_seq = ldq; p.kv_div = 1;
+    p.o_outer = (long long)hw * ldo; p.o_inner_stride = 0; p.o_seq = ldo;
+  } else if (mode == 1) {
+    p.q = q; p.k = kv; p.v = kv + C;
+    p.nbatch = nimg; p.Lq = hw; p.Lk = Lk;
+    p.inner = 1; p.q_outer = (long long)hw * ldq; p.q_inner_stride = 0; p.q_seq = ldq;
+    p.kv_inner = 1; p.kv_outer = (long long)Lk * ldkv; p.kv_inner_stride = 0; p.kv_seq = ldkv; p.kv_div = kv_div;
+    p.o_outer = (long long)hw * ldo; p.o_inner_stride = 0; p.o_seq = ldo;
+  } else {
+    const int F = frames;
+    p.q = q; p.k = q + C; p.v = q + 2 * C;
+    p.nbatch = (nimg / F) * hw; p.Lq = F; p.Lk = F;
+    p.inner = hw; p.q_outer = (long long)F * hw * ldq; p.q_inner_stride = ldq; p.q_seq = (long long)hw * ldq;
+    p.kv_inner = hw; p.kv_outer = p.q_outer; p.kv_inner_stride = ldq; p.kv_seq = p.q_seq; p.kv_div = 1;
+    p.o_outer = (long long)F * hw * ldo; p.o_inner_stride = ldo; p.o_seq = (long long)hw * ldo;
+  }
+  return p;
+}
+
+// sources, shape, affine and output of a GroupNorm; the chunking (plan_nimg, pix_per_blk, nchunk) is the launcher's, `partial` its scratch
+inline NrGnParams nr_gn_params(const bf16* x0, int c0, int ld0, const bf16* x1, int c1, int ld1, int nimg, int hw, int groups, const float* gamma,
+                               const float* beta, float eps, int silu, float* partial, bf16* out, int ldo) {
+  NrGnParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.x0 = x0; p.c0 = c0; p.ld0 = ld0;
+  p.x1 = x1; p.c1 = x1 ? c1 : 0; p.ld1 = ld1;
+  p.nimg = nimg; p.hw = hw; p.groups = groups; p.partial = partial;
+  p.gamma = gamma; p.beta = beta; p.eps = eps; p.silu = silu;
+  p.out = out; p.ldo = ldo;
+  return p;
+}

@@ -9,7 +9,7 @@
 //   add_bf16        : out = a + b (ControlNet residual adds, unet.py:425-428,436-439)
 //   condembed_*     : the SparseCtrl image-condition embedding (end of this file): a first conv from the fp32 condition planes, the
 //                     small-channel 3x3 convs on MFMA (implicit GEMM, K = 9 Cin <= 864) and the batch / frame broadcast
-#include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -13,7 +13,7 @@
 //   ResnetBlock3D                       animatediff/models/resnet.py:182-212
 //   Transformer3DModel / BasicTransformerBlock   animatediff/models/attention.py:95-142,256-300
 //   TemporalTransformer3DModel / Block / VersatileAttention   animatediff/models/motion_module.py:134-158,210-222,270-329
-#include "common.h"
+#include "launchers.h"
 #include "../../include/neurons_amd.h"
 
 #include <algorithm>
@@ -27,109 +27,6 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
-
-extern "C" {
-int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStream_t stream);
-size_t nr_igemm_workspace_bytes(const NrGemmParams* pp);
-// lin160.hip: short-K Linears (K = 640 / 1280, N % 160 == 0, >= 2048 rows) on fragment-major weights
-size_t nr_lin160_stream_bytes(int N, int K);
-int nr_lin160_eligible(const NrGemmParams* pp);
-int nr_lin160_panel_rule(int Mp, int N, int K);
-size_t nr_lin128q_stream_bytes(int N, int K);
-int nr_launch_lin128q_w_pack(const bf16* w, int N, int K, bf16* stream, hipStream_t s);
-int nr_launch_lin160_w_pack(const bf16* w, int N, int K, bf16* stream, hipStream_t s);
-int nr_launch_lin160(const NrGemmParams* pp, const bf16* stream, hipStream_t s);
-int nr_gn_workspace_floats(int nimg, int hw, int groups, int* pix_per_blk_out, int* nchunk_out);
-int nr_launch_groupnorm(NrGnParams* pp, hipStream_t stream);
-int nr_launch_layernorm(const bf16* x, int ldx, bf16* out, int ldo, int M, int C, const float* gamma, const float* beta,
-                        float eps, const float* pe, int pe_hw, int pe_F, hipStream_t stream);
-int nr_launch_attention(const NrAttnParams* pp, hipStream_t stream);
-int nr_launch_conv_in_small(const float* s0, const float* s1, int c0, int c1, int src_batch, int nimg, int F, int H, int W,
-                            const float* wT, const float* bias, const float* addend, int Cout, bf16* out, float in_scale,
-                            float in_shift, hipStream_t stream);
-int nr_launch_clip_embed(const int* ids, const float* tok, const float* pos, bf16* out, int M, int L, int C, int vocab,
-                         hipStream_t stream);
-int nr_launch_bf16_to_f32(const bf16* a, float* out, long long n, hipStream_t stream);
-int nr_launch_gaussian_sample(const float* moments, const float* noise, float* out, int n, int zc, int hw, float scale,
-                              hipStream_t stream);
-int nr_launch_post_quant(const float* z, float scale, const float* Q, const float* qb, float* out, int nimg, int C, int hw,
-                         hipStream_t stream);
-int nr_launch_softmax_rows(const float* S, bf16* P, int rows, int L, float scale, hipStream_t stream);
-int nr_launch_conv_out_small(const bf16* x, int Cin, int nimg, int F, int H, int W, const bf16* w, const float* bias,
-                             int Cout, float* out, float out_mul, float out_add, int clamp01, hipStream_t stream);
-int nr_launch_timestep_sincos(const float* t, int M, int dim, float* out, hipStream_t stream);
-int nr_launch_linear_small(const float* x, int M, int K, const bf16* W, const float* b, int N, int in_act, int out_act,
-                           float* y, const float* addend, hipStream_t stream);
-int nr_launch_edm_cfg_euler(const float* net, const float* x, float* x_out, long long total, float scale, float sigma_q,
-                            float sigma, float sigma_next, hipStream_t stream);
-int nr_launch_cfg_combine(const float* eps, float* out, long long total, float guidance, hipStream_t stream);
-int nr_launch_cfg_ddim_step(const float* eps, const float* x, float* x_out, long long total, float guidance, int do_cfg,
-                            float sqrt_at, float sqrt_1mat, float sqrt_ap, float sqrt_1map, hipStream_t stream);
-int nr_launch_cfg_ddim_full(const float* eps, const float* x, const float* noise, float* x_out, float* x0_out, long long total, float guidance,
-                            int do_cfg, int pred, int clip, int clipped_out, float sqrt_at, float sqrt_1mat, float sqrt_ap, float dir, float sigma,
-                            hipStream_t stream);
-int nr_launch_add_bf16(const bf16* a, const bf16* b, bf16* out, long long n, hipStream_t stream);
-int nr_launch_prior_p_sample(const float* pred, const float* pred_null, const float* x, const float* noise, float* x_out, float* x_start_out,
-                             long long total, float cond_scale, int mode, int clamp, float sqrt_ac, float sqrt_1mac, float sqrt_recip_ac,
-                             float sqrt_recipm1_ac, float coef1, float coef2, float sigma, hipStream_t stream);
-int nr_launch_f32_to_bf16(const float* a, bf16* out, long long n, hipStream_t stream);
-int nr_launch_add_bf16_multi(const NrAddMulti* p, hipStream_t stream);
-int nr_launch_frame_gather(const bf16* src, bf16* dst, int B, int Fs, int Fd, long long frame_elems, const int* map, hipStream_t stream);
-int nr_launch_ncfhw_to_nhwc(const float* src, bf16* dst, int B, int C, int F, int HW, hipStream_t stream);
-int nr_launch_nhwc_to_ncfhw(const bf16* src, float* dst, int B, int C, int F, int HW, hipStream_t stream);
-int nr_groupnorm_launches(const NrGnParams* p);
-int nr_launch_fold_linear_pair(const float* w2, const float* w1, const float* b2, const float* b1, int C, int J, bf16* wc, float* bc,
-                               hipStream_t stream);
-// smallm.hip: panel-resident kernel of the M <= 512 Linears (fragment-major weights)
-int nr_smallm_eligible(const NrGemmParams* pp);
-int nr_launch_smallm_w_pack(const void* w, void* out, int N, int K, hipStream_t stream);
-// tattn.hip: one kernel per temporal-attention block of the C = 320 level
-size_t nr_xattn_wstream_bytes(void);
-size_t nr_xattn_kvstream_bytes(int nctx);
-int nr_xattn_fused_eligible(int C, int heads, int Lk, int hw, long long rows);
-int nr_launch_xattn_w_pack(const bf16* wq, const bf16* wo, bf16* stream, hipStream_t s);
-int nr_launch_xattn_kv_pack(const bf16* kv, int ldkv, int Lk, int nctx, bf16* stream, hipStream_t s);
-int nr_launch_xattn_fused(bf16* t, int nimg, int hw, int img_per_ctx, int nctx, int Lk, const bf16* wstream, const bf16* kvstream, const float* gamma,
-                          const float* beta, const float* bo, float ln_eps, int norot, hipStream_t s);
-size_t nr_tattn_stream_bytes(void);
-int nr_tattn_fused_eligible(int C, int heads, int frames, int hw, long long rows);
-int nr_launch_tattn_stream_pack(const bf16* wq, const bf16* wk, const bf16* wv, const bf16* wo, bf16* stream, hipStream_t s);
-int nr_launch_tattn_fused(bf16* t, int nbatch, int frames, int hw, const bf16* stream, const float* gamma, const float* gb, const float* bo, float ln_eps,
-                          int norot, hipStream_t s);
-// xattnw.hip: q projection + context attention per (64 rows, 160 columns) above the C = 320 level (C = 640 / 1280, <= 80 text tokens)
-size_t nr_xattnw_wstream_bytes(int C);
-size_t nr_xattnw_kvstream_bytes(int C, int nctx);
-size_t nr_xattnw_table_bytes(int C);
-int nr_xattnw_eligible(int C, int heads, int Lk, int hw, long long rows);
-int nr_launch_xattnw_w_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s);
-int nr_launch_xattnw_table_pack(const float* lnc, const float* bias, int C, float* table, hipStream_t s);
-int nr_launch_xattnw_kv_pack(const bf16* kv, int ldkv, int Lk, int nctx, int C, bf16* kvs, hipStream_t s);
-int nr_launch_xattnw(const bf16* t, bf16* out, int nimg, int hw, int img_per_ctx, int nctx, int Lk, int C, const bf16* wstream, const bf16* kvstream,
-                     const float* table, float ln_eps, hipStream_t s);
-// tattnw.hip: q|k|v projection of one head + F x F attention per (pixel group, head) above the C = 320 level (C = 640 / 1280, F = 16 / 32)
-size_t nr_tattnw_stream_bytes(int C);
-int nr_tattnw_eligible(int C, int heads, int frames, int hw, long long rows);
-int nr_launch_tattnw_stream_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s);
-size_t nr_tattnw_table_bytes(int C, int frames);
-int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, const float* rowvec, int C, int frames, float* table, hipStream_t s);
-int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int frames, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s);
-// ffpanel.hip: fused FeedForward(GEGLU) + proj_out of the C = 320 level
-size_t nr_ff_stream_bytes(int C);
-int nr_ff_fused_eligible(int C, long long M);
-int nr_launch_ff_stream_pack(const bf16* w1, const bf16* wc, bf16* stream, hipStream_t s);
-int nr_launch_ff_fused(const bf16* t, int ldt, const bf16* x, int ldx, bf16* out, int ldo, int M, const bf16* stream, const float* gamma,
-                       const float* beta, const float* b1, const float* bc, float ln_eps, int norot, hipStream_t s);
-// elementwise.hip condembed_*: SparseCtrl image-condition embedding (first conv from the fp32 planes, small-channel MFMA convs, batch / frame broadcast)
-int nr_condembed_in_supported(int cin, int Cout);
-int nr_launch_condembed_in(const float* cond, const float* mask, int c0, int nsrc, int F, int H, int W, const int* fmap, int Fe,
-                           const float* wT, const float* bias, int Cout, bf16* out, hipStream_t s);
-int nr_condembed_conv_supported(int Cin, int stride, int Cout);
-long long nr_condembed_wfm_elems(int Cin, int Cout);
-int nr_launch_condembed_conv(const bf16* x, int nimg, int H, int W, int Cin, int stride, const bf16* wfm, const float* bias, int Cout,
-                             int silu, bf16* out, hipStream_t s);
-int nr_launch_condembed_bcast(const bf16* emb, int cb, int Fe, const int* emap, int B, int F, long long img_elems, const bf16* add,
-                              bf16* out, hipStream_t s);
-}
 
 namespace {
 
@@ -169,6 +66,30 @@ inline uint16_t f2bf_host(float f) {
   if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;  // NaN stays NaN
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
+}
+
+// GEGLU row order of the kernels: each 32-row group is 16 value rows, then their 16 gate rows.  Source row of output row n of a
+// [2 * inner][K] projection (value rows [0, inner), gate rows [inner, 2 * inner))
+inline int geglu_src_row(int n, int inner) {
+  const int q = n / 32, j = n % 32;
+  return j < 16 ? q * 16 + j : inner + q * 16 + (j - 16);
+}
+// sinusoidal position table [max_len][C] (motion_module.py:225-239), fp32 throughout
+inline std::vector<float> sinusoid_table(int max_len, int C) {
+  std::vector<float> h((size_t)max_len * C);
+  const float k = (float)(-std::log(10000.0) / (double)C);
+  for (int pos = 0; pos < max_len; ++pos)
+    for (int i = 0; i < C; i += 2) {
+      const float a = (float)pos * std::exp((float)i * k);
+      h[(size_t)pos * C + i] = std::sin(a);
+      if (i + 1 < C) h[(size_t)pos * C + i + 1] = std::cos(a);
+    }
+  return h;
+}
+
+inline bool env_is_1(const char* name) {
+  const char* v = getenv(name);
+  return v && v[0] == '1';
 }
 
 struct HostTensor {
@@ -236,26 +157,34 @@ struct Act {
 struct Tap { std::string name; bf16* ptr; int64_t rows; int C, ld; };
 
 struct IO {
-  const float* sample = nullptr;
-  const float* ctx = nullptr;
-  float* out = nullptr;
-  const void* down_res[16] = {nullptr};
-  const void* mid_res = nullptr;
-  int has_res = 0;
-  const float* cond = nullptr;
-  const float* mask = nullptr;
-  int cond_batch = 1;
-  float scale = 1.f;
-  void* out_down[16] = {nullptr};
-  void* out_mid = nullptr;
-  const float* y = nullptr;     // sgm "vector" conditioning
-  float in_scale = 1.f;         // sgm c_in; VAE: 1 / scale_factor
-  const int* ids = nullptr;             // CLIP text encoder: token ids [batch][L]
-  float in_shift = 0.f;                 // VAE encoder: x * in_scale + in_shift fused into conv_in
-  float out_mul = 1.f, out_add = 0.f;   // VAE: image post-scaling fused into conv_out
-  int clamp01 = 0;
+  const float* sample;
+  const float* ctx;
+  float* out;
+  const void* down_res[16];
+  const void* mid_res;
+  int has_res;
+  const float* cond;
+  const float* mask;
+  int cond_batch;
+  float scale;
+  void* out_down[16];
+  void* out_mid;
+  const float* y;               // sgm "vector" conditioning
+  float in_scale;               // sgm c_in; VAE: 1 / scale_factor
+  const int* ids;               // CLIP text encoder: token ids [batch][L]
+  float in_shift;               // VAE encoder: x * in_scale + in_shift fused into conv_in
+  float out_mul, out_add;       // VAE: image post-scaling fused into conv_out
+  int clamp01;
   bool operator==(const IO& o) const { return std::memcmp(this, &o, sizeof(IO)) == 0; }
 };
+// The IO every forward entry point starts from: all bytes zero (padding too: operator== is a memcmp and IO is the graph-cache key) and the
+// defaults the networks share, so one set of pointers gives one key whichever entry point it came through
+inline IO new_io() {
+  IO io;
+  std::memset(&io, 0, sizeof(io));
+  io.scale = 1.f; io.in_scale = 1.f; io.out_mul = 1.f; io.cond_batch = 1;
+  return io;
+}
 
 __global__ void copy16_kernel(const uint4* __restrict__ a, uint4* __restrict__ b, long long n16) {   // debug snapshots only
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -273,9 +202,9 @@ __global__ void set_timesteps_kernel(float* dst, TimestepVals tv, int n) {
 struct nr_net {
   nr_net_config cfg;
   std::map<std::string, HostTensor> host;
-  std::map<std::string, void*> dev;  // converted weights by derived name
-  std::map<std::string, size_t> dev_bytes;
-  size_t weight_bytes = 0;
+  struct DevW { void* ptr; size_t bytes; };
+  std::map<std::string, DevW> dev;   // converted weights by derived name: changed only by adopt() / erase()
+  size_t weight_bytes = 0;           // sum of dev[].bytes (what is resident)
   // converted weights received from another handle (nr_net_import_weights): ONE device allocation, dev[] points into it
   char* import_base = nullptr;
   size_t import_bytes = 0;
@@ -321,7 +250,7 @@ struct nr_net {
   int cond_frames[64] = {0};
   bool cfg_dup = false;          // nr_net_set_cfg_pair_identical: the caller promises sample[b] == sample[b + B2/2] and timestep[b] == timestep[b + B2/2]
   bool attn_fp8 = false;         // nr_net_set_attention_fp8: spatial / cross attention on e4m3 MFMA operands (config 5)
-  IO io;
+  IO io = new_io();
   int n_res = 0;
   struct ResShape { int C, h, w; };
   std::vector<ResShape> res_shapes;  // n_res down + 1 mid
@@ -335,7 +264,7 @@ struct nr_net {
   // [0] ops before the ControlNet-residual adds, [1] the adds, [2] the rest
   // captured graphs per segment, keyed by the IO block they were captured with (pointers are baked into the kernel nodes): the grouped
   // SparseCtrl schedule alternates between a few residual-buffer sets, each gets its own executable graph (small LRU)
-  struct GraphSlot { IO io; hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
+  struct GraphSlot { IO io = new_io(); hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
   static constexpr int NR_GRAPH_SLOTS = 64;     // the sgm Euler loop bakes c_in(sigma) into its graphs: one per step of a 38 / 50-step schedule
   std::vector<GraphSlot> gcache[3];
   unsigned long long gclock = 0;
@@ -347,14 +276,14 @@ struct nr_net {
   // not depend on the latents, only on the timestep / context / condition
   bool prefetch_valid = false;
   float prefetch_t[NR_MAX_BATCH] = {0};
-  IO prefetch_io;
+  IO prefetch_io = new_io();
   // graph replay happens on an engine-owned non-blocking stream (capture is illegal on the legacy default
   // stream PyTorch hands over); it is fenced to the caller's stream with two events per forward
   hipStream_t own_stream = nullptr;
   hipEvent_t ev_in = nullptr, ev_out = nullptr;
 
   ~nr_net() {
-    for (auto& kv : dev) if (kv.second && !in_import(kv.second)) (void)hipFree(kv.second);
+    while (!dev.empty()) erase(std::string(dev.begin()->first));
     if (import_base) (void)hipFree(import_base);
     if (arena_base) (void)hipFree(arena_base);
     drop_graphs();
@@ -393,61 +322,61 @@ struct nr_net {
     void* d = nullptr;
     HIP_OK(hipMalloc(&d, bytes));
     HIP_OK(hipMemcpy(d, data, bytes, hipMemcpyHostToDevice));
-    dev[name] = d;
-    dev_bytes[name] = bytes;
+    return adopt(name, d, bytes);
+  }
+  // the only place that inserts a converted buffer and adds it to the resident total
+  void* adopt(const std::string& name, void* d, size_t bytes) {
+    dev[name] = DevW{d, bytes};
     weight_bytes += bytes;
     return d;
   }
-  // frees a converted buffer that only fed another conversion (the packed weight streams of the fused kernels): it then neither stays
+  // the only place that removes one: frees it (unless it lies inside the imported arena) and takes it out of the resident total.  Also how
+  // a converted buffer that only fed another conversion (the packed weight streams of the fused kernels) goes again: it then neither stays
   // resident nor travels in the exported arena
-  void drop(const std::string& name) {
+  void erase(const std::string& name) {
     auto it = dev.find(name);
     if (it == dev.end()) return;
-    if (!in_import(it->second)) (void)hipFree(it->second);
-    auto ib = dev_bytes.find(name);
-    if (ib != dev_bytes.end()) { weight_bytes -= ib->second; dev_bytes.erase(ib); }
+    if (it->second.ptr && !in_import(it->second.ptr)) (void)hipFree(it->second.ptr);
+    weight_bytes -= it->second.bytes;
     dev.erase(it);
+  }
+  void drop(const std::string& name) { erase(name); }
+  // derived name of the converted matrix this pointer is
+  std::string name_of(const void* p, const char* who) const {
+    for (const auto& kv : dev) if (kv.second.ptr == p) return kv.first;
+    throw NrError(NR_ERR_STATE, std::string(who) + ": not a converted weight matrix");
   }
   template <class Fn>
   void* cached(const std::string& name, Fn make) {
     if (dry) return nullptr;
     auto it = dev.find(name);
-    if (it != dev.end()) return it->second;
+    if (it != dev.end()) return it->second.ptr;
     return make();
+  }
+  // a buffer a pack kernel fills on the device: fn(d) enqueues the kernel(s) on the null stream, which have run when this returns
+  template <class Fn>
+  void* packed(const std::string& name, size_t bytes, Fn fn) {
+    return cached(name, [&]() {
+      void* d = nullptr;
+      HIP_OK(hipMalloc(&d, bytes));
+      try { fn(d); HIP_OK(hipDeviceSynchronize()); }
+      catch (...) { (void)hipFree(d); throw; }
+      return adopt(name, d, bytes);
+    });
   }
   // fragment-major copy (smallm.hip) of a converted [N][K] weight matrix, cached as "fm:<its name>"; the row-major matrix stays (launches of
   // other row counts use it)
   const bf16* w_fragmajor(const bf16* w, int N, int K) {
-    std::string src;
-    for (const auto& kv : dev) if (kv.second == (const void*)w) { src = kv.first; break; }
-    if (src.empty()) throw NrError(NR_ERR_STATE, "w_fragmajor: not a converted weight matrix");
-    const std::string name = "fm:" + src;
-    return (const bf16*)cached(name, [&]() {
-      void* d = nullptr;
-      const size_t nb = (size_t)N * K * sizeof(bf16);
-      HIP_OK(hipMalloc(&d, nb));
-      LAUNCH_OK(nr_launch_smallm_w_pack(w, d, N, K, nullptr));
-      HIP_OK(hipDeviceSynchronize());
-      dev[name] = d; dev_bytes[name] = nb; weight_bytes += nb;
-      return d;
-    });
+    return (const bf16*)packed("fm:" + name_of(w, "w_fragmajor"), (size_t)N * K * sizeof(bf16),
+                               [&](void* d) { LAUNCH_OK(nr_launch_smallm_w_pack(w, d, N, K, nullptr)); });
   }
   // stage stream (lin160.hip) of a converted [N][K] weight matrix, cached as "l160:<its name>" ("l128:": the 128-column layout of the register-panel kernel);
   // the row-major matrix stays (other row counts use it)
   const bf16* w_lin160(const bf16* w, int N, int K, bool panel = false) {
-    std::string src;
-    for (const auto& kv : dev) if (kv.second == (const void*)w) { src = kv.first; break; }
-    if (src.empty()) throw NrError(NR_ERR_STATE, "w_lin160: not a converted weight matrix");
-    const std::string name = (panel ? "l128:" : "l160:") + src;
-    return (const bf16*)cached(name, [&]() {
-      void* d = nullptr;
-      const size_t nb = panel ? nr_lin128q_stream_bytes(N, K) : nr_lin160_stream_bytes(N, K);
-      if (!nb) throw NrError(NR_ERR_STATE, "w_lin160: shape has no stage stream");
-      HIP_OK(hipMalloc(&d, nb));
+    const size_t nb = panel ? nr_lin128q_stream_bytes(N, K) : nr_lin160_stream_bytes(N, K);
+    if (!nb) throw NrError(NR_ERR_STATE, "w_lin160: shape has no stage stream");
+    return (const bf16*)packed((panel ? "l128:" : "l160:") + name_of(w, "w_lin160"), nb, [&](void* d) {
       LAUNCH_OK(panel ? nr_launch_lin128q_w_pack(w, N, K, (bf16*)d, nullptr) : nr_launch_lin160_w_pack(w, N, K, (bf16*)d, nullptr));
-      HIP_OK(hipDeviceSynchronize());
-      dev[name] = d; dev_bytes[name] = nb; weight_bytes += nb;
-      return d;
     });
   }
   void check_shape(const std::string& key, const HostTensor& t, std::initializer_list<int64_t> want) const {
@@ -512,7 +441,7 @@ struct nr_net {
     {
       auto it = dev.find(nw), ic = dev.find(nc), ib = dev.find(nb);
       if (ic != dev.end() && ib != dev.end() && (it != dev.end() || !need_w)) {
-        r.w = it != dev.end() ? (const bf16*)it->second : nullptr; r.c = (const float*)ic->second; r.b = (const float*)ib->second;
+        r.w = it != dev.end() ? (const bf16*)it->second.ptr : nullptr; r.c = (const float*)ic->second.ptr; r.b = (const float*)ib->second.ptr;
         return r;
       }
       drop(nw); drop(nc); drop(nb);                                  // partly present (matrix dropped after a stream pack): rebuild all three
@@ -526,8 +455,7 @@ struct nr_net {
       const HostTensor& W = data_of(wkeys[mi]);
       const HostTensor* B = bkeys.empty() ? nullptr : &data_of(bkeys[mi]);
       for (int n = 0; n < rows_each; ++n) {
-        int src = n;
-        if (geglu) { const int q = n / 32, j = n % 32; src = j < 16 ? q * 16 + j : Neach + q * 16 + (j - 16); }
+        const int src = geglu ? geglu_src_row(n, Neach) : n;
         const float* wr = W.data.data() + (size_t)src * K;
         const size_t dst = mi * rows_each + n;
         double c = 0.0, b = B ? (double)B->data[src] : 0.0;
@@ -552,14 +480,7 @@ struct nr_net {
     for (auto& k : wkeys) name += k + "|";
     return (const float*)cached(name, [&]() {
       const size_t N = (size_t)Neach * wkeys.size();
-      std::vector<float> pe((size_t)max_len * K);
-      const float kk = (float)(-std::log(10000.0) / (double)K);
-      for (int pos = 0; pos < max_len; ++pos)
-        for (int i = 0; i < K; i += 2) {
-          const float a = (float)pos * std::exp((float)i * kk);
-          pe[(size_t)pos * K + i] = std::sin(a);
-          if (i + 1 < K) pe[(size_t)pos * K + i + 1] = std::cos(a);
-        }
+      const std::vector<float> pe = sinusoid_table(max_len, K);
       std::vector<float> rv((size_t)max_len * N);
       for (size_t mi = 0; mi < wkeys.size(); ++mi) {
         const HostTensor& W = data_of(wkeys[mi]);
@@ -591,28 +512,28 @@ struct nr_net {
     const std::string nb = "foldb:" + po + ".weight|" + po + ".bias|" + ff2 + ".weight|" + ff2 + ".bias";
     auto it = dev.find(nw);
     auto itb = dev.find(nb);
-    if (itb != dev.end() && (it != dev.end() || !need_w)) { r.w = it != dev.end() ? (const bf16*)it->second : nullptr; r.b = (const float*)itb->second; return r; }
+    if (itb != dev.end() && (it != dev.end() || !need_w)) { r.w = it != dev.end() ? (const bf16*)it->second.ptr : nullptr; r.b = (const float*)itb->second.ptr; return r; }
     if (itb != dev.end()) drop(nb);                                  // bias kept, matrix dropped after a stream pack: rebuild both
     const HostTensor& W2 = data_of(po + ".weight");
     const HostTensor& B2 = data_of(po + ".bias");
     const HostTensor& W1 = data_of(ff2 + ".weight");
     const HostTensor& B1 = data_of(ff2 + ".bias");
-    float *dw2 = nullptr, *dw1 = nullptr, *db2 = nullptr, *db1 = nullptr;
-    void *dwc = nullptr, *dbc = nullptr;
     const size_t wcb = (size_t)C * (C + J) * sizeof(bf16), bcb = (size_t)C * sizeof(float);
-    HIP_OK(hipMalloc(&dw2, W2.data.size() * 4)); HIP_OK(hipMalloc(&dw1, W1.data.size() * 4));
-    HIP_OK(hipMalloc(&db2, B2.data.size() * 4)); HIP_OK(hipMalloc(&db1, B1.data.size() * 4));
-    HIP_OK(hipMalloc(&dwc, wcb)); HIP_OK(hipMalloc(&dbc, bcb));
-    HIP_OK(hipMemcpy(dw2, W2.data.data(), W2.data.size() * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dw1, W1.data.data(), W1.data.size() * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(db2, B2.data.data(), B2.data.size() * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(db1, B1.data.data(), B1.data.size() * 4, hipMemcpyHostToDevice));
-    LAUNCH_OK(nr_launch_fold_linear_pair(dw2, dw1, db2, db1, C, J, (bf16*)dwc, (float*)dbc, nullptr));
-    HIP_OK(hipDeviceSynchronize());
-    (void)hipFree(dw2); (void)hipFree(dw1); (void)hipFree(db2); (void)hipFree(db1);
-    dev[nw] = dwc; dev_bytes[nw] = wcb; dev[nb] = dbc; dev_bytes[nb] = bcb;
-    weight_bytes += wcb + bcb;
-    r.w = (const bf16*)dwc; r.b = (const float*)dbc;
+    r.w = (const bf16*)packed(nw, wcb, [&](void* dwc) {
+      float *dw2 = nullptr, *dw1 = nullptr, *db2 = nullptr, *db1 = nullptr;
+      void* dbc = nullptr;
+      HIP_OK(hipMalloc(&dw2, W2.data.size() * 4)); HIP_OK(hipMalloc(&dw1, W1.data.size() * 4));
+      HIP_OK(hipMalloc(&db2, B2.data.size() * 4)); HIP_OK(hipMalloc(&db1, B1.data.size() * 4));
+      HIP_OK(hipMalloc(&dbc, bcb));
+      HIP_OK(hipMemcpy(dw2, W2.data.data(), W2.data.size() * 4, hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(dw1, W1.data.data(), W1.data.size() * 4, hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(db2, B2.data.data(), B2.data.size() * 4, hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(db1, B1.data.data(), B1.data.size() * 4, hipMemcpyHostToDevice));
+      LAUNCH_OK(nr_launch_fold_linear_pair(dw2, dw1, db2, db1, C, J, (bf16*)dwc, (float*)dbc, nullptr));
+      HIP_OK(hipDeviceSynchronize());
+      (void)hipFree(dw2); (void)hipFree(dw1); (void)hipFree(db2); (void)hipFree(db1);
+      r.b = (const float*)adopt(nb, dbc, bcb);
+    });
     return r;
   }
   // GEGLU projection [2*inner][K]: rows permuted so each 32-row group is 16 value rows then their 16 gate rows
@@ -623,8 +544,7 @@ struct nr_net {
       (void)data_of(key);
       std::vector<uint16_t> h((size_t)2 * inner * K);
       for (int n = 0; n < 2 * inner; ++n) {
-        const int q = n / 32, j = n % 32;
-        const int src = j < 16 ? q * 16 + j : inner + q * 16 + (j - 16);
+        const int src = geglu_src_row(n, inner);
         for (int k = 0; k < K; ++k) h[(size_t)n * K + k] = f2bf_host(t.data[(size_t)src * K + k]);
       }
       return upload("geglu:" + key, h.data(), h.size() * 2);
@@ -636,10 +556,7 @@ struct nr_net {
     return (const float*)cached("geglub:" + key, [&]() {
       (void)data_of(key);
       std::vector<float> h((size_t)2 * inner);
-      for (int n = 0; n < 2 * inner; ++n) {
-        const int q = n / 32, j = n % 32;
-        h[n] = t.data[j < 16 ? q * 16 + j : inner + q * 16 + (j - 16)];
-      }
+      for (int n = 0; n < 2 * inner; ++n) h[n] = t.data[geglu_src_row(n, inner)];
       return upload("geglub:" + key, h.data(), h.size() * 4);
     });
   }
@@ -731,15 +648,7 @@ struct nr_net {
   const float* pe_table(int C, int max_len) {
     const std::string name = "pe:" + std::to_string(C) + ":" + std::to_string(max_len);
     return (const float*)cached(name, [&]() {
-      std::vector<float> h((size_t)max_len * C);
-      const float k = (float)(-std::log(10000.0) / (double)C);
-      for (int pos = 0; pos < max_len; ++pos)
-        for (int i = 0; i < C; i += 2) {
-          const float div = std::exp((float)i * k);
-          const float a = (float)pos * div;
-          h[(size_t)pos * C + i] = std::sin(a);
-          if (i + 1 < C) h[(size_t)pos * C + i + 1] = std::cos(a);
-        }
+      const std::vector<float> h = sinusoid_table(max_len, C);
       return upload(name, h.data(), h.size() * 4);
     });
   }
@@ -806,31 +715,18 @@ struct nr_net {
 
   // generic conv / linear.  x1: optional channel-concat second source.
   Act conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksize, int stride, int ups, const GemmOpt& o) {
-    NrGemmParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.a0 = x0.ptr; p.c0 = x0.C; p.lda0 = x0.ld;
-    if (x1) { p.a1 = x1->ptr; p.c1 = x1->C; p.lda1 = x1->ld; }
-    p.H = x0.H; p.W = x0.W;
-    int OH = x0.H, OW = x0.W;
-    if (ksize == 3) {
-      if (ups) { OH *= 2; OW *= 2; }
-      if (stride == 2) { OH = (OH - 1) / 2 + 1; OW = (OW - 1) / 2 + 1; }
-    }
-    p.OH = OH; p.OW = OW; p.ksize = ksize; p.stride = stride; p.ups = ups;
-    p.w = w;
-    p.M = x0.nimg * OH * OW; p.N = Cout; p.K = ksize * ksize * (p.c0 + p.c1);
-    p.bias = o.bias; p.rowvec = o.rowvec; p.rowvec_div = o.rowvec_div; p.rowvec_ld = o.rowvec_ld; p.rowvec_mod = o.rowvec_mod;
+    int OH, OW;
+    nr_conv_out_hw(x0.H, x0.W, ksize, stride, ups, &OH, &OW);
+    const int outC = o.geglu ? Cout / 2 : Cout;
+    Act out = o.out ? *o.out : new_act(x0.nimg, OH, OW, outC);
+    if (out.C != outC || out.rows() != (int64_t)x0.nimg * OH * OW) throw NrError(NR_ERR_STATE, "conv: output shape mismatch");
+    if (o.res && (o.res->C != outC || o.res->rows() != out.rows())) throw NrError(NR_ERR_STATE, "conv: residual shape mismatch");
+    NrGemmParams p = nr_gemm_params(x0.ptr, x0.C, x0.ld, x1 ? x1->ptr : nullptr, x1 ? x1->C : 0, x1 ? x1->ld : 0, x0.nimg, x0.H, x0.W, ksize, stride, ups,
+                                    w, Cout, o.bias, o.res ? o.res->ptr : nullptr, o.res ? o.res->ld : 0, out.ptr, out.ld);
+    p.rowvec = o.rowvec; p.rowvec_div = o.rowvec_div; p.rowvec_ld = o.rowvec_ld; p.rowvec_mod = o.rowvec_mod;
     p.out_scale = o.scale; p.geglu = o.geglu; p.pad_tl0 = o.pad_tl0; p.act = o.act; p.ln_c = o.ln_c; p.ln_eps = 1e-5f;
     p.tap_inner = o.tap_inner;
     p.plan_m = det_batch ? (int)det_rows(p.M) : 0;
-    const int outC = o.geglu ? Cout / 2 : Cout;
-    Act out = o.out ? *o.out : new_act(x0.nimg, OH, OW, outC);
-    if (out.C != outC || out.rows() != p.M) throw NrError(NR_ERR_STATE, "conv: output shape mismatch");
-    if (o.res) {
-      if (o.res->C != outC || o.res->rows() != p.M) throw NrError(NR_ERR_STATE, "conv: residual shape mismatch");
-      p.res = o.res->ptr; p.ldr = o.res->ld;
-    }
-    p.out = out.ptr; p.ldo = out.ld;
     if (ksize == 1 && nr_smallm_eligible(&p))               // M <= 512 Linears: the panel-resident kernel reads fragment-major weights
       p.w_fm = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : w_fragmajor(w, Cout, p.K);
     if (const int l1 = (ksize == 1 && !p.w_fm) ? nr_lin160_eligible(&p) : 0) {
@@ -863,21 +759,18 @@ struct nr_net {
 
   Act groupnorm(const Act& x0, const Act* x1, const std::string& prefix, float eps, int silu) {
     const int C = x0.C + (x1 ? x1->C : 0);
-    NrGnParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.x0 = x0.ptr; p.c0 = x0.C; p.ld0 = x0.ld;
-    if (x1) { p.x1 = x1->ptr; p.c1 = x1->C; p.ld1 = x1->ld; }
-    p.nimg = x0.nimg; p.hw = x0.H * x0.W; p.groups = cfg.norm_num_groups;
-    p.gamma = w_f32(prefix + ".weight", C); p.beta = w_f32(prefix + ".bias", C);
-    p.eps = eps; p.silu = silu;
-    p.plan_nimg = det_batch ? (int)det_rows(p.nimg) : 0;
+    const float* gamma = w_f32(prefix + ".weight", C);
+    const float* beta = w_f32(prefix + ".bias", C);
+    const int hw = x0.H * x0.W, groups = cfg.norm_num_groups;
+    const int plan_nimg = det_batch ? (int)det_rows(x0.nimg) : 0;
     int nch = 0;
-    (void)nr_gn_workspace_floats(p.plan_nimg > 0 ? p.plan_nimg : p.nimg, p.hw, p.groups, nullptr, &nch);   // chunking as the launcher will choose it
-    const int nfl = p.nimg * (nch * p.groups * 2 + p.groups * 2);
+    (void)nr_gn_workspace_floats(plan_nimg > 0 ? plan_nimg : x0.nimg, hw, groups, nullptr, &nch);   // chunking as the launcher will choose it
+    const int nfl = x0.nimg * (nch * groups * 2 + groups * 2);
     auto ws = new_tmp((size_t)nfl * sizeof(float));
-    p.partial = at<float>(ws->off);
     Act out = new_act(x0.nimg, x0.H, x0.W, C);
-    p.out = out.ptr; p.ldo = out.ld;
+    NrGnParams p = nr_gn_params(x0.ptr, x0.C, x0.ld, x1 ? x1->ptr : nullptr, x1 ? x1->C : 0, x1 ? x1->ld : 0, x0.nimg, hw, groups, gamma, beta, eps, silu,
+                                at<float>(ws->off), out.ptr, out.ld);
+    p.plan_nimg = plan_nimg;
     if (getenv("NR_OP_TAPS") && keep_all && !x1) {     // debug: what the GroupNorm's input looked like when it ran
       Act snap = new_act(x0.nimg, x0.H, x0.W, x0.C);
       const bf16* src = x0.ptr; bf16* dst = snap.ptr; const size_t nb = (size_t)x0.rows() * x0.C * sizeof(bf16);
@@ -912,32 +805,9 @@ struct nr_net {
 
   // mode 0 spatial self (qkv fused [M][3C]); 1 cross (q [M][C], kv [B2*ctx][2C]); 2 temporal self (qkv fused)
   Act attention(int mode, const Act& q, const Act* kv, int C, int heads, int causal = 0) {
-    NrAttnParams p;
-    std::memset(&p, 0, sizeof(p));
-    const int hw = q.H * q.W;
-    const int d = C / heads;
     Act out = new_act(q.nimg, q.H, q.W, C);
-    p.heads = heads; p.d = d; p.scale = 1.0f / std::sqrt((float)d);
-    p.out = out.ptr; p.causal = causal; p.fp8 = (attn_fp8 && mode != 2) ? 1 : 0;
-    if (mode == 0) {
-      p.q = q.ptr; p.k = q.ptr + C; p.v = q.ptr + 2 * C;
-      p.nbatch = q.nimg; p.Lq = hw; p.Lk = hw;
-      p.inner = 1; p.q_outer = (long long)hw * q.ld; p.q_inner_stride = 0; p.q_seq = q.ld;
-      p.kv_inner = 1; p.kv_outer = p.q_outer; p.kv_inner_stride = 0; p.kv_seq = q.ld; p.kv_div = 1;
-      p.o_outer = (long long)hw * out.ld; p.o_inner_stride = 0; p.o_seq = out.ld;
-    } else if (mode == 1) {
-      p.q = q.ptr; p.k = kv->ptr; p.v = kv->ptr + C;
-      p.nbatch = q.nimg; p.Lq = hw; p.Lk = ctx_len;
-      p.inner = 1; p.q_outer = (long long)hw * q.ld; p.q_inner_stride = 0; p.q_seq = q.ld;
-      p.kv_inner = 1; p.kv_outer = (long long)ctx_len * kv->ld; p.kv_inner_stride = 0; p.kv_seq = kv->ld; p.kv_div = F;
-      p.o_outer = (long long)hw * out.ld; p.o_inner_stride = 0; p.o_seq = out.ld;
-    } else {
-      p.q = q.ptr; p.k = q.ptr + C; p.v = q.ptr + 2 * C;
-      p.nbatch = (q.nimg / F) * hw; p.Lq = F; p.Lk = F;
-      p.inner = hw; p.q_outer = (long long)F * hw * q.ld; p.q_inner_stride = q.ld; p.q_seq = (long long)hw * q.ld;
-      p.kv_inner = hw; p.kv_outer = p.q_outer; p.kv_inner_stride = q.ld; p.kv_seq = p.q_seq; p.kv_div = 1;
-      p.o_outer = (long long)F * hw * out.ld; p.o_inner_stride = out.ld; p.o_seq = (long long)hw * out.ld;
-    }
+    const NrAttnParams p = nr_attn_params(mode, q.ptr, kv ? kv->ptr : nullptr, out.ptr, q.ld, kv ? kv->ld : 0, out.ld, q.nimg, q.H * q.W, ctx_len, C, heads, F,
+                                          F, causal, (attn_fp8 && mode != 2) ? 1 : 0);
     {
       const double flops = 4.0 * (double)p.nbatch * p.heads * (double)p.Lq * p.Lk * p.d;
       const double kvrows = mode == 1 ? (double)(p.nbatch / p.kv_div) * p.Lk : (double)p.nbatch * p.Lk;
@@ -1088,22 +958,20 @@ struct nr_net {
       const float* beta = w_f32(ln + ".bias", C);
       const std::string sname = "ffs:" + ff + ".net.0.proj.weight|" + ff + ".net.2.weight|" + ff + ".net.2.bias|" + pre + ".proj_out.weight|" + pre +
                                 ".proj_out.bias";
-      const bf16* stream = (const bf16*)cached(sname, [&]() {
-        void* d = nullptr;
-        const size_t nb = nr_ff_stream_bytes(C);
-        // the two matrices the stream is packed from are only its inputs: the fused launch never reads them, so they are freed again
-        // (they neither stay resident nor travel in the exported arena); the folded bias stays
-        const bool had_w1 = dev.count("geglu:" + ff + ".net.0.proj.weight") != 0;
+      // the two matrices the stream is packed from are only its inputs: the fused launch never reads them, so they are freed again
+      // (they neither stay resident nor travel in the exported arena); the folded bias stays
+      bool made = false, had_w1 = false;
+      const bf16* stream = (const bf16*)packed(sname, nr_ff_stream_bytes(C), [&](void* d) {
+        had_w1 = dev.count("geglu:" + ff + ".net.0.proj.weight") != 0;
         const bf16* w1 = w_geglu(ff + ".net.0.proj.weight", inner, C);
         const FoldW fwm = w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C, true);
-        HIP_OK(hipMalloc(&d, nb));
         LAUNCH_OK(nr_launch_ff_stream_pack(w1, fwm.w, (bf16*)d, nullptr));
-        HIP_OK(hipDeviceSynchronize());
-        dev[sname] = d; dev_bytes[sname] = nb; weight_bytes += nb;
+        made = true;
+      });
+      if (made) {
         if (!had_w1) drop("geglu:" + ff + ".net.0.proj.weight");
         drop("foldw:" + pre + ".proj_out.weight|" + pre + ".proj_out.bias|" + ff + ".net.2.weight|" + ff + ".net.2.bias");
-        return d;
-      });
+      }
       const FoldW fw = w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C, false);
       Act out = new_act(x.nimg, x.H, x.W, C);
       const bf16* tp = t.ptr; const bf16* xp = x.ptr; bf16* op = out.ptr;
@@ -1191,21 +1059,16 @@ struct nr_net {
         ctx_persist.push_back(kvs);
         for (const char* wn : {".attn2.to_q.weight", ".attn2.to_out.0.weight"}) check_shape(b + wn, need(b + wn), {C, C});
         const std::string sname = "xas:" + b + ".attn2.to_q.weight|" + b + ".attn2.to_out.0.weight";
-        const bf16* wstream = (const bf16*)cached(sname, [&]() {
-          void* d = nullptr;
-          const size_t nb = nr_xattn_wstream_bytes();
-          // the two Linear matrices are only the inputs of the packed stream: freed again once it exists (unless another plan made them)
-          const bool had_q = dev.count("lin:" + b + ".attn2.to_q.weight") != 0, had_o = dev.count("lin:" + b + ".attn2.to_out.0.weight") != 0;
+        // the two Linear matrices are only the inputs of the packed stream: freed again once it exists (unless another plan made them)
+        bool had_q = true, had_o = true;
+        const bf16* wstream = (const bf16*)packed(sname, nr_xattn_wstream_bytes(), [&](void* d) {
+          had_q = dev.count("lin:" + b + ".attn2.to_q.weight") != 0; had_o = dev.count("lin:" + b + ".attn2.to_out.0.weight") != 0;
           const bf16* wq = w_linear(b + ".attn2.to_q.weight", C, C);
           const bf16* wo = w_linear(b + ".attn2.to_out.0.weight", C, C);
-          HIP_OK(hipMalloc(&d, nb));
           LAUNCH_OK(nr_launch_xattn_w_pack(wq, wo, (bf16*)d, nullptr));
-          HIP_OK(hipDeviceSynchronize());
-          dev[sname] = d; dev_bytes[sname] = nb; weight_bytes += nb;
-          if (!had_q) drop("lin:" + b + ".attn2.to_q.weight");
-          if (!had_o) drop("lin:" + b + ".attn2.to_out.0.weight");
-          return d;
         });
+        if (!had_q) drop("lin:" + b + ".attn2.to_q.weight");
+        if (!had_o) drop("lin:" + b + ".attn2.to_out.0.weight");
         const float* gamma = w_f32(b + ".norm2.weight", C);
         const float* beta = w_f32(b + ".norm2.bias", C);
         const float* bo = w_f32(b + ".attn2.to_out.0.bias", C);
@@ -1238,28 +1101,17 @@ struct nr_net {
         const std::string nrm = b + ".norm2", wq = b + ".attn2.to_q.weight";
         const std::string lnw_name = "lnw:" + nrm + "|" + wq + "|";
         const std::string sname = "xaws:" + nrm + "|" + wq;
-        const bf16* wstream = (const bf16*)cached(sname, [&]() {
-          void* d = nullptr;
-          const size_t nb = nr_xattnw_wstream_bytes(C);
-          const bool had = dev.count(lnw_name) != 0;       // the folded [C][C] matrix is only the input of the packed stream
+        bool had = true;       // the folded [C][C] matrix is only the input of the packed stream
+        const bf16* wstream = (const bf16*)packed(sname, nr_xattnw_wstream_bytes(C), [&](void* d) {
+          had = dev.count(lnw_name) != 0;
           const LnW lwm = w_ln_linear({wq}, {}, nrm, C, C, false, true);
-          HIP_OK(hipMalloc(&d, nb));
           LAUNCH_OK(nr_launch_xattnw_w_pack(lwm.w, C, (bf16*)d, nullptr));
-          HIP_OK(hipDeviceSynchronize());
-          dev[sname] = d; dev_bytes[sname] = nb; weight_bytes += nb;
-          if (!had) drop(lnw_name);
-          return d;
         });
+        if (!had) drop(lnw_name);
         const std::string tname = "xawt:" + nrm + "|" + wq;
-        const float* table = (const float*)cached(tname, [&]() {
+        const float* table = (const float*)packed(tname, nr_xattnw_table_bytes(C), [&](void* d) {
           const LnW lw = w_ln_linear({wq}, {}, nrm, C, C, false, false);
-          void* d = nullptr;
-          const size_t nb = nr_xattnw_table_bytes(C);
-          HIP_OK(hipMalloc(&d, nb));
           LAUNCH_OK(nr_launch_xattnw_table_pack(lw.c, lw.b, C, (float*)d, nullptr));
-          HIP_OK(hipDeviceSynchronize());
-          dev[tname] = d; dev_bytes[tname] = nb; weight_bytes += nb;
-          return d;
         });
         if (dry) (void)w_ln_linear({wq}, {}, nrm, C, C, false, false);      // shape checks in the sizing pass too
         Act a = new_act(t.nimg, t.H, t.W, C);
@@ -1315,33 +1167,23 @@ struct nr_net {
         const std::string nrm = b + ".norms." + std::to_string(k);
         for (const char* wn : {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"}) check_shape(ab + wn, need(ab + wn), {C, C});
         const std::string sname = "tas:" + ab + ".to_q.weight|" + ab + ".to_k.weight|" + ab + ".to_v.weight|" + ab + ".to_out.0.weight";
-        const bf16* stream = (const bf16*)cached(sname, [&]() {
-          void* d = nullptr;
-          const size_t nb = nr_tattn_stream_bytes();
-          // the four Linear matrices are only the inputs of the packed stream: freed again once it exists (unless another plan made them)
-          bool had[4]; const bf16* wm[4];
-          const char* wn[4] = {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"};
+        // the four Linear matrices are only the inputs of the packed stream: freed again once it exists (unless another plan made them)
+        bool had[4] = {true, true, true, true};
+        const char* wn[4] = {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"};
+        const bf16* stream = (const bf16*)packed(sname, nr_tattn_stream_bytes(), [&](void* d) {
+          const bf16* wm[4];
           for (int i = 0; i < 4; ++i) { had[i] = dev.count("lin:" + ab + wn[i]) != 0; wm[i] = w_linear(ab + wn[i], C, C); }
-          HIP_OK(hipMalloc(&d, nb));
           LAUNCH_OK(nr_launch_tattn_stream_pack(wm[0], wm[1], wm[2], wm[3], (bf16*)d, nullptr));
-          HIP_OK(hipDeviceSynchronize());
-          dev[sname] = d; dev_bytes[sname] = nb; weight_bytes += nb;
-          for (int i = 0; i < 4; ++i) if (!had[i]) drop("lin:" + ab + wn[i]);
-          return d;
         });
+        for (int i = 0; i < 4; ++i) if (!had[i]) drop("lin:" + ab + wn[i]);
         // gb[f][c] = LayerNorm bias + sinusoidal positional encoding of frame f (motion_module.py:225-243)
         check_shape(nrm + ".bias", need(nrm + ".bias"), {C});
         const std::string gname = "tagb:" + std::to_string(F) + ":" + nrm;
         const float* gb = (const float*)cached(gname, [&]() {
           const HostTensor& be = data_of(nrm + ".bias");
-          std::vector<float> h((size_t)F * C);
-          const float kk = (float)(-std::log(10000.0) / (double)C);
+          std::vector<float> h = sinusoid_table(F, C);
           for (int pos = 0; pos < F; ++pos)
-            for (int i = 0; i < C; i += 2) {
-              const float a = (float)pos * std::exp((float)i * kk);
-              h[(size_t)pos * C + i] = be.data[i] + std::sin(a);
-              if (i + 1 < C) h[(size_t)pos * C + i + 1] = be.data[i + 1] + std::cos(a);
-            }
+            for (int i = 0; i < C; ++i) h[(size_t)pos * C + i] = be.data[i] + h[(size_t)pos * C + i];
           return upload(gname, h.data(), h.size() * 4);
         });
         const float* gamma = w_f32(nrm + ".weight", C);
@@ -1365,32 +1207,21 @@ struct nr_net {
         const std::vector<std::string> wk = {ab + ".to_q.weight", ab + ".to_k.weight", ab + ".to_v.weight"};
         const float* rv = pe_projection(wk, C, C, cfg.motion_pe_max_len);
         const std::string sname = "taws:" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
-        const bf16* stream = (const bf16*)cached(sname, [&]() {
-          void* d = nullptr;
-          const size_t nb = nr_tattnw_stream_bytes(C);
-          // the folded [3C][C] matrix is only the input of the packed stream: freed again once it exists (unless another plan made it)
-          const std::string lnw_name = "lnw:" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2] + "|";
-          const bool had = dev.count(lnw_name) != 0;
+        // the folded [3C][C] matrix is only the input of the packed stream: freed again once it exists (unless another plan made it)
+        const std::string lnw_name = "lnw:" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2] + "|";
+        bool had = true;
+        const bf16* stream = (const bf16*)packed(sname, nr_tattnw_stream_bytes(C), [&](void* d) {
+          had = dev.count(lnw_name) != 0;
           const LnW lwm = w_ln_linear(wk, {}, nrm, C, C, false, true);
-          HIP_OK(hipMalloc(&d, nb));
           LAUNCH_OK(nr_launch_tattnw_stream_pack(lwm.w, C, (bf16*)d, nullptr));
-          HIP_OK(hipDeviceSynchronize());
-          dev[sname] = d; dev_bytes[sname] = nb; weight_bytes += nb;
-          if (!had) drop(lnw_name);
-          return d;
         });
+        if (!had) drop(lnw_name);
         // the head-major epilogue table (LayerNorm-fold vectors + positional-encoding projections of the first F positions) the kernel stages
         // through LDS: one per frame count a handle was planned with
         const std::string tname = "tawe:" + std::to_string(cfg.motion_pe_max_len) + ":" + std::to_string(F) + ":" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
-        const float* table = (const float*)cached(tname, [&]() {
+        const float* table = (const float*)packed(tname, nr_tattnw_table_bytes(C, F), [&](void* d) {
           const LnW lw = w_ln_linear(wk, {}, nrm, C, C, false, false);
-          void* d = nullptr;
-          const size_t nb = nr_tattnw_table_bytes(C, F);
-          HIP_OK(hipMalloc(&d, nb));
           LAUNCH_OK(nr_launch_tattnw_table_pack(lw.c, lw.b, rv, C, F, (float*)d, nullptr));
-          HIP_OK(hipDeviceSynchronize());
-          dev[tname] = d; dev_bytes[tname] = nb; weight_bytes += nb;
-          return d;
         });
         a = new_act(t.nimg, t.H, t.W, C);
         const bf16* tp = t.ptr; bf16* ap = a.ptr;
@@ -2287,7 +2118,7 @@ struct nr_net {
       // (a lowest-priority stream for SparseCtrl, meant to fill only the CUs the U-Net leaves free, measured neutral: 16.56 vs 16.53 frames/s)
       // NR_STREAM_PRIO=1 (A/B): SparseCtrl on the lowest-priority queue, the U-Net on the highest, so that under the grouped schedule the
       // pending group only takes the CUs the U-Net's small launches leave free
-      static const bool prio = getenv("NR_STREAM_PRIO") && getenv("NR_STREAM_PRIO")[0] == '1';
+      static const bool prio = env_is_1("NR_STREAM_PRIO");
       if (prio) {
         int lo = 0, hi = 0;
         HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi));     // lo = numerically greatest = lowest priority
@@ -2359,12 +2190,29 @@ struct nr_net {
     HIP_OK(hipGraphLaunch(hit->exec, s));
   }
 
+  // what every evaluation starts with on the stream it runs on
+  void begin(hipStream_t s, const float* timesteps) {
+    set_timesteps(s, timesteps);
+    run_context(s);
+  }
+  // eager evaluation: everything in stream order on s
+  void run_eager(hipStream_t s, const float* timesteps) {
+    begin(s, timesteps);
+    for (auto& op : ops) op(s);
+  }
+  // graph mode: the engine's own stream, fenced behind everything the caller enqueued so far (readers of the buffers, staged inputs)
+  hipStream_t begin_fenced(hipStream_t caller, const float* timesteps) {
+    HIP_OK(hipEventRecord(ev_in, caller));
+    HIP_OK(hipStreamWaitEvent(own_stream, ev_in, 0));
+    begin(own_stream, timesteps);
+    return own_stream;
+  }
+
   void run(hipStream_t caller, const float* timesteps) {
     if (!use_graph) {
-      set_timesteps(caller, timesteps);
-      run_context(caller);
       static const bool trace = getenv("NR_TRACE_OPS") != nullptr;      // fault localisation: one line and one stream sync per launch (eager handles only)
       if (trace) {
+        begin(caller, timesteps);
         for (size_t i = 0; i < ops.size(); ++i) {
           fprintf(stderr, "[nr op %zu] %s\n", i, op_meta[i].desc.c_str());
           ops[i](caller);
@@ -2372,15 +2220,11 @@ struct nr_net {
         }
         return;
       }
-      for (auto& op : ops) op(caller);
+      run_eager(caller, timesteps);
       return;
     }
     ensure_streams();
-    hipStream_t s = own_stream;
-    HIP_OK(hipEventRecord(ev_in, caller));
-    HIP_OK(hipStreamWaitEvent(s, ev_in, 0));
-    set_timesteps(s, timesteps);
-    run_context(s);
+    hipStream_t s = begin_fenced(caller, timesteps);
     launch_segment(s, 0);
     launch_segment(s, 1);
     launch_segment(s, 2);
@@ -2426,9 +2270,8 @@ static void profile_last(nr_net* h, hipStream_t s, nr_profile* out, const char* 
 
 extern "C" const char* nr_last_error(void) { return g_err.c_str(); }
 
-extern "C" nr_status nr_net_create(const nr_net_config* cfg, nr_net** out) {
-  NR_TRY
-  if (!cfg || !out) throw NrError(NR_ERR_ARG, "null argument");
+// what nr_net_create accepts
+static void check_config(const nr_net_config* cfg) {
   if (cfg->kind < NR_KIND_UNET3D || cfg->kind > NR_KIND_LEAF_TEMPORAL) throw NrError(NR_ERR_ARG, "bad kind");
   const bool leaf_kind = cfg->kind == NR_KIND_LEAF_TRANSFORMER3D || cfg->kind == NR_KIND_LEAF_TEMPORAL;
   if (cfg->num_levels < (leaf_kind ? 1 : 2) || cfg->num_levels > NR_MAX_LEVELS) throw NrError(NR_ERR_ARG, "num_levels must be 2..4");
@@ -2437,14 +2280,7 @@ extern "C" nr_status nr_net_create(const nr_net_config* cfg, nr_net** out) {
     if (C % 64 != 0 || cfg->num_heads <= 0 || C % cfg->num_heads != 0 || (C / cfg->num_heads) % 8 != 0 || C / cfg->num_heads > 160 ||
         cfg->cross_attention_dim % 64 != 0 || cfg->in_channels <= 0 || cfg->layers_per_block <= 0 || cfg->motion_pe_max_len <= 0)
       throw NrError(NR_ERR_UNSUPPORTED, "CLIP text encoder: hidden/intermediate sizes must be multiples of 64, head dim a multiple of 8 and <= 160");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) throw NrError(NR_ERR_HIP, "no HIP device available: libneurons_amd requires an MI355X (gfx950) GPU");
-    nr_net* h = new nr_net();
-    h->cfg = *cfg;
-    h->device = dev;
-    h->det_batch = getenv("NR_DETERMINISTIC_BATCH") && getenv("NR_DETERMINISTIC_BATCH")[0] == '1';
-    *out = h;
-    return NR_OK;
+    return;
   }
   const bool vae = cfg->kind == NR_KIND_VAE_DECODER || cfg->kind == NR_KIND_VAE_ENCODER;
   if (cfg->kind == NR_KIND_VAE_DECODER && (cfg->in_channels != 4 || cfg->out_channels != 3))
@@ -2471,12 +2307,18 @@ extern "C" nr_status nr_net_create(const nr_net_config* cfg, nr_net** out) {
       throw NrError(NR_ERR_UNSUPPORTED, "SparseCtrl condition embedding: 1..4 levels, conditioning_channels + 1 <= 8, first level 16 or 32 "
                                         "channels, the others 16 / 32 / 64 / 96 / 128 / 256");
   }
+}
+
+extern "C" nr_status nr_net_create(const nr_net_config* cfg, nr_net** out) {
+  NR_TRY
+  if (!cfg || !out) throw NrError(NR_ERR_ARG, "null argument");
+  check_config(cfg);
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) throw NrError(NR_ERR_HIP, "no HIP device available: libneurons_amd requires an MI355X (gfx950) GPU");
   nr_net* h = new nr_net();
   h->cfg = *cfg;
   h->device = dev;
-  h->det_batch = getenv("NR_DETERMINISTIC_BATCH") && getenv("NR_DETERMINISTIC_BATCH")[0] == '1';
+  h->det_batch = env_is_1("NR_DETERMINISTIC_BATCH");
   *out = h;
   NR_CATCH
 }
@@ -2511,15 +2353,12 @@ extern "C" nr_status nr_net_load_tensor(nr_net* h, const char* key, const float*
     }
     return false;
   };
-  for (auto it = h->dev.begin(); it != h->dev.end();) {
-    if (derived_from(it->first) || (is_temb_src && it->first.rfind("temb", 0) == 0)) {
-      (void)hipDeviceSynchronize();
-      if (!h->in_import(it->second)) (void)hipFree(it->second);
-      auto ib = h->dev_bytes.find(it->first);
-      if (ib != h->dev_bytes.end()) { h->weight_bytes -= ib->second; h->dev_bytes.erase(ib); }      // nr_net_weight_bytes stays the sum of what is resident
-      it = h->dev.erase(it);
-      h->planned = false;
-    } else ++it;
+  std::vector<std::string> stale;
+  for (auto& kv : h->dev) if (derived_from(kv.first) || (is_temb_src && kv.first.rfind("temb", 0) == 0)) stale.push_back(kv.first);
+  if (!stale.empty()) {
+    (void)hipDeviceSynchronize();
+    for (auto& name : stale) h->erase(name);      // nr_net_weight_bytes stays the sum of what is resident
+    h->planned = false;
   }
   NR_CATCH
 }
@@ -2530,6 +2369,14 @@ static void check_device(const nr_net* h) {
   if (hipGetDevice(&cur) != hipSuccess || cur != h->device)
     throw NrError(NR_ERR_STATE, "handle was created on HIP device " + std::to_string(h->device) + " but device " + std::to_string(cur) +
                                     " is current (hipSetDevice / torch.cuda.device before calling)");
+}
+
+// common preamble of the forward entry points: a handle of an accepted kind, planned (not_planned = null: not required), on the current device
+static void check_forward(const nr_net* h, std::initializer_list<int> kinds, const char* not_kind,
+                          const char* not_planned = "nr_net_plan() has not been called (or weights changed since)") {
+  if (!h || std::find(kinds.begin(), kinds.end(), (int)h->cfg.kind) == kinds.end()) throw NrError(NR_ERR_ARG, not_kind);
+  if (not_planned && !h->planned) throw NrError(NR_ERR_STATE, not_planned);
+  check_device(h);
 }
 
 extern "C" nr_status nr_net_plan(nr_net* h, int32_t batch, int32_t frames, int32_t lat_h, int32_t lat_w, int32_t ctx_len) {
@@ -2552,7 +2399,7 @@ static std::string build_manifest(const nr_net* h, size_t* total) {
   }
   size_t off = 0;
   for (auto& kv : h->dev) {
-    const size_t b = h->dev_bytes.at(kv.first);
+    const size_t b = kv.second.bytes;
     m += "D " + kv.first + " " + std::to_string(off) + " " + std::to_string(b) + "\n";
     off += (b + 255) & ~(size_t)255;
   }
@@ -2579,8 +2426,8 @@ extern "C" nr_status nr_net_export_weights(nr_net* h, nr_stream stream, void* ds
   if ((size_t)capacity < total) throw NrError(NR_ERR_ARG, "export buffer too small");
   size_t off = 0;
   for (auto& kv : h->dev) {
-    const size_t b = h->dev_bytes.at(kv.first);
-    HIP_OK(hipMemcpyAsync((char*)dst_dev + off, kv.second, b, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    const size_t b = kv.second.bytes;
+    HIP_OK(hipMemcpyAsync((char*)dst_dev + off, kv.second.ptr, b, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     off += (b + 255) & ~(size_t)255;
   }
   NR_CATCH
@@ -2642,7 +2489,7 @@ extern "C" nr_status nr_net_import_weights(nr_net* h, nr_stream stream, const ch
   h->import_base = base;
   h->import_bytes = (size_t)arena_bytes;
   h->host = std::move(new_host);
-  for (auto& r : new_dev) { h->dev[r.name] = base + r.off; h->dev_bytes[r.name] = r.bytes; h->weight_bytes += r.bytes; }
+  for (auto& r : new_dev) h->adopt(r.name, base + r.off, r.bytes);
   NR_CATCH
 }
 
@@ -2743,15 +2590,12 @@ extern "C" nr_status nr_unet3d_forward(nr_net* h, nr_stream stream, const float*
                                        const float* ctx_dev, int32_t ctx_len, const void* const* down_res_dev,
                                        const void* mid_res_dev, float* out_dev) {
   NR_TRY
-  if (!h || h->cfg.kind != NR_KIND_UNET3D) throw NrError(NR_ERR_ARG, "handle is not a UNet3D");
-  if (!h->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called (or weights changed since)");
-  check_device(h);
+  check_forward(h, {NR_KIND_UNET3D}, "handle is not a UNet3D");
   if (!sample_dev || !timesteps || !ctx_dev || !out_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
   if (ctx_len != h->ctx_len) throw NrError(NR_ERR_ARG, "ctx_len differs from the planned value");
   if ((down_res_dev == nullptr) != (mid_res_dev == nullptr)) throw NrError(NR_ERR_ARG, "down/mid residuals must be given together");
-  IO io;
-  std::memset(&io, 0, sizeof(io));
-  io.sample = sample_dev; io.ctx = ctx_dev; io.out = out_dev; io.scale = 1.f; io.cond_batch = 1;
+  IO io = new_io();
+  io.sample = sample_dev; io.ctx = ctx_dev; io.out = out_dev;
   if (down_res_dev) {
     io.has_res = 1;
     for (int i = 0; i < h->n_res; ++i) {
@@ -2770,15 +2614,12 @@ extern "C" nr_status nr_sparsectrl_forward(nr_net* h, nr_stream stream, const fl
                                            const float* mask_dev, int32_t cond_batch, float scale,
                                            void* const* out_down_dev, void* out_mid_dev) {
   NR_TRY
-  if (!h || h->cfg.kind != NR_KIND_SPARSECTRL) throw NrError(NR_ERR_ARG, "handle is not a SparseCtrl");
-  if (!h->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called (or weights changed since)");
-  check_device(h);
+  check_forward(h, {NR_KIND_SPARSECTRL}, "handle is not a SparseCtrl");
   if (!timesteps || !ctx_dev || !cond_dev || !mask_dev || !out_down_dev || !out_mid_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
   if (!h->cfg.set_noisy_sample_input_to_zero && !sample_dev) throw NrError(NR_ERR_ARG, "sample required");
   if (ctx_len != h->ctx_len) throw NrError(NR_ERR_ARG, "ctx_len differs from the planned value");
   if (cond_batch <= 0 || h->B2 % cond_batch != 0) throw NrError(NR_ERR_ARG, "cond_batch must divide the planned batch");
-  IO io;
-  std::memset(&io, 0, sizeof(io));
+  IO io = new_io();
   io.sample = sample_dev; io.ctx = ctx_dev; io.cond = cond_dev; io.mask = mask_dev; io.cond_batch = cond_batch; io.scale = scale;
   for (int i = 0; i < h->n_res; ++i) {
     if (!out_down_dev[i]) throw NrError(NR_ERR_ARG, "null output pointer");
@@ -2796,9 +2637,8 @@ extern "C" nr_status nr_denoise_step_forward(nr_net* unet, nr_net* ctrl, nr_stre
                                              void* const* res_down_dev, void* res_mid_dev, float* out_dev,
                                              const float* next_timesteps) {
   NR_TRY
-  if (!unet || unet->cfg.kind != NR_KIND_UNET3D || !ctrl || ctrl->cfg.kind != NR_KIND_SPARSECTRL) throw NrError(NR_ERR_ARG, "need a UNet3D and a SparseCtrl handle");
-  if (!unet->planned || !ctrl->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called on both handles");
-  check_device(unet); check_device(ctrl);
+  check_forward(unet, {NR_KIND_UNET3D}, "need a UNet3D and a SparseCtrl handle", "nr_net_plan() has not been called on both handles");
+  check_forward(ctrl, {NR_KIND_SPARSECTRL}, "need a UNet3D and a SparseCtrl handle", "nr_net_plan() has not been called on both handles");
   if (!sample_dev || !timesteps || !ctx_dev || !cond_dev || !mask_dev || !res_down_dev || !res_mid_dev || !out_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
   if (ctx_len != unet->ctx_len || ctx_len != ctrl->ctx_len) throw NrError(NR_ERR_ARG, "ctx_len differs from the planned value");
   if (unet->n_res != ctrl->n_res || unet->B2 != ctrl->B2 || unet->F != ctrl->F || unet->H != ctrl->H || unet->W != ctrl->W)
@@ -2806,12 +2646,10 @@ extern "C" nr_status nr_denoise_step_forward(nr_net* unet, nr_net* ctrl, nr_stre
   if (!ctrl->cfg.set_noisy_sample_input_to_zero) throw NrError(NR_ERR_UNSUPPORTED, "overlapped step requires set_noisy_sample_input_to_zero");
   if (cond_batch <= 0 || ctrl->B2 % cond_batch != 0) throw NrError(NR_ERR_ARG, "cond_batch must divide the planned batch");
   hipStream_t caller = (hipStream_t)stream;
-  IO ic;
-  std::memset(&ic, 0, sizeof(ic));
-  ic.ctx = ctx_dev; ic.cond = cond_dev; ic.mask = mask_dev; ic.cond_batch = cond_batch; ic.scale = scale; ic.in_scale = 1.f;
-  IO iu;
-  std::memset(&iu, 0, sizeof(iu));
-  iu.sample = sample_dev; iu.ctx = ctx_dev; iu.out = out_dev; iu.scale = 1.f; iu.cond_batch = 1; iu.in_scale = 1.f; iu.has_res = 1;
+  IO ic = new_io();
+  ic.ctx = ctx_dev; ic.cond = cond_dev; ic.mask = mask_dev; ic.cond_batch = cond_batch; ic.scale = scale;
+  IO iu = new_io();
+  iu.sample = sample_dev; iu.ctx = ctx_dev; iu.out = out_dev; iu.has_res = 1;
   for (int i = 0; i < ctrl->n_res; ++i) {
     if (!res_down_dev[i]) throw NrError(NR_ERR_ARG, "null residual pointer");
     ic.out_down[i] = res_down_dev[i];
@@ -2820,12 +2658,8 @@ extern "C" nr_status nr_denoise_step_forward(nr_net* unet, nr_net* ctrl, nr_stre
   ic.out_mid = res_mid_dev; iu.mid_res = res_mid_dev;
   ctrl->io = ic; unet->io = iu;
   if (!unet->use_graph || !ctrl->use_graph) {   // eager: plain sequential launches on the caller's stream
-    ctrl->set_timesteps(caller, timesteps);
-    ctrl->run_context(caller);
-    for (auto& op : ctrl->ops) op(caller);
-    unet->set_timesteps(caller, timesteps);
-    unet->run_context(caller);
-    for (auto& op : unet->ops) op(caller);
+    ctrl->run_eager(caller, timesteps);
+    unet->run_eager(caller, timesteps);
   } else {
     unet->ensure_streams(); ctrl->ensure_streams();
     HIP_OK(hipEventRecord(unet->ev_in, caller));
@@ -2838,16 +2672,14 @@ extern "C" nr_status nr_denoise_step_forward(nr_net* unet, nr_net* ctrl, nr_stre
     static const int dbg_mode = getenv("NR_OVERLAP_DBG") ? atoi(getenv("NR_OVERLAP_DBG")) : 0;   // 1: eager launches on the two streams; 2: graphs, serialised
     if (!hit) {
       HIP_OK(hipStreamWaitEvent(ctrl->own_stream, unet->ev_in, 0));
-      ctrl->set_timesteps(ctrl->own_stream, timesteps);
-      ctrl->run_context(ctrl->own_stream);
+      ctrl->begin(ctrl->own_stream, timesteps);
       if (dbg_mode == 1) { for (auto& op : ctrl->ops) op(ctrl->own_stream); }
       else for (int seg = 0; seg < 3; ++seg) ctrl->launch_segment(ctrl->own_stream, seg);
       HIP_OK(hipEventRecord(ctrl->ev_out, ctrl->own_stream));
     }
     if (dbg_mode == 2) HIP_OK(hipStreamWaitEvent(unet->own_stream, ctrl->ev_out, 0));
     // ... concurrently with the U-Net's encoder + mid block; the residual adds wait for SparseCtrl
-    unet->set_timesteps(unet->own_stream, timesteps);
-    unet->run_context(unet->own_stream);
+    unet->begin(unet->own_stream, timesteps);
     if (dbg_mode == 1) { for (size_t i = 0; i < unet->split_op; ++i) unet->ops[i](unet->own_stream); }
     else unet->launch_segment(unet->own_stream, 0);
     HIP_OK(hipStreamWaitEvent(unet->own_stream, ctrl->ev_out, 0));
@@ -2885,17 +2717,14 @@ extern "C" nr_status nr_sparsectrl_forward_async(nr_net* h, nr_stream stream, co
                                                  const float* cond_dev, const float* mask_dev, int32_t cond_batch, float scale,
                                                  void* const* out_down_dev, void* out_mid_dev, int32_t slot) {
   NR_TRY
-  if (!h || h->cfg.kind != NR_KIND_SPARSECTRL) throw NrError(NR_ERR_ARG, "handle is not a SparseCtrl");
-  if (!h->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called (or weights changed since)");
-  check_device(h);
+  check_forward(h, {NR_KIND_SPARSECTRL}, "handle is not a SparseCtrl");
   if (!h->cfg.set_noisy_sample_input_to_zero) throw NrError(NR_ERR_UNSUPPORTED, "the asynchronous evaluation requires set_noisy_sample_input_to_zero");
   if (!timesteps || !ctx_dev || !cond_dev || !mask_dev || !out_down_dev || !out_mid_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
   if (ctx_len != h->ctx_len) throw NrError(NR_ERR_ARG, "ctx_len differs from the planned value");
   if (cond_batch <= 0 || h->B2 % cond_batch != 0) throw NrError(NR_ERR_ARG, "cond_batch must divide the planned batch");
   if (slot < 0 || slot > 1) throw NrError(NR_ERR_ARG, "slot must be 0 or 1");
-  IO io;
-  std::memset(&io, 0, sizeof(io));
-  io.ctx = ctx_dev; io.cond = cond_dev; io.mask = mask_dev; io.cond_batch = cond_batch; io.scale = scale; io.in_scale = 1.f;
+  IO io = new_io();
+  io.ctx = ctx_dev; io.cond = cond_dev; io.mask = mask_dev; io.cond_batch = cond_batch; io.scale = scale;
   for (int i = 0; i < h->n_res; ++i) {
     if (!out_down_dev[i]) throw NrError(NR_ERR_ARG, "null residual pointer");
     io.out_down[i] = out_down_dev[i];
@@ -2906,16 +2735,10 @@ extern "C" nr_status nr_sparsectrl_forward_async(nr_net* h, nr_stream stream, co
   hipStream_t caller = (hipStream_t)stream;
   h->ensure_streams();
   if (!h->use_graph) {                       // eager handles: evaluate in stream order on the caller's stream
-    h->set_timesteps(caller, timesteps);
-    h->run_context(caller);
-    for (auto& op : h->ops) op(caller);
+    h->run_eager(caller, timesteps);
     HIP_OK(hipEventRecord(h->ev_slot[slot], caller));
   } else {
-    hipStream_t s = h->own_stream;
-    HIP_OK(hipEventRecord(h->ev_in, caller));          // everything the caller enqueued so far (readers of the buffers, staged inputs)
-    HIP_OK(hipStreamWaitEvent(s, h->ev_in, 0));
-    h->set_timesteps(s, timesteps);
-    h->run_context(s);
+    hipStream_t s = h->begin_fenced(caller, timesteps);
     for (int seg = 0; seg < 3; ++seg) h->launch_segment(s, seg);
     HIP_OK(hipEventRecord(h->ev_slot[slot], s));
   }
@@ -2926,17 +2749,14 @@ extern "C" nr_status nr_unet3d_forward_after(nr_net* unet, nr_net* ctrl, int32_t
                                              const float* timesteps, const float* ctx_dev, int32_t ctx_len,
                                              const void* const* down_res_dev, const void* mid_res_dev, float* out_dev) {
   NR_TRY
-  if (!unet || unet->cfg.kind != NR_KIND_UNET3D) throw NrError(NR_ERR_ARG, "first handle is not a UNet3D");
-  if (!ctrl || ctrl->cfg.kind != NR_KIND_SPARSECTRL) throw NrError(NR_ERR_ARG, "second handle is not a SparseCtrl");
-  if (!unet->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called (or weights changed since)");
-  check_device(unet); check_device(ctrl);
+  check_forward(unet, {NR_KIND_UNET3D}, "first handle is not a UNet3D");
+  check_forward(ctrl, {NR_KIND_SPARSECTRL}, "second handle is not a SparseCtrl", nullptr);
   if (!sample_dev || !timesteps || !ctx_dev || !out_dev || !down_res_dev || !mid_res_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
   if (ctx_len != unet->ctx_len) throw NrError(NR_ERR_ARG, "ctx_len differs from the planned value");
   if (slot < 0 || slot > 1) throw NrError(NR_ERR_ARG, "slot must be 0 or 1");
   if (unet->n_res != ctrl->n_res) throw NrError(NR_ERR_ARG, "the two handles have different residual counts");
-  IO io;
-  std::memset(&io, 0, sizeof(io));
-  io.sample = sample_dev; io.ctx = ctx_dev; io.out = out_dev; io.scale = 1.f; io.cond_batch = 1; io.in_scale = 1.f; io.has_res = 1;
+  IO io = new_io();
+  io.sample = sample_dev; io.ctx = ctx_dev; io.out = out_dev; io.has_res = 1;
   for (int i = 0; i < unet->n_res; ++i) {
     if (!down_res_dev[i]) throw NrError(NR_ERR_ARG, "null residual pointer");
     io.down_res[i] = down_res_dev[i];
@@ -2947,15 +2767,9 @@ extern "C" nr_status nr_unet3d_forward_after(nr_net* unet, nr_net* ctrl, int32_t
   unet->ensure_streams(); ctrl->ensure_streams();
   if (!unet->use_graph) {
     HIP_OK(hipStreamWaitEvent(caller, ctrl->ev_slot[slot], 0));
-    unet->set_timesteps(caller, timesteps);
-    unet->run_context(caller);
-    for (auto& op : unet->ops) op(caller);
+    unet->run_eager(caller, timesteps);
   } else {
-    hipStream_t s = unet->own_stream;
-    HIP_OK(hipEventRecord(unet->ev_in, caller));
-    HIP_OK(hipStreamWaitEvent(s, unet->ev_in, 0));
-    unet->set_timesteps(s, timesteps);
-    unet->run_context(s);
+    hipStream_t s = unet->begin_fenced(caller, timesteps);
     unet->launch_segment(s, 0);                                    // encoder + mid block: overlaps the pending SparseCtrl group
     HIP_OK(hipStreamWaitEvent(s, ctrl->ev_slot[slot], 0));
     unet->launch_segment(s, 1);                                    // the residual adds
@@ -2969,14 +2783,11 @@ extern "C" nr_status nr_unet3d_forward_after(nr_net* unet, nr_net* ctrl, int32_t
 extern "C" nr_status nr_sgm_unet_forward(nr_net* h, nr_stream stream, const float* x_dev, float in_scale, const float* timesteps,
                                          const float* ctx_dev, int32_t ctx_len, const float* y_dev, float* out_dev) {
   NR_TRY
-  if (!h || h->cfg.kind != NR_KIND_SGM_UNET) throw NrError(NR_ERR_ARG, "handle is not an sgm UNetModel");
-  if (!h->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called (or weights changed since)");
-  check_device(h);
+  check_forward(h, {NR_KIND_SGM_UNET}, "handle is not an sgm UNetModel");
   if (!x_dev || !timesteps || !ctx_dev || !y_dev || !out_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
   if (ctx_len != h->ctx_len) throw NrError(NR_ERR_ARG, "ctx_len differs from the planned value");
-  IO io;
-  std::memset(&io, 0, sizeof(io));
-  io.sample = x_dev; io.ctx = ctx_dev; io.y = y_dev; io.out = out_dev; io.in_scale = in_scale; io.scale = 1.f; io.cond_batch = 1;
+  IO io = new_io();
+  io.sample = x_dev; io.ctx = ctx_dev; io.y = y_dev; io.out = out_dev; io.in_scale = in_scale;
   h->io = io;
   h->run((hipStream_t)stream, timesteps);
   NR_CATCH
@@ -2984,14 +2795,11 @@ extern "C" nr_status nr_sgm_unet_forward(nr_net* h, nr_stream stream, const floa
 
 extern "C" nr_status nr_leaf_forward(nr_net* h, nr_stream stream, const float* x_dev, const float* ctx_dev, int32_t ctx_len, float* out_dev) {
   NR_TRY
-  if (!h || (h->cfg.kind != NR_KIND_LEAF_TRANSFORMER3D && h->cfg.kind != NR_KIND_LEAF_TEMPORAL)) throw NrError(NR_ERR_ARG, "handle is not a leaf module");
-  if (!h->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called (or weights changed since)");
-  check_device(h);
+  check_forward(h, {NR_KIND_LEAF_TRANSFORMER3D, NR_KIND_LEAF_TEMPORAL}, "handle is not a leaf module");
   if (!x_dev || !out_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
   if (h->cfg.kind == NR_KIND_LEAF_TRANSFORMER3D && (!ctx_dev || ctx_len != h->ctx_len)) throw NrError(NR_ERR_ARG, "context missing or ctx_len differs from the planned value");
-  IO io;
-  std::memset(&io, 0, sizeof(io));
-  io.sample = x_dev; io.ctx = ctx_dev; io.out = out_dev; io.in_scale = 1.f; io.scale = 1.f; io.cond_batch = 1;
+  IO io = new_io();
+  io.sample = x_dev; io.ctx = ctx_dev; io.out = out_dev;
   h->io = io;
   const float zeros[NR_MAX_BATCH] = {0};
   h->run((hipStream_t)stream, zeros);
@@ -3007,13 +2815,10 @@ extern "C" const char* nr_net_op_desc(const nr_net* h, int32_t i) {
 extern "C" nr_status nr_vae_decode(nr_net* h, nr_stream stream, const float* z_dev, float z_scale, float out_mul, float out_add,
                                    int32_t clamp01, float* out_dev) {
   NR_TRY
-  if (!h || h->cfg.kind != NR_KIND_VAE_DECODER) throw NrError(NR_ERR_ARG, "handle is not a VAE decoder");
-  if (!h->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called (or weights changed since)");
-  check_device(h);
+  check_forward(h, {NR_KIND_VAE_DECODER}, "handle is not a VAE decoder");
   if (!z_dev || !out_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
-  IO io;
-  std::memset(&io, 0, sizeof(io));
-  io.sample = z_dev; io.out = out_dev; io.in_scale = z_scale; io.out_mul = out_mul; io.out_add = out_add; io.clamp01 = clamp01 ? 1 : 0; io.scale = 1.f; io.cond_batch = 1;
+  IO io = new_io();
+  io.sample = z_dev; io.out = out_dev; io.in_scale = z_scale; io.out_mul = out_mul; io.out_add = out_add; io.clamp01 = clamp01 ? 1 : 0;
   h->io = io;
   const float zeros[NR_MAX_BATCH] = {0};
   h->run((hipStream_t)stream, zeros);
@@ -3022,13 +2827,10 @@ extern "C" nr_status nr_vae_decode(nr_net* h, nr_stream stream, const float* z_d
 
 extern "C" nr_status nr_clip_text_forward(nr_net* h, nr_stream stream, const int32_t* ids_dev, float* out_dev) {
   NR_TRY
-  if (!h || h->cfg.kind != NR_KIND_CLIP_TEXT) throw NrError(NR_ERR_ARG, "handle is not a CLIP text encoder");
-  if (!h->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called (or weights changed since)");
-  check_device(h);
+  check_forward(h, {NR_KIND_CLIP_TEXT}, "handle is not a CLIP text encoder");
   if (!ids_dev || !out_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
-  IO io;
-  std::memset(&io, 0, sizeof(io));
-  io.ids = ids_dev; io.out = out_dev; io.in_scale = 1.f; io.out_mul = 1.f; io.scale = 1.f; io.cond_batch = 1;
+  IO io = new_io();
+  io.ids = ids_dev; io.out = out_dev;
   h->io = io;
   const float zeros[NR_MAX_BATCH] = {0};
   h->run((hipStream_t)stream, zeros);
@@ -3037,13 +2839,10 @@ extern "C" nr_status nr_clip_text_forward(nr_net* h, nr_stream stream, const int
 
 extern "C" nr_status nr_vae_encode(nr_net* h, nr_stream stream, const float* x_dev, float in_mul, float in_add, float* moments_dev) {
   NR_TRY
-  if (!h || h->cfg.kind != NR_KIND_VAE_ENCODER) throw NrError(NR_ERR_ARG, "handle is not a VAE encoder");
-  if (!h->planned) throw NrError(NR_ERR_STATE, "nr_net_plan() has not been called (or weights changed since)");
-  check_device(h);
+  check_forward(h, {NR_KIND_VAE_ENCODER}, "handle is not a VAE encoder");
   if (!x_dev || !moments_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
-  IO io;
-  std::memset(&io, 0, sizeof(io));
-  io.sample = x_dev; io.out = moments_dev; io.in_scale = in_mul; io.in_shift = in_add; io.out_mul = 1.f; io.scale = 1.f; io.cond_batch = 1;
+  IO io = new_io();
+  io.sample = x_dev; io.out = moments_dev; io.in_scale = in_mul; io.in_shift = in_add;
   h->io = io;
   const float zeros[NR_MAX_BATCH] = {0};
   h->run((hipStream_t)stream, zeros);
@@ -3163,17 +2962,23 @@ extern "C" nr_status nr_net_read_tap(nr_net* h, int32_t i, float* host_out, int6
 }
 
 // ---- single-op entry points ---------------------------------------------------------------------
+// grow-only device scratch of the op hooks (process lifetime).  Growing waits for the device first (the old buffer may still be read) and
+// returns true
+struct OpScratch { void* ptr = nullptr; size_t cap = 0; };
+static bool op_scratch(OpScratch& b, size_t need) {
+  if (need <= b.cap) return false;
+  if (b.ptr) { HIP_OK(hipDeviceSynchronize()); (void)hipFree(b.ptr); }
+  b.ptr = nullptr; b.cap = 0;
+  HIP_OK(hipMalloc(&b.ptr, need));
+  b.cap = need;
+  return true;
+}
+
 static float* op_workspace(const NrGemmParams& p) {
-  static float* ws = nullptr;
-  static size_t cap = 0;
+  static OpScratch ws;
   const size_t need = nr_igemm_workspace_bytes(&p);
-  if (need > cap) {
-    HIP_OK(hipDeviceSynchronize());
-    if (ws) (void)hipFree(ws);
-    HIP_OK(hipMalloc((void**)&ws, need));
-    cap = need;
-  }
-  return need ? ws : nullptr;
+  op_scratch(ws, need);
+  return need ? (float*)ws.ptr : nullptr;
 }
 
 // Test / tool hooks and the panel-resident small-M kernel (smallm.hip): an eligible launch gets a fragment-major copy of its weights, packed on
@@ -3188,8 +2993,7 @@ extern "C" void nr_op_fm_cache_clear() {
 static void op_fragmajor(NrGemmParams& p, hipStream_t s) {
   if (!nr_smallm_eligible(&p)) return;
   const size_t need = (size_t)p.N * p.K * sizeof(bf16);
-  const char* e = getenv("NR_OP_FM_CACHE");
-  if (e && e[0] == '1') {
+  if (env_is_1("NR_OP_FM_CACHE")) {
     auto it = g_op_fm_cache.find(p.w);
     if (it == g_op_fm_cache.end()) {
       bf16* d = nullptr;
@@ -3200,31 +3004,19 @@ static void op_fragmajor(NrGemmParams& p, hipStream_t s) {
     p.w_fm = it->second;
     return;
   }
-  static bf16* scratch = nullptr;
-  static size_t cap = 0;
-  if (need > cap) {
-    HIP_OK(hipDeviceSynchronize());
-    if (scratch) (void)hipFree(scratch);
-    HIP_OK(hipMalloc((void**)&scratch, need));
-    cap = need;
-  }
-  LAUNCH_OK(nr_launch_smallm_w_pack(p.w, scratch, p.N, p.K, s));
-  p.w_fm = scratch;
+  static OpScratch scratch;
+  op_scratch(scratch, need);
+  LAUNCH_OK(nr_launch_smallm_w_pack(p.w, scratch.ptr, p.N, p.K, s));
+  p.w_fm = (const bf16*)scratch.ptr;
 }
 
 // the engine's choice for short-K Linears on 2048..8192 rows (lin160.hip): the stage stream is packed on the launch stream on every call
 static bool op_lin160(const NrGemmParams& p, hipStream_t s) {
   const int l1 = nr_lin160_eligible(&p);
   if (!l1) return false;
-  static bf16* l160 = nullptr;
-  static size_t l160_cap = 0;
-  const size_t need = l1 == 4 ? nr_lin128q_stream_bytes(p.N, p.K) : nr_lin160_stream_bytes(p.N, p.K);
-  if (need > l160_cap) {
-    HIP_OK(hipDeviceSynchronize());
-    if (l160) (void)hipFree(l160);
-    HIP_OK(hipMalloc((void**)&l160, need));
-    l160_cap = need;
-  }
+  static OpScratch buf;
+  op_scratch(buf, l1 == 4 ? nr_lin128q_stream_bytes(p.N, p.K) : nr_lin160_stream_bytes(p.N, p.K));
+  bf16* l160 = (bf16*)buf.ptr;
   LAUNCH_OK(l1 == 4 ? nr_launch_lin128q_w_pack(p.w, p.N, p.K, l160, s) : nr_launch_lin160_w_pack(p.w, p.N, p.K, l160, s));
   LAUNCH_OK(nr_launch_lin160(&p, l160, s));
   return true;
@@ -3234,11 +3026,8 @@ extern "C" nr_status nr_op_gemm(nr_stream stream, const void* a, int32_t lda, co
                                 const void* res, int32_t ldr, void* out, int32_t ldo, int32_t M, int32_t N, int32_t K,
                                 int32_t geglu) {
   NR_TRY
-  NrGemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.a0 = (const bf16*)a; p.c0 = K; p.lda0 = lda; p.H = p.W = p.OH = p.OW = 1; p.ksize = 1; p.stride = 1;
-  p.w = (const bf16*)w; p.M = M; p.N = N; p.K = K; p.bias = bias; p.res = (const bf16*)res; p.ldr = ldr;
-  p.out = (bf16*)out; p.ldo = ldo; p.out_scale = 1.f; p.geglu = geglu; p.rowvec_div = 1;
+  NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr, (bf16*)out, ldo);
+  p.geglu = geglu;
   if (op_lin160(p, (hipStream_t)stream)) return NR_OK;
   op_fragmajor(p, (hipStream_t)stream);
   LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
@@ -3249,12 +3038,8 @@ extern "C" nr_status nr_op_gemm(nr_stream stream, const void* a, int32_t lda, co
 extern "C" nr_status nr_op_gemm2(nr_stream stream, const void* a0, int32_t c0, int32_t lda0, const void* a1, int32_t c1, int32_t lda1,
                                  const void* w, const float* bias, const void* res, int32_t ldr, void* out, int32_t ldo, int32_t M, int32_t N) {
   NR_TRY
-  NrGemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.a0 = (const bf16*)a0; p.c0 = c0; p.lda0 = lda0; p.a1 = (const bf16*)a1; p.c1 = a1 ? c1 : 0; p.lda1 = lda1;
-  p.H = p.W = p.OH = p.OW = 1; p.ksize = 1; p.stride = 1;
-  p.w = (const bf16*)w; p.M = M; p.N = N; p.K = p.c0 + p.c1; p.bias = bias; p.res = (const bf16*)res; p.ldr = ldr;
-  p.out = (bf16*)out; p.ldo = ldo; p.out_scale = 1.f; p.rowvec_div = 1;
+  NrGemmParams p = nr_gemm_params((const bf16*)a0, c0, lda0, (const bf16*)a1, c1, lda1, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr,
+                                  (bf16*)out, ldo);
   op_fragmajor(p, (hipStream_t)stream);
   LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
   NR_CATCH
@@ -3265,11 +3050,9 @@ extern "C" nr_status nr_op_ln_gemm(nr_stream stream, const void* a, int32_t lda,
                                    int32_t M, int32_t N, int32_t K, int32_t geglu, int32_t act) {
   NR_TRY
   if (!ln_c) throw NrError(NR_ERR_ARG, "ln_c is required");
-  NrGemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.a0 = (const bf16*)a; p.c0 = K; p.lda0 = lda; p.H = p.W = p.OH = p.OW = 1; p.ksize = 1; p.stride = 1;
-  p.w = (const bf16*)w_scaled; p.M = M; p.N = N; p.K = K; p.bias = bias_folded; p.res = (const bf16*)res; p.ldr = ldr;
-  p.out = (bf16*)out; p.ldo = ldo; p.out_scale = 1.f; p.geglu = geglu; p.rowvec_div = 1; p.ln_c = ln_c; p.ln_eps = eps; p.act = act;
+  NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w_scaled, N, bias_folded, (const bf16*)res, ldr,
+                                  (bf16*)out, ldo);
+  p.geglu = geglu; p.ln_c = ln_c; p.ln_eps = eps; p.act = act;
   if (op_lin160(p, (hipStream_t)stream)) return NR_OK;
   op_fragmajor(p, (hipStream_t)stream);
   LAUNCH_OK(nr_launch_igemm(&p, nullptr, (hipStream_t)stream));
@@ -3281,11 +3064,8 @@ extern "C" nr_status nr_op_gemm_ex(nr_stream stream, const void* a, int32_t lda,
                                    const void* res, int32_t ldr, void* out, int32_t ldo, int32_t M, int32_t N, int32_t K, int32_t geglu,
                                    int32_t act, float out_scale) {
   NR_TRY
-  NrGemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.a0 = (const bf16*)a; p.c0 = K; p.lda0 = lda; p.H = p.W = p.OH = p.OW = 1; p.ksize = 1; p.stride = 1;
-  p.w = (const bf16*)w; p.M = M; p.N = N; p.K = K; p.bias = bias; p.res = (const bf16*)res; p.ldr = ldr;
-  p.out = (bf16*)out; p.ldo = ldo; p.out_scale = out_scale; p.geglu = geglu; p.act = act;
+  NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr, (bf16*)out, ldo);
+  p.out_scale = out_scale; p.geglu = geglu; p.act = act;
   p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_mod = rowvec_mod; p.rowvec_ld = rowvec_ld;
   p.ln_c = ln_c; p.ln_eps = ln_eps;
   op_fragmajor(p, (hipStream_t)stream);
@@ -3297,17 +3077,9 @@ extern "C" nr_status nr_op_conv3x3(nr_stream stream, const void* x0, int32_t c0,
                                    int32_t H, int32_t W, int32_t stride, int32_t ups, const void* w, const float* bias,
                                    const float* rowvec, int32_t rowvec_div, const void* res, void* out, int32_t Cout) {
   NR_TRY
-  NrGemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.a0 = (const bf16*)x0; p.c0 = c0; p.lda0 = c0; p.a1 = (const bf16*)x1; p.c1 = x1 ? c1 : 0; p.lda1 = c1;
-  p.H = H; p.W = W;
-  int OH = H, OW = W;
-  if (ups) { OH *= 2; OW *= 2; }
-  if (stride == 2) { OH = (OH - 1) / 2 + 1; OW = (OW - 1) / 2 + 1; }
-  p.OH = OH; p.OW = OW; p.ksize = 3; p.stride = stride; p.ups = ups;
-  p.w = (const bf16*)w; p.M = nimg * OH * OW; p.N = Cout; p.K = 9 * (p.c0 + p.c1);
-  p.bias = bias; p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
-  p.res = (const bf16*)res; p.ldr = Cout; p.out = (bf16*)out; p.ldo = Cout; p.out_scale = 1.f;
+  NrGemmParams p = nr_gemm_params((const bf16*)x0, c0, c0, (const bf16*)x1, c1, c1, nimg, H, W, 3, stride, ups, (const bf16*)w, Cout, bias, (const bf16*)res,
+                                  Cout, (bf16*)out, Cout);
+  p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
   LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
   NR_CATCH
 }
@@ -3334,13 +3106,10 @@ extern "C" nr_status nr_op_conv3x3_tap_inner(nr_stream stream, const void* x0, i
                                              const float* bias, const float* rowvec, int32_t rowvec_div, const void* res, void* out,
                                              int32_t Cout) {
   NR_TRY
-  NrGemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.a0 = (const bf16*)x0; p.c0 = c0; p.lda0 = c0;
-  p.H = H; p.W = W; p.OH = H; p.OW = W; p.ksize = 3; p.stride = 1; p.tap_inner = 1;
-  p.w = (const bf16*)w; p.M = nimg * H * W; p.N = Cout; p.K = 9 * c0;
-  p.bias = bias; p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
-  p.res = (const bf16*)res; p.ldr = Cout; p.out = (bf16*)out; p.ldo = Cout; p.out_scale = 1.f;
+  NrGemmParams p = nr_gemm_params((const bf16*)x0, c0, c0, nullptr, 0, 0, nimg, H, W, 3, 1, 0, (const bf16*)w, Cout, bias, (const bf16*)res, Cout, (bf16*)out,
+                                  Cout);
+  p.tap_inner = 1;
+  p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
   LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
   NR_CATCH
 }
@@ -3349,11 +3118,8 @@ extern "C" nr_status nr_op_groupnorm(nr_stream stream, const void* x0, int32_t c
                                      int32_t hw, int32_t groups, const float* gamma, const float* beta, float eps,
                                      int32_t silu, float* partial_ws, void* out) {
   NR_TRY
-  NrGnParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.x0 = (const bf16*)x0; p.c0 = c0; p.ld0 = c0; p.x1 = (const bf16*)x1; p.c1 = x1 ? c1 : 0; p.ld1 = c1;
-  p.nimg = nimg; p.hw = hw; p.groups = groups; p.partial = partial_ws; p.gamma = gamma; p.beta = beta; p.eps = eps;
-  p.silu = silu; p.out = (bf16*)out; p.ldo = p.c0 + p.c1;
+  NrGnParams p = nr_gn_params((const bf16*)x0, c0, c0, (const bf16*)x1, c1, c1, nimg, hw, groups, gamma, beta, eps, silu, partial_ws, (bf16*)out,
+                              c0 + (x1 ? c1 : 0));
   LAUNCH_OK(nr_launch_groupnorm(&p, (hipStream_t)stream));
   NR_CATCH
 }
@@ -3370,31 +3136,14 @@ extern "C" nr_status nr_op_attention(nr_stream stream, int32_t mode, const void*
                                      int32_t nimg, int32_t L, int32_t Lk, int32_t C, int32_t heads, int32_t frames,
                                      int32_t kv_div) {
   NR_TRY
-  NrAttnParams p;
-  std::memset(&p, 0, sizeof(p));
-  const bf16* q = (const bf16*)qp; const bf16* kv = (const bf16*)kvp;
   const int fp8_flag = (mode & 8) ? 1 : 0;      // mode | 8: e4m3 MFMA operands (spatial / cross kernels)
   const int causal_flag = (mode & 16) ? 1 : 0;  // mode | 16: causal mask (mode 0 only; the CLIP text encoder's form)
   mode &= 7;
   if (causal_flag && (mode != 0 || fp8_flag)) throw NrError(NR_ERR_ARG, "causal attention: mode 0 only");
-  p.heads = heads; p.d = C / heads; p.scale = 1.0f / std::sqrt((float)p.d); p.out = (bf16*)outp;
-  if (mode == 0) {
-    const int ld = 3 * C;
-    p.q = q; p.k = q + C; p.v = q + 2 * C; p.nbatch = nimg; p.Lq = L; p.Lk = L; p.inner = 1; p.kv_inner = 1; p.kv_div = 1;
-    p.q_outer = (long long)L * ld; p.q_seq = ld; p.kv_outer = p.q_outer; p.kv_seq = ld;
-    p.o_outer = (long long)L * C; p.o_seq = C;
-  } else if (mode == 1) {
-    p.q = q; p.k = kv; p.v = kv + C; p.nbatch = nimg; p.Lq = L; p.Lk = Lk; p.inner = 1; p.kv_inner = 1; p.kv_div = kv_div;
-    p.q_outer = (long long)L * C; p.q_seq = C; p.kv_outer = (long long)Lk * 2 * C; p.kv_seq = 2 * C;
-    p.o_outer = (long long)L * C; p.o_seq = C;
-  } else if (mode == 2) {
-    const int ld = 3 * C, hw = L, F = frames;
-    p.q = q; p.k = q + C; p.v = q + 2 * C; p.nbatch = (nimg / F) * hw; p.Lq = F; p.Lk = F; p.inner = hw; p.kv_inner = hw; p.kv_div = 1;
-    p.q_outer = (long long)F * hw * ld; p.q_inner_stride = ld; p.q_seq = (long long)hw * ld;
-    p.kv_outer = p.q_outer; p.kv_inner_stride = ld; p.kv_seq = p.q_seq;
-    p.o_outer = (long long)F * hw * C; p.o_inner_stride = C; p.o_seq = (long long)hw * C;
-  } else throw NrError(NR_ERR_ARG, "bad attention mode");
-  p.fp8 = fp8_flag; p.causal = causal_flag;
+  if (mode > 2) throw NrError(NR_ERR_ARG, "bad attention mode");
+  // the hook's tensors are dense: q|k|v rows of 3C (modes 0 / 2), q rows of C and k|v rows of 2C (mode 1), output rows of C
+  const NrAttnParams p = nr_attn_params(mode, (const bf16*)qp, (const bf16*)kvp, (bf16*)outp, mode == 1 ? C : 3 * C, 2 * C, C, nimg, L, Lk, C, heads, frames, kv_div,
+                                        causal_flag, fp8_flag);
   LAUNCH_OK(nr_launch_attention(&p, (hipStream_t)stream));
   NR_CATCH
 }
@@ -3411,7 +3160,7 @@ extern "C" nr_status nr_op_ff_fused(nr_stream stream, const void* t_dev, const v
   // w1 == NULL: reuse the stage stream packed by the previous call (timing loops)
   if (w1_geglu_dev) LAUNCH_OK(nr_launch_ff_stream_pack((const bf16*)w1_geglu_dev, (const bf16*)wc_dev, (bf16*)ws, (hipStream_t)stream));
   LAUNCH_OK(nr_launch_ff_fused((const bf16*)t_dev, C, (const bf16*)x_dev, C, (bf16*)out_dev, C, M, (const bf16*)ws, gamma_dev, beta_dev,
-                               b1_geglu_dev, bc_dev, ln_eps, getenv("NR_DETERMINISTIC_BATCH") && getenv("NR_DETERMINISTIC_BATCH")[0] == '1', (hipStream_t)stream));
+                               b1_geglu_dev, bc_dev, ln_eps, env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
   NR_CATCH
 }
 
@@ -3430,7 +3179,7 @@ extern "C" nr_status nr_op_tattn_fused_frames(nr_stream stream, void* t_dev, int
   if (wq_dev) LAUNCH_OK(nr_launch_tattn_stream_pack((const bf16*)wq_dev, (const bf16*)wk_dev, (const bf16*)wv_dev, (const bf16*)wo_dev, (bf16*)ws,
                                                     (hipStream_t)stream));
   LAUNCH_OK(nr_launch_tattn_fused((bf16*)t_dev, nbatch, frames, hw, (const bf16*)ws, gamma_dev, gb_dev, bo_dev, ln_eps,
-                                  getenv("NR_DETERMINISTIC_BATCH") && getenv("NR_DETERMINISTIC_BATCH")[0] == '1', (hipStream_t)stream));
+                                  env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
   NR_CATCH
 }
 extern "C" nr_status nr_op_xattn_fused(nr_stream stream, void* t_dev, int32_t nimg, int32_t hw, int32_t img_per_ctx, const void* wq_dev,
@@ -3441,21 +3190,17 @@ extern "C" nr_status nr_op_xattn_fused(nr_stream stream, void* t_dev, int32_t ni
   if (!nr_xattn_fused_eligible(320, 8, Lk, hw, 1 << 30) || nimg <= 0 || img_per_ctx <= 0 || nctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
     throw NrError(NR_ERR_UNSUPPORTED, "fused cross attention: C = 320, 8 heads, Lk <= 80, hw % 128 == 0, one context per img_per_ctx images");
   static void* ws = nullptr;
-  static void* kvs = nullptr;
-  static size_t kvs_bytes = 0;
+  static OpScratch kvbuf;
   if (!ws) HIP_OK(hipMalloc(&ws, nr_xattn_wstream_bytes()));
-  if (kvs_bytes < nr_xattn_kvstream_bytes(nctx)) {
-    if (kvs) { HIP_OK(hipDeviceSynchronize()); HIP_OK(hipFree(kvs)); }
-    kvs_bytes = nr_xattn_kvstream_bytes(nctx);
-    HIP_OK(hipMalloc(&kvs, kvs_bytes));
-  }
+  op_scratch(kvbuf, nr_xattn_kvstream_bytes(nctx));
+  void* kvs = kvbuf.ptr;
   // wq == NULL: reuse the streams packed by the previous call (timing loops)
   if (wq_dev) {
     LAUNCH_OK(nr_launch_xattn_w_pack((const bf16*)wq_dev, (const bf16*)wo_dev, (bf16*)ws, (hipStream_t)stream));
     LAUNCH_OK(nr_launch_xattn_kv_pack((const bf16*)kv_dev, ldkv, Lk, nctx, (bf16*)kvs, (hipStream_t)stream));
   }
   LAUNCH_OK(nr_launch_xattn_fused((bf16*)t_dev, nimg, hw, img_per_ctx, nctx, Lk, (const bf16*)ws, (const bf16*)kvs, gamma_dev, beta_dev, bo_dev, ln_eps,
-                                  getenv("NR_DETERMINISTIC_BATCH") && getenv("NR_DETERMINISTIC_BATCH")[0] == '1', (hipStream_t)stream));
+                                  env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
   NR_CATCH
 }
 // ---- q projection + context attention above the C = 320 level (xattnw.hip), op-level entry for tests.  t: bf16 [nimg * hw][C] (C = 640 or 1280,
@@ -3471,19 +3216,13 @@ extern "C" nr_status nr_op_xattn_head(nr_stream stream, const void* t_dev, void*
     throw NrError(NR_ERR_UNSUPPORTED, "cross-attention head kernel: C = 640 or 1280, 8 heads, Lk <= 80, hw % 64 == 0, one context per img_per_ctx images");
   static void* ws[2] = {nullptr, nullptr};
   static void* tbl[2] = {nullptr, nullptr};
-  static void* kvs = nullptr;
-  static size_t kvs_cap = 0;
+  static OpScratch kvbuf;
   const int ci = C == 640 ? 0 : 1;
   if (!ws[ci]) HIP_OK(hipMalloc(&ws[ci], nr_xattnw_wstream_bytes(C)));
   if (!tbl[ci]) HIP_OK(hipMalloc(&tbl[ci], nr_xattnw_table_bytes(C)));
   const size_t need = nr_xattnw_kvstream_bytes(C, nctx);
-  if (need > kvs_cap) {
-    HIP_OK(hipDeviceSynchronize());
-    if (kvs) (void)hipFree(kvs);
-    HIP_OK(hipMalloc(&kvs, need));
-    HIP_OK(hipMemset(kvs, 0, need));
-    kvs_cap = need;
-  }
+  if (op_scratch(kvbuf, need)) HIP_OK(hipMemset(kvbuf.ptr, 0, need));
+  void* kvs = kvbuf.ptr;
   // wq_folded == NULL: reuse the streams packed by the previous call at this C (timing loops)
   if (wq_folded_dev) {
     if (!lnc_dev || !bias_dev) throw NrError(NR_ERR_ARG, "null argument");

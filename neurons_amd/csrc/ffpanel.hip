@@ -23,7 +23,7 @@
 //     g-piece columns is permuted to exactly that at weight-conversion time, so the accumulator -> operand hand-over is lane-local
 //     (no LDS round trip, no shuffles).
 // Algorithmic work per launch at M = 32768: 87 GFLOP; HBM: t + x + out = 63 MB (+ 2.6 MB of weights, L2-resident per XCD).
-#include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 namespace {

@@ -20,7 +20,7 @@
 //   * split-K for small-M / huge-K layers (the 4x4 and 8x8 levels: M = 512..2048, K up to 23 040):
 //     each slice writes an fp32 slab, a second kernel sums the slabs in fixed order (deterministic, no
 //     atomics) and applies the epilogue.
-#include "common.h"
+#include "launchers.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -773,15 +773,6 @@ void apply_override(const NrGemmParams& p, Plan& pl, int& m_fast) {
 }
 
 }  // namespace
-
-extern "C" int nr_rowpanel_eligible(const NrGemmParams* pp);
-extern "C" int nr_launch_rowpanel(const NrGemmParams* pp, hipStream_t stream);
-// gemm8p.hip: 256-row ping-pong kernel for the big launches (SparseCtrl groups, several clips per call, 32-frame clips, the VAE)
-extern "C" int nr_g8p_plan(const NrGemmParams* pp);
-extern "C" int nr_launch_g8p(const NrGemmParams* pp, int m_fast, hipStream_t stream);
-// smallm.hip: panel-resident kernel for the M <= 512 Linears; needs the fragment-major copy of the weights (NrGemmParams::w_fm)
-extern "C" int nr_smallm_eligible(const NrGemmParams* pp);
-extern "C" int nr_launch_smallm(const NrGemmParams* pp, hipStream_t stream);
 
 // fp32 scratch (bytes) a launch of this shape needs for split-K slabs (0 if none)
 extern "C" size_t nr_igemm_workspace_bytes(const NrGemmParams* pp) {

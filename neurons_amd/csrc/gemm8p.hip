@@ -25,7 +25,7 @@
 //     coalesced bias / row-vector / residual / output accesses, identical arithmetic to gemm.hip's staged epilogue (incl. GEGLU, even NT).
 // Not here (the launcher falls back to gemm.hip): split-K, the LayerNorm-folded variant, raw fp32 output, strided / upsampling /
 // tap-major 3x3 convs, grids that would leave the chip under-filled.
-#include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 namespace {

@@ -1,0 +1,116 @@
+// The one declaration of every launcher, eligibility rule and size function that crosses a translation unit of this library.
+// Included by the file that defines a function and by every file that calls it, so the compiler checks each definition against the
+// prototype its callers see (the names are extern "C": a mismatch would otherwise link cleanly).
+#pragma once
+#include "common.h"
+
+extern "C" {
+// gemm.hip: tiled implicit GEMM (1x1 / 3x3) and its split-K scratch
+int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStream_t stream);
+size_t nr_igemm_workspace_bytes(const NrGemmParams* pp);
+// rowpanel.hip: K = 320 row-panel GEMM
+int nr_rowpanel_eligible(const NrGemmParams* pp);
+int nr_launch_rowpanel(const NrGemmParams* pp, hipStream_t stream);
+// gemm8p.hip: 256-row ping-pong kernel for the big launches (SparseCtrl groups, several clips per call, 32-frame clips, the VAE)
+int nr_g8p_plan(const NrGemmParams* pp);
+int nr_launch_g8p(const NrGemmParams* pp, int m_fast, hipStream_t stream);
+// lin160.hip: short-K Linears (K = 640 / 1280, N % 160 == 0, >= 2048 rows) on fragment-major weights
+size_t nr_lin160_stream_bytes(int N, int K);
+int nr_lin160_eligible(const NrGemmParams* pp);
+int nr_lin160_panel_rule(int Mp, int N, int K);
+size_t nr_lin128q_stream_bytes(int N, int K);
+int nr_launch_lin128q_w_pack(const bf16* w, int N, int K, bf16* stream, hipStream_t s);
+int nr_launch_lin160_w_pack(const bf16* w, int N, int K, bf16* stream, hipStream_t s);
+int nr_launch_lin160(const NrGemmParams* pp, const bf16* stream, hipStream_t s);
+int nr_gn_workspace_floats(int nimg, int hw, int groups, int* pix_per_blk_out, int* nchunk_out);
+int nr_launch_groupnorm(NrGnParams* pp, hipStream_t stream);
+int nr_launch_layernorm(const bf16* x, int ldx, bf16* out, int ldo, int M, int C, const float* gamma, const float* beta,
+                        float eps, const float* pe, int pe_hw, int pe_F, hipStream_t stream);
+int nr_launch_attention(const NrAttnParams* pp, hipStream_t stream);
+int nr_launch_conv_in_small(const float* s0, const float* s1, int c0, int c1, int src_batch, int nimg, int F, int H, int W,
+                            const float* wT, const float* bias, const float* addend, int Cout, bf16* out, float in_scale,
+                            float in_shift, hipStream_t stream);
+int nr_launch_clip_embed(const int* ids, const float* tok, const float* pos, bf16* out, int M, int L, int C, int vocab,
+                         hipStream_t stream);
+int nr_launch_bf16_to_f32(const bf16* a, float* out, long long n, hipStream_t stream);
+int nr_launch_gaussian_sample(const float* moments, const float* noise, float* out, int n, int zc, int hw, float scale,
+                              hipStream_t stream);
+int nr_launch_post_quant(const float* z, float scale, const float* Q, const float* qb, float* out, int nimg, int C, int hw,
+                         hipStream_t stream);
+int nr_launch_softmax_rows(const float* S, bf16* P, int rows, int L, float scale, hipStream_t stream);
+int nr_launch_conv_out_small(const bf16* x, int Cin, int nimg, int F, int H, int W, const bf16* w, const float* bias,
+                             int Cout, float* out, float out_mul, float out_add, int clamp01, hipStream_t stream);
+int nr_launch_timestep_sincos(const float* t, int M, int dim, float* out, hipStream_t stream);
+int nr_launch_linear_small(const float* x, int M, int K, const bf16* W, const float* b, int N, int in_act, int out_act,
+                           float* y, const float* addend, hipStream_t stream);
+int nr_launch_edm_cfg_euler(const float* net, const float* x, float* x_out, long long total, float scale, float sigma_q,
+                            float sigma, float sigma_next, hipStream_t stream);
+int nr_launch_cfg_combine(const float* eps, float* out, long long total, float guidance, hipStream_t stream);
+int nr_launch_cfg_ddim_step(const float* eps, const float* x, float* x_out, long long total, float guidance, int do_cfg,
+                            float sqrt_at, float sqrt_1mat, float sqrt_ap, float sqrt_1map, hipStream_t stream);
+int nr_launch_cfg_ddim_full(const float* eps, const float* x, const float* noise, float* x_out, float* x0_out, long long total, float guidance,
+                            int do_cfg, int pred, int clip, int clipped_out, float sqrt_at, float sqrt_1mat, float sqrt_ap, float dir, float sigma,
+                            hipStream_t stream);
+int nr_launch_add_bf16(const bf16* a, const bf16* b, bf16* out, long long n, hipStream_t stream);
+int nr_launch_prior_p_sample(const float* pred, const float* pred_null, const float* x, const float* noise, float* x_out, float* x_start_out,
+                             long long total, float cond_scale, int mode, int clamp, float sqrt_ac, float sqrt_1mac, float sqrt_recip_ac,
+                             float sqrt_recipm1_ac, float coef1, float coef2, float sigma, hipStream_t stream);
+int nr_launch_f32_to_bf16(const float* a, bf16* out, long long n, hipStream_t stream);
+int nr_launch_add_bf16_multi(const NrAddMulti* p, hipStream_t stream);
+int nr_launch_frame_gather(const bf16* src, bf16* dst, int B, int Fs, int Fd, long long frame_elems, const int* map, hipStream_t stream);
+int nr_launch_ncfhw_to_nhwc(const float* src, bf16* dst, int B, int C, int F, int HW, hipStream_t stream);
+int nr_launch_nhwc_to_ncfhw(const bf16* src, float* dst, int B, int C, int F, int HW, hipStream_t stream);
+int nr_groupnorm_launches(const NrGnParams* p);
+int nr_launch_fold_linear_pair(const float* w2, const float* w1, const float* b2, const float* b1, int C, int J, bf16* wc, float* bc,
+                               hipStream_t stream);
+// smallm.hip: panel-resident kernel of the M <= 512 Linears (fragment-major weights)
+int nr_smallm_eligible(const NrGemmParams* pp);
+int nr_launch_smallm(const NrGemmParams* pp, hipStream_t stream);
+int nr_launch_smallm_w_pack(const void* w, void* out, int N, int K, hipStream_t stream);
+// tattn.hip: one kernel per temporal-attention block of the C = 320 level
+size_t nr_xattn_wstream_bytes(void);
+size_t nr_xattn_kvstream_bytes(int nctx);
+int nr_xattn_fused_eligible(int C, int heads, int Lk, int hw, long long rows);
+int nr_launch_xattn_w_pack(const bf16* wq, const bf16* wo, bf16* stream, hipStream_t s);
+int nr_launch_xattn_kv_pack(const bf16* kv, int ldkv, int Lk, int nctx, bf16* stream, hipStream_t s);
+int nr_launch_xattn_fused(bf16* t, int nimg, int hw, int img_per_ctx, int nctx, int Lk, const bf16* wstream, const bf16* kvstream, const float* gamma,
+                          const float* beta, const float* bo, float ln_eps, int norot, hipStream_t s);
+size_t nr_tattn_stream_bytes(void);
+int nr_tattn_fused_eligible(int C, int heads, int frames, int hw, long long rows);
+int nr_launch_tattn_stream_pack(const bf16* wq, const bf16* wk, const bf16* wv, const bf16* wo, bf16* stream, hipStream_t s);
+int nr_launch_tattn_fused(bf16* t, int nbatch, int frames, int hw, const bf16* stream, const float* gamma, const float* gb, const float* bo, float ln_eps,
+                          int norot, hipStream_t s);
+// xattnw.hip: q projection + context attention per (64 rows, 160 columns) above the C = 320 level (C = 640 / 1280, <= 80 text tokens)
+size_t nr_xattnw_wstream_bytes(int C);
+size_t nr_xattnw_kvstream_bytes(int C, int nctx);
+size_t nr_xattnw_table_bytes(int C);
+int nr_xattnw_eligible(int C, int heads, int Lk, int hw, long long rows);
+int nr_launch_xattnw_w_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s);
+int nr_launch_xattnw_table_pack(const float* lnc, const float* bias, int C, float* table, hipStream_t s);
+int nr_launch_xattnw_kv_pack(const bf16* kv, int ldkv, int Lk, int nctx, int C, bf16* kvs, hipStream_t s);
+int nr_launch_xattnw(const bf16* t, bf16* out, int nimg, int hw, int img_per_ctx, int nctx, int Lk, int C, const bf16* wstream, const bf16* kvstream,
+                     const float* table, float ln_eps, hipStream_t s);
+// tattnw.hip: q|k|v projection of one head + F x F attention per (pixel group, head) above the C = 320 level (C = 640 / 1280, F = 16 / 32)
+size_t nr_tattnw_stream_bytes(int C);
+int nr_tattnw_eligible(int C, int heads, int frames, int hw, long long rows);
+int nr_launch_tattnw_stream_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s);
+size_t nr_tattnw_table_bytes(int C, int frames);
+int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, const float* rowvec, int C, int frames, float* table, hipStream_t s);
+int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int frames, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s);
+// ffpanel.hip: fused FeedForward(GEGLU) + proj_out of the C = 320 level
+size_t nr_ff_stream_bytes(int C);
+int nr_ff_fused_eligible(int C, long long M);
+int nr_launch_ff_stream_pack(const bf16* w1, const bf16* wc, bf16* stream, hipStream_t s);
+int nr_launch_ff_fused(const bf16* t, int ldt, const bf16* x, int ldx, bf16* out, int ldo, int M, const bf16* stream, const float* gamma,
+                       const float* beta, const float* b1, const float* bc, float ln_eps, int norot, hipStream_t s);
+// elementwise.hip condembed_*: SparseCtrl image-condition embedding (first conv from the fp32 planes, small-channel MFMA convs, batch / frame broadcast)
+int nr_condembed_in_supported(int cin, int Cout);
+int nr_launch_condembed_in(const float* cond, const float* mask, int c0, int nsrc, int F, int H, int W, const int* fmap, int Fe,
+                           const float* wT, const float* bias, int Cout, bf16* out, hipStream_t s);
+int nr_condembed_conv_supported(int Cin, int stride, int Cout);
+long long nr_condembed_wfm_elems(int Cin, int Cout);
+int nr_launch_condembed_conv(const bf16* x, int nimg, int H, int W, int Cin, int stride, const bf16* wfm, const float* bias, int Cout,
+                             int silu, bf16* out, hipStream_t s);
+int nr_launch_condembed_bcast(const bf16* emb, int cb, int Fe, const int* emap, int B, int F, long long img_elems, const bf16* add,
+                              bf16* out, hipStream_t s);
+}

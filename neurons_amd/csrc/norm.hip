@@ -11,7 +11,7 @@
 // float atomics) and gn_apply (re-reduces the partials, folds gamma/beta/mean/rstd into a per-channel
 // scale+shift held in LDS, streams the pixels).  Both accept a channel-concat of two sources so the
 // up-block skip concat (unet_blocks.py:634,740) is never materialised for the norm.
-#include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 

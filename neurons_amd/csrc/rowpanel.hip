@@ -18,7 +18,7 @@
 //     wave-private LDS transpose so that every global store is 16 bytes per lane over whole 128-byte row segments.
 //   All vector-memory instructions of an iteration have fixed counts (raw buffer loads/stores with range checking instead of
 //   branches), which is what makes the counted s_waitcnt in front of the barrier valid.
-#include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 namespace {

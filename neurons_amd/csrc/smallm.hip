@@ -26,7 +26,7 @@
 // wave), with the wait + barrier of a chunk (1.0-1.9 k) not overlapped.
 // Round 3 had rejected the row-major form of this kernel (0.62-0.68x the igemm: 40 fragment-shaped loads took 8,400 cycles to ISSUE);
 // DESIGN_HISTORY.md has that story, profiles/r05_smallm_fm_ab.txt the first fragment-major A/B.
-#include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 namespace {

@@ -25,7 +25,7 @@
 //   * out += Wo_h . O_h^T accumulates over the heads in 160 VGPRs; epilogue t + bo + acc, written in place (rows are private).
 // Algorithmic work per launch at M = 32768: 26.8 GFLOP GEMM + 0.17 GFLOP attention; HBM: t in + t out = 42 MB (+ 1.1 MB of weights,
 // L2-resident per XCD).
-#include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 namespace {

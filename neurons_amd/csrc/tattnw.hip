@@ -35,7 +35,7 @@
 // loop has left.  Per query tile: S^T = 2 tiles of 16 keys, softmax over the 32 keys, O^T = V^T P^T in ONE v_mfma_f32_16x16x32_bf16 per 16 channels (the
 // lane's four keys of each half, concatenated, are its eight k-slots of both operands).  The epilogue table has one 17-row part per half (row 0: c again,
 // row 1 + f: frame 16 half + f), DMA'd into the two slots the last two finished stages left.  Registers and LDS: the header of TW.
-#include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 namespace {

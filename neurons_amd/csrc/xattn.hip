@@ -21,7 +21,7 @@
 //     slots = 5 x 4 registers x 4 lane groups (keys >= Lk masked), O^T = V^T P^T (3 x 5); every accumulator -> operand hand-over is lane-local.
 //   * out += Wo_h . O_h^T accumulates over the heads in 160 VGPRs; epilogue t + bo + acc, written in place (rows are private).
 // Algorithmic work per launch at M = 32768: 13.4 GFLOP of projections + 3.2 GFLOP of attention; HBM: t in + t out = 42 MB.
-#include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 namespace {

@@ -14,7 +14,7 @@
 //   * behind the k-loop the ring is re-used for the K / V^T images of the workgroup's 160 columns for the row's context (packed once per context by
 //     xattnw_kv_pack_kernel: MFMA fragments of v_mfma_f32_16x16x16_bf16, keys >= Lk zero / masked);  S^T = K Q^T (5 key tiles), softmax over the 80 key
 //     slots (4 registers x 5 tiles x 4 lane groups), O^T = V^T P^T, 8-byte stores of a[row][cols].
-#include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 namespace {

@@ -105,6 +105,16 @@ int main(int argc, char** argv) {
       OK(nr_denoise_step_forward(u, c, nullptr, sample, ts, ctx, 77, cond, mask, 1, 1.0f, res.data(), res[nres], out, ts));
       OK(nr_denoise_step_forward(u, c, nullptr, sample, ts, ctx, 77, cond, mask, 1, 1.0f, res.data(), res[nres], out, nullptr));
     }
+    // graphs still on.  One set of pointers gives one graph key whichever entry point it came through: a U-Net evaluation captured by
+    // nr_unet3d_forward is replayed by nr_denoise_step_forward.  (SparseCtrl's graphs for these pointers were captured by the loop above and
+    // its last call left no prefetch pending, so every capture counted here is the U-Net's.)
+    {
+      float* out2 = out + (1 << 20);
+      OK(nr_unet3d_forward(u, nullptr, sample, ts, ctx, 77, (const void* const*)res.data(), res[nres], out2));
+      const long captured = nr_stub_captures();
+      OK(nr_denoise_step_forward(u, c, nullptr, sample, ts, ctx, 77, cond, mask, 1, 1.0f, res.data(), res[nres], out2, nullptr));
+      CHECK(nr_stub_captures() == captured, "the same U-Net pointers through another entry point must not capture again");
+    }
     CHECK(nr_unet3d_forward(u, nullptr, sample, ts, ctx, 76, nullptr, nullptr, out) == NR_ERR_ARG, "wrong ctx_len");
     // graph-slot LRU: 80 different output pointers -> 80 captures of the segments that see `out`, at most 64 live per segment
     for (int i = 0; i < 80; ++i) OK(nr_unet3d_forward(u, nullptr, sample, ts, ctx, 77, nullptr, nullptr, out + 16 * i));
