@@ -15,6 +15,7 @@
 // registers.  Row max / row sum are two xor-shuffles across the 4 lane groups.  V tiles are staged
 // transposed in a per-wave LDS region.
 #include "launchers.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -196,22 +197,6 @@ __device__ __forceinline__ long to_fp8x8(const float (&v)[8]) {
 // registers (Q, K, V from their bf16 tiles; P straight from its fp32 exponentials, scaled by 256 so the probabilities use the
 // e4m3 normal range, and the sum divided back in fp32); softmax statistics and accumulators stay fp32.  The non-scaled fp8 MFMA
 // issues at the bf16 rate (MI355X_MICROARCH.md), so this variant is about the numerics of config 5, not about speed.
-// max / sum over the four 16-lane rows of a wave (lanes l, l^16, l^32, l^48) on the VALU: v_permlane16_swap exchanges the odd rows of
-// its first operand with the even rows of its second, v_permlane32_swap the upper half of the first with the lower half of the second;
-// with both operands = v every lane gets {own, partner} in the two results (a ds_bpermute round trip through the LDS otherwise).
-__device__ __forceinline__ float rows_max(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float rows_sum(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
 // acc += A B with the accumulator TIED (vDst = SrcC).  In the ONES instantiation hipcc 7.2 otherwise allocates the third accumulator as a
 // v[2:5] -> v[0:3] -> v[2:5] chain (destination partially overlapping the SrcC the previous MFMA wrote) with no wait states between the
 // dependent MFMAs, and the kernel returns wrong sums on gfx950 (tools/check_mfma_overlap.py scans the shipped ISA for that pattern).
@@ -276,7 +261,6 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(NrAttnParams p) {
   // d = 40 / 48 (DK = 2, DT = 3): the second k-step of K Q^T covers dims 32..47 only, so it runs on v_mfma_f32_16x16x16_bf16 (K = 16: half the
   // matrix-pipe cycles of the 32-deep form, whose upper 16 dims would multiply zeros): lane group g supplies dims 32 + 4g .. 32 + 4g + 3
   constexpr bool K48 = !FP8 && DK == 2 && DT == 3;
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
   s16x4 qf4 = {0, 0, 0, 0};
   if constexpr (K48) {
     const int dim0 = 32 + 4 * g;
@@ -412,7 +396,7 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(NrAttnParams p) {
     mx *= sl2;                                 // sl2 > 0: the max of this lane's scaled scores
     float m_new = m_i;
     if (__builtin_amdgcn_ballot_w64(mx > m_i + LAZY) != 0ull) {
-      mx = rows_max(mx);
+      mx = nr_rows_max(mx);
       m_new = mx > m_i + LAZY ? mx : m_i;
       // l_i stays a per-lane partial sum (this lane's 16 keys of every tile); the four rows are added once after the loop
       const float alpha = __builtin_amdgcn_exp2f(m_i - m_new);      // 1 for the queries whose reference stays
@@ -463,7 +447,7 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(NrAttnParams p) {
   // compiled stream happened to leave ~13 (two branches, a wait, a barrier, four VALU ops): state the distance instead of relying on it.
   if constexpr (ONES) asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
   if constexpr (ONES) l_all = __shfl(acc[2][0], 32 + c, 64);
-  else l_all = rows_sum(l_i);
+  else l_all = nr_rows_sum(l_i);
   if (qrow < p.Lq) {
     const float inv = (FP8 && !ONES ? 1.0f / 256.0f : 1.0f) / l_all;      // ONES + FP8: the 256 of the scaled probabilities is in l_all too
     bf16* op = p.out + obase + (long long)qrow * p.o_seq;

@@ -24,19 +24,10 @@
 //     (no LDS round trip, no shuffles).
 // Algorithmic work per launch at M = 32768: 87 GFLOP; HBM: t + x + out = 63 MB (+ 2.6 MB of weights, L2-resident per XCD).
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdlib>
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(lds_wave_base) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int FF_C = 320;
 constexpr int FF_ROWS = 128;                 // rows per workgroup: 4 waves x 32 rows (MT = 2) or 8 waves x 16 rows (MT = 1)
@@ -62,9 +53,6 @@ struct NrFFParams {
   float ln_eps;
 };
 
-// exact-erf GELU gate times the value, two outputs at a time (Abramowitz-Stegun 7.1.25 as gelu_erf_fast of common.h)
-__device__ __forceinline__ float geglu1(float v, float g) { return v * gelu_erf_fast(g); }
-
 // MT = 16-row tiles per wave.  MT = 2: four waves, one per SIMD (round 3).  MT = 1 (round 4): EIGHT waves of 16 rows, two per SIMD: the same
 // 128-row workgroup, weight stream and LDS ring, but the matrix pipe of a SIMD now has a second wave to take MFMAs from while the first is in
 // its GELU / packing VALU work (round 3 measured the one-wave form issue-bound: 83 k MFMA + 71 k VALU + 59 k wait cycles, nothing overlapping).
@@ -88,7 +76,7 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
   // alone, so they are reproducible run to run). ----
   const int pair0 = p.norot ? 0 : (int)((blockIdx.x >> 3) % FF_PAIRS);
   const char* wsrc = reinterpret_cast<const char*>(p.stream) + (size_t)wave * (FF_DMA * 1024) + (size_t)lane * 16;
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)smem) + (unsigned)wave * (FF_DMA * 1024);
+  const unsigned lds0 = nr_lds_addr(smem) + (unsigned)wave * (FF_DMA * 1024);
   // logical stage s (order of execution) -> stage of the stream
   auto phys_stage = [&](int s) {
     if (s < FF_TSTAGES) return s;
@@ -99,7 +87,7 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
   };
   auto issue_piece = [&](int s, int slot, int i) {      // one of the 10 LDS-DMA instructions of logical stage s
     const char* src = wsrc + (size_t)phys_stage(s) * (FF_STAGE * 2);
-    glds16(src + i * 1024, lds0 + (unsigned)(slot * FF_STAGE * 2) + (unsigned)(i * 1024));
+    nr_glds16(src + i * 1024, lds0 + (unsigned)(slot * FF_STAGE * 2) + (unsigned)(i * 1024));
   };
 #pragma unroll
   for (int i = 0; i < FF_DMA; ++i) issue_piece(0, 0, i);
@@ -136,7 +124,7 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
   auto stage_begin = [&]() -> const bf16* {
     // stage s must have landed: this wave's 10 DMA pieces of stage s + 1 (issued during stage s - 1) may stay outstanding.  No other
     // vector-memory operation is issued inside the loop, so the count is exact.
-    if (s + 1 < FF_NSTAGES) wait_vmcnt<FF_DMA>(); else wait_vmcnt<0>();
+    if (s + 1 < FF_NSTAGES) nr_wait_vmcnt<FF_DMA>(); else nr_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();            // everyone's pieces of stage s landed; everyone is done reading stage s - 1
     // where the pieces of stage s + 2 come from / go to (the slot stage s - 1 occupied).  The last two stages re-fetch the final stage into
     // that free slot, so the piece issue stays unconditional (a branch per piece would cut the MFMA groups into separate scheduling regions)
@@ -149,7 +137,7 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
   };
   // piece i of stage s + 2 goes out behind MFMA group i of stage s: spreads the ~100-cycle issue cost of an LDS-DMA piece over the stage
   // instead of stalling its head
-  auto prefetch_piece = [&](int i) { if (i < FF_DMA) glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
+  auto prefetch_piece = [&](int i) { if (i < FF_DMA) nr_glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
   auto stage_end = [&]() { ++s; ring = ring + 1 == FF_NS ? 0 : ring + 1; };
 
   auto frag_n320 = [&](const bf16* sW, int nt, int ks2) {
@@ -285,8 +273,8 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
   float gt[MT][8];
   auto epi_slice = [&](const f32x4 (&acc)[4][MT], int i) {
     const int mt = i >> 2, h = (i >> 1) & 1, e0 = 2 * (i & 1);
-    float r0 = geglu1(acc[2 * h][mt][e0], acc[2 * h + 1][mt][e0]);
-    float r1 = geglu1(acc[2 * h][mt][e0 + 1], acc[2 * h + 1][mt][e0 + 1]);
+    float r0 = nr_geglu(acc[2 * h][mt][e0], acc[2 * h + 1][mt][e0]);
+    float r1 = nr_geglu(acc[2 * h][mt][e0 + 1], acc[2 * h + 1][mt][e0 + 1]);
     // pin the slice where it is written: without the opaque statement LLVM sinks the whole epilogue (pure arithmetic) down to its first
     // use, the operand packing in front of the g-piece, where no MFMA is left to hide it
     asm volatile("" : "+v"(r0), "+v"(r1));
@@ -364,7 +352,7 @@ __global__ __launch_bounds__(MT == 2 ? 256 : 512, MT == 2 ? 1 : 2) void ff_fused
     }
   }
 
-  wait_vmcnt<0>();      // the tail's dummy pieces
+  nr_wait_vmcnt<0>();      // the tail's dummy pieces
   // ---- epilogue: out = x + bc + acc.  In the accumulator layout a lane holds rows (16 mt + fr), columns 16 nt + 4 fg .. +3: 8-byte accesses in 32-byte
   // row segments.  Round 5 (as xattn.hip / tattn.hip): v_permlane16_swap between the column tiles (2 k, 2 k + 1) hands every lane 8 CONSECUTIVE columns
   // (even lane rows: tile 2 k, columns 4 fg .. 4 fg + 7; odd: tile 2 k + 1, columns 4 (fg - 1) ..), so residual loads and stores are 16 bytes per lane in

@@ -21,71 +21,27 @@
 //     each slice writes an fp32 slab, a second kernel sums the slabs in fixed order (deterministic, no
 //     atomics) and applies the epilogue.
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace {
 
-__device__ __attribute__((aligned(16))) const unsigned int nr_zero16[4] = {0u, 0u, 0u, 0u};
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// LDS-DMA as inline asm (glds16_asm), hidden from the compiler: a BUILTIN global_load_lds is a pending LDS write to hipcc, which then places
-// s_waitcnt vmcnt(0) in front of the next ds_read that may alias it, i.e. behind every barrier of the main loop, so a ring deeper
-// than two stages never actually has more than one tile in flight.  With the asm form only the counted wait + barrier of the main
-// loop order the DMA against the fragment reads (cdna_hip_programming.md 5.7); M0 is written and restored in the same statement.
-// M0 (the LDS destination) is written in the same statement that reads it and declared clobbered, so nothing is saved or
-// restored per transfer (hipcc only warns that m0 is a reserved register; it keeps no value in it across the statement).
-__device__ __forceinline__ void glds16_asm(const void* src, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(lds_wave_base) : "memory", "m0");
-}
+// the BUILTIN form of nr_glds16 (device_prims.h says what the compiler does with it): see ADMA below
 __device__ __forceinline__ void glds16_builtin(const void* src, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_wave_base, 16, 0, 0);
 }
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)p);
-}
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N <= 63) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-__device__ __forceinline__ size_t rowvec_row(const NrGemmParams& p, int m) {
-  int r = m / p.rowvec_div;
-  if (p.rowvec_mod) r %= p.rowvec_mod;
-  return (size_t)r * p.rowvec_ld;
-}
+// Diagnostic build only (make stamp -> libneurons_amd_stamp.so, tools/igemm_timeline.py): shader-clock stamps of wave 0 of the first
+// 512 workgroups; _RT: the chip-wide 100 MHz counter
+NR_STAMP_BUF(nr_stamp_buf, 512, 48);
+#define NR_STAMP_AT(slot) NR_STAMP_PUT(nr_stamp_buf, slot)
+#define NR_STAMP_RT(slot) NR_STAMP_PUT_RT(nr_stamp_buf, slot)
 
 // WGM x WGN = wave grid over the (M, N) tile; 64*WGM*WGN threads
 // ADMA: LDS-DMA issued from inline asm (tiles really stay in flight across the barrier; pays for long K) instead of the builtin
 // (the compiler then drains the DMA in front of the next fragment read: DMA and MFMA of a k-tile do not overlap, but its M0
 // handling is cheaper: measured faster for the short-K Linears of this workload).
-// a / d for 0 <= a < 2^22, d > 0 through the float reciprocal with one correction step (exact in that range).  The tile-index and
-// im2col-row arithmetic of the prologue used ~10 integer (two of them 64-bit) divisions = 2,300-3,100 of the 4,400-4,900 cycles between
-// kernel entry and the first LDS-DMA (in-kernel stamps, profiles/r03_igemm_timeline_smallm.txt): per WORKGROUP, i.e. once per tile.
-__device__ __forceinline__ int fdiv_small(int a, int d) {
-  int q = (int)((float)a * __builtin_amdgcn_rcpf((float)d));
-  const int r = a - q * d;
-  q += (r >= d ? 1 : 0) - (r < 0 ? 1 : 0);
-  return q;
-}
-
-#ifdef NR_STAMP
-// Diagnostic build only (make stamp -> libneurons_amd_stamp.so, tools/igemm_timeline.py): shader-clock stamps of wave 0 of the first
-// 512 workgroups.  The stamps go to a buffer of their own; no output value depends on them.
-#define NR_STAMP_SLOTS 48
-__device__ unsigned long long nr_stamp_buf[512][NR_STAMP_SLOTS];
-#define NR_STAMP_AT(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512 && (slot) < NR_STAMP_SLOTS) nr_stamp_buf[blockIdx.x][(slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-// the chip-wide 100 MHz counter (s_memtime counters are not synchronised across the chip): entry spread / kernel span over all workgroups
-#define NR_STAMP_RT(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512) nr_stamp_buf[blockIdx.x][(slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define NR_STAMP_AT(slot) do { } while (0)
-#define NR_STAMP_RT(slot) do { } while (0)
-#endif
-
 // LIN: the launch is a plain Linear (1x1, one source): the im2col / tap / two-source paths are compiled out.  Same arithmetic; what it buys is
 // code size: a launch starts with a cold instruction cache (tools/icache_probe.py: +0.4-1.4 us per launch when instantiations alternate, as
 // they do in the engine's graphs), and two thirds of the launches of a denoising step are Linears.  LayerNorm-folded launches are always Linears.
@@ -120,7 +76,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, local = orig >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
   }
-  const int slice = splitk > 1 ? fdiv_small(bid, ntn * ntm) : 0;
+  const int slice = splitk > 1 ? nr_fdiv_small(bid, ntn * ntm) : 0;
   bid -= slice * ntn * ntm;
   // tile order inside an XCD's range: the operand that is re-used by neighbouring tiles should be the BIG
   // one.  m_fast: neighbours share a weight panel (weight-heavy 4x4 / 8x8 levels); else an activation panel.
@@ -130,13 +86,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     // flight together on an XCD (2 per CU) then form a G x (64 / G) block: both operand panels of the block fit its 4 MiB L2, where
     // a plain n-fastest walk streams the whole weight matrix past the L2 once per m-tile row (W > L2: GEGLU / q|k|v at 16x16, 8x8)
     const int G = m_fast;
-    const int band = fdiv_small(bid, G * ntn);
+    const int band = nr_fdiv_small(bid, G * ntn);
     const int first = band * G;
     const int gsz = min(G, ntm - first);
     const int r = bid - band * G * ntn;
-    bn = fdiv_small(r, gsz);
+    bn = nr_fdiv_small(r, gsz);
     bm = first + r - bn * gsz;
-  } else if (m_fast) { bn = fdiv_small(bid, ntm); bm = bid - bn * ntm; } else { bm = fdiv_small(bid, ntn); bn = bid - bm * ntn; }
+  } else if (m_fast) { bn = nr_fdiv_small(bid, ntm); bm = bid - bn * ntm; } else { bm = nr_fdiv_small(bid, ntn); bn = bid - bm * ntn; }
   const int m0 = bm * BM, n0 = bn * BN;
   NR_STAMP_AT(40);
   const int lr = lane >> 3;                 // row within the 8-row group
@@ -157,9 +113,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
       a_pix[j] = mm; a_oy[j] = 0; a_ox[j] = 0;
     } else {
       const int ohw = p.OH * p.OW;
-      const int n = fdiv_small(mm, ohw);
+      const int n = nr_fdiv_small(mm, ohw);
       const int r = mm - n * ohw;
-      a_pix[j] = n; a_oy[j] = fdiv_small(r, p.OW); a_ox[j] = r - a_oy[j] * p.OW;
+      a_pix[j] = n; a_oy[j] = nr_fdiv_small(r, p.OW); a_ox[j] = r - a_oy[j] * p.OW;
     }
   }
   const bf16* zsrc = (const bf16*)nr_zero16;
@@ -186,7 +142,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   NR_STAMP_AT(41);
   const int nk_total = p.K / BK;
   int kt_begin = 0, kt_end = nk_total;
-  if (splitk > 1) { kt_begin = fdiv_small(nk_total * slice, splitk); kt_end = fdiv_small(nk_total * (slice + 1), splitk); }
+  if (splitk > 1) { kt_begin = nr_fdiv_small(nk_total * slice, splitk); kt_end = nr_fdiv_small(nk_total * (slice + 1), splitk); }
 
   // ---- running source pointers of the NEXT k-tile to stage.  The k index walks (tap, channel) with the
   // channel fastest, so between two k-tiles every pointer simply advances by 64 elements; the im2col
@@ -200,8 +156,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   int st_tap, st_c;
   {
     const int kbase = kt_begin * BK;
-    if (tap_inner) { const int q9 = fdiv_small(kt_begin, 9); st_tap = kt_begin - 9 * q9; st_c = q9 * BK; }
-    else { st_tap = p.ksize == 3 ? fdiv_small(kbase, Cin) : 0; st_c = kbase - st_tap * Cin; }
+    if (tap_inner) { const int q9 = nr_fdiv_small(kt_begin, 9); st_tap = kt_begin - 9 * q9; st_c = q9 * BK; }
+    else { st_tap = p.ksize == 3 ? nr_fdiv_small(kbase, Cin) : 0; st_c = kbase - st_tap * Cin; }
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
       const int n = n0 + 8 * (wave * GB + j) + lr;
@@ -255,11 +211,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     bf16* sA = smem + buf * TILE;
     bf16* sB = sA + BM * BK;
     if constexpr (ADMA) {
-      const unsigned la = lds_addr(sA + wave * GA * 8 * BK), lb = lds_addr(sB + wave * GB * 8 * BK);
+      const unsigned la = nr_lds_addr(sA + wave * GA * 8 * BK), lb = nr_lds_addr(sB + wave * GB * 8 * BK);
 #pragma unroll
-      for (int j = 0; j < GA; ++j) glds16_asm(ap[j], la + (unsigned)(j * 8 * BK * (int)sizeof(bf16)));
+      for (int j = 0; j < GA; ++j) nr_glds16(ap[j], la + (unsigned)(j * 8 * BK * (int)sizeof(bf16)));
 #pragma unroll
-      for (int j = 0; j < GB; ++j) glds16_asm(wp[j], lb + (unsigned)(j * 8 * BK * (int)sizeof(bf16)));
+      for (int j = 0; j < GB; ++j) nr_glds16(wp[j], lb + (unsigned)(j * 8 * BK * (int)sizeof(bf16)));
     } else {
 #pragma unroll
       for (int j = 0; j < GA; ++j) glds16_builtin(ap[j], sA + (wave * GA + j) * 8 * BK);
@@ -310,7 +266,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   NR_STAMP_AT(1);
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     // tile kt must have landed; the younger (NS-2) tiles may stay outstanding (vmcnt counts in issue order)
-    if (kt + (NS - 2) < kt_end) wait_vmcnt<(NS - 2) * G>(); else wait_vmcnt<0>();
+    if (kt + (NS - 2) < kt_end) nr_wait_vmcnt<(NS - 2) * G>(); else nr_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();            // everyone's pieces of tile kt landed; everyone left tile kt-1
     NR_STAMP_AT(4 + (kt - kt_begin));
     const bf16* sA = smem + cur * TILE;
@@ -472,7 +428,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
       if (!p.geglu) {
         if (p.bias) { va += *(const f32x4*)(p.bias + n); vb += *(const f32x4*)(p.bias + n + 4); }
         if (p.rowvec) {
-          const float* rv = p.rowvec + rowvec_row(p, m) + n;
+          const float* rv = p.rowvec + nr_rowvec_row(p, m) + n;
           va += *(const f32x4*)rv; vb += *(const f32x4*)(rv + 4);
         }
         va *= p.out_scale; vb *= p.out_scale;
@@ -502,7 +458,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   for (int j = 0; j < MT; ++j) {
     const int m = m0 + wm * WM + j * 16 + fr;
     if (m >= p.M) continue;
-    const float* rv = p.rowvec ? p.rowvec + rowvec_row(p, m) : nullptr;
+    const float* rv = p.rowvec ? p.rowvec + nr_rowvec_row(p, m) : nullptr;
     if (!p.geglu) {
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
@@ -562,7 +518,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(NrGemmParams p_arg, 
   f32x4 v = *(const f32x4*)src;
   for (int s = 1; s < splitk; ++s) v += *(const f32x4*)(src + s * slab);
   if (p.bias) v += *(const f32x4*)(p.bias + n);
-  if (p.rowvec) v += *(const f32x4*)(p.rowvec + rowvec_row(p, m) + n);
+  if (p.rowvec) v += *(const f32x4*)(p.rowvec + nr_rowvec_row(p, m) + n);
   v *= p.out_scale;
   if (p.act == 1) {
 #pragma unroll
@@ -866,11 +822,5 @@ extern "C" int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStre
 }
 
 #ifdef NR_STAMP
-extern "C" int nr_stamp_read(void* dst, size_t bytes, int clear) {
-  const size_t n = bytes < sizeof(nr_stamp_buf) ? bytes : sizeof(nr_stamp_buf);
-  int rc = 0;
-  if (dst) rc = (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(nr_stamp_buf), n, 0, hipMemcpyDeviceToHost);
-  if (clear) { void* d = nullptr; (void)hipGetSymbolAddress(&d, HIP_SYMBOL(nr_stamp_buf)); (void)hipMemset(d, 0, sizeof(nr_stamp_buf)); }
-  return rc;
-}
+extern "C" int nr_stamp_read(void* dst, size_t bytes, int clear) { return nr_stamp_read_buf(nr_stamp_buf, dst, bytes, clear); }
 #endif

@@ -26,29 +26,13 @@
 // Not here (the launcher falls back to gemm.hip): split-K, the LayerNorm-folded variant, raw fp32 output, strided / upsampling /
 // tap-major 3x3 convs, grids that would leave the chip under-filled.
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdlib>
 
 namespace {
 
+// a copy of device_prims.h's nr_zero16 under this file's own name: the symbol is part of the device code (its address is an operand)
 __device__ __attribute__((aligned(16))) const unsigned int g8p_zero16[4] = {0u, 0u, 0u, 0u};
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(lds_wave_base) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-__device__ __forceinline__ int fdiv_small(int a, int d) {      // exact for 0 <= a < 2^24, quotient < 2^22 (see gemm.hip)
-  int q = (int)((float)a * __builtin_amdgcn_rcpf((float)d));
-  const int r = a - q * d;
-  q += (r >= d ? 1 : 0) - (r < 0 ? 1 : 0);
-  return q;
-}
-__device__ __forceinline__ size_t rowvec_row(const NrGemmParams& p, int m) {
-  int r = m / p.rowvec_div;
-  if (p.rowvec_mod) r %= p.rowvec_mod;
-  return (size_t)r * p.rowvec_ld;
-}
 
 constexpr int G8_BM = 256, G8_BK = 64;
 
@@ -75,13 +59,13 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
   int bm, bn;
   if (m_fast >= 2) {
     const int G = m_fast;
-    const int band = fdiv_small(bid, G * ntn);
+    const int band = nr_fdiv_small(bid, G * ntn);
     const int first = band * G;
     const int gsz = min(G, ntm - first);
     const int r = bid - band * G * ntn;
-    bn = fdiv_small(r, gsz);
+    bn = nr_fdiv_small(r, gsz);
     bm = first + r - bn * gsz;
-  } else if (m_fast) { bn = fdiv_small(bid, ntm); bm = bid - bn * ntm; } else { bm = fdiv_small(bid, ntn); bn = bid - bm * ntn; }
+  } else if (m_fast) { bn = nr_fdiv_small(bid, ntm); bm = bid - bn * ntm; } else { bm = nr_fdiv_small(bid, ntn); bn = bid - bm * ntn; }
   const int m0 = bm * G8_BM, n0 = bn * BN;
 
   const int lr = lane >> 3, lp = lane & 7;
@@ -100,9 +84,9 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
     a_m[j] = ok ? m : 0;
     if constexpr (TAPI) {
       const int ohw = p.OH * p.OW;
-      const int n = fdiv_small(a_m[j], ohw);
+      const int n = nr_fdiv_small(a_m[j], ohw);
       const int r = a_m[j] - n * ohw;
-      const int oy = fdiv_small(r, p.OW), ox = r - oy * p.OW;
+      const int oy = nr_fdiv_small(r, p.OW), ox = r - oy * p.OW;
       a_off[j] = (unsigned)((((size_t)n * p.H + oy) * p.W + ox) * (size_t)p.lda0 * sizeof(bf16)) + lchunk_b;
       unsigned msk = 0;
 #pragma unroll
@@ -129,7 +113,7 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
   }
 
   const int nk = p.K / G8_BK;
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)smem);
+  const unsigned lds0 = nr_lds_addr(smem);
   const unsigned lds_a = lds0 + (unsigned)((16 * g + 4 * wn) * 1024);                // + stage * STAGE + j * 1024
   const unsigned lds_w = lds0 + (unsigned)A_BYTES + (unsigned)(NT * wave * 1024);
 
@@ -165,12 +149,12 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
     if constexpr (TAPI) ok = ((j < 3 ? (a_msk >> (9 * j)) : a_msk3) >> tap) & 1u;
     else ok = (a_msk >> j) & 1u;
     const char* src = ok ? base + a_off[j] : zsrc;
-    glds16(src, lds_a + (unsigned)(stage * STAGE + j * 1024));
+    nr_glds16(src, lds_a + (unsigned)(stage * STAGE + j * 1024));
   };
   auto issue_w = [&](int kt, int stage, int j) {
     const char* base = reinterpret_cast<const char*>(p.w) + (size_t)kt * (G8_BK * sizeof(bf16));
     const char* src = ((w_msk >> j) & 1u) ? base + w_off[j] : zsrc;
-    glds16(src, lds_w + (unsigned)(stage * STAGE + j * 1024));
+    nr_glds16(src, lds_w + (unsigned)(stage * STAGE + j * 1024));
   };
 
   f32x4 acc[NT][8];
@@ -196,7 +180,7 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
 #pragma unroll
       for (int j = 0; j < NT; ++j) issue_w(1, 1, j);
     }
-    wait_vm<0>();
+    nr_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
   }
   if (g == 1) __builtin_amdgcn_s_barrier();            // stagger: group 1 runs one interval behind group 0
@@ -261,8 +245,8 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       // counted waits: everything but the N youngest pieces of this wave has landed (vmcnt counts in issue order)
-      if (ph == NPH - 2 && has1) { if (has2) wait_vm<4 + W_BEFORE_LAST>(); else wait_vm<4>(); }   // W(t+1) landed; A(t+1) [+ part of W(t+2)] may fly
-      if (ph == NPH - 1 && has1) { if (has2) wait_vm<NT>(); else wait_vm<0>(); }                  // A(t+1) landed; W(t+2) may fly
+      if (ph == NPH - 2 && has1) { if (has2) nr_wait_vmcnt<4 + W_BEFORE_LAST>(); else nr_wait_vmcnt<4>(); }   // W(t+1) landed; A(t+1) [+ part of W(t+2)] may fly
+      if (ph == NPH - 1 && has1) { if (has2) nr_wait_vmcnt<NT>(); else nr_wait_vmcnt<0>(); }                  // A(t+1) landed; W(t+2) may fly
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -318,7 +302,7 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
       if (!p.geglu) {
         if (p.bias) { va += *(const f32x4*)(p.bias + n); vb += *(const f32x4*)(p.bias + n + 4); }
         if (p.rowvec) {
-          const float* rv = p.rowvec + rowvec_row(p, m) + n;
+          const float* rv = p.rowvec + nr_rowvec_row(p, m) + n;
           va += *(const f32x4*)rv; vb += *(const f32x4*)(rv + 4);
         }
         va *= p.out_scale; vb *= p.out_scale;

@@ -14,32 +14,21 @@
 // GEGLU, N = 8 C, motion_module_new.py:441-518; the spatial self-attention's fused to_q|to_k|to_v, N = 3 C, motion_module_new.py:201-230 behind norm1 of attention.py:272-285):
 // the rows stay in registers for the whole launch and only W streams.
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdlib>
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(lds_wave_base) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-#ifdef NR_STAMP
 // diagnostic build only (make stamp, tools/tattnw_timeline.py lin160): shader-clock stamps of wave 0 of the first 512 workgroups.  Slots: 0 entry, 1 prologue issued,
 // 2 + 3 s / 3 + 3 s / 4 + 3 s = stage s (< 40) after its DMA wait / barrier / MFMAs, 125 loop end, 126 kernel end
-__device__ unsigned long long lin160_stamp_buf[512][128];
-#define L1_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512 && (slot) < 128) lin160_stamp_buf[blockIdx.x][(slot)] = __builtin_amdgcn_s_memtime(); } while (0)
+NR_STAMP_BUF(lin160_stamp_buf, 512, 128);
+#define L1_STAMP(slot) NR_STAMP_PUT(lin160_stamp_buf, slot)
 // panel kernel, fine stamps of ONE steady-state stage (g = 11) for wave 0 (rows 0 .. 255 of the buffer) and its SIMD-mate wave 4 (rows 256 .. 511): slots 64 + 3 kk = k-step kk
 // begins, 65 + 3 kk = its DMA burst (if any) issued, 66 + 3 kk = its MFMAs issued; 76 / 77 / 78 = in front of the DMA wait / behind it / behind the barrier (inside k-step 3)
 #ifdef NR_STAMP_FINE
-#define Q_STAMPW(slot) do { if ((threadIdx.x & 63) == 0 && (wave == 0 || wave == 4) && blockIdx.x < 256) lin160_stamp_buf[blockIdx.x + (wave ? 256 : 0)][(slot)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define Q_STAMPW(slot) NR_STAMP_PUT_AT((threadIdx.x & 63) == 0 && (wave == 0 || wave == 4) && blockIdx.x < 256, lin160_stamp_buf, blockIdx.x + (wave ? 256 : 0), slot)
 #else
 #define Q_STAMPW(slot) do { } while (0)      // (they perturb the stage they measure: every stamp's store drains the DMA ring; kept for relative order only)
-#endif
-#else
-#define L1_STAMP(slot) do { } while (0)
-#define Q_STAMPW(slot) do { } while (0)
 #endif
 
 constexpr int L1_BN = 160, L1_NT = 10;
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(512) void lin160_kernel(NrLin160Params p) {
   const int r0 = rg * BM;
   const int rot = p.norot ? 0 : rg % S;
 
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)smem);
+  const unsigned lds0 = nr_lds_addr(smem);
   const char* wsrc = reinterpret_cast<const char*>(p.stream) + (size_t)cb * ((size_t)S * L1_W_STAGE) + (size_t)(wave * 3) * 1024 + (size_t)lane * 16;
   // row pieces: piece (tile, kk) = 16 rows x 64 B of k-step kk; BM = 128: wave w fetches (w, 0) and (w, 1); BM = 64: wave w fetches (w & 3, w >> 2)
   const bf16* arow;
@@ -100,10 +89,10 @@ __global__ __launch_bounds__(512) void lin160_kernel(NrLin160Params p) {
   auto issue_piece = [&](int s, int slot, int i) {
     const unsigned dst = lds0 + (unsigned)(slot * STAGE);
     int st = s + rot; if (st >= S) st -= S;
-    if (i < 3) glds16(wsrc + (size_t)st * L1_W_STAGE + (size_t)i * 1024, dst + (unsigned)((wave * 3 + i) * 1024));
+    if (i < 3) nr_glds16(wsrc + (size_t)st * L1_W_STAGE + (size_t)i * 1024, dst + (unsigned)((wave * 3 + i) * 1024));
     else {
       const int kk = BM == 128 ? i - 3 : (wave >> 2);
-      glds16(arow + 64 * st + 32 * kk, dst + (unsigned)(L1_W_STAGE + (kk * RT + rt) * 1024));
+      nr_glds16(arow + 64 * st + 32 * kk, dst + (unsigned)(L1_W_STAGE + (kk * RT + rt) * 1024));
     }
   };
 #pragma unroll
@@ -122,7 +111,7 @@ __global__ __launch_bounds__(512) void lin160_kernel(NrLin160Params p) {
 
   int slot = 0;
   for (int s = 0; s < S; ++s) {
-    if (s + 1 < S) wait_vmcnt<(L1_NS - 2) * PPW>(); else wait_vmcnt<0>();      // in flight behind stage s: the one stage issued after it
+    if (s + 1 < S) nr_wait_vmcnt<(L1_NS - 2) * PPW>(); else nr_wait_vmcnt<0>();      // in flight behind stage s: the one stage issued after it
     if (s < 40) L1_STAMP(2 + 3 * s);
     __builtin_amdgcn_s_barrier();             // every wave's pieces landed; every wave has left stage s - 1 (its slot may be refilled)
     if (s < 40) L1_STAMP(3 + 3 * s);
@@ -159,15 +148,9 @@ __global__ __launch_bounds__(512) void lin160_kernel(NrLin160Params p) {
   L1_STAMP(125);
 
   if constexpr (GLN) {
-    auto rows_sum = [](float v) {
-      auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-      v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-      auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-      return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-    };
     const float inv_k = 1.0f / (float)p.K;
-    const float mu = rows_sum(s1) * inv_k;
-    const float rstd = rsqrtf(fmaxf(rows_sum(s2) * inv_k - mu * mu, 0.f) + p.ln_eps);
+    const float mu = nr_rows_sum(s1) * inv_k;
+    const float rstd = rsqrtf(fmaxf(nr_rows_sum(s2) * inv_k - mu * mu, 0.f) + p.ln_eps);
     const int row = r0 + 16 * rt + fr;
     // ---- LayerNorm fold + GEGLU: tiles (2 i, 2 i + 1) of the block are the values / gates of output columns 80 cb + 16 i .. ----
     const int nb = cb * L1_BN + 4 * fg;
@@ -321,13 +304,13 @@ __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
   const int rot = p.norot ? 0 : rg % S;                // first stage of every block for this row group
   const int G = J * S;                                 // stages of this workgroup (>= NS - 1: host)
 
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)smem);
+  const unsigned lds0 = nr_lds_addr(smem);
   const char* wbase = reinterpret_cast<const char*>(p.stream) + (size_t)cg * J * ((size_t)S * Q_STAGE) + (size_t)(wave * 4) * 1024 + (size_t)lane * 16;
   auto issue_piece = [&](int g, int i) {               // piece i (0 .. 3) of this wave for stage g -> slot g mod NS
     const int gs = g < G ? g : G - 1;                  // behind the last stage nobody consumes the piece: a valid source keeps the loop branch-free and its vmcnt constant
     const int j = gs / S;
     int st = gs - j * S + rot; if (st >= S) st -= S;
-    glds16(wbase + ((size_t)j * S + st) * Q_STAGE + (size_t)i * 1024, lds0 + (unsigned)((g % NS) * Q_STAGE + (wave * 4 + i) * 1024));
+    nr_glds16(wbase + ((size_t)j * S + st) * Q_STAGE + (size_t)i * 1024, lds0 + (unsigned)((g % NS) * Q_STAGE + (wave * 4 + i) * 1024));
   };
 #pragma unroll
   for (int g = 0; g < NS - 1; ++g)
@@ -356,12 +339,6 @@ __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
       xb[rt][ks] = *(const bf16x8*)(xr + 32 * kq);
     }
   }
-  auto rows_sum = [](float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-  };
   L1_STAMP(124);
   // row statistics on the MATRIX unit, one pass over the register panel: with A = ones, D[i][r] = sum_k x[r][k] for every i (each lane gets its row's sum);
   // with A = the fragment itself (the A and B register images of v_mfma_f32_16x16x32_bf16 coincide), D[i][r] = x_i . x_r, whose diagonal is sum_k x[r][k]^2 --
@@ -385,7 +362,7 @@ __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
       float d = e_d == 0 ? a2[0] : e_d == 1 ? a2[1] : e_d == 2 ? a2[2] : a2[3];
       d = (fg == (fr >> 2)) ? d : 0.f;
       sx[rt] = a1[0];
-      sq2[rt] = rows_sum(d);
+      sq2[rt] = nr_rows_sum(d);
     }
     if constexpr (KSPLIT) {                            // the other half of K lives in the SIMD-mate (wave ^ 4)
       float* xs = reinterpret_cast<float*>(smem + NS * Q_STAGE);          // [8 waves][2 rt][2][16 rows]
@@ -404,7 +381,7 @@ __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
     }
   }
   L1_STAMP(127);
-  wait_vmcnt<0>();                                   // the panel is the youngest: stages 0 .. NS - 2 of this wave have landed
+  nr_wait_vmcnt<0>();                                   // the panel is the youngest: stages 0 .. NS - 2 of this wave have landed
   __builtin_amdgcn_s_barrier();                      // ... of every wave, and the table (and, KSPLIT, everyone has read the statistics exchange)
   L1_STAMP(1);
 
@@ -498,7 +475,7 @@ __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
         const unsigned char* nbase;
         if (kk < 3) nbase = smem + slot * Q_STAGE + (kk + 1) * (NTB * 1024);
         else {
-          wait_vmcnt<(NS - 2) * 4>();            // stage g + 1 landed: younger pieces of this wave in flight = stages g + 2 .. g + NS - 1 (4 each)
+          nr_wait_vmcnt<(NS - 2) * 4>();            // stage g + 1 landed: younger pieces of this wave in flight = stages g + 2 .. g + NS - 1 (4 each)
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's reads of slot g are in registers: the slot may be refilled behind the barrier
           if (g < 40) L1_STAMP(2 + 3 * g);
           __builtin_amdgcn_s_barrier();
@@ -536,7 +513,7 @@ __global__ __launch_bounds__(512) void lin128q_kernel(NrLin128QParams p) {
     }
   }
   L1_STAMP(125);
-  wait_vmcnt<0>();                                   // the pieces issued behind the last stage still write this workgroup's LDS
+  nr_wait_vmcnt<0>();                                   // the pieces issued behind the last stage still write this workgroup's LDS
   L1_STAMP(126);
 }
 
@@ -559,13 +536,7 @@ unsigned long long g_l1_attr = 0;
 }  // namespace
 
 #ifdef NR_STAMP
-extern "C" int nr_lin160_stamp_read(void* dst, size_t bytes, int clear) {
-  const size_t n = bytes < sizeof(lin160_stamp_buf) ? bytes : sizeof(lin160_stamp_buf);
-  int rc = 0;
-  if (dst) rc = (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(lin160_stamp_buf), n, 0, hipMemcpyDeviceToHost);
-  if (clear) { void* d = nullptr; (void)hipGetSymbolAddress(&d, HIP_SYMBOL(lin160_stamp_buf)); (void)hipMemset(d, 0, sizeof(lin160_stamp_buf)); }
-  return rc;
-}
+extern "C" int nr_lin160_stamp_read(void* dst, size_t bytes, int clear) { return nr_stamp_read_buf(lin160_stamp_buf, dst, bytes, clear); }
 #endif
 
 extern "C" size_t nr_lin160_stream_bytes(int N, int K) { return (N % L1_BN == 0 && K % 64 == 0) ? (size_t)(N / L1_BN) * (K / 64) * L1_W_STAGE : 0; }

@@ -19,27 +19,12 @@
 //   All vector-memory instructions of an iteration have fixed counts (raw buffer loads/stores with range checking instead of
 //   branches), which is what makes the counted s_waitcnt in front of the barrier valid.
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdlib>
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-// LDS-DMA (global_load_lds_dwordx4) as inline asm: the compiler must NOT see it.  A builtin LDS-DMA is a pending LDS write to
-// hipcc, which then puts s_waitcnt vmcnt(0) in front of the next ds_read that may alias it, i.e. at the top of every iteration,
-// draining the chunks in flight AND the previous iteration's output stores (measured: 4.2 us per chunk instead of ~1.3).  Hidden
-// in asm, only the counted wait + barrier below order the DMA against the fragment reads (cdna_hip_programming.md 5.7).  M0 (the
-// wave-uniform LDS destination) is written and restored inside the same statement.
-__device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(lds_wave_base) : "memory");
-}
-
-// Output store as inline asm, for the same reason: hipcc keeps the data registers of a store it issued locked until the store has
+// Output store as inline asm, for the reason the LDS-DMA is (nr_glds16, device_prims.h): hipcc keeps the data registers of a store it issued locked until the store has
 // RETIRED (it puts s_waitcnt vmcnt(0) in front of the next write to them, i.e. right after the next barrier), which serialises
 // every chunk behind the previous chunk's HBM writes.  The hardware only needs the registers for two wait states (s_nop 1).
 // rsrc: the four descriptor words in SGPRs; off: byte offset per lane (range-checked: out-of-range lanes are dropped).
@@ -75,9 +60,6 @@ constexpr int RP_ROWS = 256;          // rows per workgroup (8 waves x 32)
 constexpr int RP_NS = 3;              // W ring depth (chunks)
 constexpr unsigned RP_OOB = 0x7fffff00u;   // byte offset beyond any buffer: the range check drops the lane
 
-// GEGLU gate: gelu_erf_fast of common.h (A&S 7.1.25; the epilogue is what bounds this kernel at K = 320)
-__device__ __forceinline__ float gelu_gate(float x) { return gelu_erf_fast(x); }
-
 // LN: LayerNorm folded (p.ln_c); RV: fp32 row-vector term (p.rowvec); RES: residual add (p.res); GEGLU: value * gelu(gate) epilogue
 template <int C, bool LN, bool RV, bool RES, bool GEGLU>
 __global__ __launch_bounds__(512) void rowpanel_kernel(NrRowPanelParams p) {
@@ -110,11 +92,11 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(NrRowPanelParams p) {
 
   // ---- W staging: wave w moves rows [8w, 8w+8) of every sub-tile; the 16-byte chunk a lane fetches is XOR-swizzled ----
   const bf16* wnext = p.w + (size_t)(c_begin * 64 + wave * 8 + lr) * C + ((lp ^ lr) << 3);
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)(smem + wave * 8 * 64));
+  const unsigned lds0 = nr_lds_addr(smem + wave * 8 * 64);
   auto issue = [&](int buf) {
     const unsigned dst = lds0 + (unsigned)(buf * STAGE * (int)sizeof(bf16));
 #pragma unroll
-    for (int t = 0; t < KT; ++t) glds16(wnext + 64 * t, dst + (unsigned)(t * SUB * (int)sizeof(bf16)));
+    for (int t = 0; t < KT; ++t) nr_glds16_keep_m0(wnext + 64 * t, dst + (unsigned)(t * SUB * (int)sizeof(bf16)));
     wnext += (size_t)64 * C;
   };
   if (nc > 0) issue(0);
@@ -350,7 +332,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(NrRowPanelParams p) {
             if constexpr (LN) { tv -= cv[2 * qq] * mr[mt]; tg -= cv[2 * qq + 1] * mr[mt]; }
             const f32x4 v = acc[2 * qq][mt] * rs[mt] + tv, g = acc[2 * qq + 1][mt] * rs[mt] + tg;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o4[e] = v[e] * gelu_gate(g[e]);
+            for (int e = 0; e < 4; ++e) o4[e] = nr_geglu(v[e], g[e]);
           }
           if constexpr (RES) {
             const bf16x4 r = __builtin_bit_cast(bf16x4, rr[mt][qq]);

@@ -27,34 +27,19 @@
 // Round 3 had rejected the row-major form of this kernel (0.62-0.68x the igemm: 40 fragment-shaped loads took 8,400 cycles to ISSUE);
 // DESIGN_HISTORY.md has that story, profiles/r05_smallm_fm_ab.txt the first fragment-major A/B.
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdlib>
 
 namespace {
 
+// a copy of device_prims.h's nr_zero16 under this file's own name: the symbol is part of the device code (its address is an operand)
 __device__ __attribute__((aligned(16))) const unsigned int smallm_zero16[4] = {0u, 0u, 0u, 0u};
-typedef __attribute__((address_space(3))) void* lptr_t;
 
-__device__ __forceinline__ void glds16_asm(const void* src, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(lds_wave_base) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt_c() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
-
-__device__ __forceinline__ size_t rowvec_row(const NrGemmParams& p, int m) {
-  int r = m / p.rowvec_div;
-  if (p.rowvec_mod) r %= p.rowvec_mod;
-  return (size_t)r * p.rowvec_ld;
-}
-
-#ifdef NR_STAMP
 // diagnostic build only (make stamp, tools/igemm_timeline.py): shader-clock stamps of wave 0 of the first 512 workgroups
 // (slots 6 / 7: the chip-wide 100 MHz counter at entry / exit)
-__device__ unsigned long long smallm_stamp_buf[512][40];      // 8 + 3 t: step t < 10 after its wait / after its barrier / after its MFMAs
-#define SM_STAMP_AT(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512 && (slot) < 40) smallm_stamp_buf[blockIdx.x][(slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define SM_STAMP_RT(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512) smallm_stamp_buf[blockIdx.x][(slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define SM_STAMP_AT(slot) do { } while (0)
-#define SM_STAMP_RT(slot) do { } while (0)
-#endif
+NR_STAMP_BUF(smallm_stamp_buf, 512, 40);      // 8 + 3 t: step t < 10 after its wait / after its barrier / after its MFMAs
+#define SM_STAMP_AT(slot) NR_STAMP_PUT(smallm_stamp_buf, slot)
+#define SM_STAMP_RT(slot) NR_STAMP_PUT_RT(smallm_stamp_buf, slot)
 
 constexpr int SM_KSW = 10;                    // k-steps (32 deep) of one wave per 640-deep chunk: two wave groups share the 20
 constexpr int SM_SUBB = 32 * 64 * 2;          // one [32 rows][64 k] sub-tile of the panel
@@ -110,7 +95,7 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
   };
 
   // ---- panel: piece q of a chunk = rows 8 (q & 3) .. + 7 of sub-tile q >> 2, lane (lr, lp) fetches the 16-byte chunk lp ^ lr of row lr ----
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)smem);
+  const unsigned lds0 = nr_lds_addr(smem);
   auto issue_panel = [&](int t) {
     const int c = t % C;
     const int slot = streaming ? t % SM_NSLOT : c;
@@ -122,7 +107,7 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
       // two-source operand [a0 | a1] (skip concat as a 1x1 GEMM, the [t | g] operand of the folded FeedForward): whole chunks from either
       const bf16* row = k0 < p.c0 ? p.a0 + (size_t)am * p.lda0 + k0 : p.a1 + (size_t)am * p.lda1 + (k0 - p.c0);
       const bf16* src = am < p.M ? row : (const bf16*)smallm_zero16;
-      glds16_asm(src, lds0 + (unsigned)(slot * SM_CHB + q * 1024));
+      nr_glds16(src, lds0 + (unsigned)(slot * SM_CHB + q * 1024));
     }
   };
 
@@ -155,8 +140,8 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
     const bool has_next = t + 1 < T;
     if (t == 0) SM_STAMP_AT(2);
     // this step's weights and panel chunk are older than: [the next panel chunk] + [the next step's weights]
-    if (has_next) { if (pnext) wait_vmcnt_c<SM_KSW + PP>(); else wait_vmcnt_c<SM_KSW>(); }
-    else wait_vmcnt_c<0>();
+    if (has_next) { if (pnext) nr_wait_vmcnt<SM_KSW + PP>(); else nr_wait_vmcnt<SM_KSW>(); }
+    else nr_wait_vmcnt<0>();
     SM_STAMP_AT(8 + 3 * t);
     __builtin_amdgcn_s_barrier();             // every wave's pieces landed; every wave has left step t - 1 (its slot may be refilled)
     if (t == 0) SM_STAMP_AT(3);
@@ -177,7 +162,7 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
         for (int mt = 0; mt < 2; ++mt) {
           const int m = m0 + 16 * mt + fr;
           const int mc = m < p.M ? m : p.M - 1;
-          if (p.rowvec) rvv[mt] = *(const f32x4*)(p.rowvec + rowvec_row(p, mc) + nq);
+          if (p.rowvec) rvv[mt] = *(const f32x4*)(p.rowvec + nr_rowvec_row(p, mc) + nq);
           if (p.res) rr[mt] = *(const bf16x4*)(p.res + (size_t)mc * p.ldr + nq);
         }
       }
@@ -291,7 +276,7 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
         f32x4 v = acc[mt];
         if constexpr (LN) {
           v = (v - cv * mu[mt]) * rs[mt];
-          if (p.rowvec) rvv[mt] = *(const f32x4*)(p.rowvec + rowvec_row(p, m) + nq);
+          if (p.rowvec) rvv[mt] = *(const f32x4*)(p.rowvec + nr_rowvec_row(p, m) + nq);
           if (p.res) rr[mt] = *(const bf16x4*)(p.res + (size_t)m * p.ldr + nq);
         }
         v += bv;
@@ -431,11 +416,5 @@ extern "C" int nr_launch_smallm_w_pack(const void* w, void* out, int N, int K, h
 }
 
 #ifdef NR_STAMP
-extern "C" int nr_smallm_stamp_read(void* dst, size_t bytes, int clear) {
-  const size_t n = bytes < sizeof(smallm_stamp_buf) ? bytes : sizeof(smallm_stamp_buf);
-  int rc = 0;
-  if (dst) rc = (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(smallm_stamp_buf), n, 0, hipMemcpyDeviceToHost);
-  if (clear) { void* d = nullptr; (void)hipGetSymbolAddress(&d, HIP_SYMBOL(smallm_stamp_buf)); (void)hipMemset(d, 0, sizeof(smallm_stamp_buf)); }
-  return rc;
-}
+extern "C" int nr_smallm_stamp_read(void* dst, size_t bytes, int clear) { return nr_stamp_read_buf(smallm_stamp_buf, dst, bytes, clear); }
 #endif

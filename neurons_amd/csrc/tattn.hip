@@ -26,20 +26,10 @@
 // Algorithmic work per launch at M = 32768: 26.8 GFLOP GEMM + 0.17 GFLOP attention; HBM: t in + t out = 42 MB (+ 1.1 MB of weights,
 // L2-resident per XCD).
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdlib>
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-__device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(lds_wave_base) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int TA_C = 320, TA_HEADS = 8, TA_D = 40;
 constexpr int TA_ROWS = 128;                    // rows per workgroup = 8 pixels x 16 frames or 4 pixels x 32 frames
@@ -63,43 +53,6 @@ struct NrTAttnParams {
   float scale_log2e;       // d^-0.5 * log2(e)
 };
 
-// out-tile accumulation with the accumulator PINNED in the AGPR half of the register file (round 5, as xattn.hip: "+a": vDst = SrcC = an AGPR quad).
-// Left to hipcc the 160 accumulator registers of the out tile lived in VGPRs between the heads and the MFMA groups were bracketed by v_accvgpr
-// copies (584 copies per head iteration for 272 MFMAs).  The asm MFMA is invisible to the compiler's hazard bookkeeping: its A operand comes from
-// LDS (s_waitcnt placed for the asm input), its B operand (ob_prev*) is written by the attention's last phase, which never sits directly in front
-// of one of these MFMAs (phase 6 runs behind the last group), and the accumulator is next touched one head later or by the epilogue behind an
-// explicit s_nop.  tattn.o is compiled with -amdgpu-mfma-vgpr-form so the short-lived projection / attention accumulators stay in VGPRs.
-__device__ __forceinline__ void mfma_acc_agpr(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-
-// own and partner value across 16-lane rows on the VALU (round 5): v_permlane16_swap / v_permlane32_swap with both operands = v give every lane
-// {own, partner} in the two results (lane ^ 16 / lane ^ 32), where __shfl_xor is a ds_bpermute round trip through the LDS -- eight of them per head
-// sat on the latency chain of the attention phases.  max / + are commutative: bit-identical to the shuffle form.
-__device__ __forceinline__ float xmax16(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-}
-__device__ __forceinline__ float xmax32(float v) {
-  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-}
-__device__ __forceinline__ float xsum16(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-__device__ __forceinline__ float xsum32(float v) {
-  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-
-__device__ __forceinline__ s16x4 pack4(const f32x4& v) {
-  bf16x4 b;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) b[e] = (bf16)v[e];
-  return __builtin_bit_cast(s16x4, b);
-}
-
 // F = 16 (round 3): a wave owns 2 pixels, row tile mt = pixel.  F = 32 (round 4, BASELINE config 5): a wave owns ONE pixel, row tile mt = frames
 // 16 mt .. 16 mt + 15; the projections and the out GEMM do not care what a row tile means, only the attention core and the addressing do.
 template <int F>
@@ -119,7 +72,7 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
   // 32 KiB (the same few L2 channels) in lockstep.  blockIdx % 8 labels the XCD (speed only; results depend on blockIdx alone). ----
   const int head0 = p.norot ? 0 : (int)((blockIdx.x >> 3) & (TA_HEADS - 1));
   const char* wsrc = reinterpret_cast<const char*>(p.stream) + (size_t)lane * 16;
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)smem);
+  const unsigned lds0 = nr_lds_addr(smem);
   // Stage order: q k v o per head.  (Running the o stage one head late, so that its 80 MFMAs cover the shuffle / exp latency chain of the next
   // head's attention, was built and spilled 129 VGPRs: the panel, the packed q|k|v tiles and the attention state do not fit 256 VGPRs.)
   // piece i of a stage: q / k / v stages have 32 pieces of 1 KiB (8 per wave), o stages 40 (10 per wave)
@@ -132,7 +85,7 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
     pf_src = wsrc + (size_t)head * TA_HEAD_BYTES + (size_t)part * TA_QKV_BYTES + (size_t)(wave * pf_n) * 1024;
     pf_dst = lds0 + (unsigned)(slot * TA_SLOT) + (unsigned)(wave * pf_n * 1024);
   };
-  auto prefetch_piece = [&](int i) { glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
+  auto prefetch_piece = [&](int i) { nr_glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
   set_prefetch(0, 0, 0);
 #pragma unroll
   for (int i = 0; i < 8; ++i) prefetch_piece(i);
@@ -164,14 +117,14 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
       for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += (float)xb[mt][ks][e];
-      s = xsum32(xsum16(s));
+      s = nr_xsum32(nr_xsum16(s));
       mu[mt] = s * (1.0f / C);
       float q = 0.f;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float d = (float)xb[mt][ks][e] - mu[mt]; q += d * d; }
-      q = xsum32(xsum16(q));
+      q = nr_xsum32(nr_xsum16(q));
       rstd[mt] = rsqrtf(q * (1.0f / C) + p.ln_eps);
     }
     const float* gbr = p.gb + (size_t)fr * C + 8 * fg;
@@ -203,7 +156,7 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
   int slot = 0;
   // stage start: this wave's pieces of the stage (landed) vs the FOLLOWING stage's pieces (next_dma of them may stay in flight)
   auto stage_wait = [&](int next_dma) {
-    if (next_dma == 10) wait_vmcnt<10>(); else wait_vmcnt<8>();
+    if (next_dma == 10) nr_wait_vmcnt<10>(); else nr_wait_vmcnt<8>();
     __builtin_amdgcn_s_barrier();
   };
   auto next_slot = [&]() { slot = slot + 1 == TA_NS ? 0 : slot + 1; };
@@ -252,7 +205,7 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         asm volatile("" : "+v"(acc[nt][mt]));
-        outp[nt][mt] = pack4(acc[nt][mt]);
+        outp[nt][mt] = nr_pack4(acc[nt][mt]);
       }
   };
   auto frag_o = [&](const bf16* sW, int nt, int ks2) {
@@ -283,28 +236,28 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
       } else if (ph == 1) {
         float mx = fmaxf(fmaxf(at_s[0][mt][0], at_s[0][mt][1]), fmaxf(at_s[0][mt][2], at_s[0][mt][3]));
         if constexpr (KT == 2) mx = fmaxf(mx, fmaxf(fmaxf(at_s[1][mt][0], at_s[1][mt][1]), fmaxf(at_s[1][mt][2], at_s[1][mt][3])));
-        at_m[mt] = xmax16(mx);
+        at_m[mt] = nr_xmax16(mx);
       } else if (ph == 2) {
-        at_m[mt] = xmax32(at_m[mt]);
+        at_m[mt] = nr_xmax32(at_m[mt]);
       } else if (ph == 3) {
         float l = 0.f;
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) { at_s[kt][mt][r] = __builtin_amdgcn_exp2f((at_s[kt][mt][r] - at_m[mt]) * p.scale_log2e); l += at_s[kt][mt][r]; }
-        at_l[mt] = xsum16(l);
+        at_l[mt] = nr_xsum16(l);
       } else if (ph == 4) {
-        at_l[mt] = xsum32(at_l[mt]);
+        at_l[mt] = nr_xsum32(at_l[mt]);
       } else if (ph == 5) {        // O^T[channel 16 g + 4 fg + r][query fr] = V^T P^T
         if constexpr (KT == 1) {
-          const s16x4 pb = pack4(at_s[0][mt]);
+          const s16x4 pb = nr_pack4(at_s[0][mt]);
 #pragma unroll
           for (int g = 0; g < 3; ++g)
             at_o[g][mt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(va[g][mt], pb, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         } else {
           // 32 keys = ONE 32-deep MFMA: k-slot 8 fg + j <-> key (j < 4 ? 4 fg + j : 16 + 4 fg + j - 4), i.e. the lane's own registers of key
           // tile 0 then key tile 1 -- for P (accumulator layout of S^T) and for V^T (the swapped projection leaves 4 frames of each tile per lane)
-          const s16x4 p0 = pack4(at_s[0][mt]), p1 = pack4(at_s[1][mt]);
+          const s16x4 p0 = nr_pack4(at_s[0][mt]), p1 = nr_pack4(at_s[1][mt]);
           typedef __attribute__((ext_vector_type(8))) short s16x8;
           const s16x8 pb8 = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
 #pragma unroll
@@ -355,11 +308,14 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
       __builtin_amdgcn_sched_barrier(0);
       if (with_attn && grp < 6) attn_phase(grp);      // phase 6 overwrites the B fragments this stage reads: after the last group
       __builtin_amdgcn_sched_barrier(0);
+      // asm MFMAs (nr_mfma_acc_agpr), their hazards by construction: the A operand comes from LDS (s_waitcnt placed for the asm input), the B operand
+      // (ob_prev*) is written by the attention's last phase, which never sits directly in front of one of these MFMAs (phase 6 runs behind the last
+      // group), and the accumulator is next touched one head later or by the epilogue behind an explicit s_nop
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int nt = 4 * q + i;
-        mfma_acc_agpr(oacc[nt][0], cur[i], ks2 ? ob_prev1[0] : ob_prev0[0]);
-        mfma_acc_agpr(oacc[nt][1], cur[i], ks2 ? ob_prev1[1] : ob_prev0[1]);
+        nr_mfma_acc_agpr(oacc[nt][0], cur[i], ks2 ? ob_prev1[0] : ob_prev0[0]);
+        nr_mfma_acc_agpr(oacc[nt][1], cur[i], ks2 ? ob_prev1[1] : ob_prev0[1]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -393,7 +349,7 @@ __global__ __launch_bounds__(256) void tattn_fused_kernel(NrTAttnParams p) {
     gemm_o(smem + slot * (TA_SLOT / 2), false);
     next_slot();
   }
-  wait_vmcnt<0>();      // the tail's dummy pieces
+  nr_wait_vmcnt<0>();      // the tail's dummy pieces
 
   asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");     // the last asm MFMAs' results -> the accumulator reads below (>= 18 wait states, stated not assumed)
   // ---- epilogue: t <- t + bo + acc, in place.  In the accumulator layout a lane holds 4 channels (16 nt + 4 fg .. + 3) of row fr: 8-byte accesses in

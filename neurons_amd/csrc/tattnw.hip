@@ -36,60 +36,18 @@
 // lane's four keys of each half, concatenated, are its eight k-slots of both operands).  The epilogue table has one 17-row part per half (row 0: c again,
 // row 1 + f: frame 16 half + f), DMA'd into the two slots the last two finished stages left.  Registers and LDS: the header of TW.
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdlib>
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-__device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(lds_wave_base) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-__device__ __forceinline__ float xmax16(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-}
-__device__ __forceinline__ float xmax32(float v) {
-  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-}
-__device__ __forceinline__ float xsum16(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-__device__ __forceinline__ float xsum32(float v) {
-  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-__device__ __forceinline__ s16x4 pack4(const f32x4& v) {
-  bf16x4 b;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) b[e] = (bf16)v[e];
-  return __builtin_bit_cast(s16x4, b);
-}
-
-// acc += A B (16 x 16 x 16) with the accumulator TIED (vDst = SrcC), as attention.hip's mfma_bf16_tied: in the two interleaved K Q^T chains of the 32-frame
-// epilogue hipcc 7.2 otherwise gives MFMAs of the d = 80 instantiation a destination that partially overlaps the SrcC the previous MFMA wrote (wrong sums on
-// gfx950; tools/check_mfma_overlap.py scans the shipped ISA for that pattern; an empty-asm pin between the steps did not cure it here).  The compiler keeps no
-// hazard bookkeeping for an MFMA it cannot see: the leading s_nop 1 covers VALU write -> MFMA read, the caller waits before the first VALU read of the result.
-__device__ __forceinline__ void mfma16_tied(f32x4& acc, const s16x4& a, const s16x4& b) {
-  asm volatile("s_nop 1\n\tv_mfma_f32_16x16x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-
 constexpr int TW_HEADS = 8;
 
-#ifdef NR_STAMP
 // diagnostic build only (make stamp, tools/tattnw_timeline.py): shader-clock stamps of wave 0 of the first 512 workgroups.  Slots: 0 entry, 1 prologue
 // issued, 2 + 3 s / 3 + 3 s / 4 + 3 s = stage s after its DMA wait / after its barrier / after its MFMAs were issued, 125 loop end, 126 kernel end,
 // 127 the XCC_ID register (which XCD ran the workgroup)
-__device__ unsigned long long tattnw_stamp_buf[512][128];
-#define TW_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512 && (slot) < 128) tattnw_stamp_buf[blockIdx.x][(slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define TW_STAMP(slot) do { } while (0)
-#endif
+NR_STAMP_BUF(tattnw_stamp_buf, 512, 128);
+#define TW_STAMP(slot) NR_STAMP_PUT(tattnw_stamp_buf, slot)
 
 // F = 16 / 32 frames.  F is a template parameter, not a run-time tile count: the k-loop and its 30 accumulator tiles (120 registers) are the same in
 // all four instantiations, only the epilogue differs, and a run-time branch there would keep both epilogues' registers live in one kernel.
@@ -179,7 +137,7 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
   // (16 frames of one pixel) x 64 bytes: lane (r = lane >> 2, phys = lane & 3) fetches the 16-byte chunk phys ^ f(r) of row r, f(r) = (-(r >> 2)) & 3:
   // with this permutation the ds_read_b128 of the MFMA fragment (lane (fr, fg) reads chunk fg of row fr) is bank-conflict-free in every
   // 16-lane group of the instruction (the four rows r, r + 4, r + 8, r + 12 that share a bank quarter get four different slots) ----
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)smem);
+  const unsigned lds0 = nr_lds_addr(smem);
   const char* wsrc = reinterpret_cast<const char*>(p.stream) + (size_t)head * ((size_t)T::S * T::W_STAGE) + (size_t)(wave * T::W_PIECES) * 1024 + (size_t)lane * 16;
   const bf16* arow[T::A_PIECES];
 #pragma unroll
@@ -195,8 +153,8 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
   auto issue_piece = [&](int s, int slot, int i) {
     const unsigned dst = lds0 + (unsigned)(slot * T::STAGE);
     int ks = s + rot; if (ks >= T::S) ks -= T::S;
-    if (i < T::W_PIECES) glds16(wsrc + (size_t)ks * T::W_STAGE + (size_t)i * 1024, dst + (unsigned)((wave * T::W_PIECES + i) * 1024));
-    else glds16(arow[i - T::W_PIECES] + 32 * ks, dst + (unsigned)(T::W_STAGE + wave * (T::ROWS_W * 64) + (i - T::W_PIECES) * 1024));
+    if (i < T::W_PIECES) nr_glds16(wsrc + (size_t)ks * T::W_STAGE + (size_t)i * 1024, dst + (unsigned)((wave * T::W_PIECES + i) * 1024));
+    else nr_glds16(arow[i - T::W_PIECES] + 32 * ks, dst + (unsigned)(T::W_STAGE + wave * (T::ROWS_W * 64) + (i - T::W_PIECES) * 1024));
   };
   const char* tsrc = reinterpret_cast<const char*>(p.table) + (size_t)head * (RT * T::TBL_HEAD) + (size_t)(wave * T::TBL_PIECES) * 1024 + (size_t)lane * 16;
   // table piece i (part i / TBL_PIECES) at the last stage: part 0 into the slot stage S - 2 just left (tslot0), part 1 into the one stage S - 3 left
@@ -204,7 +162,7 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
     const int part = i / T::TBL_PIECES, ii = i - part * T::TBL_PIECES;
     int ts = tslot0;
     if (part) { ts += T::NS - 1; if (ts >= T::NS) ts -= T::NS; }
-    glds16(tsrc + (size_t)part * T::TBL_HEAD + (size_t)ii * 1024, lds0 + (unsigned)(ts * T::STAGE + (wave * T::TBL_PIECES + ii) * 1024));
+    nr_glds16(tsrc + (size_t)part * T::TBL_HEAD + (size_t)ii * 1024, lds0 + (unsigned)(ts * T::STAGE + (wave * T::TBL_PIECES + ii) * 1024));
   };
   // prologue: stages 0 .. NS - 2
   if (!T::SPLIT || producer) {
@@ -219,9 +177,9 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
       int pslot = T::NS - 1;
       for (int s = 0; s < T::S; ++s) {
         const int rem = T::S - 1 - s;
-        if (rem >= T::NS - 2) wait_vmcnt<(T::NS - 2) * T::PPW>();
-        else if (rem == 1) wait_vmcnt<T::PPW>();
-        else wait_vmcnt<0>();
+        if (rem >= T::NS - 2) nr_wait_vmcnt<(T::NS - 2) * T::PPW>();
+        else if (rem == 1) nr_wait_vmcnt<T::PPW>();
+        else nr_wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         const int s_next = s + T::NS - 1;
         if (s_next < T::S) {
@@ -233,7 +191,7 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
         }
         pslot = pslot + 1 == T::NS ? 0 : pslot + 1;
       }
-      wait_vmcnt<0>();
+      nr_wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();           // the table is in LDS: the consumers' epilogue may read it
       if constexpr (T::PAIR) __builtin_amdgcn_s_barrier();   // the consumers' K | V^T exchange barrier counts every wave of the workgroup
       return;
@@ -261,9 +219,9 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
     // (issued so far: stages <= min(s + NS - 2, S - 1); allowed in flight: min(NS - 2, S - 1 - s) stages of PPW pieces)
     if constexpr (!T::SPLIT) {
       const int rem = T::S - 1 - s;
-      if (rem >= T::NS - 2) wait_vmcnt<(T::NS - 2) * T::PPW>();
-      else if (rem == 1) wait_vmcnt<T::PPW>();
-      else wait_vmcnt<0>();
+      if (rem >= T::NS - 2) nr_wait_vmcnt<(T::NS - 2) * T::PPW>();
+      else if (rem == 1) nr_wait_vmcnt<T::PPW>();
+      else nr_wait_vmcnt<0>();
     }
     TW_STAMP(2 + 3 * s);
     __builtin_amdgcn_s_barrier();             // every wave's pieces landed; every wave has left stage s - 1 (its slot may be refilled)
@@ -327,15 +285,15 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
   // (F = 32: its second part one slot further back)
   int tslot = slot + T::NS - 2; if (tslot >= T::NS) tslot -= T::NS;
   const float* tb = reinterpret_cast<const float*>(smem + tslot * T::STAGE);
-  wait_vmcnt<0>();
+  nr_wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   // ---- LayerNorm statistics of the wave's rows: lane (fr, fg) holds a quarter of row fr's sums ----
   float mu[MT], rstd[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
-    const float a = xsum32(xsum16(s1[mt])) * (1.0f / C);
-    const float q = xsum32(xsum16(s2[mt])) * (1.0f / C);
+    const float a = nr_xsum32(nr_xsum16(s1[mt])) * (1.0f / C);
+    const float q = nr_xsum32(nr_xsum16(s2[mt])) * (1.0f / C);
     mu[mt] = a;
     rstd[mt] = rsqrtf(fmaxf(q - a * a, 0.f) + p.ln_eps);
   }
@@ -353,7 +311,7 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
         f32x4 v = acc[part * DT + nt][mt];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (v[e] - mu[mt] * c4[e]) * rstd[mt] + e4[e];
-        if (part == 0) qa[nt] = pack4(v); else ka[nt] = pack4(v);
+        if (part == 0) qa[nt] = nr_pack4(v); else ka[nt] = nr_pack4(v);
       }
     }
     float muf[4], rsf[4];
@@ -366,7 +324,7 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
       f32x4 v = acc[2 * DT + nt][mt];
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = (v[r] - muf[r] * cs) * rsf[r] + tbh[(1 + 4 * fg + r) * (3 * D) + col];
-      va[nt] = pack4(v);
+      va[nt] = nr_pack4(v);
     }
   };
 
@@ -381,13 +339,13 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
 #pragma unroll
       for (int nt = 0; nt < DT; ++nt) s4 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ka[nt], qa[nt], s4, 0, 0, 0);
       float mx = fmaxf(fmaxf(s4[0], s4[1]), fmaxf(s4[2], s4[3]));
-      mx = xmax32(xmax16(mx));
+      mx = nr_xmax32(nr_xmax16(mx));
       float l = 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) { s4[r] = __builtin_amdgcn_exp2f((s4[r] - mx) * p.scale_log2e); l += s4[r]; }
-      l = xsum32(xsum16(l));
+      l = nr_xsum32(nr_xsum16(l));
       const float inv = __builtin_amdgcn_rcpf(l);
-      const s16x4 pb = pack4(s4);
+      const s16x4 pb = nr_pack4(s4);
       // O^T[channel 16 g + 4 fg + r][query fr] = V^T P^T ; a[row of (frame fr, pixel)][head D + 16 g + 4 fg + r]
       bf16* orow = p.out + ((size_t)(b * F + fr) * p.hw + tile_pix(mt)) * C + head * D + 4 * fg;
 #pragma unroll
@@ -436,21 +394,21 @@ __global__ __launch_bounds__((TW<D, F>::THREADS), (TW<D, F>::WG_PER_CU)) void ta
       f32x4 sa = f32x4{0.f, 0.f, 0.f, 0.f}, sb = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int nt = 0; nt < DT; ++nt) {
-        mfma16_tied(sa, ka[0][nt], qa[mt][nt]);
-        mfma16_tied(sb, ka[1][nt], qa[mt][nt]);
+        nr_mfma16_tied_ordered(sa, ka[0][nt], qa[mt][nt]);
+        nr_mfma16_tied_ordered(sb, ka[1][nt], qa[mt][nt]);
       }
       asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+v"(sa), "+v"(sb));     // MFMA result -> VALU read: the wait states hipcc would count for its own MFMAs
       float mx = fmaxf(fmaxf(fmaxf(sa[0], sa[1]), fmaxf(sa[2], sa[3])), fmaxf(fmaxf(sb[0], sb[1]), fmaxf(sb[2], sb[3])));
-      mx = xmax32(xmax16(mx));
+      mx = nr_xmax32(nr_xmax16(mx));
       float l = 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) { sa[r] = __builtin_amdgcn_exp2f((sa[r] - mx) * p.scale_log2e); l += sa[r]; }
 #pragma unroll
       for (int r = 0; r < 4; ++r) { sb[r] = __builtin_amdgcn_exp2f((sb[r] - mx) * p.scale_log2e); l += sb[r]; }
-      l = xsum32(xsum16(l));
+      l = nr_xsum32(nr_xsum16(l));
       const float inv = __builtin_amdgcn_rcpf(l);
       // the lane's k-slots 0-3 | 4-7 of the K = 32 product = its keys 4 fg + r of half 0 | half 1, in P^T and in V^T alike
-      const bf16x8 pb = __builtin_shufflevector(__builtin_bit_cast(bf16x4, pack4(sa)), __builtin_bit_cast(bf16x4, pack4(sb)), 0, 1, 2, 3, 4, 5, 6, 7);
+      const bf16x8 pb = __builtin_shufflevector(__builtin_bit_cast(bf16x4, nr_pack4(sa)), __builtin_bit_cast(bf16x4, nr_pack4(sb)), 0, 1, 2, 3, 4, 5, 6, 7);
       // O^T[channel 16 g + 4 fg + r][query fr] = V^T P^T ; a[row of (frame 16 half + fr, pixel)][head D + 16 g + 4 fg + r]
       bf16* orow = p.out + ((size_t)(b * F + 16 * tile_half(mt) + fr) * p.hw + tile_pix(mt)) * C + head * D + 4 * fg;
 #pragma unroll
@@ -519,13 +477,7 @@ __global__ __launch_bounds__(256) void tattnw_table_pack_kernel(const float* __r
 }  // namespace
 
 #ifdef NR_STAMP
-extern "C" int nr_tattnw_stamp_read(void* dst, size_t bytes, int clear) {
-  const size_t n = bytes < sizeof(tattnw_stamp_buf) ? bytes : sizeof(tattnw_stamp_buf);
-  int rc = 0;
-  if (dst) rc = (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tattnw_stamp_buf), n, 0, hipMemcpyDeviceToHost);
-  if (clear) { void* d = nullptr; (void)hipGetSymbolAddress(&d, HIP_SYMBOL(tattnw_stamp_buf)); (void)hipMemset(d, 0, sizeof(tattnw_stamp_buf)); }
-  return rc;
-}
+extern "C" int nr_tattnw_stamp_read(void* dst, size_t bytes, int clear) { return nr_stamp_read_buf(tattnw_stamp_buf, dst, bytes, clear); }
 #endif
 
 extern "C" size_t nr_tattnw_stream_bytes(int C) {

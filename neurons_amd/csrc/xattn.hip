@@ -22,20 +22,10 @@
 //   * out += Wo_h . O_h^T accumulates over the heads in 160 VGPRs; epilogue t + bo + acc, written in place (rows are private).
 // Algorithmic work per launch at M = 32768: 13.4 GFLOP of projections + 3.2 GFLOP of attention; HBM: t in + t out = 42 MB.
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdlib>
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-__device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(lds_wave_base) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int XA_C = 320, XA_HEADS = 8, XA_D = 40;
 constexpr int XA_ROWS = 128;                    // rows per workgroup
@@ -51,13 +41,9 @@ constexpr int XA_KV_BYTES = 20 * 1024;          // K image at 0, V^T image (48 x
 constexpr int XA_SLOT = XA_O_BYTES;             // ring slot
 constexpr int XA_NS = 3;
 
-#ifdef NR_STAMP
 // Diagnostic build only (make stamp, tools/xattn_timeline.py): shader-clock stamps of wave 0 of the first 256 workgroups; no output depends on them
-__device__ unsigned long long xa_stamp_buf[256][64];
-#define XA_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 256 && (slot) < 64) xa_stamp_buf[blockIdx.x][(slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define XA_STAMP(slot) do { } while (0)
-#endif
+NR_STAMP_BUF(xa_stamp_buf, 256, 64);
+#define XA_STAMP(slot) NR_STAMP_PUT(xa_stamp_buf, slot)
 
 struct NrXAttnParams {
   bf16* t;                 // [nimg * hw][C], updated in place
@@ -73,39 +59,6 @@ struct NrXAttnParams {
   float ln_eps;
   float scale_log2e;       // d^-0.5 * log2(e)
 };
-
-// max / sum over the four 16-lane rows of a wave (lanes l, l^16, l^32, l^48) on the VALU (v_permlane16_swap / v_permlane32_swap, as attention.hip:
-// a ds_bpermute round trip through the LDS otherwise -- four of them per row tile sit on the latency chain of the attention stage)
-__device__ __forceinline__ float rows_max(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float rows_sum(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-// out-tile accumulation with the accumulator PINNED in the AGPR half of the register file ("+a": vDst = SrcC = an AGPR quad).  Left to hipcc the
-// 160 accumulator registers of the out tile live in VGPRs between the heads and every group of 8 MFMAs is bracketed by 64 v_accvgpr_write / _read
-// copies (478 copies for 200 MFMAs in the first build of this kernel; the o stage ran at 37 instead of 16 cycles per MFMA, tools/xattn_timeline.py).
-// An asm MFMA is invisible to the compiler's hazard bookkeeping: its A operand comes from LDS (covered by the s_waitcnt the compiler places for
-// the asm input), its B operand was converted many instructions earlier, and the accumulator is next touched one head later or by the epilogue
-// behind an explicit s_nop (below).  No VALU-written operand ever sits directly in front of these MFMAs (the VALU -> MFMA-operand hazard
-// attention.hip's mfma_bf16_tied pays an s_nop for): the weight fragments come from ds_read, O^T was packed before the stage's barrier.
-__device__ __forceinline__ void mfma_acc_agpr(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-
-__device__ __forceinline__ s16x4 pack4(const f32x4& v) {
-  bf16x4 b;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) b[e] = (bf16)v[e];
-  return __builtin_bit_cast(s16x4, b);
-}
 
 __global__ __launch_bounds__(256) void xattn_fused_kernel(NrXAttnParams p) {
   constexpr int C = XA_C, KS = C / 32, NT2 = C / 16, KT = XA_KEYS / 16;
@@ -127,7 +80,7 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(NrXAttnParams p) {
   const int head0 = p.norot ? 0 : (int)((blockIdx.x >> 3) & (XA_HEADS - 1));
   const char* wsrc = reinterpret_cast<const char*>(p.wstream) + (size_t)lane * 16;
   const char* kvsrc = reinterpret_cast<const char*>(p.kvstream) + (size_t)cb * XA_HEADS * XA_KV_BYTES + (size_t)lane * 16;
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)smem);
+  const unsigned lds0 = nr_lds_addr(smem);
   // stage s of head position hidx: 0 = q (slot 0, 8 pieces per wave), 1 = kv (slot 1, 5 pieces), 2 = o (slot 2, 10 pieces): three stages per head
   // and three slots, so every stage type owns a slot; a stage is prefetched two stages ahead = into the slot the PREVIOUS stage has just left
   const char* pf_src = wsrc;
@@ -139,7 +92,7 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(NrXAttnParams p) {
     else pf_src = wsrc + (size_t)head * XA_W_HEAD_BYTES + (size_t)(part == 2 ? XA_Q_BYTES : 0) + (size_t)(wave * n) * 1024;
     pf_dst = lds0 + (unsigned)(part * XA_SLOT) + (unsigned)(wave * n * 1024);
   };
-  auto prefetch_piece = [&](int i) { glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
+  auto prefetch_piece = [&](int i) { nr_glds16(pf_src + i * 1024, pf_dst + (unsigned)(i * 1024)); };
   set_prefetch(0, 0);
 #pragma unroll
   for (int i = 0; i < 8; ++i) prefetch_piece(i);
@@ -166,14 +119,14 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(NrXAttnParams p) {
       for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += (float)xb[mt][ks][e];
-      s = rows_sum(s);
+      s = nr_rows_sum(s);
       mu[mt] = s * (1.0f / C);
       float q = 0.f;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float d = (float)xb[mt][ks][e] - mu[mt]; q += d * d; }
-      q = rows_sum(q);
+      q = nr_rows_sum(q);
       rstd[mt] = rsqrtf(q * (1.0f / C) + p.ln_eps);
     }
     const float* gbr = p.beta + 8 * fg;
@@ -223,7 +176,7 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(NrXAttnParams p) {
     const bool last = it + 1 == XA_HEADS;
     XA_STAMP(2 + 6 * it);
     // ================= q stage (slot 0); behind it in flight: kv (5).  Prefetch during its 10 k-steps: o of this head (10 pieces) =================
-    wait_vmcnt<5>();
+    nr_wait_vmcnt<5>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -257,11 +210,11 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(NrXAttnParams p) {
 #pragma unroll
       for (int nt = 0; nt < 3; ++nt)
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt) qa[nt][mt] = pack4(acc[nt][mt]);     // lane: channels 16 nt + 4 fg .. + 3 of row fr
+        for (int mt = 0; mt < 2; ++mt) qa[nt][mt] = nr_pack4(acc[nt][mt]);     // lane: channels 16 nt + 4 fg .. + 3 of row fr
     }
     XA_STAMP(4 + 6 * it);
     // ================= kv stage (slot 1); behind it: o (10).  Prefetch: q of the next head (8; last head: a harmless re-fetch of the first) =================
-    wait_vmcnt<10>();
+    nr_wait_vmcnt<10>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -298,20 +251,20 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(NrXAttnParams p) {
             if (16 * kt + 4 * fg + r >= p.Lk) sc[kt][mt][r] = -1e30f;       // key slots beyond the context (their K rows are zero, not -inf)
             mx = fmaxf(mx, sc[kt][mt][r]);
           }
-        mx = rows_max(mx);
+        mx = nr_rows_max(mx);
         float l = 0.f;
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) { sc[kt][mt][r] = __builtin_amdgcn_exp2f((sc[kt][mt][r] - mx) * p.scale_log2e); l += sc[kt][mt][r]; }
-        l = rows_sum(l);
+        l = nr_rows_sum(l);
         // ---- O^T[channel 16 g + 4 fg + r][query fr] = sum_key V^T[channel][key] P[query][key]: A = V^T tile (lane: channel fr, keys 4 fg ..), B = P ----
         f32x4 ao[3];
 #pragma unroll
         for (int g = 0; g < 3; ++g) ao[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
-          const s16x4 pb = pack4(sc[kt][mt]);
+          const s16x4 pb = nr_pack4(sc[kt][mt]);
 #pragma unroll
           for (int g = 0; g < 3; ++g) {
             const s16x4 vf = *(const s16x4*)(sV + (16 * g + fr) * XA_VLD + 16 * kt + 4 * fg);
@@ -330,7 +283,7 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(NrXAttnParams p) {
     }
     XA_STAMP(6 + 6 * it);
     // ================= o stage (slot 2); behind it: q of the next head (8).  Prefetch: kv of the next head (5 pieces) =================
-    wait_vmcnt<8>();
+    nr_wait_vmcnt<8>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -352,18 +305,21 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(NrXAttnParams p) {
         }
         if (grp < 5) prefetch_piece(grp);
         __builtin_amdgcn_sched_barrier(0);
+        // asm MFMAs (nr_mfma_acc_agpr), their hazards by construction: the A operand comes from LDS (the s_waitcnt the compiler places for the asm
+        // input), O^T (the B operand) was packed before the stage's barrier, so no VALU-written operand sits directly in front of them; the
+        // accumulator is next touched one head later or by the epilogue behind an explicit s_nop
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int nt = 4 * q + i;
-          mfma_acc_agpr(oacc[nt][0], cur[i], ks2 ? ob1[0] : ob0[0]);
-          mfma_acc_agpr(oacc[nt][1], cur[i], ks2 ? ob1[1] : ob0[1]);
+          nr_mfma_acc_agpr(oacc[nt][0], cur[i], ks2 ? ob1[0] : ob0[0]);
+          nr_mfma_acc_agpr(oacc[nt][1], cur[i], ks2 ? ob1[1] : ob0[1]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
   }
   XA_STAMP(50);
-  wait_vmcnt<0>();      // the tail's dummy pieces
+  nr_wait_vmcnt<0>();      // the tail's dummy pieces
 
   asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");     // the last asm MFMAs' results -> the accumulator reads below (>= 18 wait states, stated not assumed)
   // ---- epilogue: t <- t + bo + acc, in place.  In the accumulator layout a lane holds 4 channels (16 nt + 4 fg .. + 3) of row fr: 8-byte accesses in
@@ -455,13 +411,7 @@ unsigned long long g_xa_attr = 0;
 }  // namespace
 
 #ifdef NR_STAMP
-extern "C" int nr_xattn_stamp_read(void* dst, size_t bytes, int clear) {
-  const size_t n = bytes < sizeof(xa_stamp_buf) ? bytes : sizeof(xa_stamp_buf);
-  int rc = 0;
-  if (dst) rc = (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(xa_stamp_buf), n, 0, hipMemcpyDeviceToHost);
-  if (clear) { void* d = nullptr; (void)hipGetSymbolAddress(&d, HIP_SYMBOL(xa_stamp_buf)); (void)hipMemset(d, 0, sizeof(xa_stamp_buf)); }
-  return rc;
-}
+extern "C" int nr_xattn_stamp_read(void* dst, size_t bytes, int clear) { return nr_stamp_read_buf(xa_stamp_buf, dst, bytes, clear); }
 #endif
 
 extern "C" size_t nr_xattn_wstream_bytes(void) { return (size_t)XA_HEADS * XA_W_HEAD_BYTES; }

@@ -15,56 +15,15 @@
 //     xattnw_kv_pack_kernel: MFMA fragments of v_mfma_f32_16x16x16_bf16, keys >= Lk zero / masked);  S^T = K Q^T (5 key tiles), softmax over the 80 key
 //     slots (4 registers x 5 tiles x 4 lane groups), O^T = V^T P^T, 8-byte stores of a[row][cols].
 #include "launchers.h"
+#include "device_prims.h"
 #include <cstdlib>
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-__device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(lds_wave_base) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-__device__ __forceinline__ float xmax_rows(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float xsum_rows(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-__device__ __forceinline__ s16x4 pack4(const f32x4& v) {
-  bf16x4 b;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) b[e] = (bf16)v[e];
-  return __builtin_bit_cast(s16x4, b);
-}
-
-// acc += A B (16 x 16 x 16 bf16) with the accumulator TIED (vDst = SrcC).  Left to hipcc 7.2 the five-/ten-long accumulation chains of this kernel are
-// allocated as v[28:31] <- v[30:33] style chains (destination PARTIALLY overlapping the SrcC the previous MFMA wrote) with no wait states between the
-// dependent MFMAs -- the pattern that returned wrong sums on gfx950 in attention.hip (tools/check_mfma_overlap.py scans the shipped ISA for it; it
-// flagged the first build of this file).  An asm MFMA is invisible to the compiler's hazard bookkeeping, so the asm carries its own: the leading
-// s_nop 1 covers a VALU-written operand (the packed q / P tiles, the zeroed accumulator) directly in front of it; mfma_results() puts the wait
-// states of an MFMA result -> VALU read behind the chain.
-__device__ __forceinline__ void mfma16_tied(f32x4& acc, const s16x4& a, const s16x4& b) {
-  asm("s_nop 1\n\tv_mfma_f32_16x16x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma_results(f32x4& acc) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(acc)); }
-
-#ifdef NR_STAMP
 // diagnostic build only (make stamp, tools/tattnw_timeline.py xattn): shader-clock stamps of wave 0 of the first 512 workgroups.  Slots: 0 entry, 1 prologue
 // issued, 2 + 3 s / 3 + 3 s / 4 + 3 s = stage s after its DMA wait / barrier / MFMAs, 123 K|V pieces issued, 124 K|V landed, 125 kernel end
-__device__ unsigned long long xattnw_stamp_buf[512][128];
-#define XW_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512 && (slot) < 128) xattnw_stamp_buf[blockIdx.x][(slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define XW_STAMP(slot) do { } while (0)
-#endif
+NR_STAMP_BUF(xattnw_stamp_buf, 512, 128);
+#define XW_STAMP(slot) NR_STAMP_PUT(xattnw_stamp_buf, slot)
 
 constexpr int XW_HEADS = 8;
 constexpr int XW_KT = 5;                         // key tiles of 16: 80 key slots, Lk <= 80
@@ -110,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void xattn_head_kernel(NrXAttnWParams p) {
   const int ctx = img / p.img_per_ctx;
   const int rot = ((r0 - img * p.hw) / XW_ROWS) % S;          // position inside the image: batch-independent
 
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lptr_t)smem);
+  const unsigned lds0 = nr_lds_addr(smem);
   const char* wsrc = reinterpret_cast<const char*>(p.stream) + (size_t)cb * ((size_t)S * XW_W_STAGE) + (size_t)(wave * 3) * 1024 + (size_t)lane * 16;
   const bf16* arow;
   {
@@ -120,11 +79,11 @@ __global__ __launch_bounds__(256, 2) void xattn_head_kernel(NrXAttnWParams p) {
   auto issue_piece = [&](int s, int slot, int i) {
     const unsigned dst = lds0 + (unsigned)(slot * XW_STAGE);
     int ks = s + rot; if (ks >= S) ks -= S;
-    if (i < 3) glds16(wsrc + (size_t)ks * XW_W_STAGE + (size_t)i * 1024, dst + (unsigned)((wave * 3 + i) * 1024));
-    else glds16(arow + 32 * ks, dst + (unsigned)(XW_W_STAGE + wave * 1024));
+    if (i < 3) nr_glds16(wsrc + (size_t)ks * XW_W_STAGE + (size_t)i * 1024, dst + (unsigned)((wave * 3 + i) * 1024));
+    else nr_glds16(arow + 32 * ks, dst + (unsigned)(XW_W_STAGE + wave * 1024));
   };
   // the fold vectors of the workgroup's columns: wave 0 fetches c[cols ..], wave 1 b'[cols ..] (1 KiB each: 160 floats + over-read inside the padded table)
-  if (wave < 2) glds16(reinterpret_cast<const char*>(p.table + (size_t)wave * (C + 256) + cb * XW_COLS) + (size_t)lane * 16, lds0 + (unsigned)(XW_NS * XW_STAGE + wave * 1024));
+  if (wave < 2) nr_glds16(reinterpret_cast<const char*>(p.table + (size_t)wave * (C + 256) + cb * XW_COLS) + (size_t)lane * 16, lds0 + (unsigned)(XW_NS * XW_STAGE + wave * 1024));
 #pragma unroll
   for (int s = 0; s < XW_NS - 1; ++s)
 #pragma unroll
@@ -143,9 +102,9 @@ __global__ __launch_bounds__(256, 2) void xattn_head_kernel(NrXAttnWParams p) {
   for (int s = 0; s < S; ++s) {
     // outstanding allowed: the stages issued after stage s (min(NS - 2, S - 1 - s) of them); the two table pieces are older than everything
     const int rem = S - 1 - s;
-    if (rem >= XW_NS - 2) wait_vmcnt<(XW_NS - 2) * XW_PPW>();
-    else if (rem == 1) wait_vmcnt<XW_PPW>();
-    else wait_vmcnt<0>();
+    if (rem >= XW_NS - 2) nr_wait_vmcnt<(XW_NS - 2) * XW_PPW>();
+    else if (rem == 1) nr_wait_vmcnt<XW_PPW>();
+    else nr_wait_vmcnt<0>();
     XW_STAMP(2 + 3 * s);
     __builtin_amdgcn_s_barrier();
     XW_STAMP(3 + 3 * s);
@@ -182,13 +141,13 @@ __global__ __launch_bounds__(256, 2) void xattn_head_kernel(NrXAttnWParams p) {
   {
     const char* kvsrc = reinterpret_cast<const char*>(p.kvstream) + ((size_t)ctx * NCB + cb) * XW_KV_BLOCK + (size_t)(wave * XW_KV_PIECES) * 1024 + (size_t)lane * 16;
 #pragma unroll
-    for (int i = 0; i < XW_KV_PIECES; ++i) glds16(kvsrc + (size_t)i * 1024, lds0 + (unsigned)((wave * XW_KV_PIECES + i) * 1024));
+    for (int i = 0; i < XW_KV_PIECES; ++i) nr_glds16(kvsrc + (size_t)i * 1024, lds0 + (unsigned)((wave * XW_KV_PIECES + i) * 1024));
   }
   XW_STAMP(123);
   // LayerNorm statistics of the wave's 16 rows (lane (fr, fg) holds a quarter of row fr's sums) while the images land
-  const float mu = xsum_rows(s1) * (1.0f / C);
-  const float rstd = rsqrtf(fmaxf(xsum_rows(s2) * (1.0f / C) - mu * mu, 0.f) + p.ln_eps);
-  wait_vmcnt<0>();
+  const float mu = nr_rows_sum(s1) * (1.0f / C);
+  const float rstd = rsqrtf(fmaxf(nr_rows_sum(s2) * (1.0f / C) - mu * mu, 0.f) + p.ln_eps);
+  nr_wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   XW_STAMP(124);
@@ -201,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void xattn_head_kernel(NrXAttnWParams p) {
     f32x4 v = acc[n];
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = (v[e] - mu * c4[e]) * rstd + b4[e];
-    qa[n] = pack4(v);
+    qa[n] = nr_pack4(v);
   }
   const unsigned char* kimg = smem + (unsigned)lane * 8;                       // K fragment (kt, n10) at ((kt 10 + n10) 64 + lane) 8 B
   const unsigned char* vimg = smem + XW_KT * XW_NT * 512 + (unsigned)lane * 8;   // V^T fragment (g10, kt) at ((g10 5 + kt) 64 + lane) 8 B
@@ -216,9 +175,9 @@ __global__ __launch_bounds__(256, 2) void xattn_head_kernel(NrXAttnWParams p) {
 #pragma unroll
       for (int nt = 0; nt < DT; ++nt) {
         const s16x4 kf = *(const s16x4*)(kimg + (unsigned)((kt * XW_NT + hh * DT + nt) * 512));
-        mfma16_tied(s4, kf, qa[hh * DT + nt]);
+        nr_mfma16_tied(s4, kf, qa[hh * DT + nt]);
       }
-      mfma_results(s4);
+      nr_mfma_results(s4);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         if (16 * kt + 4 * fg + r >= p.Lk) s4[r] = -1.0e30f;           // key slots beyond the context
@@ -226,16 +185,16 @@ __global__ __launch_bounds__(256, 2) void xattn_head_kernel(NrXAttnWParams p) {
       }
       sc[kt] = s4;
     }
-    mx = xmax_rows(mx);
+    mx = nr_rows_max(mx);
     float l = 0.f;
     s16x4 pb[XW_KT];
 #pragma unroll
     for (int kt = 0; kt < XW_KT; ++kt) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) { sc[kt][r] = __builtin_amdgcn_exp2f((sc[kt][r] - mx) * p.scale_log2e); l += sc[kt][r]; }
-      pb[kt] = pack4(sc[kt]);
+      pb[kt] = nr_pack4(sc[kt]);
     }
-    l = xsum_rows(l);
+    l = nr_rows_sum(l);
     const float inv = __builtin_amdgcn_rcpf(l);
 #pragma unroll
     for (int g = 0; g < DT; ++g) {
@@ -243,9 +202,9 @@ __global__ __launch_bounds__(256, 2) void xattn_head_kernel(NrXAttnWParams p) {
 #pragma unroll
       for (int kt = 0; kt < XW_KT; ++kt) {
         const s16x4 vf = *(const s16x4*)(vimg + (unsigned)(((hh * DT + g) * XW_KT + kt) * 512));
-        mfma16_tied(o4, vf, pb[kt]);
+        nr_mfma16_tied(o4, vf, pb[kt]);
       }
-      mfma_results(o4);
+      nr_mfma_results(o4);
       bf16x4 o;
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r] = (bf16)(o4[r] * inv);
@@ -317,13 +276,7 @@ unsigned long long g_xw_attr = 0;
 }  // namespace
 
 #ifdef NR_STAMP
-extern "C" int nr_xattnw_stamp_read(void* dst, size_t bytes, int clear) {
-  const size_t n = bytes < sizeof(xattnw_stamp_buf) ? bytes : sizeof(xattnw_stamp_buf);
-  int rc = 0;
-  if (dst) rc = (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(xattnw_stamp_buf), n, 0, hipMemcpyDeviceToHost);
-  if (clear) { void* d = nullptr; (void)hipGetSymbolAddress(&d, HIP_SYMBOL(xattnw_stamp_buf)); (void)hipMemset(d, 0, sizeof(xattnw_stamp_buf)); }
-  return rc;
-}
+extern "C" int nr_xattnw_stamp_read(void* dst, size_t bytes, int clear) { return nr_stamp_read_buf(xattnw_stamp_buf, dst, bytes, clear); }
 #endif
 
 extern "C" size_t nr_xattnw_wstream_bytes(int C) { return (C == 640 || C == 1280) ? (size_t)(C / XW_COLS) * (C / 32) * XW_W_STAGE : 0; }

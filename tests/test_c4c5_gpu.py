@@ -139,7 +139,7 @@ def test_c5_configured_batch_of_four_clips_one_evaluation(cuda, nets):
     arena-reuse bugs show up exactly here and nowhere smaller), (b) clips 0 and 3 against the fp32 oracle evaluated one clip at a time.
     Largest element offsets at this shape: 1 048 576 rows x 1280 channels (GEGLU output, K = 5C operand halves) = 1.34e9 < 2^31 elements,
     2.7e9 BYTES (> 2^31: every kernel forms byte addresses in 64 bits; the row-panel kernel's 32-bit buffer offsets are gated by
-    nr_rowpanel_eligible).  fdiv_small's dividends stay below 2^24 (exact float conversion): 1 048 576 rows, 9 x 5 = 45 k-tiles."""
+    nr_rowpanel_eligible).  nr_fdiv_small's dividends stay below 2^24 (exact float conversion): 1 048 576 rows, 9 x 5 = 45 k-tiles."""
     n = nets
     O, unet, ctrl = n["O"], n["unet"], n["ctrl"]
     unet.set_attention_fp8(False)
