@@ -6,192 +6,20 @@
 // list of kernel launches over one workspace arena with plan-time buffer reuse, (4) optionally that
 // plan captured as a hipGraph.  forward() allocates nothing.
 //
-// The plan follows the reference module graph:
-//   UNet3DConditionModel.forward        animatediff/models/unet.py:357-475
-//   SparseControlNetModel.forward       animatediff/models/sparse_controlnet.py:467-581
-//   Cross/Down/Mid/Up blocks            animatediff/models/unet_blocks.py:271-278,382-421,493-521,621-667,735-760
-//   ResnetBlock3D                       animatediff/models/resnet.py:182-212
-//   Transformer3DModel / BasicTransformerBlock   animatediff/models/attention.py:95-142,256-300
-//   TemporalTransformer3DModel / Block / VersatileAttention   animatediff/models/motion_module.py:134-158,210-222,270-329
-#include "launchers.h"
-#include "../../include/neurons_amd.h"
+// This file: the graph-replay runtime of a handle, the C ABI, and the engine's two small kernels.  engine.h says where the rest lives.
+#include "engine.h"
 
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <stdexcept>
-#include <string>
-#include <vector>
+using namespace nre;
 
 namespace {
 
 thread_local std::string g_err;
-void set_err(const std::string& s) { g_err = s; }
-
-struct NrError : std::runtime_error {
-  nr_status code;
-  NrError(nr_status c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-#define HIP_OK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t _e = (expr);                                                                            \
-    if (_e != hipSuccess) throw NrError(NR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-// launcher return code (unsupported shape) AND the HIP launch status: a rejected launch (bad LDS size, bad grid) must
-// fail loudly instead of leaving the previous contents of the output buffer in place
-#define LAUNCH_OK(expr)                                                                              \
-  do {                                                                                               \
-    int _r = (expr);                                                                                 \
-    if (_r != 0) throw NrError(NR_ERR_UNSUPPORTED, std::string(#expr) + " -> " + std::to_string(_r)); \
-    hipError_t _le = hipGetLastError();                                                              \
-    if (_le != hipSuccess) throw NrError(NR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_le)); \
-  } while (0)
-
-inline float bf2f_host(uint16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-inline uint16_t f2bf_host(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;  // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-// GEGLU row order of the kernels: each 32-row group is 16 value rows, then their 16 gate rows.  Source row of output row n of a
-// [2 * inner][K] projection (value rows [0, inner), gate rows [inner, 2 * inner))
-inline int geglu_src_row(int n, int inner) {
-  const int q = n / 32, j = n % 32;
-  return j < 16 ? q * 16 + j : inner + q * 16 + (j - 16);
-}
-// sinusoidal position table [max_len][C] (motion_module.py:225-239), fp32 throughout
-inline std::vector<float> sinusoid_table(int max_len, int C) {
-  std::vector<float> h((size_t)max_len * C);
-  const float k = (float)(-std::log(10000.0) / (double)C);
-  for (int pos = 0; pos < max_len; ++pos)
-    for (int i = 0; i < C; i += 2) {
-      const float a = (float)pos * std::exp((float)i * k);
-      h[(size_t)pos * C + i] = std::sin(a);
-      if (i + 1 < C) h[(size_t)pos * C + i + 1] = std::cos(a);
-    }
-  return h;
-}
-
-inline bool env_is_1(const char* name) {
-  const char* v = getenv(name);
-  return v && v[0] == '1';
-}
-
-struct HostTensor {
-  std::vector<float> data;
-  std::vector<int64_t> shape;
-  int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
-};
-
-// ---- plan-time arena allocator (offsets only; first fit with coalescing) ----
-struct Arena {
-  struct Blk { size_t off, size; };
-  std::vector<Blk> free_;
-  size_t top = 0, high = 0;
-  static size_t align(size_t b) { return (b + 255) & ~(size_t)255; }
-  size_t alloc(size_t bytes) {
-    bytes = align(bytes);
-    for (size_t i = 0; i < free_.size(); ++i) {
-      if (free_[i].size >= bytes) {
-        const size_t off = free_[i].off;
-        if (free_[i].size == bytes) free_.erase(free_.begin() + i);
-        else { free_[i].off += bytes; free_[i].size -= bytes; }
-        return off;
-      }
-    }
-    const size_t off = top;
-    top += bytes;
-    if (top > high) high = top;
-    return off;
-  }
-  void release(size_t off, size_t bytes) {
-    bytes = align(bytes);
-    size_t i = 0;
-    while (i < free_.size() && free_[i].off < off) ++i;
-    free_.insert(free_.begin() + i, Blk{off, bytes});
-    if (i + 1 < free_.size() && free_[i].off + free_[i].size == free_[i + 1].off) {
-      free_[i].size += free_[i + 1].size;
-      free_.erase(free_.begin() + i + 1);
-    }
-    if (i > 0 && free_[i - 1].off + free_[i - 1].size == free_[i].off) {
-      free_[i - 1].size += free_[i].size;
-      free_.erase(free_.begin() + i);
-    }
-    if (!free_.empty() && free_.back().off + free_.back().size == top) {
-      top = free_.back().off;
-      free_.pop_back();
-    }
-  }
-  void reset() { free_.clear(); top = 0; high = 0; }
-};
-
-struct Buf {
-  Arena* arena; size_t off, bytes; bool keep;
-  ~Buf() { if (!keep) arena->release(off, bytes); }
-};
-
-// channels-last activation [nimg][H][W][C] (row stride ld elements)
-struct Act {
-  std::shared_ptr<Buf> buf;
-  bf16* ptr = nullptr;
-  int nimg = 0, H = 0, W = 0, C = 0, ld = 0;
-  int64_t rows() const { return (int64_t)nimg * H * W; }
-  bool valid() const { return nimg > 0; }
-};
-
-struct Tap { std::string name; bf16* ptr; int64_t rows; int C, ld; };
-
-struct IO {
-  const float* sample;
-  const float* ctx;
-  float* out;
-  const void* down_res[16];
-  const void* mid_res;
-  int has_res;
-  const float* cond;
-  const float* mask;
-  int cond_batch;
-  float scale;
-  void* out_down[16];
-  void* out_mid;
-  const float* y;               // sgm "vector" conditioning
-  float in_scale;               // sgm c_in; VAE: 1 / scale_factor
-  const int* ids;               // CLIP text encoder: token ids [batch][L]
-  float in_shift;               // VAE encoder: x * in_scale + in_shift fused into conv_in
-  float out_mul, out_add;       // VAE: image post-scaling fused into conv_out
-  int clamp01;
-  bool operator==(const IO& o) const { return std::memcmp(this, &o, sizeof(IO)) == 0; }
-};
-// The IO every forward entry point starts from: all bytes zero (padding too: operator== is a memcmp and IO is the graph-cache key) and the
-// defaults the networks share, so one set of pointers gives one key whichever entry point it came through
-inline IO new_io() {
-  IO io;
-  std::memset(&io, 0, sizeof(io));
-  io.scale = 1.f; io.in_scale = 1.f; io.out_mul = 1.f; io.cond_batch = 1;
-  return io;
-}
 
 __global__ void copy16_kernel(const uint4* __restrict__ a, uint4* __restrict__ b, long long n16) {   // debug snapshots only
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n16) b[i] = a[i];
 }
 
-constexpr int NR_MAX_BATCH = 64;   // samples per evaluation (CFG-expanded; the grouped SparseCtrl schedule runs G x 2B of them)
 struct TimestepVals { float v[NR_MAX_BATCH]; };
 __global__ void set_timesteps_kernel(float* dst, TimestepVals tv, int n) {
   if (threadIdx.x < n) dst[threadIdx.x] = tv.v[threadIdx.x];
@@ -199,2039 +27,140 @@ __global__ void set_timesteps_kernel(float* dst, TimestepVals tv, int n) {
 
 }  // namespace
 
-struct nr_net {
-  nr_net_config cfg;
-  std::map<std::string, HostTensor> host;
-  struct DevW { void* ptr; size_t bytes; };
-  std::map<std::string, DevW> dev;   // converted weights by derived name: changed only by adopt() / erase()
-  size_t weight_bytes = 0;           // sum of dev[].bytes (what is resident)
-  // converted weights received from another handle (nr_net_import_weights): ONE device allocation, dev[] points into it
-  char* import_base = nullptr;
-  size_t import_bytes = 0;
-  int device = -1;                   // HIP device the handle was created on
+void nre::set_err(const std::string& s) { g_err = s; }
+void nre::launch_copy16(const void* src, void* dst, size_t nbytes, hipStream_t s) {
+  const long long n16 = (long long)(nbytes / 16);
+  hipLaunchKernelGGL(copy16_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, n16);
+}
 
-  // plan
-  int B2 = 0, F = 0, H = 0, W = 0, ctx_len = 0;
-  bool planned = false;
-  bool dry = false;
-  Arena arena;
-  // buffers written by the context ops live in their OWN region behind the main arena: context ops execute before
-  // everything else, so they must never share memory with any temporary of the main plan
-  Arena parena;
-  size_t main_high = 0;          // bytes of the main region (known after the sizing pass)
-  char* arena_base = nullptr;
-  size_t arena_bytes = 0;
-  std::vector<std::function<void(hipStream_t)>> ops;
-  // ops that depend only on the cross-attention context (fp32->bf16 convert + every to_k|to_v projection): the
-  // context is constant over all denoising steps of a clip, so they run once per context (nr_net_invalidate_context)
-  std::vector<std::function<void(hipStream_t)>> ctx_ops;
-  std::vector<Act> ctx_persist;      // K|V buffers that must survive between forwards
-  bool building_ctx = false;
-  bool ctx_dirty = true;
-  struct OpMeta { int kind; double flops, bytes; std::string desc; int launches = 1; };   // launches: kernels this op enqueues
-  std::vector<OpMeta> op_meta;   // parallel to ops: kernel class + algorithmic work (for roofline reporting)
-  std::vector<Tap> taps;
-  bool keep_all = false;
-  // nr_net_set_deterministic_batch / NR_DETERMINISTIC_BATCH=1: every plan choice that can move a rounding point or a summation order (LayerNorm
-  // folded vs separate, split-K depth, row-panel / fused-kernel eligibility, GroupNorm variant and chunking, the weight-stream rotation of
-  // the fused kernels) is made for the rows of ONE clip's CFG pair, so a clip's result does not depend on how many clips share the call
-  bool det_batch = false;
-  int clip_samples = 2;          // nr_net_set_clip_samples: samples of ONE clip in the batch (2 = CFG pair, 1 = no guidance)
-  long long det_rows(long long rows) const {       // rows of this op that belong to one clip (rows itself when not in that mode)
-    if (!det_batch || B2 <= clip_samples) return rows;
-    return rows / B2 * clip_samples;
-  }
-  // SparseCtrl only (nr_sparsectrl_set_condition_frames): the frames whose condition / mask is not all zero.  With the noisy sample zeroed
-  // (sparse_controlnet.py:468-469) every OTHER frame enters the network as the same constant image (conv_in(0) + cond_embedding(0) =
-  // the two biases, :513-521), so until the first motion module mixes frames (unet_blocks.py:382-421: resnet -> attention -> motion
-  // module) all of them carry identical activations: down_blocks[0].resnets[0] + attentions[0] run on the conditioned frames plus ONE
-  // representative of the rest and are broadcast before motion_modules[0].  Exact (per-frame operators, identical inputs); < 0 = off.
-  int n_cond_frames = -1;
-  int cond_frames[64] = {0};
-  bool cfg_dup = false;          // nr_net_set_cfg_pair_identical: the caller promises sample[b] == sample[b + B2/2] and timestep[b] == timestep[b + B2/2]
-  bool attn_fp8 = false;         // nr_net_set_attention_fp8: spatial / cross attention on e4m3 MFMA operands (config 5)
-  IO io = new_io();
-  int n_res = 0;
-  struct ResShape { int C, h, w; };
-  std::vector<ResShape> res_shapes;  // n_res down + 1 mid
+// ================================================================================================
+// runtime
+// ================================================================================================
+nr_net::~nr_net() {
+  if (arena_base) (void)hipFree(arena_base);
+  drop_graphs();
+  for (auto& e : ev_slot) if (e) (void)hipEventDestroy(e);
+  if (ev_in) (void)hipEventDestroy(ev_in);
+  if (ev_out) (void)hipEventDestroy(ev_out);
+  if (ev_adds) (void)hipEventDestroy(ev_adds);
+  if (own_stream) (void)hipStreamDestroy(own_stream);
+}
 
-  // small persistent fp32 buffers (allocated from the arena, pinned)
-  float* t_dev = nullptr;
-  int temb_total = 0;
+void nr_net::drop_graphs() {
+  for (auto& c : gcache) { for (auto& g : c) if (g.exec) (void)hipGraphExecDestroy(g.exec); c.clear(); }
+}
 
-  // graph
-  bool use_graph = false;
-  // [0] ops before the ControlNet-residual adds, [1] the adds, [2] the rest
-  // captured graphs per segment, keyed by the IO block they were captured with (pointers are baked into the kernel nodes): the grouped
-  // SparseCtrl schedule alternates between a few residual-buffer sets, each gets its own executable graph (small LRU)
-  struct GraphSlot { IO io = new_io(); hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
-  static constexpr int NR_GRAPH_SLOTS = 64;     // the sgm Euler loop bakes c_in(sigma) into its graphs: one per step of a 38 / 50-step schedule
-  std::vector<GraphSlot> gcache[3];
-  unsigned long long gclock = 0;
-  hipEvent_t ev_slot[2] = {nullptr, nullptr};   // completion of nr_sparsectrl_forward_async evaluations (two in flight at most)
-  size_t split_op = 0;                            // index of the first op of segment 1 (== ops.size() if none)
-  size_t split_op2 = 0;                           // index of the first op of segment 2
-  hipEvent_t ev_adds = nullptr;                   // U-Net: the residual adds have consumed SparseCtrl's outputs
-  // SparseCtrl evaluation issued ahead of time for the NEXT denoising step (nr_denoise_step_forward): its inputs do
-  // not depend on the latents, only on the timestep / context / condition
-  bool prefetch_valid = false;
-  float prefetch_t[NR_MAX_BATCH] = {0};
-  IO prefetch_io = new_io();
-  // graph replay happens on an engine-owned non-blocking stream (capture is illegal on the legacy default
-  // stream PyTorch hands over); it is fenced to the caller's stream with two events per forward
-  hipStream_t own_stream = nullptr;
-  hipEvent_t ev_in = nullptr, ev_out = nullptr;
-
-  ~nr_net() {
-    while (!dev.empty()) erase(std::string(dev.begin()->first));
-    if (import_base) (void)hipFree(import_base);
-    if (arena_base) (void)hipFree(arena_base);
-    drop_graphs();
-    for (auto& e : ev_slot) if (e) (void)hipEventDestroy(e);
-    if (ev_in) (void)hipEventDestroy(ev_in);
-    if (ev_out) (void)hipEventDestroy(ev_out);
-    if (ev_adds) (void)hipEventDestroy(ev_adds);
-    if (own_stream) (void)hipStreamDestroy(own_stream);
-  }
-
-  void drop_graphs() {
-    for (auto& c : gcache) { for (auto& g : c) if (g.exec) (void)hipGraphExecDestroy(g.exec); c.clear(); }
-  }
-  bool in_import(const void* p) const { return import_base && (const char*)p >= import_base && (const char*)p < import_base + import_bytes; }
-
-  // ------------------------------------------------------------------ weights
-  const HostTensor& need(const std::string& key) const {
-    auto it = host.find(key);
-    if (it == host.end()) throw NrError(NR_ERR_MISSING_WEIGHT, "missing state-dict entry: " + key);
-    return it->second;
-  }
-  bool has(const std::string& key) const { return host.count(key) != 0; }
-  // host copies may have been released after the first plan (nr_net_release_host_weights)
-  const HostTensor& data_of(const std::string& key) const {
-    const HostTensor& t = need(key);
-    if ((int64_t)t.data.size() != t.numel())
-      throw NrError(NR_ERR_STATE, import_base
-                                      ? "this handle was filled by nr_net_import_weights (no fp32 host weights) and the requested shape needs a converted "
-                                        "weight the exporting plan did not make (" + key + "): export from a handle planned for THIS shape, or load a state dict"
-                                      : "host copy of " + key + " was released (nr_net_release_host_weights) and this shape needs a conversion the earlier "
-                                        "plans did not make; load the state dict again, or do not release the host copies");
-    return t;
-  }
-
-  void* upload(const std::string& name, const void* data, size_t bytes) {
-    void* d = nullptr;
-    HIP_OK(hipMalloc(&d, bytes));
-    HIP_OK(hipMemcpy(d, data, bytes, hipMemcpyHostToDevice));
-    return adopt(name, d, bytes);
-  }
-  // the only place that inserts a converted buffer and adds it to the resident total
-  void* adopt(const std::string& name, void* d, size_t bytes) {
-    dev[name] = DevW{d, bytes};
-    weight_bytes += bytes;
-    return d;
-  }
-  // the only place that removes one: frees it (unless it lies inside the imported arena) and takes it out of the resident total.  Also how
-  // a converted buffer that only fed another conversion (the packed weight streams of the fused kernels) goes again: it then neither stays
-  // resident nor travels in the exported arena
-  void erase(const std::string& name) {
-    auto it = dev.find(name);
-    if (it == dev.end()) return;
-    if (it->second.ptr && !in_import(it->second.ptr)) (void)hipFree(it->second.ptr);
-    weight_bytes -= it->second.bytes;
-    dev.erase(it);
-  }
-  void drop(const std::string& name) { erase(name); }
-  // derived name of the converted matrix this pointer is
-  std::string name_of(const void* p, const char* who) const {
-    for (const auto& kv : dev) if (kv.second.ptr == p) return kv.first;
-    throw NrError(NR_ERR_STATE, std::string(who) + ": not a converted weight matrix");
-  }
-  template <class Fn>
-  void* cached(const std::string& name, Fn make) {
-    if (dry) return nullptr;
-    auto it = dev.find(name);
-    if (it != dev.end()) return it->second.ptr;
-    return make();
-  }
-  // a buffer a pack kernel fills on the device: fn(d) enqueues the kernel(s) on the null stream, which have run when this returns
-  template <class Fn>
-  void* packed(const std::string& name, size_t bytes, Fn fn) {
-    return cached(name, [&]() {
-      void* d = nullptr;
-      HIP_OK(hipMalloc(&d, bytes));
-      try { fn(d); HIP_OK(hipDeviceSynchronize()); }
-      catch (...) { (void)hipFree(d); throw; }
-      return adopt(name, d, bytes);
-    });
-  }
-  // fragment-major copy (smallm.hip) of a converted [N][K] weight matrix, cached as "fm:<its name>"; the row-major matrix stays (launches of
-  // other row counts use it)
-  const bf16* w_fragmajor(const bf16* w, int N, int K) {
-    return (const bf16*)packed("fm:" + name_of(w, "w_fragmajor"), (size_t)N * K * sizeof(bf16),
-                               [&](void* d) { LAUNCH_OK(nr_launch_smallm_w_pack(w, d, N, K, nullptr)); });
-  }
-  // stage stream (lin160.hip) of a converted [N][K] weight matrix, cached as "l160:<its name>" ("l128:": the 128-column layout of the register-panel kernel);
-  // the row-major matrix stays (other row counts use it)
-  const bf16* w_lin160(const bf16* w, int N, int K, bool panel = false) {
-    const size_t nb = panel ? nr_lin128q_stream_bytes(N, K) : nr_lin160_stream_bytes(N, K);
-    if (!nb) throw NrError(NR_ERR_STATE, "w_lin160: shape has no stage stream");
-    return (const bf16*)packed((panel ? "l128:" : "l160:") + name_of(w, "w_lin160"), nb, [&](void* d) {
-      LAUNCH_OK(panel ? nr_launch_lin128q_w_pack(w, N, K, (bf16*)d, nullptr) : nr_launch_lin160_w_pack(w, N, K, (bf16*)d, nullptr));
-    });
-  }
-  void check_shape(const std::string& key, const HostTensor& t, std::initializer_list<int64_t> want) const {
-    std::vector<int64_t> w(want);
-    int64_t nw = 1; for (auto s : w) nw *= s;
-    if (t.numel() != nw) {
-      std::string m = "state-dict entry " + key + " has " + std::to_string(t.numel()) + " elements, expected " + std::to_string(nw);
-      throw NrError(NR_ERR_ARG, m);
-    }
-  }
-
-  // nn.Linear / 1x1 conv weight [N][K] -> bf16 [N][K]
-  const bf16* w_linear(const std::string& key, int N, int K) {
-    const HostTensor& t = need(key);
-    check_shape(key, t, {N, K});
-    return (const bf16*)cached("lin:" + key, [&]() {
-      const HostTensor& td = data_of(key);
-      std::vector<uint16_t> h((size_t)N * K);
-      for (size_t i = 0; i < h.size(); ++i) h[i] = f2bf_host(td.data[i]);
-      return upload("lin:" + key, h.data(), h.size() * 2);
-    });
-  }
-  // rows of several [Ni][K] matrices concatenated (fused q|k|v, k|v)
-  const bf16* w_linear_cat(const std::vector<std::string>& keys, int Neach, int K) {
-    std::string name = "cat:";
-    for (auto& k : keys) { const HostTensor& t = need(k); check_shape(k, t, {Neach, K}); name += k + "|"; }
-    return (const bf16*)cached(name, [&]() {
-      std::vector<uint16_t> h((size_t)keys.size() * Neach * K);
-      size_t o = 0;
-      for (auto& k : keys) { const HostTensor& t = data_of(k); for (size_t i = 0; i < t.data.size(); ++i) h[o++] = f2bf_host(t.data[i]); }
-      return upload(name, h.data(), h.size() * 2);
-    });
-  }
-  const float* b_cat(const std::vector<std::string>& keys, int Neach) {
-    std::string name = "bcat:";
-    for (auto& k : keys) { const HostTensor& t = need(k); check_shape(k, t, {Neach}); name += k + "|"; }
-    return (const float*)cached(name, [&]() {
-      std::vector<float> h;
-      for (auto& k : keys) { const HostTensor& t = data_of(k); h.insert(h.end(), t.data.begin(), t.data.end()); }
-      return upload(name, h.data(), h.size() * 4);
-    });
-  }
-
-  // LayerNorm folded into the consuming Linear: y = W (gamma * xhat + beta) + b = rstd * (W' x - mean * c) + b'
-  // with W'[n][k] = gamma[k] W[n][k] (bf16), c[n] = sum_k W'[n][k], b'[n] = b[n] + sum_k beta[k] W[n][k].
-  // The igemm accumulates the row statistics of x itself (gemm.hip, LNF), so no LayerNorm pass touches HBM.
-  // wkeys: matrices [Neach][K] stacked along N (fused q|k|v); bkeys: their biases (empty = none);
-  // geglu: single [2*Neach][K] projection with the value/gate row interleave of w_geglu.
-  struct LnW { const bf16* w; const float* c; const float* b; };
-  // need_w = false: only c / b' are wanted (the matrix was packed into a kernel's weight stream and dropped again)
-  LnW w_ln_linear(const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys, const std::string& ln, int Neach,
-                  int K, bool geglu, bool need_w = true) {
-    std::string name = ln + "|";
-    const int rows_each = geglu ? 2 * Neach : Neach;
-    for (auto& k : wkeys) { check_shape(k, need(k), {rows_each, K}); name += k + "|"; }
-    for (auto& k : bkeys) { check_shape(k, need(k), {rows_each}); name += k + "|"; }
-    check_shape(ln + ".weight", need(ln + ".weight"), {K});
-    check_shape(ln + ".bias", need(ln + ".bias"), {K});
-    LnW r{nullptr, nullptr, nullptr};
-    if (dry) return r;
-    const std::string nw = "lnw:" + name, nc = "lnc:" + name, nb = "lnb:" + name;
-    {
-      auto it = dev.find(nw), ic = dev.find(nc), ib = dev.find(nb);
-      if (ic != dev.end() && ib != dev.end() && (it != dev.end() || !need_w)) {
-        r.w = it != dev.end() ? (const bf16*)it->second.ptr : nullptr; r.c = (const float*)ic->second.ptr; r.b = (const float*)ib->second.ptr;
-        return r;
-      }
-      drop(nw); drop(nc); drop(nb);                                  // partly present (matrix dropped after a stream pack): rebuild all three
-    }
-    const HostTensor& g = data_of(ln + ".weight");
-    const HostTensor& be = data_of(ln + ".bias");
-    const size_t N = (size_t)rows_each * wkeys.size();
-    std::vector<uint16_t> hw(N * K);
-    std::vector<float> hc(N), hb(N);
-    for (size_t mi = 0; mi < wkeys.size(); ++mi) {
-      const HostTensor& W = data_of(wkeys[mi]);
-      const HostTensor* B = bkeys.empty() ? nullptr : &data_of(bkeys[mi]);
-      for (int n = 0; n < rows_each; ++n) {
-        const int src = geglu ? geglu_src_row(n, Neach) : n;
-        const float* wr = W.data.data() + (size_t)src * K;
-        const size_t dst = mi * rows_each + n;
-        double c = 0.0, b = B ? (double)B->data[src] : 0.0;
-        for (int k = 0; k < K; ++k) {
-          const uint16_t q16 = f2bf_host(g.data[k] * wr[k]);
-          hw[dst * K + k] = q16;
-          c += (double)bf2f_host(q16);
-          b += (double)be.data[k] * (double)wr[k];
-        }
-        hc[dst] = (float)c; hb[dst] = (float)b;
-      }
-    }
-    r.w = (const bf16*)upload(nw, hw.data(), hw.size() * 2);
-    r.c = (const float*)upload(nc, hc.data(), hc.size() * 4);
-    r.b = (const float*)upload(nb, hb.data(), hb.size() * 4);
-    return r;
-  }
-  // temporal positional encoding pushed through the q|k|v projection: rv[f][n] = sum_k pe[f][k] W[n][k], f < max_len
-  // (motion_module.py:241-243,274-278 add pe AFTER the LayerNorm, so W(LN(x) + pe) = W LN(x) + W pe)
-  const float* pe_projection(const std::vector<std::string>& wkeys, int Neach, int K, int max_len) {
-    std::string name = "perv:" + std::to_string(max_len) + ":";
-    for (auto& k : wkeys) name += k + "|";
-    return (const float*)cached(name, [&]() {
-      const size_t N = (size_t)Neach * wkeys.size();
-      const std::vector<float> pe = sinusoid_table(max_len, K);
-      std::vector<float> rv((size_t)max_len * N);
-      for (size_t mi = 0; mi < wkeys.size(); ++mi) {
-        const HostTensor& W = data_of(wkeys[mi]);
-        for (int n = 0; n < Neach; ++n)
-          for (int f = 0; f < max_len; ++f) {
-            double a = 0.0;
-            const float* wr = W.data.data() + (size_t)n * K;
-            const float* pr = pe.data() + (size_t)f * K;
-            for (int k = 0; k < K; ++k) a += (double)pr[k] * (double)wr[k];
-            rv[(size_t)f * N + mi * Neach + n] = (float)a;
-          }
-      }
-      return upload(name, rv.data(), rv.size() * 4);
-    });
-  }
-  // FeedForward.net.2 followed by proj_out (only the residual add of the block between them) folded into one Linear over the
-  // concatenated operand [t | g]: Wc = [Wpo | Wpo Wff2] ([C][5C] bf16), bc = bpo + Wpo bff2.  The C x C x 4C product runs on the device
-  // in fp32 (fold_linear_pair_kernel), once per plan of new weights.
-  struct FoldW { const bf16* w; const float* b; };
-  FoldW w_fold_ff_proj(const std::string& ff2, const std::string& po, int C, bool need_w = true) {
-    const int J = 4 * C;
-    check_shape(ff2 + ".weight", need(ff2 + ".weight"), {C, J});
-    check_shape(ff2 + ".bias", need(ff2 + ".bias"), {C});
-    check_shape(po + ".weight", need(po + ".weight"), {C, C});
-    check_shape(po + ".bias", need(po + ".bias"), {C});
-    FoldW r{nullptr, nullptr};
-    if (dry) return r;
-    const std::string nw = "foldw:" + po + ".weight|" + po + ".bias|" + ff2 + ".weight|" + ff2 + ".bias";
-    const std::string nb = "foldb:" + po + ".weight|" + po + ".bias|" + ff2 + ".weight|" + ff2 + ".bias";
-    auto it = dev.find(nw);
-    auto itb = dev.find(nb);
-    if (itb != dev.end() && (it != dev.end() || !need_w)) { r.w = it != dev.end() ? (const bf16*)it->second.ptr : nullptr; r.b = (const float*)itb->second.ptr; return r; }
-    if (itb != dev.end()) drop(nb);                                  // bias kept, matrix dropped after a stream pack: rebuild both
-    const HostTensor& W2 = data_of(po + ".weight");
-    const HostTensor& B2 = data_of(po + ".bias");
-    const HostTensor& W1 = data_of(ff2 + ".weight");
-    const HostTensor& B1 = data_of(ff2 + ".bias");
-    const size_t wcb = (size_t)C * (C + J) * sizeof(bf16), bcb = (size_t)C * sizeof(float);
-    r.w = (const bf16*)packed(nw, wcb, [&](void* dwc) {
-      float *dw2 = nullptr, *dw1 = nullptr, *db2 = nullptr, *db1 = nullptr;
-      void* dbc = nullptr;
-      HIP_OK(hipMalloc(&dw2, W2.data.size() * 4)); HIP_OK(hipMalloc(&dw1, W1.data.size() * 4));
-      HIP_OK(hipMalloc(&db2, B2.data.size() * 4)); HIP_OK(hipMalloc(&db1, B1.data.size() * 4));
-      HIP_OK(hipMalloc(&dbc, bcb));
-      HIP_OK(hipMemcpy(dw2, W2.data.data(), W2.data.size() * 4, hipMemcpyHostToDevice));
-      HIP_OK(hipMemcpy(dw1, W1.data.data(), W1.data.size() * 4, hipMemcpyHostToDevice));
-      HIP_OK(hipMemcpy(db2, B2.data.data(), B2.data.size() * 4, hipMemcpyHostToDevice));
-      HIP_OK(hipMemcpy(db1, B1.data.data(), B1.data.size() * 4, hipMemcpyHostToDevice));
-      LAUNCH_OK(nr_launch_fold_linear_pair(dw2, dw1, db2, db1, C, J, (bf16*)dwc, (float*)dbc, nullptr));
-      HIP_OK(hipDeviceSynchronize());
-      (void)hipFree(dw2); (void)hipFree(dw1); (void)hipFree(db2); (void)hipFree(db1);
-      r.b = (const float*)adopt(nb, dbc, bcb);
-    });
-    return r;
-  }
-  // GEGLU projection [2*inner][K]: rows permuted so each 32-row group is 16 value rows then their 16 gate rows
-  const bf16* w_geglu(const std::string& key, int inner, int K) {
-    const HostTensor& t = need(key);
-    check_shape(key, t, {2 * inner, K});
-    return (const bf16*)cached("geglu:" + key, [&]() {
-      (void)data_of(key);
-      std::vector<uint16_t> h((size_t)2 * inner * K);
-      for (int n = 0; n < 2 * inner; ++n) {
-        const int src = geglu_src_row(n, inner);
-        for (int k = 0; k < K; ++k) h[(size_t)n * K + k] = f2bf_host(t.data[(size_t)src * K + k]);
-      }
-      return upload("geglu:" + key, h.data(), h.size() * 2);
-    });
-  }
-  const float* b_geglu(const std::string& key, int inner) {
-    const HostTensor& t = need(key);
-    check_shape(key, t, {2 * inner});
-    return (const float*)cached("geglub:" + key, [&]() {
-      (void)data_of(key);
-      std::vector<float> h((size_t)2 * inner);
-      for (int n = 0; n < 2 * inner; ++n) h[n] = t.data[geglu_src_row(n, inner)];
-      return upload("geglub:" + key, h.data(), h.size() * 4);
-    });
-  }
-  // conv weight [Cout][Cin][3][3] -> bf16 [Cout][ky][kx][Cin]
-  // 3x3 conv weight in the tap-inner K order of the igemm (NrGemmParams::tap_inner): [Cout][Cin/64][ky][kx][64]
-  static bool conv_tap_inner() {
-    static const bool on = !(getenv("NR_CONV_TAP_INNER") && getenv("NR_CONV_TAP_INNER")[0] == '0');
-    return on;
-  }
-  const bf16* w_conv3_tap_inner(const std::string& key, int Cout, int Cin) {
-    const HostTensor& t = need(key);
-    check_shape(key, t, {Cout, Cin, 3, 3});
-    if (Cin % 64 != 0) throw NrError(NR_ERR_UNSUPPORTED, "tap-inner conv layout needs Cin % 64 == 0: " + key);
-    return (const bf16*)cached("conv3t:" + key, [&]() {
-      (void)data_of(key);
-      std::vector<uint16_t> h((size_t)Cout * 9 * Cin);
-      for (int o = 0; o < Cout; ++o)
-        for (int c = 0; c < Cin; ++c)
-          for (int k = 0; k < 9; ++k)
-            h[(size_t)o * 9 * Cin + (size_t)(c / 64) * 9 * 64 + (size_t)k * 64 + (c % 64)] = f2bf_host(t.data[((size_t)o * Cin + c) * 9 + k]);
-      return upload("conv3t:" + key, h.data(), h.size() * 2);
-    });
-  }
-  const bf16* w_conv3(const std::string& key, int Cout, int Cin) {
-    const HostTensor& t = need(key);
-    check_shape(key, t, {Cout, Cin, 3, 3});
-    return (const bf16*)cached("conv3:" + key, [&]() {
-      (void)data_of(key);
-      std::vector<uint16_t> h((size_t)Cout * 9 * Cin);
-      for (int o = 0; o < Cout; ++o)
-        for (int c = 0; c < Cin; ++c)
-          for (int k = 0; k < 9; ++k)
-            h[((size_t)o * 9 + k) * Cin + c] = f2bf_host(t.data[((size_t)o * Cin + c) * 9 + k]);
-      return upload("conv3:" + key, h.data(), h.size() * 2);
-    });
-  }
-  // small-Cin conv weight [Cout][Cin][3][3] -> fp32 [Cin*9][Cout]
-  const float* w_conv_in(const std::string& key, int Cout, int Cin) {
-    const HostTensor& t = need(key);
-    check_shape(key, t, {Cout, Cin, 3, 3});
-    return (const float*)cached("convin:" + key, [&]() {
-      (void)data_of(key);
-      std::vector<float> h((size_t)Cin * 9 * Cout);
-      for (int o = 0; o < Cout; ++o)
-        for (int k = 0; k < Cin * 9; ++k) h[(size_t)k * Cout + o] = t.data[(size_t)o * Cin * 9 + k];
-      return upload("convin:" + key, h.data(), h.size() * 4);
-    });
-  }
-  // 3x3 conv weight [Cout][Cin][3][3] -> the fragment-major bf16 layout of condembed_conv: [Cout/16][KS][64 lanes][8], KS = ceil(9 Cin / 32);
-  // lane (fr, g) of block (T, ks) holds W[16 T + fr][k], k = 32 ks + 8 g .. + 7 = tap * Cin + c (zero beyond K = 9 Cin)
-  const bf16* w_condembed(const std::string& key, int Cout, int Cin) {
-    const HostTensor& t = need(key);
-    check_shape(key, t, {Cout, Cin, 3, 3});
-    return (const bf16*)cached("cefm:" + key, [&]() {
-      (void)data_of(key);
-      const int K = 9 * Cin, KS = (K + 31) / 32;
-      std::vector<uint16_t> h((size_t)nr_condembed_wfm_elems(Cin, Cout), 0);
-      for (int T = 0; T < Cout / 16; ++T)
-        for (int ks = 0; ks < KS; ++ks)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-              const int o = 16 * T + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + j;
-              if (k >= K) continue;
-              const int tap = k / Cin, c = k % Cin;
-              h[(((size_t)T * KS + ks) * 64 + lane) * 8 + j] = f2bf_host(t.data[((size_t)o * Cin + c) * 9 + tap]);
-            }
-      return upload("cefm:" + key, h.data(), h.size() * 2);
-    });
-  }
-  // elementwise sum of two fp32 vectors (the embedding's conv_out bias with conv_in.bias folded in)
-  const float* w_f32_sum(const std::string& a, const std::string& b, int64_t n) {
-    check_shape(a, need(a), {n});
-    check_shape(b, need(b), {n});
-    const std::string name = "f32sum:" + a + "|" + b;
-    return (const float*)cached(name, [&]() {
-      const HostTensor& ta = data_of(a);
-      const HostTensor& tb = data_of(b);
-      std::vector<float> h((size_t)n);
-      for (int64_t i = 0; i < n; ++i) h[i] = ta.data[i] + tb.data[i];
-      return upload(name, h.data(), h.size() * 4);
-    });
-  }
-  const float* w_f32(const std::string& key, int64_t n) {
-    const HostTensor& t = need(key);
-    check_shape(key, t, {n});
-    return (const float*)cached("f32:" + key, [&]() { (void)data_of(key); return upload("f32:" + key, t.data.data(), t.data.size() * 4); });
-  }
-  // sinusoidal temporal PE table [max_len][C]  (motion_module.py:225-239), regenerated (non-persistent buffer)
-  const float* pe_table(int C, int max_len) {
-    const std::string name = "pe:" + std::to_string(C) + ":" + std::to_string(max_len);
-    return (const float*)cached(name, [&]() {
-      const std::vector<float> h = sinusoid_table(max_len, C);
-      return upload(name, h.data(), h.size() * 4);
-    });
-  }
-
-  // ------------------------------------------------------------------ plan helpers
-  // (integer arithmetic: during the sizing pass arena_base is null and the pointers are never used; `null + offset` on a pointer is UB)
-  template <class T>
-  T* at(size_t off) const { return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(arena_base) + off); }
-
-  Act new_act(int nimg, int h, int w, int C) {
-    Act a;
-    const size_t bytes = (size_t)nimg * h * w * C * sizeof(bf16);
-    auto b = std::make_shared<Buf>();
-    b->arena = &arena; b->bytes = bytes; b->off = arena.alloc(bytes); b->keep = keep_all;
-    a.buf = b; a.ptr = at<bf16>(b->off); a.nimg = nimg; a.H = h; a.W = w; a.C = C; a.ld = C;
-    return a;
-  }
-  Act new_act_persistent(int nimg, int h, int w, int C) {
-    Act a;
-    const size_t bytes = (size_t)nimg * h * w * C * sizeof(bf16);
-    auto b = std::make_shared<Buf>();
-    b->arena = &parena; b->bytes = bytes; b->off = parena.alloc(bytes); b->keep = true;
-    a.buf = b; a.ptr = at<bf16>(main_high + b->off); a.nimg = nimg; a.H = h; a.W = w; a.C = C; a.ld = C;
-    return a;
-  }
-  // raw pinned scratch (lives for the whole plan)
-  template <class T>
-  T* new_scratch(size_t count) { return at<T>(arena.alloc(count * sizeof(T))); }
-  // temporary fp32 scratch with lifetime of the returned handle
-  std::shared_ptr<Buf> new_tmp(size_t bytes) {
-    auto b = std::make_shared<Buf>();
-    b->arena = &arena; b->bytes = bytes; b->off = arena.alloc(bytes); b->keep = keep_all;
-    return b;
-  }
-  void emit(std::function<void(hipStream_t)> fn, int kind = NR_PROF_OTHER, double flops = 0, double bytes = 0,
-            const std::string& desc = std::string()) {
-    if (dry) return;
-    if (building_ctx) { ctx_ops.push_back(std::move(fn)); return; }
-    ops.push_back(std::move(fn));
-    op_meta.push_back(OpMeta{kind, flops, bytes, desc});
-  }
-  void last_op_launches(int n) { if (!dry && !building_ctx && !op_meta.empty()) op_meta.back().launches = n; }
-  void tap(const std::string& name, const Act& a) {
-    if (!dry && keep_all) taps.push_back(Tap{name, a.ptr, a.rows(), a.C, a.ld});
-  }
-  // debug only (NR_OP_TAPS=1 with nr_net_set_debug): one tap per kernel output, named by plan position and kernel class
-  void op_tap(const char* kind, const Act& a) {
-    static const bool on = getenv("NR_OP_TAPS") != nullptr;
-    if (on && !dry && keep_all && !building_ctx) taps.push_back(Tap{"op" + std::to_string(ops.size()) + "." + kind, a.ptr, a.rows(), a.C, a.ld});
-  }
-
-  struct GemmOpt {
-    const float* bias = nullptr;
-    const float* rowvec = nullptr; int rowvec_div = 1, rowvec_ld = 0, rowvec_mod = 0;
-    const Act* res = nullptr;
-    float scale = 1.f;
-    int geglu = 0;
-    Act* out = nullptr;      // write into this existing activation (may alias res)
-    int pad_tl0 = 0;         // 3x3: no top/left padding (VAE Downsample)
-    int act = 0;             // 1: quick_gelu
-    const float* ln_c = nullptr;   // LayerNorm folded into this GEMM (see w_ln_linear)
-    int tap_inner = 0;       // 3x3 stride 1 single source: weights in the tap-inner layout of w_conv3_tap_inner
-  };
-
-  // generic conv / linear.  x1: optional channel-concat second source.
-  Act conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksize, int stride, int ups, const GemmOpt& o) {
-    int OH, OW;
-    nr_conv_out_hw(x0.H, x0.W, ksize, stride, ups, &OH, &OW);
-    const int outC = o.geglu ? Cout / 2 : Cout;
-    Act out = o.out ? *o.out : new_act(x0.nimg, OH, OW, outC);
-    if (out.C != outC || out.rows() != (int64_t)x0.nimg * OH * OW) throw NrError(NR_ERR_STATE, "conv: output shape mismatch");
-    if (o.res && (o.res->C != outC || o.res->rows() != out.rows())) throw NrError(NR_ERR_STATE, "conv: residual shape mismatch");
-    NrGemmParams p = nr_gemm_params(x0.ptr, x0.C, x0.ld, x1 ? x1->ptr : nullptr, x1 ? x1->C : 0, x1 ? x1->ld : 0, x0.nimg, x0.H, x0.W, ksize, stride, ups,
-                                    w, Cout, o.bias, o.res ? o.res->ptr : nullptr, o.res ? o.res->ld : 0, out.ptr, out.ld);
-    p.rowvec = o.rowvec; p.rowvec_div = o.rowvec_div; p.rowvec_ld = o.rowvec_ld; p.rowvec_mod = o.rowvec_mod;
-    p.out_scale = o.scale; p.geglu = o.geglu; p.pad_tl0 = o.pad_tl0; p.act = o.act; p.ln_c = o.ln_c; p.ln_eps = 1e-5f;
-    p.tap_inner = o.tap_inner;
-    p.plan_m = det_batch ? (int)det_rows(p.M) : 0;
-    if (ksize == 1 && nr_smallm_eligible(&p))               // M <= 512 Linears: the panel-resident kernel reads fragment-major weights
-      p.w_fm = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : w_fragmajor(w, Cout, p.K);
-    if (const int l1 = (ksize == 1 && !p.w_fm) ? nr_lin160_eligible(&p) : 0) {
-      // short-K Linear (K = 640 / 1280) on >= 2048 rows: the stage-stream kernel (lin160.hip) instead of the tiled igemm; 4 = its register-panel form
-      const bf16* stream = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : w_lin160(w, Cout, p.K, l1 == 4);
-      char d[160];
-      snprintf(d, sizeof(d), "%s M=%d N=%d K=%d res=%d geglu=%d ln=%d", l1 == 4 ? "lin160 panel" : "lin160", p.M, p.N, p.K, o.res ? 1 : 0, p.geglu, p.ln_c ? 1 : 0);
-      const double bytes = 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * outC * (o.res ? 2.0 : 1.0));
-      emit([p, stream](hipStream_t s) { LAUNCH_OK(nr_launch_lin160(&p, stream, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
-      op_tap("lin160", out);
-      return out;
-    }
-    {
-      const double in_elems = (double)x0.rows() * (p.c0 + p.c1);   // every input element is needed at least once
-      const double bytes = 2.0 * (in_elems + (double)p.N * p.K + (double)p.M * outC + (o.res ? (double)p.M * outC : 0.0));
-      char d[160];
-      snprintf(d, sizeof(d), "igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0);
-      // split-K slabs (small-M / huge-K layers): scratch with the lifetime of this launch
-      const size_t wsb = nr_igemm_workspace_bytes(&p);
-      float* ws = nullptr;
-      std::shared_ptr<Buf> wsbuf;
-      if (wsb) { wsbuf = new_tmp(wsb); ws = at<float>(wsbuf->off); }
-      emit([p, ws](hipStream_t s) { LAUNCH_OK(nr_launch_igemm(&p, ws, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
-      if (wsb) last_op_launches(2);          // split-K: the igemm + its reduce kernel
-      op_tap(ksize == 3 ? "conv3" : (p.ln_c ? "lngemm" : "gemm"), out);
-    }
-    return out;
-  }
-  Act linear(const Act& x, const bf16* w, int N, const GemmOpt& o) { return conv(x, nullptr, w, N, 1, 1, 0, o); }
-
-  Act groupnorm(const Act& x0, const Act* x1, const std::string& prefix, float eps, int silu) {
-    const int C = x0.C + (x1 ? x1->C : 0);
-    const float* gamma = w_f32(prefix + ".weight", C);
-    const float* beta = w_f32(prefix + ".bias", C);
-    const int hw = x0.H * x0.W, groups = cfg.norm_num_groups;
-    const int plan_nimg = det_batch ? (int)det_rows(x0.nimg) : 0;
-    int nch = 0;
-    (void)nr_gn_workspace_floats(plan_nimg > 0 ? plan_nimg : x0.nimg, hw, groups, nullptr, &nch);   // chunking as the launcher will choose it
-    const int nfl = x0.nimg * (nch * groups * 2 + groups * 2);
-    auto ws = new_tmp((size_t)nfl * sizeof(float));
-    Act out = new_act(x0.nimg, x0.H, x0.W, C);
-    NrGnParams p = nr_gn_params(x0.ptr, x0.C, x0.ld, x1 ? x1->ptr : nullptr, x1 ? x1->C : 0, x1 ? x1->ld : 0, x0.nimg, hw, groups, gamma, beta, eps, silu,
-                                at<float>(ws->off), out.ptr, out.ld);
-    p.plan_nimg = plan_nimg;
-    if (getenv("NR_OP_TAPS") && keep_all && !x1) {     // debug: what the GroupNorm's input looked like when it ran
-      Act snap = new_act(x0.nimg, x0.H, x0.W, x0.C);
-      const bf16* src = x0.ptr; bf16* dst = snap.ptr; const size_t nb = (size_t)x0.rows() * x0.C * sizeof(bf16);
-      if (x0.ld == x0.C) {
-        emit([=](hipStream_t s) {
-          const long long n16 = (long long)(nb / 16);
-          hipLaunchKernelGGL(copy16_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, n16);
-        });
-        op_tap("gn_input_snapshot", snap);
-      }
-    }
-    emit([p](hipStream_t s) { NrGnParams q = p; LAUNCH_OK(nr_launch_groupnorm(&q, s)); }, NR_PROF_GROUPNORM,
-         8.0 * (double)x0.rows() * C, 2.0 * 2.0 * (double)x0.rows() * C,
-         "groupnorm nimg=" + std::to_string(x0.nimg) + " hw=" + std::to_string(x0.H * x0.W) + " C=" + std::to_string(C));
-    { NrGnParams q = p; last_op_launches(nr_groupnorm_launches(&q)); }
-    op_tap("gn", out);
-    return out;
-  }
-
-  Act layernorm(const Act& x, const std::string& prefix, const float* pe, int pe_F) {
-    const float* g = w_f32(prefix + ".weight", x.C);
-    const float* b = w_f32(prefix + ".bias", x.C);
-    Act out = new_act(x.nimg, x.H, x.W, x.C);
-    const bf16* xp = x.ptr; bf16* op = out.ptr;
-    const int ldx = x.ld, ldo = out.ld, M = (int)x.rows(), C = x.C, hw = x.H * x.W;
-    emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_layernorm(xp, ldx, op, ldo, M, C, g, b, 1e-5f, pe, hw, pe_F, s)); },
-         NR_PROF_LAYERNORM, 8.0 * (double)M * C, 2.0 * 2.0 * (double)M * C,
-         "layernorm M=" + std::to_string(M) + " C=" + std::to_string(C));
-    op_tap("ln", out);
-    return out;
-  }
-
-  // mode 0 spatial self (qkv fused [M][3C]); 1 cross (q [M][C], kv [B2*ctx][2C]); 2 temporal self (qkv fused)
-  Act attention(int mode, const Act& q, const Act* kv, int C, int heads, int causal = 0) {
-    Act out = new_act(q.nimg, q.H, q.W, C);
-    const NrAttnParams p = nr_attn_params(mode, q.ptr, kv ? kv->ptr : nullptr, out.ptr, q.ld, kv ? kv->ld : 0, out.ld, q.nimg, q.H * q.W, ctx_len, C, heads, F,
-                                          F, causal, (attn_fp8 && mode != 2) ? 1 : 0);
-    {
-      const double flops = 4.0 * (double)p.nbatch * p.heads * (double)p.Lq * p.Lk * p.d;
-      const double kvrows = mode == 1 ? (double)(p.nbatch / p.kv_div) * p.Lk : (double)p.nbatch * p.Lk;
-      const double bytes = 2.0 * ((double)p.nbatch * p.Lq * C * 2.0 + kvrows * C * 2.0);   // q + out + k + v
-      char d[160];
-      snprintf(d, sizeof(d), "attention mode=%d nbatch=%d heads=%d d=%d Lq=%d Lk=%d", mode, p.nbatch, p.heads, p.d, p.Lq, p.Lk);
-      emit([p](hipStream_t s) { LAUNCH_OK(nr_launch_attention(&p, s)); }, NR_PROF_ATTENTION, flops, bytes, d);
-      op_tap(mode == 2 ? "tattn" : (mode == 1 ? "xattn" : "sattn"), out);
-    }
-    return out;
-  }
-
-  // ------------------------------------------------------------------ module builders
-  struct TembSlot { std::string prefix; int off, C; };
-  std::vector<TembSlot> temb_slots;   // filled by a pre-pass over the topology
-  float* temb_all = nullptr;          // [B2][temb_total]
-  const float* temb_for(const std::string& prefix, int C) {
-    for (auto& s : temb_slots) if (s.prefix == prefix) {
-      if (s.C != C) throw NrError(NR_ERR_STATE, "temb slot size mismatch for " + prefix);
-      return temb_all + s.off;
-    }
-    throw NrError(NR_ERR_STATE, "no temb slot for " + prefix);
-  }
-
-  // parameter names of one residual block: diffusers-style (animatediff) or sgm-style (openaimodel.py:255-312)
-  struct ResKeys { std::string norm1, conv1, norm2, conv2, shortcut; };
-  ResKeys res_keys(const std::string& pre) const {
-    if (cfg.kind == NR_KIND_SGM_UNET)
-      return ResKeys{pre + ".in_layers.0", pre + ".in_layers.2", pre + ".out_layers.0", pre + ".out_layers.3", pre + ".skip_connection"};
-    if (cfg.kind == NR_KIND_VAE_DECODER || cfg.kind == NR_KIND_VAE_ENCODER)   // sgm/modules/diffusionmodules/model.py:94-151
-      return ResKeys{pre + ".norm1", pre + ".conv1", pre + ".norm2", pre + ".conv2", pre + ".nin_shortcut"};
-    return ResKeys{pre + ".norm1", pre + ".conv1", pre + ".norm2", pre + ".conv2", pre + ".conv_shortcut"};
-  }
-
-  // ResnetBlock3D.forward (resnet.py:182-212) == sgm ResBlock._forward (openaimodel.py:328-354, no up/down, no
-  // scale-shift): GN+SiLU -> conv (+bias +Linear(SiLU(emb))) -> GN+SiLU -> conv (+bias) + skip(x).
-  // x1 = skip tensor for the decoder concat.
-  Act resnet(const Act& x0, const Act* x1, const std::string& pre, int Cout) {
-    const ResKeys k = res_keys(pre);
-    const int Cin = x0.C + (x1 ? x1->C : 0);
-    const int hw = x0.H * x0.W;
-    Act h = groupnorm(x0, x1, k.norm1, cfg.norm_eps, 1);
-    GemmOpt o1;
-    o1.bias = w_f32(k.conv1 + ".bias", Cout);
-    if (cfg.kind != NR_KIND_VAE_DECODER && cfg.kind != NR_KIND_VAE_ENCODER) {   // the VAE's ResnetBlock runs with temb = None (model.py:138-139,727)
-      o1.rowvec = temb_for(pre, Cout); o1.rowvec_div = F * hw; o1.rowvec_ld = temb_total;
-    }
-    const bool ti1 = conv_tap_inner() && Cin % 64 == 0, ti2 = conv_tap_inner() && Cout % 64 == 0;
-    o1.tap_inner = ti1 ? 1 : 0;
-    Act h1 = conv(h, nullptr, ti1 ? w_conv3_tap_inner(k.conv1 + ".weight", Cout, Cin) : w_conv3(k.conv1 + ".weight", Cout, Cin), Cout, 3, 1, 0, o1);
-    h = Act();
-    Act h2 = groupnorm(h1, nullptr, k.norm2, cfg.norm_eps, 1);
-    h1 = Act();
-    Act sc;
-    const bool shortcut = has(k.shortcut + ".weight");
-    if (shortcut) {
-      GemmOpt os; os.bias = w_f32(k.shortcut + ".bias", Cout);
-      sc = conv(x0, x1, w_linear(k.shortcut + ".weight", Cout, Cin), Cout, 1, 1, 0, os);
+void nr_net::ensure_streams() {
+  if (!own_stream) {
+    // (a lowest-priority stream for SparseCtrl, meant to fill only the CUs the U-Net leaves free, measured neutral: 16.56 vs 16.53 frames/s)
+    // NR_STREAM_PRIO=1 (A/B): SparseCtrl on the lowest-priority queue, the U-Net on the highest, so that under the grouped schedule the
+    // pending group only takes the CUs the U-Net's small launches leave free
+    static const bool prio = env_is_1("NR_STREAM_PRIO");
+    if (prio) {
+      int lo = 0, hi = 0;
+      HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi));     // lo = numerically greatest = lowest priority
+      HIP_OK(hipStreamCreateWithPriority(&own_stream, hipStreamNonBlocking, cfg.kind == NR_KIND_SPARSECTRL ? lo : hi));
     } else {
-      if (x1 || Cin != Cout) throw NrError(NR_ERR_MISSING_WEIGHT, "missing state-dict entry: " + k.shortcut + ".weight");
-      sc = x0;
+      HIP_OK(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
     }
-    GemmOpt o2;
-    o2.bias = w_f32(k.conv2 + ".bias", Cout);
-    o2.res = &sc;
-    o2.tap_inner = ti2 ? 1 : 0;
-    Act out = conv(h2, nullptr, ti2 ? w_conv3_tap_inner(k.conv2 + ".weight", Cout, Cout) : w_conv3(k.conv2 + ".weight", Cout, Cout), Cout, 3, 1, 0, o2);
-    tap(pre, out);
-    return out;
+    HIP_OK(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
+    HIP_OK(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
+    HIP_OK(hipEventCreateWithFlags(&ev_adds, hipEventDisableTiming));
+    for (auto& e : ev_slot) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
-
-
-  // LayerNorm (+ temporal PE) -> Linear as one launch (LN folded into the igemm) or, with NR_NO_LN_FUSE=1, as the
-  // layernorm kernel followed by a plain igemm (A/B and fallback path; same results to rounding).
-  // Neach: rows of each stacked matrix (geglu: the inner width, the matrix has 2*Neach rows).
-  Act ln_linear(const Act& x, const std::string& ln, const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys,
-                int Neach, bool geglu, int act, bool temporal_pe) {
-    static const char* mode = getenv("NR_LN_FUSE");            // "0" never, "1" always, unset: per shape
-    const int K = x.C;
-    const int N = (geglu ? 2 * Neach : Neach) * (int)wkeys.size();
-    // Every n-tile block of the fused GEMM recomputes the row statistics (~1-2 us per block round), so the fusion pays
-    // when the LayerNorm launch it removes costs more than that: small M (latency-bound LN) or narrow N.  Measured on
-    // BASELINE config 2 (profiles/README.md): wide GEMMs at the 32x32 / 16x16 levels are faster with the separate LN.
-    const long long M = det_rows(x.rows());
-    bool fuse = !((M >= 8192 && N >= 4 * K) || (M >= 32768 && N >= 3 * K));
-    // K = 320 on >= 4096 rows runs on the row-panel kernel (rowpanel.hip): the row statistics come from the register panel once
-    // per workgroup, so the folded LayerNorm is free there
-    static const bool rowpanel_on = !(getenv("NR_ROWPANEL") && getenv("NR_ROWPANEL")[0] == '0');
-    if (rowpanel_on && K == 320 && M >= 4096) fuse = true;
-    // K = 640 wide projections (N >= 3 K) on 2048 .. 8192 rows run on the register-panel form of lin160.hip: statistics from the
-    // register-resident rows once per workgroup, so the fold is free there too (and the LayerNorm launch goes)
-    if (!temporal_pe && !act && nr_lin160_panel_rule((int)M, N, K) && x.rows() % 128 == 0 && x.ld % 8 == 0) fuse = true;
-    if (mode) fuse = mode[0] == '1';
-    GemmOpt o;
-    o.geglu = geglu ? 1 : 0; o.act = act;
-    if (fuse) {
-      const LnW lw = w_ln_linear(wkeys, bkeys, ln, Neach, K, geglu);
-      o.bias = lw.b; o.ln_c = lw.c;
-      if (temporal_pe) {
-        o.rowvec = pe_projection(wkeys, Neach, K, cfg.motion_pe_max_len);
-        o.rowvec_div = x.H * x.W; o.rowvec_ld = N; o.rowvec_mod = F;
-      }
-      return linear(x, lw.w, N, o);
-    }
-    Act n = layernorm(x, ln, temporal_pe ? pe_table(K, cfg.motion_pe_max_len) : nullptr, temporal_pe ? F : 1);
-    const bf16* w;
-    if (geglu) {
-      w = w_geglu(wkeys[0], Neach, K);
-      if (!bkeys.empty()) o.bias = b_geglu(bkeys[0], Neach);
-    } else if (wkeys.size() > 1) {
-      w = w_linear_cat(wkeys, Neach, K);
-      if (!bkeys.empty()) o.bias = b_cat(bkeys, Neach);
-    } else {
-      w = w_linear(wkeys[0], Neach, K);
-      if (!bkeys.empty()) o.bias = w_f32(bkeys[0], Neach);
-    }
-    return linear(n, w, N, o);
+}
+void nr_net::run_context(hipStream_t s) {
+  if (!ctx_dirty) return;
+  for (auto& op : ctx_ops) op(s);
+  ctx_dirty = false;
+}
+void nr_net::set_timesteps(hipStream_t s, const float* timesteps) {
+  TimestepVals tv;
+  for (int i = 0; i < NR_MAX_BATCH; ++i) tv.v[i] = i < B2 ? timesteps[i] : 0.f;
+  hipLaunchKernelGGL(set_timesteps_kernel, dim3(1), dim3(64), 0, s, t_dev, tv, B2);
+}
+// launch ops [begin, end) of segment `seg` on `s` as a (re)captured hipGraph
+void nr_net::launch_segment(hipStream_t s, int seg) {
+  const size_t begin = seg == 0 ? 0 : (seg == 1 ? split_op : split_op2);
+  const size_t end = seg == 0 ? split_op : (seg == 1 ? split_op2 : ops.size());
+  if (begin >= end) return;
+  auto& cache = gcache[seg];
+  // key = the IO fields this segment's kernels read: only segment 1 (the ControlNet-residual adds) sees the residual pointers, so the
+  // encoder / decoder graphs of the U-Net are shared by every (slot, phase) of the grouped SparseCtrl schedule instead of being
+  // captured once per residual-buffer set
+  IO key = io;
+  if (seg != 1 && cfg.kind == NR_KIND_UNET3D) {
+    std::memset((void*)key.down_res, 0, sizeof(key.down_res));
+    key.mid_res = nullptr;
+    key.has_res = 0;
   }
-
-  // FeedForward(GEGLU) + residual, in place on t (motion_module_new.py:441-471,497-518)
-  void feed_forward(Act& t, const std::string& ln, const std::string& pre) {
-    const int C = t.C, inner = 4 * C;
-    Act hmid = ln_linear(t, ln, {pre + ".net.0.proj.weight"}, {pre + ".net.0.proj.bias"}, inner, true, 0, false);
-    GemmOpt o2; o2.bias = w_f32(pre + ".net.2.bias", C); o2.res = &t; o2.out = &t;
-    linear(hmid, w_linear(pre + ".net.2.weight", C, inner), C, o2);
+  GraphSlot* hit = nullptr;
+  for (auto& g : cache) if (g.exec && g.io == key) { hit = &g; break; }
+  if (!hit) {
+    if ((int)cache.size() >= NR_GRAPH_SLOTS) {              // evict the least recently used graph
+      size_t lru = 0;
+      for (size_t i = 1; i < cache.size(); ++i) if (cache[i].used < cache[lru].used) lru = i;
+      HIP_OK(hipDeviceSynchronize());                        // it may still be executing, on this or on another stream
+      (void)hipGraphExecDestroy(cache[lru].exec);
+      cache.erase(cache.begin() + lru);
+    }
+    hipGraph_t g = nullptr;
+    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    try {
+      for (size_t i = begin; i < end; ++i) ops[i](s);
+    } catch (...) {
+      (void)hipStreamEndCapture(s, &g);
+      if (g) (void)hipGraphDestroy(g);
+      throw;
+    }
+    HIP_OK(hipStreamEndCapture(s, &g));
+    hipGraphExec_t ex = nullptr;
+    hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess) throw NrError(NR_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    GraphSlot gs; gs.io = key; gs.exec = ex;
+    cache.push_back(gs);
+    hit = &cache.back();
   }
+  hit->used = ++gclock;
+  HIP_OK(hipGraphLaunch(hit->exec, s));
+}
 
-  // The block's LAST FeedForward and the transformer's proj_out as one GEMM (w_fold_ff_proj): x + proj_out(t + FF(t)) =
-  // x + bc + [t | g] Wc^T with g = GEGLU(net.0(LN(t))).  Removes a launch and the write + read of the post-FF residual stream.
-  // Needs C % 64 == 0 (the operand switch falls on a k-tile boundary); NR_FOLD_PROJ_OUT=0 keeps the two GEMMs.
-  bool fold_proj_out(int C) const {
-    static const bool off = getenv("NR_FOLD_PROJ_OUT") && getenv("NR_FOLD_PROJ_OUT")[0] == '0';
-    return !off && C % 64 == 0;
-  }
-  Act feed_forward_proj_out(const Act& x, Act& t, const std::string& ln, const std::string& ff, const std::string& pre) {
-    const int C = t.C, inner = 4 * C;
-    if (!fold_proj_out(C)) {
-      feed_forward(t, ln, ff);
-      GemmOpt op; op.bias = w_f32(pre + ".proj_out.bias", C); op.res = &x;
-      return linear(t, w_linear(pre + ".proj_out.weight", C, C), C, op);
-    }
-    if (nr_ff_fused_eligible(C, det_rows(t.rows())) && t.ld == C && x.ld == C) {
-      // C = 320, >= 4096 rows: LayerNorm + GEGLU projection + the folded GEMM in ONE launch (ffpanel.hip); the 4C-wide hidden activation
-      // stays in registers; LayerNorm is applied to the register panel.  The weights travel as one pre-arranged stage stream.
-      check_shape(ff + ".net.0.proj.weight", need(ff + ".net.0.proj.weight"), {2 * inner, C});
-      const float* b1 = b_geglu(ff + ".net.0.proj.bias", inner);
-      const float* gamma = w_f32(ln + ".weight", C);
-      const float* beta = w_f32(ln + ".bias", C);
-      const std::string sname = "ffs:" + ff + ".net.0.proj.weight|" + ff + ".net.2.weight|" + ff + ".net.2.bias|" + pre + ".proj_out.weight|" + pre +
-                                ".proj_out.bias";
-      // the two matrices the stream is packed from are only its inputs: the fused launch never reads them, so they are freed again
-      // (they neither stay resident nor travel in the exported arena); the folded bias stays
-      bool made = false, had_w1 = false;
-      const bf16* stream = (const bf16*)packed(sname, nr_ff_stream_bytes(C), [&](void* d) {
-        had_w1 = dev.count("geglu:" + ff + ".net.0.proj.weight") != 0;
-        const bf16* w1 = w_geglu(ff + ".net.0.proj.weight", inner, C);
-        const FoldW fwm = w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C, true);
-        LAUNCH_OK(nr_launch_ff_stream_pack(w1, fwm.w, (bf16*)d, nullptr));
-        made = true;
-      });
-      if (made) {
-        if (!had_w1) drop("geglu:" + ff + ".net.0.proj.weight");
-        drop("foldw:" + pre + ".proj_out.weight|" + pre + ".proj_out.bias|" + ff + ".net.2.weight|" + ff + ".net.2.bias");
-      }
-      const FoldW fw = w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C, false);
-      Act out = new_act(x.nimg, x.H, x.W, C);
-      const bf16* tp = t.ptr; const bf16* xp = x.ptr; bf16* op = out.ptr;
-      const int M = (int)t.rows();
-      const float* bc = fw.b;
-      char d[160];
-      snprintf(d, sizeof(d), "ff_fused M=%d C=%d (LN + GEGLU 8C + folded net.2|proj_out 5C)", M, C);
-      const int norot = det_batch ? 1 : 0;
-      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_ff_fused(tp, C, xp, C, op, C, M, stream, gamma, beta, b1, bc, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
-           2.0 * M * (double)C * (8.0 * C + 5.0 * C), 2.0 * (3.0 * M * (double)C + 13.0 * C * (double)C), d);
-      op_tap("ff_fused", out);
-      return out;
-    }
-    Act g = ln_linear(t, ln, {ff + ".net.0.proj.weight"}, {ff + ".net.0.proj.bias"}, inner, true, 0, false);
-    const FoldW fw = w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C);
-    GemmOpt op; op.bias = fw.b; op.res = &x;
-    return conv(t, &g, fw.w, C, 1, 1, 0, op);
-  }
+void nr_net::run_eager(hipStream_t s, const float* timesteps) {
+  begin(s, timesteps);
+  for (auto& op : ops) op(s);
+}
+// graph mode: the engine's own stream, fenced behind everything the caller enqueued so far (readers of the buffers, staged inputs)
+hipStream_t nr_net::begin_fenced(hipStream_t caller, const float* timesteps) {
+  HIP_OK(hipEventRecord(ev_in, caller));
+  HIP_OK(hipStreamWaitEvent(own_stream, ev_in, 0));
+  begin(own_stream, timesteps);
+  return own_stream;
+}
 
-  // Exact classifier-free-guidance de-duplication (U-Net only, cfg_dup): the pipeline feeds cat([latents] * 2) with ONE timestep
-  // (pipeline_neuroclips.py:435), so the two halves of the batch are identical until the first cross-attention reads the (different) text
-  // contexts: conv_in, down_blocks[0].resnets[0] and norm / proj_in / norm1 / attn1 of down_blocks[0].attentions[0] (attention.py:256-280) are
-  // evaluated on B2 / 2 samples and broadcast.  Not in deterministic-batch mode (its plan unit is the CFG pair) and not with debug taps.
-  bool cfg_dedup_active() const {
-    static const bool off = getenv("NR_CFG_DEDUP") && getenv("NR_CFG_DEDUP")[0] == '0';      // A/B switch
-    return !off && cfg_dup && cfg.kind == NR_KIND_UNET3D && B2 % 2 == 0 && B2 <= 64 && !det_batch && !keep_all && cfg.down_block_has_attn[0];
-  }
-  // [h; h]: the half-batch activation repeated for the second half of the batch (one gather launch)
-  Act expand_cfg(const Act& h) {
-    if (h.ld != h.C) throw NrError(NR_ERR_STATE, "expand_cfg: strided activation");
-    const int Bh = B2 / 2;
-    Act f = new_act(h.nimg * 2, h.H, h.W, h.C);
-    const long long fe = (long long)(h.nimg / Bh) * h.H * h.W * h.C;      // elements of one sample
-    const bf16* sp = h.ptr; bf16* dp = f.ptr; const int b2n = B2;
-    std::vector<int> mp(B2);
-    for (int i = 0; i < B2; ++i) mp[i] = i % Bh;
-    emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_frame_gather(sp, dp, 1, Bh, b2n, fe, mp.data(), s)); }, NR_PROF_OTHER, 0.0, 2.0 * 3.0 * (double)h.rows() * h.C,
-         "cfg broadcast rows=" + std::to_string(h.rows()) + " C=" + std::to_string(h.C));
-    return f;
-  }
-
-  // Transformer3DModel.forward (attention.py:95-142) with one BasicTransformerBlock (:256-300); also sgm
-  // SpatialTransformer.forward (sgm/modules/attention.py:702-723) with `depth` BasicTransformerBlocks (:551-572):
-  // same arithmetic and parameter names (proj_in/out are nn.Linear there: same [C][C] matrix).
-  // cfg_half: x holds the first half of the batch only (cfg_dedup_active); t and x are broadcast behind the self-attention, the result is full-batch;
-  // *x_full receives the broadcast input (the caller's skip connection)
-  Act spatial_transformer(const Act& x_in, const Act& ctx_bf, const std::string& pre, int depth = 1, bool cfg_half = false, Act* x_full = nullptr) {
-    Act x = x_in;
-    const int C = x.C;
-    const int heads = cfg.num_head_channels > 0 ? C / cfg.num_head_channels : cfg.num_heads;
-    Act hn = groupnorm(x, nullptr, pre + ".norm", 1e-6f, 0);
-    GemmOpt oi; oi.bias = w_f32(pre + ".proj_in.bias", C);
-    Act t = linear(hn, w_linear(pre + ".proj_in.weight", C, C), C, oi);
-    hn = Act();
-    for (int dd = 0; dd < depth; ++dd) {
-      const std::string b = pre + ".transformer_blocks." + std::to_string(dd);
-      {  // self-attention
-        Act qkv = ln_linear(t, b + ".norm1", {b + ".attn1.to_q.weight", b + ".attn1.to_k.weight", b + ".attn1.to_v.weight"}, {}, C, false, 0, false);
-        Act a = attention(0, qkv, nullptr, C, heads);
-        qkv = Act();
-        GemmOpt oo; oo.bias = w_f32(b + ".attn1.to_out.0.bias", C); oo.res = &t; oo.out = &t;
-        linear(a, w_linear(b + ".attn1.to_out.0.weight", C, C), C, oo);
-      }
-      if (cfg_half && dd == 0) {      // from here on the two CFG halves differ (their text contexts do)
-        t = expand_cfg(t);
-        x = expand_cfg(x);
-        if (x_full) *x_full = x;
-      }
-      if (cfg.kind != NR_KIND_SGM_UNET && !attn_fp8 && t.ld == C && nr_xattn_fused_eligible(C, heads, ctx_len, x.H * x.W, det_rows(t.rows()))) {
-        // C = 320, 8 heads, <= 80 context tokens, >= 4096 rows: the whole cross-attention block (LayerNorm, q projection, attention on the cached
-        // K | V of the clip, to_out + residual) in ONE launch that updates t in place (xattn.hip); q and the attention output never reach HBM
-        GemmOpt ok;
-        building_ctx = true;      // K|V of the context + their per-head LDS images: recomputed only when the context changes
-        Act kv = new_act_persistent(ctx_bf.nimg, ctx_bf.H, ctx_bf.W, 2 * C);
-        ok.out = &kv;
-        linear(ctx_bf, w_linear_cat({b + ".attn2.to_k.weight", b + ".attn2.to_v.weight"}, C, cfg.cross_attention_dim), 2 * C, ok);
-        const int nctx = (int)(ctx_bf.rows() / ctx_len);      // ctx_bf is ONE "image" of B2 * ctx_len token rows
-        Act kvs = new_act_persistent(nctx, 1, 1, (int)(nr_xattn_kvstream_bytes(1) / sizeof(bf16)));
-        {
-          const bf16* kvp = kv.ptr; bf16* kvsp = kvs.ptr; const int ldkv = kv.ld, Lk = ctx_len;
-          emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattn_kv_pack(kvp, ldkv, Lk, nctx, kvsp, s)); });
-        }
-        building_ctx = false;
-        ctx_persist.push_back(kv);
-        ctx_persist.push_back(kvs);
-        for (const char* wn : {".attn2.to_q.weight", ".attn2.to_out.0.weight"}) check_shape(b + wn, need(b + wn), {C, C});
-        const std::string sname = "xas:" + b + ".attn2.to_q.weight|" + b + ".attn2.to_out.0.weight";
-        // the two Linear matrices are only the inputs of the packed stream: freed again once it exists (unless another plan made them)
-        bool had_q = true, had_o = true;
-        const bf16* wstream = (const bf16*)packed(sname, nr_xattn_wstream_bytes(), [&](void* d) {
-          had_q = dev.count("lin:" + b + ".attn2.to_q.weight") != 0; had_o = dev.count("lin:" + b + ".attn2.to_out.0.weight") != 0;
-          const bf16* wq = w_linear(b + ".attn2.to_q.weight", C, C);
-          const bf16* wo = w_linear(b + ".attn2.to_out.0.weight", C, C);
-          LAUNCH_OK(nr_launch_xattn_w_pack(wq, wo, (bf16*)d, nullptr));
-        });
-        if (!had_q) drop("lin:" + b + ".attn2.to_q.weight");
-        if (!had_o) drop("lin:" + b + ".attn2.to_out.0.weight");
-        const float* gamma = w_f32(b + ".norm2.weight", C);
-        const float* beta = w_f32(b + ".norm2.bias", C);
-        const float* bo = w_f32(b + ".attn2.to_out.0.bias", C);
-        bf16* tp = t.ptr; const bf16* kvsp = kvs.ptr;
-        const int nimg = t.nimg, hwx = x.H * x.W, ipc = F, Lk = ctx_len;
-        const double M = (double)t.rows();
-        char d[160];
-        snprintf(d, sizeof(d), "xattn_fused M=%d C=%d Lk=%d (LN, q, context attention, to_out + residual)", (int)t.rows(), C, Lk);
-        const int norot = det_batch ? 1 : 0;
-        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattn_fused(tp, nimg, hwx, ipc, nctx, Lk, wstream, kvsp, gamma, beta, bo, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
-             2.0 * M * C * 2.0 * C + 4.0 * M * (double)Lk * C, 2.0 * (2.0 * M * C + 2.0 * C * (double)C), d);
-        op_tap("xattn_fused", t);
-      } else if (cfg.kind != NR_KIND_SGM_UNET && !attn_fp8 && t.ld == C && nr_xattnw_eligible(C, heads, ctx_len, x.H * x.W, det_rows(t.rows()))) {
-        // C = 640 / 1280, 8 heads, <= 80 context tokens: LayerNorm (folded), the q projection and the attention on the cached K | V of the row's
-        // context in ONE launch per block (xattnw.hip); q never reaches HBM.  to_out + residual stays the GEMM below.
-        GemmOpt ok;
-        building_ctx = true;      // K|V of the context + their fragment images: recomputed only when the context changes
-        Act kv = new_act_persistent(ctx_bf.nimg, ctx_bf.H, ctx_bf.W, 2 * C);
-        ok.out = &kv;
-        linear(ctx_bf, w_linear_cat({b + ".attn2.to_k.weight", b + ".attn2.to_v.weight"}, C, cfg.cross_attention_dim), 2 * C, ok);
-        const int nctx = (int)(ctx_bf.rows() / ctx_len);
-        Act kvs = new_act_persistent(1, 1, 1, (int)(nr_xattnw_kvstream_bytes(C, nctx) / sizeof(bf16)));
-        {
-          const bf16* kvp = kv.ptr; bf16* kvsp = kvs.ptr; const int ldkv = kv.ld, Lk = ctx_len, Cc = C;
-          emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattnw_kv_pack(kvp, ldkv, Lk, nctx, Cc, kvsp, s)); });
-        }
-        building_ctx = false;
-        ctx_persist.push_back(kv);
-        ctx_persist.push_back(kvs);
-        const std::string nrm = b + ".norm2", wq = b + ".attn2.to_q.weight";
-        const std::string lnw_name = "lnw:" + nrm + "|" + wq + "|";
-        const std::string sname = "xaws:" + nrm + "|" + wq;
-        bool had = true;       // the folded [C][C] matrix is only the input of the packed stream
-        const bf16* wstream = (const bf16*)packed(sname, nr_xattnw_wstream_bytes(C), [&](void* d) {
-          had = dev.count(lnw_name) != 0;
-          const LnW lwm = w_ln_linear({wq}, {}, nrm, C, C, false, true);
-          LAUNCH_OK(nr_launch_xattnw_w_pack(lwm.w, C, (bf16*)d, nullptr));
-        });
-        if (!had) drop(lnw_name);
-        const std::string tname = "xawt:" + nrm + "|" + wq;
-        const float* table = (const float*)packed(tname, nr_xattnw_table_bytes(C), [&](void* d) {
-          const LnW lw = w_ln_linear({wq}, {}, nrm, C, C, false, false);
-          LAUNCH_OK(nr_launch_xattnw_table_pack(lw.c, lw.b, C, (float*)d, nullptr));
-        });
-        if (dry) (void)w_ln_linear({wq}, {}, nrm, C, C, false, false);      // shape checks in the sizing pass too
-        Act a = new_act(t.nimg, t.H, t.W, C);
-        const bf16* tp = t.ptr; bf16* ap = a.ptr; const bf16* kvsp = kvs.ptr;
-        const int nimg = t.nimg, hwx = x.H * x.W, ipc = F, Lk = ctx_len, Cc = C;
-        const double M = (double)t.rows();
-        char d[160];
-        snprintf(d, sizeof(d), "xattn_head M=%d C=%d Lk=%d (LN folded, q of 160 columns, context attention)", (int)t.rows(), C, Lk);
-        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattnw(tp, ap, nimg, hwx, ipc, nctx, Lk, Cc, wstream, kvsp, table, 1e-5f, s)); }, NR_PROF_IGEMM,
-             2.0 * M * C * (double)C + 4.0 * M * (double)Lk * C, 2.0 * (2.0 * M * C + C * (double)C), d);
-        op_tap("xattn_head", a);
-        GemmOpt oo; oo.bias = w_f32(b + ".attn2.to_out.0.bias", C); oo.res = &t; oo.out = &t;
-        linear(a, w_linear(b + ".attn2.to_out.0.weight", C, C), C, oo);
-      } else {  // cross-attention on the context (attention.py:100: context repeated per frame)
-        Act q = ln_linear(t, b + ".norm2", {b + ".attn2.to_q.weight"}, {}, C, false, 0, false);
-        GemmOpt ok;
-        building_ctx = true;      // K|V of the context: recomputed only when the context changes
-        Act kv = new_act_persistent(ctx_bf.nimg, ctx_bf.H, ctx_bf.W, 2 * C);
-        ok.out = &kv;
-        linear(ctx_bf, w_linear_cat({b + ".attn2.to_k.weight", b + ".attn2.to_v.weight"}, C, cfg.cross_attention_dim), 2 * C, ok);
-        building_ctx = false;
-        ctx_persist.push_back(kv);
-        Act a = attention(1, q, &kv, C, heads);
-        q = Act(); kv = Act();
-        GemmOpt oo; oo.bias = w_f32(b + ".attn2.to_out.0.bias", C); oo.res = &t; oo.out = &t;
-        linear(a, w_linear(b + ".attn2.to_out.0.weight", C, C), C, oo);
-      }
-      if (dd + 1 < depth) feed_forward(t, b + ".norm3", b + ".ff");
-    }
-    Act out = feed_forward_proj_out(x, t, pre + ".transformer_blocks." + std::to_string(depth - 1) + ".norm3",
-                                    pre + ".transformer_blocks." + std::to_string(depth - 1) + ".ff", pre);
-    tap(pre, out);
-    return out;
-  }
-
-  // VanillaTemporalModule -> TemporalTransformer3DModel.forward (motion_module.py:134-158)
-  Act temporal_module(const Act& x, const std::string& pre0) {
-    const std::string pre = pre0 + ".temporal_transformer";
-    const int C = x.C, heads = cfg.motion_num_heads;
-    if (F > cfg.motion_pe_max_len)
-      throw NrError(NR_ERR_ARG, "video_length " + std::to_string(F) + " exceeds temporal_position_encoding_max_len " +
-                                    std::to_string(cfg.motion_pe_max_len));
-    Act hn = groupnorm(x, nullptr, pre + ".norm", 1e-6f, 0);
-    GemmOpt oi; oi.bias = w_f32(pre + ".proj_in.bias", C);
-    Act t = linear(hn, w_linear(pre + ".proj_in.weight", C, C), C, oi);
-    hn = Act();
-    const std::string b = pre + ".transformer_blocks.0";
-    for (int k = 0; k < cfg.motion_num_attention_blocks; ++k) {
-      const std::string ab = b + ".attention_blocks." + std::to_string(k);
-      if (nr_tattn_fused_eligible(C, heads, F, x.H * x.W, det_rows(t.rows())) && t.ld == C) {
-        // C = 320, F = 16 or 32: the whole block (LayerNorm + PE, q|k|v, F x F attention per pixel and head, to_out + residual) in ONE launch
-        // that updates t in place (tattn.hip); q|k|v and the attention output never reach HBM
-        const std::string nrm = b + ".norms." + std::to_string(k);
-        for (const char* wn : {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"}) check_shape(ab + wn, need(ab + wn), {C, C});
-        const std::string sname = "tas:" + ab + ".to_q.weight|" + ab + ".to_k.weight|" + ab + ".to_v.weight|" + ab + ".to_out.0.weight";
-        // the four Linear matrices are only the inputs of the packed stream: freed again once it exists (unless another plan made them)
-        bool had[4] = {true, true, true, true};
-        const char* wn[4] = {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"};
-        const bf16* stream = (const bf16*)packed(sname, nr_tattn_stream_bytes(), [&](void* d) {
-          const bf16* wm[4];
-          for (int i = 0; i < 4; ++i) { had[i] = dev.count("lin:" + ab + wn[i]) != 0; wm[i] = w_linear(ab + wn[i], C, C); }
-          LAUNCH_OK(nr_launch_tattn_stream_pack(wm[0], wm[1], wm[2], wm[3], (bf16*)d, nullptr));
-        });
-        for (int i = 0; i < 4; ++i) if (!had[i]) drop("lin:" + ab + wn[i]);
-        // gb[f][c] = LayerNorm bias + sinusoidal positional encoding of frame f (motion_module.py:225-243)
-        check_shape(nrm + ".bias", need(nrm + ".bias"), {C});
-        const std::string gname = "tagb:" + std::to_string(F) + ":" + nrm;
-        const float* gb = (const float*)cached(gname, [&]() {
-          const HostTensor& be = data_of(nrm + ".bias");
-          std::vector<float> h = sinusoid_table(F, C);
-          for (int pos = 0; pos < F; ++pos)
-            for (int i = 0; i < C; ++i) h[(size_t)pos * C + i] = be.data[i] + h[(size_t)pos * C + i];
-          return upload(gname, h.data(), h.size() * 4);
-        });
-        const float* gamma = w_f32(nrm + ".weight", C);
-        const float* bo = w_f32(ab + ".to_out.0.bias", C);
-        bf16* tp = t.ptr; const int nb2 = t.nimg / F, hw = x.H * x.W;
-        const double M = (double)t.rows();
-        char d[160];
-        snprintf(d, sizeof(d), "tattn_fused M=%d C=%d F=%d (LN+PE, q|k|v, attention, to_out + residual)", (int)t.rows(), C, F);
-        const int norot = det_batch ? 1 : 0;
-        const int Fn = F;
-        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_tattn_fused(tp, nb2, Fn, hw, stream, gamma, gb, bo, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
-             2.0 * M * C * 4.0 * C + 4.0 * (M / F) * heads * (double)F * F * (C / heads), 2.0 * (2.0 * M * C + 4.0 * C * (double)C), d);
-        op_tap("tattn_fused", t);
-        continue;
-      }
-      Act a;
-      if (nr_tattnw_eligible(C, heads, F, x.H * x.W, det_rows(t.rows())) && t.ld == C) {
-        // C = 640 / 1280, F = 16 or 32: LayerNorm + PE (folded), the q|k|v projection of one head and its F x F attention per (pixel group, head) in
-        // ONE launch (tattnw.hip); q|k|v never reach HBM.  to_out + residual stays the GEMM below.
-        const std::string nrm = b + ".norms." + std::to_string(k);
-        const std::vector<std::string> wk = {ab + ".to_q.weight", ab + ".to_k.weight", ab + ".to_v.weight"};
-        const float* rv = pe_projection(wk, C, C, cfg.motion_pe_max_len);
-        const std::string sname = "taws:" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
-        // the folded [3C][C] matrix is only the input of the packed stream: freed again once it exists (unless another plan made it)
-        const std::string lnw_name = "lnw:" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2] + "|";
-        bool had = true;
-        const bf16* stream = (const bf16*)packed(sname, nr_tattnw_stream_bytes(C), [&](void* d) {
-          had = dev.count(lnw_name) != 0;
-          const LnW lwm = w_ln_linear(wk, {}, nrm, C, C, false, true);
-          LAUNCH_OK(nr_launch_tattnw_stream_pack(lwm.w, C, (bf16*)d, nullptr));
-        });
-        if (!had) drop(lnw_name);
-        // the head-major epilogue table (LayerNorm-fold vectors + positional-encoding projections of the first F positions) the kernel stages
-        // through LDS: one per frame count a handle was planned with
-        const std::string tname = "tawe:" + std::to_string(cfg.motion_pe_max_len) + ":" + std::to_string(F) + ":" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
-        const float* table = (const float*)packed(tname, nr_tattnw_table_bytes(C, F), [&](void* d) {
-          const LnW lw = w_ln_linear(wk, {}, nrm, C, C, false, false);
-          LAUNCH_OK(nr_launch_tattnw_table_pack(lw.c, lw.b, rv, C, F, (float*)d, nullptr));
-        });
-        a = new_act(t.nimg, t.H, t.W, C);
-        const bf16* tp = t.ptr; bf16* ap = a.ptr;
-        const int nb2 = t.nimg / F, hw = x.H * x.W;
-        const double M = (double)t.rows();
-        char d[160];
-        snprintf(d, sizeof(d), "tattn_head M=%d C=%d F=%d (LN+PE folded, q|k|v of one head, FxF attention)", (int)t.rows(), C, F);
-        const int Fn = F;
-        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_tattnw(tp, ap, nb2, Fn, hw, C, stream, table, 1e-5f, s)); }, NR_PROF_IGEMM,
-             2.0 * M * C * 3.0 * C + 4.0 * (M / F) * heads * (double)F * F * (C / heads), 2.0 * (2.0 * M * C + 3.0 * C * (double)C), d);
-        op_tap("tattn_head", a);
-      } else {
-        // LayerNorm, then + pe[frame] (motion_module.py:212,277): both folded into the q|k|v GEMM
-        Act qkv = ln_linear(t, b + ".norms." + std::to_string(k), {ab + ".to_q.weight", ab + ".to_k.weight", ab + ".to_v.weight"}, {}, C,
-                            false, 0, true);
-        a = attention(2, qkv, nullptr, C, heads);
-      }
-      GemmOpt oo; oo.bias = w_f32(ab + ".to_out.0.bias", C); oo.res = &t; oo.out = &t;
-      linear(a, w_linear(ab + ".to_out.0.weight", C, C), C, oo);
-    }
-    Act out = feed_forward_proj_out(x, t, b + ".ff_norm", b + ".ff", pre);
-    tap(pre0, out);
-    return out;
-  }
-
-  // ------------------------------------------------------------------ topology
-  // enumerate resnets (prefix, Cout) in definition order: used for the batched time-embedding projection
-  void enumerate_resnets(std::vector<TembSlot>& out) const {
-    int off = 0;
-    auto add = [&](const std::string& p, int C) { out.push_back(TembSlot{p, off, C}); off += C; };
-    const int L = cfg.num_levels;
-    for (int i = 0; i < L; ++i)
-      for (int j = 0; j < cfg.layers_per_block; ++j)
-        add("down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), cfg.block_out_channels[i]);
-    add("mid_block.resnets.0", cfg.block_out_channels[L - 1]);
-    add("mid_block.resnets.1", cfg.block_out_channels[L - 1]);
-    if (cfg.kind == NR_KIND_UNET3D)
-      for (int i = 0; i < L; ++i)
-        for (int j = 0; j < cfg.layers_per_block + 1; ++j)
-          add("up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), cfg.block_out_channels[L - 1 - i]);
-  }
-
-  // ---------------------------------------------------------------------------------------------------
-  // sgm UNetModel (generative_models/sgm/modules/diffusionmodules/openaimodel.py:472; forward :816-853;
-  // construction order :640-807 fixes the input_blocks / output_blocks numbering used for the key names)
-  // ---------------------------------------------------------------------------------------------------
-  struct SgmLayout {
-    struct In { int idx; int kind; int level; int Cout; };          // kind 0 conv_in, 1 res(+attn), 2 downsample
-    struct Out { int idx; int level; int Cout; bool attn; bool up; };
-    std::vector<In> in;
-    std::vector<Out> out;
-  };
-  SgmLayout sgm_layout() const {
-    SgmLayout l;
-    const int L = cfg.num_levels;
-    int idx = 0;
-    l.in.push_back({idx++, 0, 0, cfg.block_out_channels[0]});
-    for (int lev = 0; lev < L; ++lev) {
-      for (int r = 0; r < cfg.layers_per_block; ++r) l.in.push_back({idx++, 1, lev, cfg.block_out_channels[lev]});
-      if (lev != L - 1) l.in.push_back({idx++, 2, lev, cfg.block_out_channels[lev]});
-    }
-    idx = 0;
-    for (int lev = L - 1; lev >= 0; --lev)
-      for (int i = 0; i <= cfg.layers_per_block; ++i)
-        l.out.push_back({idx++, lev, cfg.block_out_channels[lev], cfg.down_block_has_attn[lev] != 0,
-                         lev > 0 && i == cfg.layers_per_block});
-    return l;
-  }
-
-  void build_sgm() {
-    const int L = cfg.num_levels;
-    const int C0 = cfg.block_out_channels[0];
-    const int temb_dim = 4 * C0;
-    const int nimg = B2 * F;
-    if (F != 1) throw NrError(NR_ERR_ARG, "sgm UNetModel is a 2-D network: plan with frames = 1");
-    const SgmLayout lay = sgm_layout();
-    ctx_persist.clear(); ops.clear(); ctx_ops.clear(); op_meta.clear(); taps.clear(); arena.reset(); parena.reset();
-    ctx_dirty = true;
-    temb_slots.clear();
-    {
-      int off = 0;
-      auto add = [&](const std::string& p, int C) { temb_slots.push_back(TembSlot{p, off, C}); off += C; };
-      for (auto& b : lay.in) if (b.kind == 1) add("input_blocks." + std::to_string(b.idx) + ".0", b.Cout);
-      add("middle_block.0", cfg.block_out_channels[L - 1]);
-      add("middle_block.2", cfg.block_out_channels[L - 1]);
-      for (auto& b : lay.out) add("output_blocks." + std::to_string(b.idx) + ".0", b.Cout);
-      temb_total = off;
-    }
-    // ---- emb = time_embed(sinusoid(t)) + label_emb(y)  (openaimodel.py:836-841); every ResBlock then applies
-    // Linear(SiLU(emb)) (emb_layers, :283-289): batched into ONE launch ----
-    t_dev = new_scratch<float>(NR_MAX_BATCH);
-    float* sincos = new_scratch<float>((size_t)B2 * C0);
-    float* e1 = new_scratch<float>((size_t)B2 * temb_dim);
-    float* et = new_scratch<float>((size_t)B2 * temb_dim);
-    float* y1 = new_scratch<float>((size_t)B2 * temb_dim);
-    float* emb = new_scratch<float>((size_t)B2 * temb_dim);
-    temb_all = new_scratch<float>((size_t)B2 * temb_total);
-    {
-      const int adm = cfg.adm_in_channels;
-      const bf16* w1 = w_linear("time_embed.0.weight", temb_dim, C0);
-      const float* b1 = w_f32("time_embed.0.bias", temb_dim);
-      const bf16* w2 = w_linear("time_embed.2.weight", temb_dim, temb_dim);
-      const float* b2 = w_f32("time_embed.2.bias", temb_dim);
-      const bf16* wy1 = w_linear("label_emb.0.0.weight", temb_dim, adm);
-      const float* by1 = w_f32("label_emb.0.0.bias", temb_dim);
-      const bf16* wy2 = w_linear("label_emb.0.2.weight", temb_dim, temb_dim);
-      const float* by2 = w_f32("label_emb.0.2.bias", temb_dim);
-      std::vector<std::string> wk, bk;
-      for (auto& sl : temb_slots) {
-        wk.push_back(sl.prefix + ".emb_layers.1.weight"); bk.push_back(sl.prefix + ".emb_layers.1.bias");
-        check_shape(wk.back(), need(wk.back()), {sl.C, temb_dim});
-        check_shape(bk.back(), need(bk.back()), {sl.C});
-      }
-      const std::string wname = "tembw:sgm", bname = "tembb:sgm";
-      const bf16* wp = (const bf16*)cached(wname, [&]() {
-        std::vector<uint16_t> h((size_t)temb_total * temb_dim);
-        size_t o = 0;
-        for (auto& k : wk) { const HostTensor& t = data_of(k); for (float f : t.data) h[o++] = f2bf_host(f); }
-        return upload(wname, h.data(), h.size() * 2);
-      });
-      const float* bp = (const float*)cached(bname, [&]() {
-        std::vector<float> h; h.reserve(temb_total);
-        for (auto& k : bk) { const HostTensor& t = data_of(k); h.insert(h.end(), t.data.begin(), t.data.end()); }
-        return upload(bname, h.data(), h.size() * 4);
-      });
-      float* td = t_dev; float* ta = temb_all;
-      const int b2n = B2, tt = temb_total;
-      emit([=, this](hipStream_t s) {
-        LAUNCH_OK(nr_launch_timestep_sincos(td, b2n, C0, sincos, s));
-        LAUNCH_OK(nr_launch_linear_small(sincos, b2n, C0, w1, b1, temb_dim, 0, 1, e1, nullptr, s));
-        LAUNCH_OK(nr_launch_linear_small(e1, b2n, temb_dim, w2, b2, temb_dim, 0, 0, et, nullptr, s));
-        LAUNCH_OK(nr_launch_linear_small(io.y, b2n, adm, wy1, by1, temb_dim, 0, 1, y1, nullptr, s));
-        LAUNCH_OK(nr_launch_linear_small(y1, b2n, temb_dim, wy2, by2, temb_dim, 0, 1, emb, et, s));   // SiLU(time + label)
-        LAUNCH_OK(nr_launch_linear_small(emb, b2n, temb_dim, wp, bp, tt, 0, 0, ta, nullptr, s));
-      });
-      last_op_launches(6);
-    }
-    // ---- context fp32 -> bf16 ----
-    Act ctx_bf = new_act_persistent(1, 1, B2 * ctx_len, cfg.cross_attention_dim);
-    {
-      bf16* cp = ctx_bf.ptr; const long long n = (long long)B2 * ctx_len * cfg.cross_attention_dim;
-      building_ctx = true;
-      emit([this, cp, n](hipStream_t s) { LAUNCH_OK(nr_launch_f32_to_bf16(io.ctx, cp, n, s)); });
-      building_ctx = false;
-      ctx_persist.push_back(ctx_bf);
-    }
-    // ---- input blocks ----
-    std::vector<Act> hs;
-    Act x;
-    for (auto& b : lay.in) {
-      const std::string bp = "input_blocks." + std::to_string(b.idx);
-      if (b.kind == 0) {
-        x = new_act(nimg, H, W, C0);
-        const float* wT = w_conv_in(bp + ".0.weight", C0, cfg.in_channels);
-        const float* bi = w_f32(bp + ".0.bias", C0);
-        bf16* xp = x.ptr; const int ic = cfg.in_channels, b2n = B2, Hn = H, Wn = W;
-        emit([=, this](hipStream_t s) {
-          LAUNCH_OK(nr_launch_conv_in_small(io.sample, nullptr, ic, 0, b2n, nimg, 1, Hn, Wn, wT, bi, nullptr, C0, xp, io.in_scale, 0.f, s));
-        });
-        tap(bp, x);
-      } else if (b.kind == 1) {
-        x = resnet(x, nullptr, bp + ".0", b.Cout);
-        if (cfg.down_block_has_attn[b.level]) x = spatial_transformer(x, ctx_bf, bp + ".1", cfg.transformer_depth[b.level]);
-      } else {
-        GemmOpt o; o.bias = w_f32(bp + ".0.op.bias", b.Cout);
-        x = conv(x, nullptr, w_conv3(bp + ".0.op.weight", b.Cout, b.Cout), b.Cout, 3, 2, 0, o);
-        tap(bp, x);
-      }
-      hs.push_back(x);
-    }
-    // ---- middle block ----
-    {
-      const int Cm = cfg.block_out_channels[L - 1];
-      x = resnet(x, nullptr, "middle_block.0", Cm);
-      x = spatial_transformer(x, ctx_bf, "middle_block.1", cfg.transformer_depth[L - 1]);
-      x = resnet(x, nullptr, "middle_block.2", Cm);
-    }
-    // ---- output blocks: h = cat([h, hs.pop()]) -> ResBlock -> [SpatialTransformer] -> [Upsample] ----
-    for (auto& b : lay.out) {
-      const std::string bp = "output_blocks." + std::to_string(b.idx);
-      Act skip = hs.back();
-      hs.pop_back();
-      x = resnet(x, &skip, bp + ".0", b.Cout);
-      skip = Act();
-      int sub = 1;
-      if (b.attn) { x = spatial_transformer(x, ctx_bf, bp + ".1", cfg.transformer_depth[b.level]); sub = 2; }
-      if (b.up) {
-        const std::string up = bp + "." + std::to_string(sub) + ".conv";
-        GemmOpt o; o.bias = w_f32(up + ".bias", b.Cout);
-        x = conv(x, nullptr, w_conv3(up + ".weight", b.Cout, b.Cout), b.Cout, 3, 1, 1, o);
-        tap(bp + "." + std::to_string(sub), x);
-      }
-    }
-    // ---- out: GroupNorm32 -> SiLU -> conv (openaimodel.py:809-813) ----
-    Act hn = groupnorm(x, nullptr, "out.0", cfg.norm_eps, 1);
-    {
-      const bf16* wo = w_conv3("out.2.weight", cfg.out_channels, C0);
-      const float* bo = w_f32("out.2.bias", cfg.out_channels);
-      const bf16* hp = hn.ptr; const int Hn = H, Wn = W, oc = cfg.out_channels;
-      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_conv_out_small(hp, C0, nimg, 1, Hn, Wn, wo, bo, oc, io.out, 1.f, 0.f, 0, s)); });
-    }
-    n_res = 0;
-    res_shapes.clear();
-  }
-
-
-  // ------------------------------------------------------------------ VAE decoder (sgm first stage)
-  // plain GEMM on raw pointers: out = A[M][K] . W[N][K]^T (+bias) -> bf16 [M][ldo], or raw fp32 [M][N] when out32
-  void gemm_raw(const bf16* a, int lda, const bf16* w, int M, int N, int K, const float* bias, bf16* out, int ldo, float* out32,
-                const char* what) {
-    NrGemmParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.a0 = a; p.c0 = K; p.lda0 = lda; p.H = p.W = p.OH = p.OW = 1; p.ksize = 1; p.stride = 1;
-    p.w = w; p.M = M; p.N = N; p.K = K; p.bias = bias; p.out = out; p.ldo = ldo; p.out_scale = 1.f; p.out_f32 = out32;
-    p.plan_m = det_batch ? (int)det_rows(M) : 0;
-    const size_t wsb = nr_igemm_workspace_bytes(&p);
-    float* ws = nullptr;
-    std::shared_ptr<Buf> wsbuf;
-    if (wsb) { wsbuf = new_tmp(wsb); ws = at<float>(wsbuf->off); }
-    char d[160];
-    snprintf(d, sizeof(d), "igemm %s M=%d N=%d K=%d", what, M, N, K);
-    emit([p, ws](hipStream_t s) { LAUNCH_OK(nr_launch_igemm(&p, ws, s)); }, NR_PROF_IGEMM, 2.0 * M * (double)N * K,
-         2.0 * ((double)M * K + (double)N * K) + (out32 ? 4.0 : 2.0) * (double)M * N, d);
-  }
-
-  // AttnBlock (model.py:161-201): GroupNorm -> q,k,v 1x1 convs -> single-head softmax(q k^T / sqrt(C)) v -> proj_out
-  // + x.  The head dimension is the full channel count (512), beyond the flash kernels' register budget, so the
-  // block is expressed as MFMA GEMMs per image: S = Q K^T (fp32 scores), row softmax -> bf16 P, O = P V.  V is
-  // produced already transposed (V^T = Wv . Xn^T, i.e. the igemm with the weight as the "activation" operand); its
-  // bias moves to the P V epilogue because every softmax row sums to one.
-  Act vae_attn(const Act& x, const std::string& pre) {
-    const int C = x.C, hw = x.H * x.W;
-    if (hw % 64 != 0) throw NrError(NR_ERR_UNSUPPORTED, "VAE attention: latent h*w must be a multiple of 64");
-    Act hn = groupnorm(x, nullptr, pre + ".norm", cfg.norm_eps, 0);
-    GemmOpt oq; oq.bias = w_f32(pre + ".q.bias", C);
-    Act q = linear(hn, w_linear(pre + ".q.weight", C, C), C, oq);
-    GemmOpt ok; ok.bias = w_f32(pre + ".k.bias", C);
-    Act k = linear(hn, w_linear(pre + ".k.weight", C, C), C, ok);
-    const bf16* wv = w_linear(pre + ".v.weight", C, C);
-    const float* bv = w_f32(pre + ".v.bias", C);
-    Act o = new_act(x.nimg, x.H, x.W, C);
-    {
-      auto vt = new_tmp((size_t)C * hw * sizeof(bf16));
-      auto sc = new_tmp((size_t)hw * hw * sizeof(float));
-      auto pr = new_tmp((size_t)hw * hw * sizeof(bf16));
-      bf16* vtp = at<bf16>(vt->off); float* scp = at<float>(sc->off); bf16* prp = at<bf16>(pr->off);
-      const float scale = 1.0f / std::sqrt((float)C);
-      for (int n = 0; n < x.nimg; ++n) {
-        const size_t off = (size_t)n * hw * C;
-        gemm_raw(wv, C, hn.ptr + off, C, hw, C, nullptr, vtp, hw, nullptr, "vae V^T");
-        gemm_raw(q.ptr + off, C, k.ptr + off, hw, hw, C, nullptr, nullptr, 0, scp, "vae QK^T");
-        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_softmax_rows(scp, prp, hw, hw, scale, s)); }, NR_PROF_ATTENTION,
-             5.0 * (double)hw * hw, 6.0 * (double)hw * hw, "softmax rows L=" + std::to_string(hw));
-        gemm_raw(prp, hw, vtp, hw, C, hw, bv, o.ptr + off, C, nullptr, "vae PV");
-      }
-    }
-    hn = Act(); q = Act(); k = Act();
-    GemmOpt op; op.bias = w_f32(pre + ".proj_out.bias", C); op.res = &x;
-    Act out = linear(o, w_linear(pre + ".proj_out.weight", C, C), C, op);
-    tap(pre, out);
-    return out;
-  }
-
-  // AutoencodingEngineLegacy.decode (sgm/models/autoencoder.py:490-494) = post_quant_conv -> Decoder.forward
-  // (sgm/modules/diffusionmodules/model.py:723-757).  Same network as diffusers AutoencoderKL.decode used by
-  // decode_latents (pipeline_animation.py:243-256) under different parameter names.
-  void build_vae() {
-    const int L = cfg.num_levels, zc = cfg.in_channels, nimg = B2;
-    if (F != 1) throw NrError(NR_ERR_ARG, "the VAE decoder is a 2-D network: plan with frames = 1");
-    ctx_persist.clear(); ops.clear(); ctx_ops.clear(); op_meta.clear(); taps.clear(); arena.reset(); parena.reset();
-    temb_slots.clear(); temb_total = 0; temb_all = nullptr;
-    t_dev = new_scratch<float>(NR_MAX_BATCH);
-    const int Cm = cfg.block_out_channels[L - 1];
-    float* zq = new_scratch<float>((size_t)nimg * zc * H * W);
-    {
-      check_shape("post_quant_conv.weight", need("post_quant_conv.weight"), {zc, zc});
-      const float* Q = (const float*)cached("f32:post_quant_conv.weight", [&]() {
-        const HostTensor& t = data_of("post_quant_conv.weight");
-        return upload("f32:post_quant_conv.weight", t.data.data(), t.data.size() * 4);
-      });
-      const float* qb = w_f32("post_quant_conv.bias", zc);
-      const int hw = H * W;
-      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_post_quant(io.sample, io.in_scale, Q, qb, zq, nimg, zc, hw, s)); });
-    }
-    Act x = new_act(nimg, H, W, Cm);
-    {
-      const float* wT = w_conv_in("decoder.conv_in.weight", Cm, zc);
-      const float* bi = w_f32("decoder.conv_in.bias", Cm);
-      bf16* xp = x.ptr; const int Hn = H, Wn = W;
-      emit([=](hipStream_t s) {
-        LAUNCH_OK(nr_launch_conv_in_small(zq, nullptr, zc, 0, nimg, nimg, 1, Hn, Wn, wT, bi, nullptr, Cm, xp, 1.f, 0.f, s));
-      });
-      tap("decoder.conv_in", x);
-    }
-    x = resnet(x, nullptr, "decoder.mid.block_1", Cm);
-    x = vae_attn(x, "decoder.mid.attn_1");
-    x = resnet(x, nullptr, "decoder.mid.block_2", Cm);
-    for (int lev = L - 1; lev >= 0; --lev) {
-      const int Co = cfg.block_out_channels[lev];
-      const std::string up = "decoder.up." + std::to_string(lev);
-      for (int j = 0; j < cfg.layers_per_block + 1; ++j) x = resnet(x, nullptr, up + ".block." + std::to_string(j), Co);
-      if (lev != 0) {
-        GemmOpt o; o.bias = w_f32(up + ".upsample.conv.bias", Co);
-        x = conv(x, nullptr, w_conv3(up + ".upsample.conv.weight", Co, Co), Co, 3, 1, 1, o);   // nearest 2x + conv (model.py:67-71)
-        tap(up + ".upsample", x);
-      }
-    }
-    Act hn = groupnorm(x, nullptr, "decoder.norm_out", cfg.norm_eps, 1);
-    {
-      const int C0 = cfg.block_out_channels[0], oc = cfg.out_channels;
-      const bf16* wo = w_conv3("decoder.conv_out.weight", oc, C0);
-      const float* bo = w_f32("decoder.conv_out.bias", oc);
-      const bf16* hp = hn.ptr; const int Hn = x.H, Wn = x.W;
-      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_conv_out_small(hp, C0, nimg, 1, Hn, Wn, wo, bo, oc, io.out, io.out_mul, io.out_add, io.clamp01, s)); });
-    }
-    n_res = 0;
-    res_shapes.clear();
-  }
-
-
-  // AutoencodingEngine.encode up to the moments (sgm/models/autoencoder.py:468-488): Encoder.forward
-  // (sgm/modules/diffusionmodules/model.py:584-609) -> quant_conv.  == diffusers AutoencoderKL.encode(x).latent_dist
-  // parameters (scripts/neuroclips_video.py:267,282).  Plan h, w are the IMAGE size; moments are [n][2z][h/8][w/8].
-  void build_vae_enc() {
-    const int L = cfg.num_levels, zc2 = cfg.out_channels, nimg = B2, ic = cfg.in_channels;
-    if (F != 1) throw NrError(NR_ERR_ARG, "the VAE encoder is a 2-D network: plan with frames = 1");
-    ctx_persist.clear(); ops.clear(); ctx_ops.clear(); op_meta.clear(); taps.clear(); arena.reset(); parena.reset();
-    temb_slots.clear(); temb_total = 0; temb_all = nullptr;
-    t_dev = new_scratch<float>(NR_MAX_BATCH);
-    const int C0 = cfg.block_out_channels[0];
-    Act x = new_act(nimg, H, W, C0);
-    {
-      const float* wT = w_conv_in("encoder.conv_in.weight", C0, ic);
-      const float* bi = w_f32("encoder.conv_in.bias", C0);
-      bf16* xp = x.ptr; const int Hn = H, Wn = W;
-      emit([=, this](hipStream_t s) {
-        LAUNCH_OK(nr_launch_conv_in_small(io.sample, nullptr, ic, 0, nimg, nimg, 1, Hn, Wn, wT, bi, nullptr, C0, xp, io.in_scale,
-                                          io.in_shift, s));
-      });
-      tap("encoder.conv_in", x);
-    }
-    for (int lev = 0; lev < L; ++lev) {
-      const int Co = cfg.block_out_channels[lev];
-      const std::string dn = "encoder.down." + std::to_string(lev);
-      for (int j = 0; j < cfg.layers_per_block; ++j) x = resnet(x, nullptr, dn + ".block." + std::to_string(j), Co);
-      if (lev != L - 1) {
-        // Downsample.forward (model.py:84-91): F.pad (0,1,0,1) then 3x3 stride-2 conv without padding
-        GemmOpt o; o.bias = w_f32(dn + ".downsample.conv.bias", Co); o.pad_tl0 = 1;
-        x = conv(x, nullptr, w_conv3(dn + ".downsample.conv.weight", Co, Co), Co, 3, 2, 0, o);
-        tap(dn + ".downsample", x);
-      }
-    }
-    const int Cm = cfg.block_out_channels[L - 1];
-    x = resnet(x, nullptr, "encoder.mid.block_1", Cm);
-    x = vae_attn(x, "encoder.mid.attn_1");
-    x = resnet(x, nullptr, "encoder.mid.block_2", Cm);
-    Act hn = groupnorm(x, nullptr, "encoder.norm_out", cfg.norm_eps, 1);
-    {
-      const int hw = x.H * x.W;
-      float* mraw = new_scratch<float>((size_t)nimg * zc2 * hw);
-      const bf16* wo = w_conv3("encoder.conv_out.weight", zc2, Cm);
-      const float* bo = w_f32("encoder.conv_out.bias", zc2);
-      check_shape("quant_conv.weight", need("quant_conv.weight"), {zc2, zc2});
-      const float* Q = (const float*)cached("f32:quant_conv.weight", [&]() {
-        const HostTensor& t = data_of("quant_conv.weight");
-        return upload("f32:quant_conv.weight", t.data.data(), t.data.size() * 4);
-      });
-      const float* qb = w_f32("quant_conv.bias", zc2);
-      const bf16* hp = hn.ptr; const int Hn = x.H, Wn = x.W;
-      emit([=, this](hipStream_t s) {
-        LAUNCH_OK(nr_launch_conv_out_small(hp, Cm, nimg, 1, Hn, Wn, wo, bo, zc2, mraw, 1.f, 0.f, 0, s));
-        LAUNCH_OK(nr_launch_post_quant(mraw, 1.f, Q, qb, io.out, nimg, zc2, hw, s));
-      });
-    }
-    n_res = 0;
-    res_shapes.clear();
-  }
-
-
-  // ------------------------------------------------------------------ CLIP text encoder
-  // transformers CLIPTextModel.forward -> last_hidden_state, as _encode_prompt calls it (pipeline_neuroclips.py:
-  // 153-240: text_encoder(ids, attention_mask=None)[0]): CLIPTextEmbeddings -> 12 x CLIPEncoderLayer (pre-LN, causal
-  // self-attention, quick_gelu MLP) -> final_layer_norm.  Config fields for this kind: block_out_channels[0] =
-  // hidden_size, num_heads, layers_per_block = num_hidden_layers, cross_attention_dim = intermediate_size,
-  // in_channels = vocab_size, motion_pe_max_len = max_position_embeddings.  Plan: (batch, 1, 1, seq_len, 0).
-  void build_clip() {
-    const int C = cfg.block_out_channels[0], heads = cfg.num_heads, inter = cfg.cross_attention_dim, vocab = cfg.in_channels;
-    const int L = W, M = B2 * L;
-    if (F != 1 || H != 1) throw NrError(NR_ERR_ARG, "CLIP text encoder: plan with frames = 1, h = 1, w = sequence length");
-    if (L > cfg.motion_pe_max_len) throw NrError(NR_ERR_ARG, "sequence longer than max_position_embeddings");
-    ctx_persist.clear(); ops.clear(); ctx_ops.clear(); op_meta.clear(); taps.clear(); arena.reset(); parena.reset();
-    temb_slots.clear(); temb_total = 0; temb_all = nullptr;
-    t_dev = new_scratch<float>(NR_MAX_BATCH);
-    const std::string tm = "text_model.";
-    Act x = new_act(B2, 1, L, C);
-    {
-      const std::string tk = tm + "embeddings.token_embedding.weight", pk = tm + "embeddings.position_embedding.weight";
-      check_shape(tk, need(tk), {vocab, C});
-      check_shape(pk, need(pk), {cfg.motion_pe_max_len, C});
-      const float* tok = (const float*)cached("f32:" + tk, [&]() { const HostTensor& t = data_of(tk); return upload("f32:" + tk, t.data.data(), t.data.size() * 4); });
-      const float* pos = (const float*)cached("f32:" + pk, [&]() { const HostTensor& t = data_of(pk); return upload("f32:" + pk, t.data.data(), t.data.size() * 4); });
-      bf16* xp = x.ptr;
-      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_clip_embed(io.ids, tok, pos, xp, M, L, C, vocab, s)); });
-      tap("text_model.embeddings", x);
-    }
-    for (int i = 0; i < cfg.layers_per_block; ++i) {
-      const std::string lp = tm + "encoder.layers." + std::to_string(i);
-      const std::string ap = lp + ".self_attn";
-      Act qkv = ln_linear(x, lp + ".layer_norm1", {ap + ".q_proj.weight", ap + ".k_proj.weight", ap + ".v_proj.weight"},
-                          {ap + ".q_proj.bias", ap + ".k_proj.bias", ap + ".v_proj.bias"}, C, false, 0, false);
-      Act ao = attention(0, qkv, nullptr, C, heads, 1);      // causal mask (CLIPTextTransformer builds it for every call)
-      qkv = Act();
-      // residual updates run in place, except in debug mode where every tap keeps its own buffer
-      GemmOpt oo; oo.bias = w_f32(ap + ".out_proj.bias", C); oo.res = &x; oo.out = keep_all ? nullptr : &x;
-      Act x1 = linear(ao, w_linear(ap + ".out_proj.weight", C, C), C, oo);
-      x = x1;
-      ao = Act();
-      Act hmid = ln_linear(x, lp + ".layer_norm2", {lp + ".mlp.fc1.weight"}, {lp + ".mlp.fc1.bias"}, inter, false, 1, false);
-      GemmOpt o2; o2.bias = w_f32(lp + ".mlp.fc2.bias", C); o2.res = &x; o2.out = keep_all ? nullptr : &x;
-      Act x2 = linear(hmid, w_linear(lp + ".mlp.fc2.weight", C, inter), C, o2);
-      x = x2;
-      tap(lp, x);
-    }
-    Act fin = layernorm(x, tm + "final_layer_norm", nullptr, 1);
-    {
-      const bf16* fp = fin.ptr; const long long n = (long long)M * C;
-      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_bf16_to_f32(fp, io.out, n, s)); });
-    }
-    n_res = 0;
-    res_shapes.clear();
-  }
-
-  // ------------------------------------------------------------------ leaf modules (test hooks)
-  // ONE reference module as a network of its own, so that the reference classes' own outputs (tests/golden/leaf_ops.npz) can be
-  // compared at the row counts where the engine picks its fused kernels:
-  //   NR_KIND_LEAF_TRANSFORMER3D  Transformer3DModel.forward      (attention.py:95-142; state-dict keys "m.<reference key>")
-  //   NR_KIND_LEAF_TEMPORAL       VanillaTemporalModule.forward   (motion_module.py:79-86,134-158; keys "m.temporal_transformer...")
-  // Input / output are the reference's fp32 "b c f h w" tensors; the plan between the two layout converts is exactly the one
-  // spatial_transformer() / temporal_module() emit inside the U-Net.
-  void build_leaf() {
-    const int C = cfg.block_out_channels[0];
-    const int nimg = B2 * F;
-    ctx_persist.clear(); ops.clear(); ctx_ops.clear(); op_meta.clear(); taps.clear(); arena.reset(); parena.reset();
-    ctx_dirty = true;
-    temb_slots.clear(); temb_total = 0; temb_all = nullptr;
-    t_dev = new_scratch<float>(NR_MAX_BATCH);
-    Act x = new_act(nimg, H, W, C);
-    {
-      bf16* xp = x.ptr; const int b2n = B2, Fn = F, hw = H * W;
-      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_ncfhw_to_nhwc(io.sample, xp, b2n, C, Fn, hw, s)); });
-    }
-    Act y;
-    if (cfg.kind == NR_KIND_LEAF_TRANSFORMER3D) {
-      Act ctx_bf = new_act_persistent(1, 1, B2 * ctx_len, cfg.cross_attention_dim);
-      bf16* cp = ctx_bf.ptr; const long long n = (long long)B2 * ctx_len * cfg.cross_attention_dim;
-      building_ctx = true;
-      emit([this, cp, n](hipStream_t s) { LAUNCH_OK(nr_launch_f32_to_bf16(io.ctx, cp, n, s)); });
-      building_ctx = false;
-      ctx_persist.push_back(ctx_bf);
-      y = spatial_transformer(x, ctx_bf, "m");
-    } else {
-      y = temporal_module(x, "m");
-    }
-    {
-      const bf16* yp = y.ptr; const int b2n = B2, Fn = F, hw = H * W;
-      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_nhwc_to_ncfhw(yp, io.out, b2n, C, Fn, hw, s)); });
-    }
-    n_res = 0;
-    res_shapes.clear();
-  }
-
-  // ---- SparseCtrl image-condition variant: SparseControlNetConditioningEmbedding (sparse_controlnet.py:49-82) added to conv_in (:513-521) ----
-  // x[b][f] = emb(cat[cond, mask])[b % cond_batch][f] + conv_in.bias (+ conv_in(sample) when the noisy sample is not zeroed).  The embedding
-  // depends on the condition and mask only: it runs once per condition image (cond_batch of them, read from io at launch; the buffers are
-  // sized for cond_batch = B2), never per CFG / grouped sample, and with the identical-frame evaluation active (nd > 0) only on the distinct
-  // frames (a zero condition with a zero mask embeds to the same constant on every other frame), then is broadcast into x.
-  Act embed_conv(const Act& in, int Fe, const std::string& key, int Cout, int stride, int silu, const float* bias) {
-    const int Cin = in.C, Hi = in.H, Wi = in.W;
-    const int OH = stride == 2 ? (Hi - 1) / 2 + 1 : Hi, OW = stride == 2 ? (Wi - 1) / 2 + 1 : Wi;
-    Act o = new_act(in.nimg, OH, OW, Cout);
-    const bf16* w = w_condembed(key + ".weight", Cout, Cin);
-    const float* b = bias ? bias : w_f32(key + ".bias", Cout);
-    const bf16* ip = in.ptr; bf16* op = o.ptr;
-    char d[160];
-    snprintf(d, sizeof(d), "condembed_conv Cin=%d Cout=%d s=%d H=%d W=%d frames=%d", Cin, Cout, stride, OH, OW, Fe);
-    emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_condembed_conv(ip, io.cond_batch * Fe, Hi, Wi, Cin, stride, w, b, Cout, silu, op, s)); },
-         NR_PROF_IGEMM, 2.0 * Fe * OH * OW * Cout * 9.0 * Cin, 2.0 * Fe * ((double)Hi * Wi * Cin + (double)OH * OW * Cout) + 2.0 * Cout * 9.0 * Cin, d);
-    return o;
-  }
-  void cond_embedding(Act& x, int nd, const int* fmap_reduce, const int* fmap_expand) {
-    const int L = cfg.cond_embedding_levels, C0 = cfg.block_out_channels[0], cc = cfg.conditioning_channels;
-    const int* ch = cfg.cond_embedding_channels;
-    const int Hc = H << (L - 1), Wc = W << (L - 1), Fn = F, Hn = H, Wn = W;
-    const int Fe = nd > 0 ? nd : F;
-    std::vector<int> fsel(Fe), emap(F);
-    for (int e = 0; e < Fe; ++e) fsel[e] = nd > 0 ? fmap_reduce[e] : e;
-    for (int f = 0; f < F; ++f) emap[f] = nd > 0 ? fmap_expand[f] : f;
-    const std::string pre = "controlnet_cond_embedding.";
-    // flops / bytes of the op descriptions are per condition image
-    Act e = new_act(B2 * Fe, Hc, Wc, ch[0]);
-    {
-      const float* w = w_conv_in(pre + "conv_in.weight", ch[0], cc + 1);
-      const float* b = w_f32(pre + "conv_in.bias", ch[0]);
-      bf16* op = e.ptr; const int C = ch[0];
-      char d[160];
-      snprintf(d, sizeof(d), "condembed_in Cin=%d Cout=%d H=%d W=%d frames=%d", cc + 1, C, Hc, Wc, Fe);
-      emit([=, this](hipStream_t s) {
-        LAUNCH_OK(nr_launch_condembed_in(io.cond, io.mask, cc, io.cond_batch, Fn, Hc, Wc, fsel.data(), Fe, w, b, C, op, s));
-      }, NR_PROF_OTHER, 2.0 * Fe * Hc * Wc * C * 9.0 * (cc + 1), 4.0 * Fe * Hc * Wc * (cc + 1) + 2.0 * Fe * Hc * Wc * C, d);
-    }
-    for (int i = 0; i + 1 < L; ++i) {
-      e = embed_conv(e, Fe, pre + "blocks." + std::to_string(2 * i), ch[i], 1, 1, nullptr);
-      e = embed_conv(e, Fe, pre + "blocks." + std::to_string(2 * i + 1), ch[i + 1], 2, 1, nullptr);
-    }
-    if (e.H != H || e.W != W) throw NrError(NR_ERR_STATE, "condition embedding: output size differs from the latent size");
-    const bool zero_sample = cfg.set_noisy_sample_input_to_zero;
-    const std::string bo_key = pre + "conv_out.bias";
-    const float* bo = zero_sample ? w_f32_sum(bo_key, "conv_in.bias", C0) : w_f32(bo_key, C0);    // conv_in(0) = conv_in.bias folded in
-    const int cl = ch[L - 1];
-    Act eo;
-    if (cl % 64 == 0) {
-      // conv_out (Cin = 256 at the latent grid) on the implicit-GEMM conv kernel; M follows the condition batch at launch
-      eo = new_act(B2 * Fe, H, W, C0);
-      NrGemmParams p;
-      std::memset(&p, 0, sizeof(p));
-      p.a0 = e.ptr; p.c0 = cl; p.lda0 = cl; p.H = H; p.W = W; p.OH = H; p.OW = W; p.ksize = 3; p.stride = 1;
-      p.w = w_conv3(pre + "conv_out.weight", C0, cl); p.N = C0; p.K = 9 * cl; p.bias = bo; p.out = eo.ptr; p.ldo = C0; p.out_scale = 1.f;
-      size_t wsb = 0;                                  // split-K scratch for the largest need of any cond_batch dividing B2
-      for (int cb = 1; cb <= B2; ++cb)
-        if (B2 % cb == 0) { p.M = cb * Fe * H * W; wsb = std::max(wsb, nr_igemm_workspace_bytes(&p)); }
-      float* ws = nullptr;
-      std::shared_ptr<Buf> wsbuf;
-      if (wsb) { wsbuf = new_tmp(wsb); ws = at<float>(wsbuf->off); }
-      p.M = Fe * H * W;
-      char d[160];
-      snprintf(d, sizeof(d), "igemm ks=3 s=1 ups=0 M=%d N=%d K=%d condembed conv_out frames=%d", p.M, p.N, p.K, Fe);
-      const int hw = H * W;
-      emit([this, p, ws, Fe, hw](hipStream_t s) {
-        NrGemmParams q = p;
-        q.M = io.cond_batch * Fe * hw;
-        LAUNCH_OK(nr_launch_igemm(&q, ws, s));
-      }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, 2.0 * ((double)p.M * cl + (double)p.N * p.K + (double)p.M * C0), d);
-    } else {
-      eo = embed_conv(e, Fe, pre + "conv_out", C0, 1, 0, bo);
-    }
-    e = Act();
-    const long long img = (long long)H * W * C0;
-    bf16* xp = x.ptr; const bf16* ep = eo.ptr; const int b2n = B2;
-    const std::string d = "condembed_bcast frames=" + std::to_string(Fe) + " -> " + std::to_string(F);
-    if (zero_sample) {
-      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_condembed_bcast(ep, io.cond_batch, Fe, emap.data(), b2n, Fn, img, nullptr, xp, s)); },
-           NR_PROF_OTHER, 0.0, 4.0 * B2 * F * img, d);
-    } else {
-      const float* wT = w_conv_in("conv_in.weight", C0, cfg.in_channels);
-      const float* bi = w_f32("conv_in.bias", C0);
-      Act x2 = new_act(B2 * F, H, W, C0);
-      bf16* x2p = x2.ptr; const int ic = cfg.in_channels, nimg = B2 * F;
-      emit([=, this](hipStream_t s) {
-        LAUNCH_OK(nr_launch_conv_in_small(io.sample, nullptr, ic, 0, b2n, nimg, Fn, Hn, Wn, wT, bi, nullptr, C0, x2p, 1.f, 0.f, s));
-        LAUNCH_OK(nr_launch_condembed_bcast(ep, io.cond_batch, Fe, emap.data(), b2n, Fn, img, x2p, xp, s));
-      }, NR_PROF_OTHER, 2.0 * nimg * H * W * C0 * 9.0 * ic, 6.0 * B2 * F * img, d);
-      last_op_launches(2);
-    }
-  }
-
-  void build() {
-    if (cfg.kind == NR_KIND_LEAF_TRANSFORMER3D || cfg.kind == NR_KIND_LEAF_TEMPORAL) { build_leaf(); return; }
-    if (cfg.kind == NR_KIND_CLIP_TEXT) { build_clip(); return; }
-    if (cfg.kind == NR_KIND_VAE_ENCODER) { build_vae_enc(); return; }
-    if (cfg.kind == NR_KIND_SGM_UNET) { build_sgm(); return; }
-    if (cfg.kind == NR_KIND_VAE_DECODER) { build_vae(); return; }
-    const int L = cfg.num_levels;
-    const int C0 = cfg.block_out_channels[0];
-    const int temb_dim = 4 * C0;
-    const int nimg = B2 * F;
-    ctx_persist.clear(); ops.clear(); ctx_ops.clear(); op_meta.clear(); taps.clear(); arena.reset(); parena.reset();
-    ctx_dirty = true;
-    temb_slots.clear();
-    enumerate_resnets(temb_slots);
-    temb_total = 0;
-    for (auto& s : temb_slots) temb_total += s.C;
-
-    // ---- time embedding (unet.py:371-392): sinusoid -> Linear -> SiLU -> Linear ; then every
-    // resnet's Linear(SiLU(emb)) (resnet.py:191) in ONE batched launch ----
-    t_dev = new_scratch<float>(NR_MAX_BATCH);
-    float* sincos = new_scratch<float>((size_t)B2 * C0);
-    float* emb1 = new_scratch<float>((size_t)B2 * temb_dim);
-    float* emb = new_scratch<float>((size_t)B2 * temb_dim);
-    temb_all = new_scratch<float>((size_t)B2 * temb_total);
-    {
-      const bf16* w1 = w_linear("time_embedding.linear_1.weight", temb_dim, C0);
-      const float* b1 = w_f32("time_embedding.linear_1.bias", temb_dim);
-      const bf16* w2 = w_linear("time_embedding.linear_2.weight", temb_dim, temb_dim);
-      const float* b2 = w_f32("time_embedding.linear_2.bias", temb_dim);
-      // concatenated time_emb_proj weights
-      std::vector<std::string> wk, bk;
-      for (auto& s : temb_slots) { wk.push_back(s.prefix + ".time_emb_proj.weight"); bk.push_back(s.prefix + ".time_emb_proj.bias"); }
-      std::string wname = "tembw:" + std::to_string(cfg.kind), bname = "tembb:" + std::to_string(cfg.kind);
-      for (auto& s : temb_slots) {
-        check_shape(s.prefix + ".time_emb_proj.weight", need(s.prefix + ".time_emb_proj.weight"), {s.C, temb_dim});
-        check_shape(s.prefix + ".time_emb_proj.bias", need(s.prefix + ".time_emb_proj.bias"), {s.C});
-      }
-      const bf16* wp = (const bf16*)cached(wname, [&]() {
-        std::vector<uint16_t> h((size_t)temb_total * temb_dim);
-        size_t o = 0;
-        for (auto& k : wk) { const HostTensor& t = data_of(k); for (float f : t.data) h[o++] = f2bf_host(f); }
-        return upload(wname, h.data(), h.size() * 2);
-      });
-      const float* bp = (const float*)cached(bname, [&]() {
-        std::vector<float> h; h.reserve(temb_total);
-        for (auto& k : bk) { const HostTensor& t = data_of(k); h.insert(h.end(), t.data.begin(), t.data.end()); }
-        return upload(bname, h.data(), h.size() * 4);
-      });
-      float* td = t_dev; float* ta = temb_all;
-      const int b2n = B2, tt = temb_total;
-      emit([=](hipStream_t s) {
-        LAUNCH_OK(nr_launch_timestep_sincos(td, b2n, C0, sincos, s));
-        LAUNCH_OK(nr_launch_linear_small(sincos, b2n, C0, w1, b1, temb_dim, 0, 1, emb1, nullptr, s));   // Linear + SiLU
-        // every consumer of emb applies SiLU first (resnet.py:191), so store SiLU(emb) once instead of re-evaluating it
-        // in each of the ~22k output rows of the batched projection
-        LAUNCH_OK(nr_launch_linear_small(emb1, b2n, temb_dim, w2, b2, temb_dim, 0, 1, emb, nullptr, s)); // SiLU(emb)
-        LAUNCH_OK(nr_launch_linear_small(emb, b2n, temb_dim, wp, bp, tt, 0, 0, ta, nullptr, s));         // Linear(SiLU(emb)) for all resnets
-      });
-      last_op_launches(4);
-    }
-
-    // ---- text context fp32 -> bf16 [B2*ctx_len][cross_dim] ----
-    Act ctx_bf = new_act_persistent(1, 1, B2 * ctx_len, cfg.cross_attention_dim);
-    {
-      bf16* cp = ctx_bf.ptr; const long long n = (long long)B2 * ctx_len * cfg.cross_attention_dim;
-      building_ctx = true;
-      emit([this, cp, n](hipStream_t s) { LAUNCH_OK(nr_launch_f32_to_bf16(io.ctx, cp, n, s)); });
-      building_ctx = false;
-      ctx_persist.push_back(ctx_bf);
-    }
-
-    // SparseCtrl identical-frame evaluation (see n_cond_frames): distinct frames = the conditioned ones + one representative of the rest
-    int nd = 0, fmap_reduce[64], fmap_expand[64];
-    if (cfg.kind == NR_KIND_SPARSECTRL && cfg.set_noisy_sample_input_to_zero && cfg.use_motion_module && n_cond_frames >= 0 && !keep_all && F <= 64) {
-      int rep = -1;
-      for (int f = 0; f < F && rep < 0; ++f) {
-        bool is_c = false;
-        for (int k = 0; k < n_cond_frames; ++k) is_c = is_c || cond_frames[k] == f;
-        if (!is_c) rep = f;
-      }
-      int nc = 0;
-      for (int k = 0; k < n_cond_frames; ++k) if (cond_frames[k] < F) fmap_reduce[nc++] = cond_frames[k];
-      if (rep >= 0 && nc + 1 < F) {
-        fmap_reduce[nc] = rep;
-        nd = nc + 1;
-        for (int f = 0; f < F; ++f) {
-          fmap_expand[f] = nc;
-          for (int k = 0; k < nc; ++k) if (fmap_reduce[k] == f) fmap_expand[f] = k;
-        }
-      }
-    }
-
-    // ---- conv_in ----
-    const bool cfg_half = cfg_dedup_active();      // conv_in .. attn1 of the first transformer on the first half of the batch only
-    Act x = new_act(cfg_half ? nimg / 2 : nimg, H, W, C0);
-    if (cfg.kind == NR_KIND_UNET3D) {
-      const float* wT = w_conv_in("conv_in.weight", C0, cfg.in_channels);
-      const float* bi = w_f32("conv_in.bias", C0);
-      bf16* xp = x.ptr; const int ic = cfg.in_channels, b2n = cfg_half ? B2 / 2 : B2, ni = x.nimg, Fn = F, Hn = H, Wn = W;
-      emit([=, this](hipStream_t s) {
-        LAUNCH_OK(nr_launch_conv_in_small(io.sample, nullptr, ic, 0, b2n, ni, Fn, Hn, Wn, wT, bi, nullptr, C0, xp, 1.f, 0.f, s));
-      });
-    } else if (cfg.cond_embedding_levels > 0) {
-      cond_embedding(x, nd, fmap_reduce, fmap_expand);
-    } else {
-      // sparse_controlnet.py:467-521: sample := 0 -> conv_in(0) = bias; + cond_embedding(cat[cond, mask])
-      const int cc = cfg.conditioning_channels;
-      const float* wTe = w_conv_in("controlnet_cond_embedding.weight", C0, cc + 1);
-      const float* be = w_f32("controlnet_cond_embedding.bias", C0);
-      const float* bi = w_f32("conv_in.bias", C0);
-      bf16* xp = x.ptr; const int Fn = F, Hn = H, Wn = W;
-      if (cfg.set_noisy_sample_input_to_zero) {
-        emit([=, this](hipStream_t s) {
-          LAUNCH_OK(nr_launch_conv_in_small(io.cond, io.mask, cc, 1, io.cond_batch, nimg, Fn, Hn, Wn, wTe, be, bi, C0, xp, 1.f, 0.f, s));
-        });
-      } else {
-        const float* wT = w_conv_in("conv_in.weight", C0, cfg.in_channels);
-        Act x2 = new_act(nimg, H, W, C0);
-        bf16* x2p = x2.ptr; const int ic = cfg.in_channels, b2n = B2;
-        const long long n = (long long)nimg * H * W * C0;
-        emit([=, this](hipStream_t s) {
-          LAUNCH_OK(nr_launch_conv_in_small(io.sample, nullptr, ic, 0, b2n, nimg, Fn, Hn, Wn, wT, bi, nullptr, C0, xp, 1.f, 0.f, s));
-          LAUNCH_OK(nr_launch_conv_in_small(io.cond, io.mask, cc, 1, io.cond_batch, nimg, Fn, Hn, Wn, wTe, be, nullptr, C0, x2p, 1.f, 0.f, s));
-          LAUNCH_OK(nr_launch_add_bf16(xp, x2p, xp, n, s));
-        });
-      }
-    }
-    tap("conv_in", x);
-
-    // ---- down blocks ----
-    std::vector<Act> skips;
-    skips.push_back(cfg_half ? expand_cfg(x) : x);          // skip connections are full-batch (the ControlNet residuals added to them differ per half)
-    for (int i = 0; i < L; ++i) {
-      const int Cout = cfg.block_out_channels[i];
-      const std::string bp = "down_blocks." + std::to_string(i);
-      for (int j = 0; j < cfg.layers_per_block; ++j) {
-        if (i == 0 && j == 0 && nd > 0) {
-          // reduce -> resnet + attention on B2 x nd frame-images -> broadcast
-          const long long fe = (long long)x.H * x.W * x.C;
-          Act xr = new_act(B2 * nd, x.H, x.W, x.C);
-          {
-            const bf16* sp = x.ptr; bf16* dp = xr.ptr; const int b2n = B2, Fs = F, Fd = nd;
-            std::vector<int> mp(fmap_reduce, fmap_reduce + nd);
-            emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_frame_gather(sp, dp, b2n, Fs, Fd, fe, mp.data(), s)); });
-          }
-          const int Fsave = F;
-          F = nd;                                           // rows per sample (time-embedding row vector, context per sample) follow the reduced set
-          xr = resnet(xr, nullptr, bp + ".resnets.0", Cout);
-          if (cfg.down_block_has_attn[0]) xr = spatial_transformer(xr, ctx_bf, bp + ".attentions.0");
-          F = Fsave;
-          Act xe = new_act(nimg, xr.H, xr.W, xr.C);
-          {
-            const long long fe2 = (long long)xr.H * xr.W * xr.C;
-            const bf16* sp = xr.ptr; bf16* dp = xe.ptr; const int b2n = B2, Fs = nd, Fd = F;
-            std::vector<int> mp(fmap_expand, fmap_expand + F);
-            emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_frame_gather(sp, dp, b2n, Fs, Fd, fe2, mp.data(), s)); });
-          }
-          x = xe;
-          x = temporal_module(x, bp + ".motion_modules.0");
-          skips.push_back(x);
-          continue;
-        }
-        x = resnet(x, nullptr, bp + ".resnets." + std::to_string(j), Cout);
-        if (cfg.down_block_has_attn[i]) x = spatial_transformer(x, ctx_bf, bp + ".attentions." + std::to_string(j), 1, cfg_half && i == 0 && j == 0);
-        if (cfg.use_motion_module) x = temporal_module(x, bp + ".motion_modules." + std::to_string(j));
-        skips.push_back(x);
-      }
-      if (i != L - 1) {
-        GemmOpt o; o.bias = w_f32(bp + ".downsamplers.0.conv.bias", Cout);
-        x = conv(x, nullptr, w_conv3(bp + ".downsamplers.0.conv.weight", Cout, Cout), Cout, 3, 2, 0, o);
-        tap(bp + ".downsamplers.0", x);
-        skips.push_back(x);
-      }
-    }
-    n_res = (int)skips.size();
-    res_shapes.clear();
-    for (auto& s : skips) res_shapes.push_back(ResShape{s.C, s.H, s.W});
-
-    // ---- mid block (unet_blocks.py:271-278) ----
-    Act mid_in = x;
-    {
-      const int Cm = cfg.block_out_channels[L - 1];
-      x = resnet(x, nullptr, "mid_block.resnets.0", Cm);
-      x = spatial_transformer(x, ctx_bf, "mid_block.attentions.0");
-      if (cfg.use_motion_module && cfg.motion_module_mid_block) x = temporal_module(x, "mid_block.motion_modules.0");
-      x = resnet(x, nullptr, "mid_block.resnets.1", Cm);
-    }
-    res_shapes.push_back(ResShape{x.C, x.H, x.W});
-    mid_in = Act();
-
-    if (cfg.kind == NR_KIND_SPARSECTRL) {
-      // ---- zero-conv heads (sparse_controlnet.py:551-566): 1x1 conv, * conditioning_scale ----
-      for (int i = 0; i <= n_res; ++i) {
-        const bool is_mid = i == n_res;
-        const Act& src = is_mid ? x : skips[i];
-        const std::string key = is_mid ? std::string("controlnet_mid_block") : "controlnet_down_blocks." + std::to_string(i);
-        NrGemmParams p;
-        std::memset(&p, 0, sizeof(p));
-        p.a0 = src.ptr; p.c0 = src.C; p.lda0 = src.ld; p.H = src.H; p.W = src.W; p.OH = src.H; p.OW = src.W;
-        p.ksize = 1; p.stride = 1; p.w = w_linear(key + ".weight", src.C, src.C);
-        p.M = (int)src.rows(); p.N = src.C; p.K = src.C; p.bias = w_f32(key + ".bias", src.C);
-        p.ldo = src.C; p.out_scale = 1.f;
-        p.plan_m = det_batch ? (int)det_rows(p.M) : 0;
-        const size_t wsb = nr_igemm_workspace_bytes(&p);
-        float* ws = nullptr;
-        std::shared_ptr<Buf> wsbuf;
-        if (wsb) { wsbuf = new_tmp(wsb); ws = at<float>(wsbuf->off); }
-        emit([this, p, i, is_mid, ws](hipStream_t s) {
-          NrGemmParams q = p;
-          q.out = (bf16*)(is_mid ? io.out_mid : io.out_down[i]);
-          q.out_scale = io.scale;
-          LAUNCH_OK(nr_launch_igemm(&q, ws, s));
-        }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, 2.0 * (2.0 * p.M * (double)p.N + (double)p.N * p.K));
+void nr_net::run(hipStream_t caller, const float* timesteps) {
+  if (!use_graph) {
+    static const bool trace = getenv("NR_TRACE_OPS") != nullptr;      // fault localisation: one line and one stream sync per launch (eager handles only)
+    if (trace) {
+      begin(caller, timesteps);
+      for (size_t i = 0; i < ops.size(); ++i) {
+        fprintf(stderr, "[nr op %zu] %s\n", i, op_meta[i].desc.c_str());
+        ops[i](caller);
+        HIP_OK(hipStreamSynchronize(caller));
       }
       return;
     }
-
-    // ---- ControlNet residual adds (unet.py:422-428,436-439).  Everything above is independent of the ControlNet,
-    // so segment 0 can run concurrently with it (nr_denoise_step_forward) ----
-    split_op = ops.size();
-    {
-      // all skips but the last have already been consumed by their successor layer -> add in place; the last one is also the
-      // mid-block input, which must stay un-added: it was consumed above, so in place is safe too.  One launch for all of them
-      // (12 skips + the mid-block output) when every size is a multiple of 8 elements, else one launch each.
-      struct AddT { bf16* dst; long long n; };
-      std::vector<AddT> adds;
-      for (int i = 0; i < n_res; ++i) adds.push_back(AddT{skips[i].ptr, (long long)skips[i].rows() * skips[i].C});
-      adds.push_back(AddT{x.ptr, (long long)x.rows() * x.C});
-      bool multi = (int)adds.size() <= 16;
-      for (auto& a : adds) multi = multi && a.n % 8 == 0;
-      if (multi) {
-        NrAddMulti am;
-        std::memset(&am, 0, sizeof(am));
-        long long acc = 0;
-        for (size_t i = 0; i < adds.size(); ++i) { am.dst[i] = adds[i].dst; acc += adds[i].n / 8; am.n8_end[i] = acc; }
-        am.count = (int)adds.size();
-        const int nr = n_res;
-        emit([this, am, nr](hipStream_t st) {
-          if (!io.has_res) return;
-          NrAddMulti q = am;
-          for (int i = 0; i < nr; ++i) q.src[i] = (const bf16*)io.down_res[i];
-          q.src[nr] = (const bf16*)io.mid_res;
-          LAUNCH_OK(nr_launch_add_bf16_multi(&q, st));
-        });
-      } else {
-        for (int i = 0; i < n_res; ++i) {
-          bf16* sp = adds[i].dst; const long long n = adds[i].n;
-          emit([this, sp, n, i](hipStream_t st) {
-            if (io.has_res) LAUNCH_OK(nr_launch_add_bf16(sp, (const bf16*)io.down_res[i], sp, n, st));
-          });
-        }
-        bf16* xp = x.ptr; const long long n = adds.back().n;
-        emit([this, xp, n](hipStream_t st) {
-          if (io.has_res) LAUNCH_OK(nr_launch_add_bf16(xp, (const bf16*)io.mid_res, xp, n, st));
-        });
-      }
-    }
-    split_op2 = ops.size();
-
-    // ---- up blocks (unet_blocks.py:621-667,735-760) ----
-    for (int i = 0; i < L; ++i) {
-      const int Cout = cfg.block_out_channels[L - 1 - i];
-      const std::string bp = "up_blocks." + std::to_string(i);
-      for (int j = 0; j < cfg.layers_per_block + 1; ++j) {
-        Act skip = skips.back();
-        skips.pop_back();
-        x = resnet(x, &skip, bp + ".resnets." + std::to_string(j), Cout);
-        skip = Act();
-        if (cfg.up_block_has_attn[i]) x = spatial_transformer(x, ctx_bf, bp + ".attentions." + std::to_string(j));
-        if (cfg.use_motion_module) x = temporal_module(x, bp + ".motion_modules." + std::to_string(j));
-      }
-      if (i != L - 1) {
-        GemmOpt o; o.bias = w_f32(bp + ".upsamplers.0.conv.bias", Cout);
-        x = conv(x, nullptr, w_conv3(bp + ".upsamplers.0.conv.weight", Cout, Cout), Cout, 3, 1, 1, o);
-        tap(bp + ".upsamplers.0", x);
-      }
-    }
-
-    // ---- out (unet.py:468-470) ----
-    Act hn = groupnorm(x, nullptr, "conv_norm_out", cfg.norm_eps, 1);
-    {
-      const HostTensor& wt = need("conv_out.weight");
-      check_shape("conv_out.weight", wt, {cfg.out_channels, C0, 3, 3});
-      const bf16* wo = w_conv3("conv_out.weight", cfg.out_channels, C0);
-      const float* bo = w_f32("conv_out.bias", cfg.out_channels);
-      const bf16* hp = hn.ptr; const int Fn = F, Hn = H, Wn = W, oc = cfg.out_channels;
-      emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_conv_out_small(hp, C0, nimg, Fn, Hn, Wn, wo, bo, oc, io.out, 1.f, 0.f, 0, s)); });
-    }
+    run_eager(caller, timesteps);
+    return;
   }
-
-  void plan(int batch, int frames, int h, int w, int ctxl) {
-    const bool leaf = cfg.kind == NR_KIND_LEAF_TRANSFORMER3D || cfg.kind == NR_KIND_LEAF_TEMPORAL;
-    const bool vae = cfg.kind == NR_KIND_VAE_DECODER || cfg.kind == NR_KIND_VAE_ENCODER || cfg.kind == NR_KIND_CLIP_TEXT || cfg.kind == NR_KIND_LEAF_TEMPORAL;
-    if (batch <= 0 || batch > NR_MAX_BATCH || frames <= 0 || h <= 0 || w <= 0 || (ctxl <= 0 && !vae)) throw NrError(NR_ERR_ARG, "plan: bad shape");
-    const int down = (cfg.kind == NR_KIND_VAE_DECODER || cfg.kind == NR_KIND_CLIP_TEXT || leaf) ? 1 : 1 << (cfg.num_levels - 1);
-    if (h % down != 0 || w % down != 0)
-      throw NrError(NR_ERR_ARG, "plan: latent h,w must be multiples of " + std::to_string(down));
-    HIP_OK(hipDeviceSynchronize());
-    drop_graphs();
-    B2 = batch; F = frames; H = h; W = w; ctx_len = ctxl;
-    planned = false;
-    // pass 1: sizes only
-    dry = true;
-    char* old = arena_base; arena_base = nullptr;
-    main_high = 0;
-    try { build(); }
-    catch (...) { dry = false; arena_base = old; throw; }      // a shape the network rejects: keep (and later free) the arena of the previous plan
-    main_high = Arena::align(arena.high + 256);
-    const size_t need_bytes = main_high + parena.high + 256;
-    dry = false;
-    arena_base = old;
-    if (need_bytes > arena_bytes) {
-      if (arena_base) { HIP_OK(hipFree(arena_base)); arena_base = nullptr; }
-      HIP_OK(hipMalloc((void**)&arena_base, need_bytes));
-      arena_bytes = need_bytes;
-    }
-    // pass 2: real pointers, weights uploaded
-    split_op = 0; split_op2 = 0;
-    prefetch_valid = false;
-    build();
-    if (split_op == 0 || split_op > ops.size()) split_op = ops.size();
-    if (split_op2 < split_op || split_op2 > ops.size()) split_op2 = ops.size();
-    HIP_OK(hipDeviceSynchronize());
-    planned = true;
-  }
-
-  void ensure_streams() {
-    if (!own_stream) {
-      // (a lowest-priority stream for SparseCtrl, meant to fill only the CUs the U-Net leaves free, measured neutral: 16.56 vs 16.53 frames/s)
-      // NR_STREAM_PRIO=1 (A/B): SparseCtrl on the lowest-priority queue, the U-Net on the highest, so that under the grouped schedule the
-      // pending group only takes the CUs the U-Net's small launches leave free
-      static const bool prio = env_is_1("NR_STREAM_PRIO");
-      if (prio) {
-        int lo = 0, hi = 0;
-        HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi));     // lo = numerically greatest = lowest priority
-        HIP_OK(hipStreamCreateWithPriority(&own_stream, hipStreamNonBlocking, cfg.kind == NR_KIND_SPARSECTRL ? lo : hi));
-      } else {
-        HIP_OK(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
-      }
-      HIP_OK(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-      HIP_OK(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
-      HIP_OK(hipEventCreateWithFlags(&ev_adds, hipEventDisableTiming));
-      for (auto& e : ev_slot) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-  }
-  // context-only work (eager, stream-ordered before the main graph); no-op while the context is unchanged
-  void run_context(hipStream_t s) {
-    if (!ctx_dirty) return;
-    for (auto& op : ctx_ops) op(s);
-    ctx_dirty = false;
-  }
-  void set_timesteps(hipStream_t s, const float* timesteps) {
-    TimestepVals tv;
-    for (int i = 0; i < NR_MAX_BATCH; ++i) tv.v[i] = i < B2 ? timesteps[i] : 0.f;
-    hipLaunchKernelGGL(set_timesteps_kernel, dim3(1), dim3(64), 0, s, t_dev, tv, B2);
-  }
-  // launch ops [begin, end) of segment `seg` on `s` as a (re)captured hipGraph
-  void launch_segment(hipStream_t s, int seg) {
-    const size_t begin = seg == 0 ? 0 : (seg == 1 ? split_op : split_op2);
-    const size_t end = seg == 0 ? split_op : (seg == 1 ? split_op2 : ops.size());
-    if (begin >= end) return;
-    auto& cache = gcache[seg];
-    // key = the IO fields this segment's kernels read: only segment 1 (the ControlNet-residual adds) sees the residual pointers, so the
-    // encoder / decoder graphs of the U-Net are shared by every (slot, phase) of the grouped SparseCtrl schedule instead of being
-    // captured once per residual-buffer set
-    IO key = io;
-    if (seg != 1 && cfg.kind == NR_KIND_UNET3D) {
-      std::memset((void*)key.down_res, 0, sizeof(key.down_res));
-      key.mid_res = nullptr;
-      key.has_res = 0;
-    }
-    GraphSlot* hit = nullptr;
-    for (auto& g : cache) if (g.exec && g.io == key) { hit = &g; break; }
-    if (!hit) {
-      if ((int)cache.size() >= NR_GRAPH_SLOTS) {              // evict the least recently used graph
-        size_t lru = 0;
-        for (size_t i = 1; i < cache.size(); ++i) if (cache[i].used < cache[lru].used) lru = i;
-        HIP_OK(hipDeviceSynchronize());                        // it may still be executing, on this or on another stream
-        (void)hipGraphExecDestroy(cache[lru].exec);
-        cache.erase(cache.begin() + lru);
-      }
-      hipGraph_t g = nullptr;
-      HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      try {
-        for (size_t i = begin; i < end; ++i) ops[i](s);
-      } catch (...) {
-        (void)hipStreamEndCapture(s, &g);
-        if (g) (void)hipGraphDestroy(g);
-        throw;
-      }
-      HIP_OK(hipStreamEndCapture(s, &g));
-      hipGraphExec_t ex = nullptr;
-      hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (e != hipSuccess) throw NrError(NR_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-      GraphSlot gs; gs.io = key; gs.exec = ex;
-      cache.push_back(gs);
-      hit = &cache.back();
-    }
-    hit->used = ++gclock;
-    HIP_OK(hipGraphLaunch(hit->exec, s));
-  }
-
-  // what every evaluation starts with on the stream it runs on
-  void begin(hipStream_t s, const float* timesteps) {
-    set_timesteps(s, timesteps);
-    run_context(s);
-  }
-  // eager evaluation: everything in stream order on s
-  void run_eager(hipStream_t s, const float* timesteps) {
-    begin(s, timesteps);
-    for (auto& op : ops) op(s);
-  }
-  // graph mode: the engine's own stream, fenced behind everything the caller enqueued so far (readers of the buffers, staged inputs)
-  hipStream_t begin_fenced(hipStream_t caller, const float* timesteps) {
-    HIP_OK(hipEventRecord(ev_in, caller));
-    HIP_OK(hipStreamWaitEvent(own_stream, ev_in, 0));
-    begin(own_stream, timesteps);
-    return own_stream;
-  }
-
-  void run(hipStream_t caller, const float* timesteps) {
-    if (!use_graph) {
-      static const bool trace = getenv("NR_TRACE_OPS") != nullptr;      // fault localisation: one line and one stream sync per launch (eager handles only)
-      if (trace) {
-        begin(caller, timesteps);
-        for (size_t i = 0; i < ops.size(); ++i) {
-          fprintf(stderr, "[nr op %zu] %s\n", i, op_meta[i].desc.c_str());
-          ops[i](caller);
-          HIP_OK(hipStreamSynchronize(caller));
-        }
-        return;
-      }
-      run_eager(caller, timesteps);
-      return;
-    }
-    ensure_streams();
-    hipStream_t s = begin_fenced(caller, timesteps);
-    launch_segment(s, 0);
-    launch_segment(s, 1);
-    launch_segment(s, 2);
-    HIP_OK(hipEventRecord(ev_out, s));
-    HIP_OK(hipStreamWaitEvent(caller, ev_out, 0));
-  }
-};
+  ensure_streams();
+  hipStream_t s = begin_fenced(caller, timesteps);
+  launch_segment(s, 0);
+  launch_segment(s, 1);
+  launch_segment(s, 2);
+  HIP_OK(hipEventRecord(ev_out, s));
+  HIP_OK(hipStreamWaitEvent(caller, ev_out, 0));
+}
 
 // ================================================================================================
 // C ABI
@@ -2260,13 +189,6 @@ static void profile_last(nr_net* h, hipStream_t s, nr_profile* out, const char* 
   if (f) fclose(f);
   for (auto& e : ev) (void)hipEventDestroy(e);
 }
-
-#define NR_TRY try {
-#define NR_CATCH                                                         \
-  }                                                                      \
-  catch (const NrError& e) { set_err(e.what()); return e.code; }         \
-  catch (const std::exception& e) { set_err(e.what()); return NR_ERR_STATE; } \
-  return NR_OK;
 
 extern "C" const char* nr_last_error(void) { return g_err.c_str(); }
 
@@ -2328,38 +250,7 @@ extern "C" void nr_net_destroy(nr_net* h) { delete h; }
 extern "C" nr_status nr_net_load_tensor(nr_net* h, const char* key, const float* host_data, const int64_t* shape, int32_t ndim) {
   NR_TRY
   if (!h || !key || !host_data || ndim < 0 || ndim > 8) throw NrError(NR_ERR_ARG, "bad argument");
-  HostTensor t;
-  int64_t n = 1;
-  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= shape[i]; }
-  t.data.assign(host_data, host_data + n);
-  h->host[key] = std::move(t);
-  // a reload invalidates the converted copies derived from exactly this key.  Converted names are "<tag>:<key>" or
-  // "<tag>:<key>|<key>|..." (keys contain neither ':' nor '|'); the stacked time-embedding projections ("temb...") are rebuilt
-  // when any time-embedding tensor changes.
-  const std::string k(key);
-  // (the sgm ResBlocks call theirs "<block>.emb_layers.1": openaimodel.py:283-289)
-  const bool is_temb_src = k.find("time_emb") != std::string::npos || k.find("label_emb") != std::string::npos ||
-                           k.find("emb_layers") != std::string::npos;
-  auto derived_from = [&](const std::string& name) {
-    size_t b = 0;
-    while (b <= name.size()) {
-      size_t e = name.find_first_of(":|", b);
-      if (e == std::string::npos) e = name.size();
-      if (e - b == k.size() && name.compare(b, k.size(), k) == 0) return true;
-      // a norm enters a name by its prefix ("lnw:<prefix>|..." uses <prefix>.weight and <prefix>.bias)
-      if (e > b && k.size() > e - b && k.compare(0, e - b, name, b, e - b) == 0 && (k.compare(e - b, std::string::npos, ".weight") == 0 ||
-                                                                                   k.compare(e - b, std::string::npos, ".bias") == 0)) return true;
-      b = e + 1;
-    }
-    return false;
-  };
-  std::vector<std::string> stale;
-  for (auto& kv : h->dev) if (derived_from(kv.first) || (is_temb_src && kv.first.rfind("temb", 0) == 0)) stale.push_back(kv.first);
-  if (!stale.empty()) {
-    (void)hipDeviceSynchronize();
-    for (auto& name : stale) h->erase(name);      // nr_net_weight_bytes stays the sum of what is resident
-    h->planned = false;
-  }
+  if (h->wts.load_tensor(key, host_data, shape, ndim)) h->planned = false;      // converted copies derived from this key were dropped
   NR_CATCH
 }
 
@@ -2387,30 +278,11 @@ extern "C" nr_status nr_net_plan(nr_net* h, int32_t batch, int32_t frames, int32
   NR_CATCH
 }
 
-// ---- converted-weight exchange between handles (rank 0 converts once, the bf16 arena travels device to device) ----
-// Manifest: text, one record per line.  "H <state-dict key> <ndim> <dims...>" for every loaded tensor (shapes only),
-// "D <converted name> <offset> <bytes>" for every converted device buffer, offsets 256-byte aligned in name order.
-static std::string build_manifest(const nr_net* h, size_t* total) {
-  std::string m = "NRW1 " + std::to_string(h->cfg.kind) + "\n";
-  for (auto& kv : h->host) {
-    m += "H " + kv.first + " " + std::to_string(kv.second.shape.size());
-    for (auto d : kv.second.shape) m += " " + std::to_string(d);
-    m += "\n";
-  }
-  size_t off = 0;
-  for (auto& kv : h->dev) {
-    const size_t b = kv.second.bytes;
-    m += "D " + kv.first + " " + std::to_string(off) + " " + std::to_string(b) + "\n";
-    off += (b + 255) & ~(size_t)255;
-  }
-  if (total) *total = off;
-  return m;
-}
-
+// ---- converted-weight exchange between handles (WeightStore::manifest / export_to / import_from) ----
 extern "C" int64_t nr_net_export_manifest(nr_net* h, char* buf, int64_t capacity, int64_t* arena_bytes) {
   if (!h || !h->planned) { set_err("nr_net_export_manifest: plan first (the converted buffers are created by nr_net_plan)"); return -1; }
   size_t total = 0;
-  const std::string m = build_manifest(h, &total);
+  const std::string m = h->wts.manifest(h->cfg.kind, &total);
   if (arena_bytes) *arena_bytes = (int64_t)total;
   if (buf && capacity >= (int64_t)m.size()) std::memcpy(buf, m.data(), m.size());
   return (int64_t)m.size();
@@ -2422,14 +294,9 @@ extern "C" nr_status nr_net_export_weights(nr_net* h, nr_stream stream, void* ds
   if (!h->planned) throw NrError(NR_ERR_STATE, "plan first");
   check_device(h);
   size_t total = 0;
-  (void)build_manifest(h, &total);
+  (void)h->wts.manifest(h->cfg.kind, &total);
   if ((size_t)capacity < total) throw NrError(NR_ERR_ARG, "export buffer too small");
-  size_t off = 0;
-  for (auto& kv : h->dev) {
-    const size_t b = kv.second.bytes;
-    HIP_OK(hipMemcpyAsync((char*)dst_dev + off, kv.second.ptr, b, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    off += (b + 255) & ~(size_t)255;
-  }
+  h->wts.export_to(dst_dev, (hipStream_t)stream);
   NR_CATCH
 }
 
@@ -2438,58 +305,7 @@ extern "C" nr_status nr_net_import_weights(nr_net* h, nr_stream stream, const ch
   NR_TRY
   if (!h || !manifest || !src_dev) throw NrError(NR_ERR_ARG, "null argument");
   check_device(h);
-  if (!h->dev.empty() || !h->host.empty()) throw NrError(NR_ERR_STATE, "import into a fresh handle (no tensors loaded, not planned)");
-  const std::string m(manifest, (size_t)manifest_bytes);
-  size_t pos = 0;
-  auto next_line = [&](std::string& line) {
-    if (pos >= m.size()) return false;
-    const size_t e = m.find('\n', pos);
-    line = m.substr(pos, e == std::string::npos ? std::string::npos : e - pos);
-    pos = e == std::string::npos ? m.size() : e + 1;
-    return true;
-  };
-  std::string line;
-  if (!next_line(line) || line.rfind("NRW1 ", 0) != 0) throw NrError(NR_ERR_ARG, "bad manifest header");
-  if (std::atoi(line.c_str() + 5) != h->cfg.kind) throw NrError(NR_ERR_ARG, "manifest is for a different network kind");
-  if (arena_bytes <= 0) throw NrError(NR_ERR_ARG, "empty arena");
-  // parse and validate the WHOLE manifest into temporaries first: a bad line must leave the handle fresh (importable again)
-  std::map<std::string, HostTensor> new_host;
-  struct DevRec { std::string name; size_t off, bytes; };
-  std::vector<DevRec> new_dev;
-  while (next_line(line)) {
-    if (line.size() < 3) continue;
-    std::vector<std::string> tok;
-    size_t a = 0;
-    while (a < line.size()) { size_t b = line.find(' ', a); if (b == std::string::npos) b = line.size(); if (b > a) tok.push_back(line.substr(a, b - a)); a = b + 1; }
-    if (tok.empty()) continue;
-    if (tok[0] == "H" && tok.size() >= 3) {
-      HostTensor t;                                   // shape only: the data never exists on this rank
-      const int nd = std::atoi(tok[2].c_str());
-      if (nd < 0 || nd > 8 || 3 + nd != (int)tok.size()) throw NrError(NR_ERR_ARG, "bad manifest line: " + line);
-      for (int i = 0; i < nd; ++i) {
-        const long long d = std::atoll(tok[3 + i].c_str());
-        if (d < 0) throw NrError(NR_ERR_ARG, "bad manifest line: " + line);
-        t.shape.push_back(d);
-      }
-      new_host[tok[1]] = std::move(t);
-    } else if (tok[0] == "D" && tok.size() == 4) {
-      const long long off = std::atoll(tok[2].c_str()), b = std::atoll(tok[3].c_str());
-      if (off < 0 || b <= 0 || off > arena_bytes || b > arena_bytes - off) throw NrError(NR_ERR_ARG, "manifest entry beyond the arena: " + tok[1]);
-      new_dev.push_back(DevRec{tok[1], (size_t)off, (size_t)b});
-    } else throw NrError(NR_ERR_ARG, "bad manifest line: " + line);
-  }
-  char* base = nullptr;
-  HIP_OK(hipMalloc((void**)&base, (size_t)arena_bytes));
-  if (hipMemcpyAsync(base, src_dev, (size_t)arena_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess ||
-      hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
-    (void)hipFree(base);
-    throw NrError(NR_ERR_HIP, "copying the weight arena failed");
-  }
-  // commit
-  h->import_base = base;
-  h->import_bytes = (size_t)arena_bytes;
-  h->host = std::move(new_host);
-  for (auto& r : new_dev) h->adopt(r.name, base + r.off, r.bytes);
+  h->wts.import_from(h->cfg.kind, std::string(manifest, (size_t)manifest_bytes), src_dev, arena_bytes, (hipStream_t)stream);
   NR_CATCH
 }
 
@@ -2497,7 +313,7 @@ extern "C" nr_status nr_net_release_host_weights(nr_net* h) {
   NR_TRY
   if (!h) throw NrError(NR_ERR_ARG, "null handle");
   if (!h->planned) throw NrError(NR_ERR_STATE, "plan first: the converted device copies must exist");
-  for (auto& kv : h->host) { std::vector<float>().swap(kv.second.data); }
+  h->wts.release_host();
   NR_CATCH
 }
 
@@ -2576,7 +392,7 @@ extern "C" nr_status nr_net_set_debug(nr_net* h, int32_t keep) {
 }
 
 extern "C" int64_t nr_net_workspace_bytes(const nr_net* h) { return h ? (int64_t)h->arena_bytes : 0; }
-extern "C" int64_t nr_net_weight_bytes(const nr_net* h) { return h ? (int64_t)h->weight_bytes : 0; }
+extern "C" int64_t nr_net_weight_bytes(const nr_net* h) { return h ? (int64_t)h->wts.weight_bytes : 0; }
 extern "C" int32_t nr_net_num_residuals(const nr_net* h) { return h ? h->n_res : 0; }
 extern "C" nr_status nr_net_residual_shape(const nr_net* h, int32_t i, int32_t* C, int32_t* hh, int32_t* ww) {
   NR_TRY
@@ -2959,315 +775,4 @@ extern "C" nr_status nr_net_read_tap(nr_net* h, int32_t i, float* host_out, int6
       host_out[(size_t)r * t.C + c] = f;
     }
   NR_CATCH
-}
-
-// ---- single-op entry points ---------------------------------------------------------------------
-// grow-only device scratch of the op hooks (process lifetime).  Growing waits for the device first (the old buffer may still be read) and
-// returns true
-struct OpScratch { void* ptr = nullptr; size_t cap = 0; };
-static bool op_scratch(OpScratch& b, size_t need) {
-  if (need <= b.cap) return false;
-  if (b.ptr) { HIP_OK(hipDeviceSynchronize()); (void)hipFree(b.ptr); }
-  b.ptr = nullptr; b.cap = 0;
-  HIP_OK(hipMalloc(&b.ptr, need));
-  b.cap = need;
-  return true;
-}
-
-static float* op_workspace(const NrGemmParams& p) {
-  static OpScratch ws;
-  const size_t need = nr_igemm_workspace_bytes(&p);
-  op_scratch(ws, need);
-  return need ? (float*)ws.ptr : nullptr;
-}
-
-// Test / tool hooks and the panel-resident small-M kernel (smallm.hip): an eligible launch gets a fragment-major copy of its weights, packed on
-// the launch stream into a scratch buffer on EVERY call (tests: always consistent with the tensor passed in); NR_OP_FM_CACHE=1 keeps one
-// copy per weight pointer instead (timing tools that replay graphs over a pool of weights; nr_op_fm_cache_clear when the pool is freed)
-static std::map<const void*, bf16*> g_op_fm_cache;
-extern "C" void nr_op_fm_cache_clear() {
-  (void)hipDeviceSynchronize();
-  for (auto& kv : g_op_fm_cache) (void)hipFree(kv.second);
-  g_op_fm_cache.clear();
-}
-static void op_fragmajor(NrGemmParams& p, hipStream_t s) {
-  if (!nr_smallm_eligible(&p)) return;
-  const size_t need = (size_t)p.N * p.K * sizeof(bf16);
-  if (env_is_1("NR_OP_FM_CACHE")) {
-    auto it = g_op_fm_cache.find(p.w);
-    if (it == g_op_fm_cache.end()) {
-      bf16* d = nullptr;
-      HIP_OK(hipMalloc((void**)&d, need));
-      LAUNCH_OK(nr_launch_smallm_w_pack(p.w, d, p.N, p.K, s));
-      it = g_op_fm_cache.emplace(p.w, d).first;
-    }
-    p.w_fm = it->second;
-    return;
-  }
-  static OpScratch scratch;
-  op_scratch(scratch, need);
-  LAUNCH_OK(nr_launch_smallm_w_pack(p.w, scratch.ptr, p.N, p.K, s));
-  p.w_fm = (const bf16*)scratch.ptr;
-}
-
-// the engine's choice for short-K Linears on 2048..8192 rows (lin160.hip): the stage stream is packed on the launch stream on every call
-static bool op_lin160(const NrGemmParams& p, hipStream_t s) {
-  const int l1 = nr_lin160_eligible(&p);
-  if (!l1) return false;
-  static OpScratch buf;
-  op_scratch(buf, l1 == 4 ? nr_lin128q_stream_bytes(p.N, p.K) : nr_lin160_stream_bytes(p.N, p.K));
-  bf16* l160 = (bf16*)buf.ptr;
-  LAUNCH_OK(l1 == 4 ? nr_launch_lin128q_w_pack(p.w, p.N, p.K, l160, s) : nr_launch_lin160_w_pack(p.w, p.N, p.K, l160, s));
-  LAUNCH_OK(nr_launch_lin160(&p, l160, s));
-  return true;
-}
-
-extern "C" nr_status nr_op_gemm(nr_stream stream, const void* a, int32_t lda, const void* w, const float* bias,
-                                const void* res, int32_t ldr, void* out, int32_t ldo, int32_t M, int32_t N, int32_t K,
-                                int32_t geglu) {
-  NR_TRY
-  NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr, (bf16*)out, ldo);
-  p.geglu = geglu;
-  if (op_lin160(p, (hipStream_t)stream)) return NR_OK;
-  op_fragmajor(p, (hipStream_t)stream);
-  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
-  NR_CATCH
-}
-
-// two-source operand [a0 | a1] (the skip concat of unet_blocks.py:634,740 as a 1x1 GEMM; the [t | g] operand of the folded FeedForward)
-extern "C" nr_status nr_op_gemm2(nr_stream stream, const void* a0, int32_t c0, int32_t lda0, const void* a1, int32_t c1, int32_t lda1,
-                                 const void* w, const float* bias, const void* res, int32_t ldr, void* out, int32_t ldo, int32_t M, int32_t N) {
-  NR_TRY
-  NrGemmParams p = nr_gemm_params((const bf16*)a0, c0, lda0, (const bf16*)a1, c1, lda1, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr,
-                                  (bf16*)out, ldo);
-  op_fragmajor(p, (hipStream_t)stream);
-  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
-  NR_CATCH
-}
-
-extern "C" nr_status nr_op_ln_gemm(nr_stream stream, const void* a, int32_t lda, const void* w_scaled, const float* ln_c,
-                                   const float* bias_folded, float eps, const void* res, int32_t ldr, void* out, int32_t ldo,
-                                   int32_t M, int32_t N, int32_t K, int32_t geglu, int32_t act) {
-  NR_TRY
-  if (!ln_c) throw NrError(NR_ERR_ARG, "ln_c is required");
-  NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w_scaled, N, bias_folded, (const bf16*)res, ldr,
-                                  (bf16*)out, ldo);
-  p.geglu = geglu; p.ln_c = ln_c; p.ln_eps = eps; p.act = act;
-  if (op_lin160(p, (hipStream_t)stream)) return NR_OK;
-  op_fragmajor(p, (hipStream_t)stream);
-  LAUNCH_OK(nr_launch_igemm(&p, nullptr, (hipStream_t)stream));
-  NR_CATCH
-}
-
-extern "C" nr_status nr_op_gemm_ex(nr_stream stream, const void* a, int32_t lda, const void* w, const float* bias, const float* ln_c,
-                                   float ln_eps, const float* rowvec, int32_t rowvec_div, int32_t rowvec_mod, int32_t rowvec_ld,
-                                   const void* res, int32_t ldr, void* out, int32_t ldo, int32_t M, int32_t N, int32_t K, int32_t geglu,
-                                   int32_t act, float out_scale) {
-  NR_TRY
-  NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr, (bf16*)out, ldo);
-  p.out_scale = out_scale; p.geglu = geglu; p.act = act;
-  p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_mod = rowvec_mod; p.rowvec_ld = rowvec_ld;
-  p.ln_c = ln_c; p.ln_eps = ln_eps;
-  op_fragmajor(p, (hipStream_t)stream);
-  LAUNCH_OK(nr_launch_igemm(&p, ln_c ? nullptr : op_workspace(p), (hipStream_t)stream));
-  NR_CATCH
-}
-
-extern "C" nr_status nr_op_conv3x3(nr_stream stream, const void* x0, int32_t c0, const void* x1, int32_t c1, int32_t nimg,
-                                   int32_t H, int32_t W, int32_t stride, int32_t ups, const void* w, const float* bias,
-                                   const float* rowvec, int32_t rowvec_div, const void* res, void* out, int32_t Cout) {
-  NR_TRY
-  NrGemmParams p = nr_gemm_params((const bf16*)x0, c0, c0, (const bf16*)x1, c1, c1, nimg, H, W, 3, stride, ups, (const bf16*)w, Cout, bias, (const bf16*)res,
-                                  Cout, (bf16*)out, Cout);
-  p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
-  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
-  NR_CATCH
-}
-
-extern "C" nr_status nr_op_condembed_in(nr_stream stream, const float* cond, const float* mask, int32_t c0, int32_t nsrc, int32_t F, int32_t H,
-                                        int32_t W, const int32_t* fmap, int32_t nframes, const float* w, const float* bias, int32_t Cout,
-                                        void* out) {
-  NR_TRY
-  if (!fmap) throw NrError(NR_ERR_ARG, "fmap is null");
-  LAUNCH_OK(nr_launch_condembed_in(cond, mask, c0, nsrc, F, H, W, fmap, nframes, w, bias, Cout, (bf16*)out, (hipStream_t)stream));
-  NR_CATCH
-}
-
-extern "C" nr_status nr_op_condembed_conv(nr_stream stream, const void* x, int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t stride,
-                                          const void* wfm, const float* bias, int32_t Cout, int32_t silu, void* out) {
-  NR_TRY
-  LAUNCH_OK(nr_launch_condembed_conv((const bf16*)x, nimg, H, W, Cin, stride, (const bf16*)wfm, bias, Cout, silu, (bf16*)out,
-                                     (hipStream_t)stream));
-  NR_CATCH
-}
-
-// as nr_op_conv3x3 (stride 1, no upsample, single source) with the weight in the tap-inner layout [Cout][Cin/64][3][3][64]
-extern "C" nr_status nr_op_conv3x3_tap_inner(nr_stream stream, const void* x0, int32_t c0, int32_t nimg, int32_t H, int32_t W, const void* w,
-                                             const float* bias, const float* rowvec, int32_t rowvec_div, const void* res, void* out,
-                                             int32_t Cout) {
-  NR_TRY
-  NrGemmParams p = nr_gemm_params((const bf16*)x0, c0, c0, nullptr, 0, 0, nimg, H, W, 3, 1, 0, (const bf16*)w, Cout, bias, (const bf16*)res, Cout, (bf16*)out,
-                                  Cout);
-  p.tap_inner = 1;
-  p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
-  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
-  NR_CATCH
-}
-
-extern "C" nr_status nr_op_groupnorm(nr_stream stream, const void* x0, int32_t c0, const void* x1, int32_t c1, int32_t nimg,
-                                     int32_t hw, int32_t groups, const float* gamma, const float* beta, float eps,
-                                     int32_t silu, float* partial_ws, void* out) {
-  NR_TRY
-  NrGnParams p = nr_gn_params((const bf16*)x0, c0, c0, (const bf16*)x1, c1, c1, nimg, hw, groups, gamma, beta, eps, silu, partial_ws, (bf16*)out,
-                              c0 + (x1 ? c1 : 0));
-  LAUNCH_OK(nr_launch_groupnorm(&p, (hipStream_t)stream));
-  NR_CATCH
-}
-
-extern "C" nr_status nr_op_layernorm(nr_stream stream, const void* x, void* out, int32_t M, int32_t C, const float* gamma,
-                                     const float* beta, float eps, const float* pe, int32_t pe_hw, int32_t pe_F) {
-  NR_TRY
-  LAUNCH_OK(nr_launch_layernorm((const bf16*)x, C, (bf16*)out, C, M, C, gamma, beta, eps, pe, pe_hw > 0 ? pe_hw : 1,
-                                pe_F > 0 ? pe_F : 1, (hipStream_t)stream));
-  NR_CATCH
-}
-
-extern "C" nr_status nr_op_attention(nr_stream stream, int32_t mode, const void* qp, const void* kvp, void* outp,
-                                     int32_t nimg, int32_t L, int32_t Lk, int32_t C, int32_t heads, int32_t frames,
-                                     int32_t kv_div) {
-  NR_TRY
-  const int fp8_flag = (mode & 8) ? 1 : 0;      // mode | 8: e4m3 MFMA operands (spatial / cross kernels)
-  const int causal_flag = (mode & 16) ? 1 : 0;  // mode | 16: causal mask (mode 0 only; the CLIP text encoder's form)
-  mode &= 7;
-  if (causal_flag && (mode != 0 || fp8_flag)) throw NrError(NR_ERR_ARG, "causal attention: mode 0 only");
-  if (mode > 2) throw NrError(NR_ERR_ARG, "bad attention mode");
-  // the hook's tensors are dense: q|k|v rows of 3C (modes 0 / 2), q rows of C and k|v rows of 2C (mode 1), output rows of C
-  const NrAttnParams p = nr_attn_params(mode, (const bf16*)qp, (const bf16*)kvp, (bf16*)outp, mode == 1 ? C : 3 * C, 2 * C, C, nimg, L, Lk, C, heads, frames, kv_div,
-                                        causal_flag, fp8_flag);
-  LAUNCH_OK(nr_launch_attention(&p, (hipStream_t)stream));
-  NR_CATCH
-}
-
-// ---- fused FeedForward + proj_out (ffpanel.hip), op-level entry for tests: inputs in the engine's converted formats ----
-extern "C" nr_status nr_op_ff_fused(nr_stream stream, const void* t_dev, const void* x_dev, void* out_dev, int32_t M, int32_t C,
-                                    const void* w1_geglu_dev, const float* gamma_dev, const float* beta_dev, const float* b1_geglu_dev,
-                                    const void* wc_dev, const float* bc_dev, float ln_eps) {
-  NR_TRY
-  if (!nr_ff_fused_eligible(C, 1 << 30)) throw NrError(NR_ERR_UNSUPPORTED, "the fused FeedForward kernel is built for C = 320");
-  static void* ws = nullptr;
-  const size_t nb = nr_ff_stream_bytes(C);
-  if (!ws) HIP_OK(hipMalloc(&ws, nb));
-  // w1 == NULL: reuse the stage stream packed by the previous call (timing loops)
-  if (w1_geglu_dev) LAUNCH_OK(nr_launch_ff_stream_pack((const bf16*)w1_geglu_dev, (const bf16*)wc_dev, (bf16*)ws, (hipStream_t)stream));
-  LAUNCH_OK(nr_launch_ff_fused((const bf16*)t_dev, C, (const bf16*)x_dev, C, (bf16*)out_dev, C, M, (const bf16*)ws, gamma_dev, beta_dev,
-                               b1_geglu_dev, bc_dev, ln_eps, env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
-  NR_CATCH
-}
-
-// ---- fused temporal-attention block (tattn.hip), op-level entry for tests.  t: bf16 [nbatch * frames * hw][320], updated in place;
-// wq / wk / wv / wo: bf16 [320][320]; gamma fp32 [320]; gb fp32 [frames][320] = LayerNorm bias + positional encoding; bo fp32 [320];
-// frames = 16 or 32 ----
-extern "C" nr_status nr_op_tattn_fused_frames(nr_stream stream, void* t_dev, int32_t nbatch, int32_t frames, int32_t hw, const void* wq_dev,
-                                              const void* wk_dev, const void* wv_dev, const void* wo_dev, const float* gamma_dev,
-                                              const float* gb_dev, const float* bo_dev, float ln_eps) {
-  NR_TRY
-  if (!nr_tattn_fused_eligible(320, 8, frames, hw, 1 << 30))
-    throw NrError(NR_ERR_UNSUPPORTED, "fused temporal attention: C = 320, 8 heads, 16 or 32 frames, hw % (128 / frames) == 0");
-  static void* ws = nullptr;
-  if (!ws) HIP_OK(hipMalloc(&ws, nr_tattn_stream_bytes()));
-  // wq == NULL: reuse the stream packed by the previous call (timing loops)
-  if (wq_dev) LAUNCH_OK(nr_launch_tattn_stream_pack((const bf16*)wq_dev, (const bf16*)wk_dev, (const bf16*)wv_dev, (const bf16*)wo_dev, (bf16*)ws,
-                                                    (hipStream_t)stream));
-  LAUNCH_OK(nr_launch_tattn_fused((bf16*)t_dev, nbatch, frames, hw, (const bf16*)ws, gamma_dev, gb_dev, bo_dev, ln_eps,
-                                  env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
-  NR_CATCH
-}
-extern "C" nr_status nr_op_xattn_fused(nr_stream stream, void* t_dev, int32_t nimg, int32_t hw, int32_t img_per_ctx, const void* wq_dev,
-                                       const void* wo_dev, const void* kv_dev, int32_t ldkv, int32_t Lk, int32_t nctx, const float* gamma_dev,
-                                       const float* beta_dev, const float* bo_dev, float ln_eps) {
-  NR_TRY
-  if (!t_dev || !kv_dev || !gamma_dev || !beta_dev || !bo_dev) throw NrError(NR_ERR_ARG, "null argument");
-  if (!nr_xattn_fused_eligible(320, 8, Lk, hw, 1 << 30) || nimg <= 0 || img_per_ctx <= 0 || nctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
-    throw NrError(NR_ERR_UNSUPPORTED, "fused cross attention: C = 320, 8 heads, Lk <= 80, hw % 128 == 0, one context per img_per_ctx images");
-  static void* ws = nullptr;
-  static OpScratch kvbuf;
-  if (!ws) HIP_OK(hipMalloc(&ws, nr_xattn_wstream_bytes()));
-  op_scratch(kvbuf, nr_xattn_kvstream_bytes(nctx));
-  void* kvs = kvbuf.ptr;
-  // wq == NULL: reuse the streams packed by the previous call (timing loops)
-  if (wq_dev) {
-    LAUNCH_OK(nr_launch_xattn_w_pack((const bf16*)wq_dev, (const bf16*)wo_dev, (bf16*)ws, (hipStream_t)stream));
-    LAUNCH_OK(nr_launch_xattn_kv_pack((const bf16*)kv_dev, ldkv, Lk, nctx, (bf16*)kvs, (hipStream_t)stream));
-  }
-  LAUNCH_OK(nr_launch_xattn_fused((bf16*)t_dev, nimg, hw, img_per_ctx, nctx, Lk, (const bf16*)ws, (const bf16*)kvs, gamma_dev, beta_dev, bo_dev, ln_eps,
-                                  env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
-  NR_CATCH
-}
-// ---- q projection + context attention above the C = 320 level (xattnw.hip), op-level entry for tests.  t: bf16 [nimg * hw][C] (C = 640 or 1280,
-// hw a multiple of 64); a: bf16, same shape (attention output before to_out); wq_folded: bf16 [C][C] = gamma-scaled rows of to_q; lnc / bias fp32 [C];
-// kv: bf16 [nctx * Lk][ldkv], K in columns [0, C), V in [C, 2C); image i attends to context i / img_per_ctx ----
-extern "C" nr_status nr_op_xattn_head(nr_stream stream, const void* t_dev, void* a_dev, int32_t nimg, int32_t hw, int32_t img_per_ctx, int32_t C,
-                                      const void* wq_folded_dev, const float* lnc_dev, const float* bias_dev, const void* kv_dev, int32_t ldkv, int32_t Lk,
-                                      int32_t nctx, float ln_eps) {
-  NR_TRY
-  if (!t_dev || !a_dev || !kv_dev) throw NrError(NR_ERR_ARG, "null argument");
-  if (!nr_xattnw_wstream_bytes(C) || nimg <= 0 || hw <= 0 || hw % 64 != 0 || Lk < 1 || Lk > 80 || nctx <= 0 || img_per_ctx <= 0 ||
-      (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
-    throw NrError(NR_ERR_UNSUPPORTED, "cross-attention head kernel: C = 640 or 1280, 8 heads, Lk <= 80, hw % 64 == 0, one context per img_per_ctx images");
-  static void* ws[2] = {nullptr, nullptr};
-  static void* tbl[2] = {nullptr, nullptr};
-  static OpScratch kvbuf;
-  const int ci = C == 640 ? 0 : 1;
-  if (!ws[ci]) HIP_OK(hipMalloc(&ws[ci], nr_xattnw_wstream_bytes(C)));
-  if (!tbl[ci]) HIP_OK(hipMalloc(&tbl[ci], nr_xattnw_table_bytes(C)));
-  const size_t need = nr_xattnw_kvstream_bytes(C, nctx);
-  if (op_scratch(kvbuf, need)) HIP_OK(hipMemset(kvbuf.ptr, 0, need));
-  void* kvs = kvbuf.ptr;
-  // wq_folded == NULL: reuse the streams packed by the previous call at this C (timing loops)
-  if (wq_folded_dev) {
-    if (!lnc_dev || !bias_dev) throw NrError(NR_ERR_ARG, "null argument");
-    LAUNCH_OK(nr_launch_xattnw_w_pack((const bf16*)wq_folded_dev, C, (bf16*)ws[ci], (hipStream_t)stream));
-    LAUNCH_OK(nr_launch_xattnw_table_pack(lnc_dev, bias_dev, C, (float*)tbl[ci], (hipStream_t)stream));
-    LAUNCH_OK(nr_launch_xattnw_kv_pack((const bf16*)kv_dev, ldkv, Lk, nctx, C, (bf16*)kvs, (hipStream_t)stream));
-  }
-  LAUNCH_OK(nr_launch_xattnw((const bf16*)t_dev, (bf16*)a_dev, nimg, hw, img_per_ctx, nctx, Lk, C, (const bf16*)ws[ci], (const bf16*)kvs, (const float*)tbl[ci],
-                             ln_eps, (hipStream_t)stream));
-  NR_CATCH
-}
-// ---- q|k|v projection of one head + F x F attention above the C = 320 level (tattnw.hip), op-level entry for tests.  t: bf16 [nbatch * frames * hw][C]
-// (C = 640 or 1280, frames = 16 or 32); a: bf16, same shape (attention output before to_out); w_folded: bf16 [3C][C] = gamma-scaled rows of
-// to_q | to_k | to_v; lnc / bias fp32 [3C]; rowvec fp32 [frames][3C] ----
-extern "C" nr_status nr_op_tattn_head_frames(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t frames, int32_t hw, int32_t C,
-                                             const void* w_folded_dev, const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
-  NR_TRY
-  if (!t_dev || !a_dev || !lnc_dev || !bias_dev || !rowvec_dev) throw NrError(NR_ERR_ARG, "null argument");
-  if (!nr_tattnw_stream_bytes(C) || (frames != 16 && frames != 32) || nbatch <= 0 || hw <= 0 || hw % (C == 640 ? 8 : 4) != 0)
-    throw NrError(NR_ERR_UNSUPPORTED, "temporal attention head kernel: C = 640 (hw % 8 == 0) or 1280 (hw % 4 == 0), 8 heads, 16 or 32 frames");
-  static void* ws[2] = {nullptr, nullptr};
-  static void* tbl[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};     // [C][frames]: a table is packed for one frame count
-  static int ws_frames[2] = {0, 0};                                       // the frame count of the last packing call at this C
-  const int ci = C == 640 ? 0 : 1, fi = frames == 16 ? 0 : 1;
-  void*& w = ws[ci];
-  void*& tb = tbl[ci][fi];
-  if (!w) HIP_OK(hipMalloc(&w, nr_tattnw_stream_bytes(C)));
-  if (!tb) HIP_OK(hipMalloc(&tb, nr_tattnw_table_bytes(C, frames)));
-  // w_folded == NULL: reuse the stream and the epilogue table packed by the previous call at this C (timing loops): same frame count only
-  if (w_folded_dev) {
-    LAUNCH_OK(nr_launch_tattnw_stream_pack((const bf16*)w_folded_dev, C, (bf16*)w, (hipStream_t)stream));
-    LAUNCH_OK(nr_launch_tattnw_table_pack(lnc_dev, bias_dev, rowvec_dev, C, frames, (float*)tb, (hipStream_t)stream));
-    ws_frames[ci] = frames;
-  } else if (ws_frames[ci] != frames) {
-    throw NrError(NR_ERR_ARG, "temporal attention head kernel: w_folded == NULL needs a previous call at this C and frame count");
-  }
-  LAUNCH_OK(nr_launch_tattnw((const bf16*)t_dev, (bf16*)a_dev, nbatch, frames, hw, C, (const bf16*)w, (const float*)tb, ln_eps, (hipStream_t)stream));
-  NR_CATCH
-}
-extern "C" nr_status nr_op_tattn_head(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t hw, int32_t C, const void* w_folded_dev,
-                                      const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
-  return nr_op_tattn_head_frames(stream, t_dev, a_dev, nbatch, 16, hw, C, w_folded_dev, lnc_dev, bias_dev, rowvec_dev, ln_eps);
-}
-extern "C" nr_status nr_op_tattn_fused(nr_stream stream, void* t_dev, int32_t nbatch, int32_t hw, const void* wq_dev, const void* wk_dev,
-                                       const void* wv_dev, const void* wo_dev, const float* gamma_dev, const float* gb_dev, const float* bo_dev,
-                                       float ln_eps) {
-  return nr_op_tattn_fused_frames(stream, t_dev, nbatch, 16, hw, wq_dev, wk_dev, wv_dev, wo_dev, gamma_dev, gb_dev, bo_dev, ln_eps);
 }

@@ -1,0 +1,633 @@
+// Plan emitters of the engine (engine.h): the arena and plan helpers, one emitter per kernel class (conv / linear, GroupNorm, LayerNorm, attention)
+// and the builders of the reference modules on top of them, through temporal_module.  The plan follows the reference module graph:
+//   ResnetBlock3D                       animatediff/models/resnet.py:182-212
+//   Transformer3DModel / BasicTransformerBlock   animatediff/models/attention.py:95-142,256-300
+//   TemporalTransformer3DModel / Block / VersatileAttention   animatediff/models/motion_module.py:134-158,210-222,270-329
+// Host code only.
+#include "engine.h"
+
+using namespace nre;
+
+size_t Arena::alloc(size_t bytes) {
+  bytes = align(bytes);
+  for (size_t i = 0; i < free_.size(); ++i) {
+    if (free_[i].size >= bytes) {
+      const size_t off = free_[i].off;
+      if (free_[i].size == bytes) free_.erase(free_.begin() + i);
+      else { free_[i].off += bytes; free_[i].size -= bytes; }
+      return off;
+    }
+  }
+  const size_t off = top;
+  top += bytes;
+  if (top > high) high = top;
+  return off;
+}
+void Arena::release(size_t off, size_t bytes) {
+  bytes = align(bytes);
+  size_t i = 0;
+  while (i < free_.size() && free_[i].off < off) ++i;
+  free_.insert(free_.begin() + i, Blk{off, bytes});
+  if (i + 1 < free_.size() && free_[i].off + free_[i].size == free_[i + 1].off) {
+    free_[i].size += free_[i + 1].size;
+    free_.erase(free_.begin() + i + 1);
+  }
+  if (i > 0 && free_[i - 1].off + free_[i - 1].size == free_[i].off) {
+    free_[i - 1].size += free_[i].size;
+    free_.erase(free_.begin() + i);
+  }
+  if (!free_.empty() && free_.back().off + free_.back().size == top) {
+    top = free_.back().off;
+    free_.pop_back();
+  }
+}
+
+// ------------------------------------------------------------------ plan helpers
+Act nr_net::act_in(Arena& ar, size_t base, bool keep, int nimg, int h, int w, int C) {
+  Act a;
+  const size_t bytes = (size_t)nimg * h * w * C * sizeof(bf16);
+  auto b = std::make_shared<Buf>();
+  b->arena = &ar; b->bytes = bytes; b->off = ar.alloc(bytes); b->keep = keep;
+  a.buf = b; a.ptr = at<bf16>(base + b->off); a.nimg = nimg; a.H = h; a.W = w; a.C = C; a.ld = C;
+  return a;
+}
+std::shared_ptr<Buf> nr_net::new_tmp(size_t bytes) {
+  auto b = std::make_shared<Buf>();
+  b->arena = &arena; b->bytes = bytes; b->off = arena.alloc(bytes); b->keep = keep_all;
+  return b;
+}
+nr_net::SplitK nr_net::splitk_scratch(size_t bytes) {
+  SplitK k;
+  if (bytes) { k.buf = new_tmp(bytes); k.ws = at<float>(k.buf->off); }
+  return k;
+}
+void nr_net::emit(std::function<void(hipStream_t)> fn, int kind, double flops, double bytes, const std::string& desc) {
+  if (dry) return;
+  if (building_ctx) { ctx_ops.push_back(std::move(fn)); return; }
+  ops.push_back(std::move(fn));
+  op_meta.push_back(OpMeta{kind, flops, bytes, desc});
+}
+// named by plan position and kernel class
+void nr_net::op_tap(const char* kind, const Act& a) {
+  static const bool on = getenv("NR_OP_TAPS") != nullptr;
+  if (on && !dry && keep_all && !building_ctx) taps.push_back(Tap{"op" + std::to_string(ops.size()) + "." + kind, a.ptr, a.rows(), a.C, a.ld});
+}
+void nr_net::begin_plan() {
+  ctx_persist.clear(); ops.clear(); ctx_ops.clear(); op_meta.clear(); taps.clear(); arena.reset(); parena.reset();
+  ctx_dirty = true;
+  temb_slots.clear(); temb_total = 0; temb_all = nullptr;
+  n_res = 0; res_shapes.clear();
+  t_dev = new_scratch<float>(NR_MAX_BATCH);
+}
+Act nr_net::stage_context() {
+  Act ctx_bf = new_act_persistent(1, 1, B2 * ctx_len, cfg.cross_attention_dim);
+  bf16* cp = ctx_bf.ptr; const long long n = (long long)B2 * ctx_len * cfg.cross_attention_dim;
+  building_ctx = true;
+  emit([this, cp, n](hipStream_t s) { LAUNCH_OK(nr_launch_f32_to_bf16(io.ctx, cp, n, s)); });
+  building_ctx = false;
+  ctx_persist.push_back(ctx_bf);
+  return ctx_bf;
+}
+Act nr_net::context_kv(const Act& ctx_bf, const std::string& b, int C, const std::function<Act(const Act& kv)>& pack) {
+  building_ctx = true;
+  Act kv = new_act_persistent(ctx_bf.nimg, ctx_bf.H, ctx_bf.W, 2 * C);
+  GemmOpt ok; ok.out = &kv;
+  linear(ctx_bf, wts.w_linear_cat({b + ".attn2.to_k.weight", b + ".attn2.to_v.weight"}, C, cfg.cross_attention_dim), 2 * C, ok);
+  Act stream;
+  if (pack) stream = pack(kv);
+  building_ctx = false;
+  ctx_persist.push_back(kv);
+  if (pack) ctx_persist.push_back(stream);
+  return pack ? stream : kv;
+}
+
+// ------------------------------------------------------------------ emitters
+// generic conv / linear.  x1: optional channel-concat second source.
+Act nr_net::conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksize, int stride, int ups, const GemmOpt& o) {
+  int OH, OW;
+  nr_conv_out_hw(x0.H, x0.W, ksize, stride, ups, &OH, &OW);
+  const int outC = o.geglu ? Cout / 2 : Cout;
+  Act out = o.out ? *o.out : new_act(x0.nimg, OH, OW, outC);
+  if (out.C != outC || out.rows() != (int64_t)x0.nimg * OH * OW) throw NrError(NR_ERR_STATE, "conv: output shape mismatch");
+  if (o.res && (o.res->C != outC || o.res->rows() != out.rows())) throw NrError(NR_ERR_STATE, "conv: residual shape mismatch");
+  NrGemmParams p = nr_gemm_params(x0.ptr, x0.C, x0.ld, x1 ? x1->ptr : nullptr, x1 ? x1->C : 0, x1 ? x1->ld : 0, x0.nimg, x0.H, x0.W, ksize, stride, ups,
+                                  w, Cout, o.bias, o.res ? o.res->ptr : nullptr, o.res ? o.res->ld : 0, out.ptr, out.ld);
+  p.rowvec = o.rowvec; p.rowvec_div = o.rowvec_div; p.rowvec_ld = o.rowvec_ld; p.rowvec_mod = o.rowvec_mod;
+  p.out_scale = o.scale; p.geglu = o.geglu; p.pad_tl0 = o.pad_tl0; p.act = o.act; p.ln_c = o.ln_c; p.ln_eps = 1e-5f;
+  p.tap_inner = o.tap_inner;
+  p.plan_m = det_batch ? (int)det_rows(p.M) : 0;
+  if (ksize == 1 && nr_smallm_eligible(&p))               // M <= 512 Linears: the panel-resident kernel reads fragment-major weights
+    p.w_fm = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : wts.w_fragmajor(w, Cout, p.K);
+  if (const int l1 = (ksize == 1 && !p.w_fm) ? nr_lin160_eligible(&p) : 0) {
+    // short-K Linear (K = 640 / 1280) on >= 2048 rows: the stage-stream kernel (lin160.hip) instead of the tiled igemm; 4 = its register-panel form
+    const bf16* stream = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : wts.w_lin160(w, Cout, p.K, l1 == 4);
+    char d[160];
+    snprintf(d, sizeof(d), "%s M=%d N=%d K=%d res=%d geglu=%d ln=%d", l1 == 4 ? "lin160 panel" : "lin160", p.M, p.N, p.K, o.res ? 1 : 0, p.geglu, p.ln_c ? 1 : 0);
+    const double bytes = 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * outC * (o.res ? 2.0 : 1.0));
+    emit([p, stream](hipStream_t s) { LAUNCH_OK(nr_launch_lin160(&p, stream, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
+    op_tap("lin160", out);
+    return out;
+  }
+  {
+    const double in_elems = (double)x0.rows() * (p.c0 + p.c1);   // every input element is needed at least once
+    const double bytes = 2.0 * (in_elems + (double)p.N * p.K + (double)p.M * outC + (o.res ? (double)p.M * outC : 0.0));
+    char d[160];
+    snprintf(d, sizeof(d), "igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0);
+    const SplitK sk = splitk_scratch(nr_igemm_workspace_bytes(&p));
+    float* ws = sk.ws;
+    emit([p, ws](hipStream_t s) { LAUNCH_OK(nr_launch_igemm(&p, ws, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
+    if (ws) last_op_launches(2);           // split-K: the igemm + its reduce kernel
+    op_tap(ksize == 3 ? "conv3" : (p.ln_c ? "lngemm" : "gemm"), out);
+  }
+  return out;
+}
+
+// plain GEMM on raw pointers (the VAE's attention): out = A[M][K] . W[N][K]^T (+bias) -> bf16 [M][ldo], or raw fp32 [M][N] when out32
+void nr_net::gemm_raw(const bf16* a, int lda, const bf16* w, int M, int N, int K, const float* bias, bf16* out, int ldo, float* out32,
+                      const char* what) {
+  NrGemmParams p = nr_gemm_params(a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, w, N, bias, nullptr, 0, out, ldo);
+  p.out_f32 = out32;
+  p.plan_m = det_batch ? (int)det_rows(M) : 0;
+  const SplitK sk = splitk_scratch(nr_igemm_workspace_bytes(&p));
+  float* ws = sk.ws;
+  char d[160];
+  snprintf(d, sizeof(d), "igemm %s M=%d N=%d K=%d", what, M, N, K);
+  emit([p, ws](hipStream_t s) { LAUNCH_OK(nr_launch_igemm(&p, ws, s)); }, NR_PROF_IGEMM, 2.0 * M * (double)N * K,
+       2.0 * ((double)M * K + (double)N * K) + (out32 ? 4.0 : 2.0) * (double)M * N, d);
+}
+
+Act nr_net::groupnorm(const Act& x0, const Act* x1, const std::string& prefix, float eps, int silu) {
+  const int C = x0.C + (x1 ? x1->C : 0);
+  const float* gamma = wts.w_f32(prefix + ".weight", C);
+  const float* beta = wts.w_f32(prefix + ".bias", C);
+  const int hw = x0.H * x0.W, groups = cfg.norm_num_groups;
+  const int plan_nimg = det_batch ? (int)det_rows(x0.nimg) : 0;
+  int nch = 0;
+  (void)nr_gn_workspace_floats(plan_nimg > 0 ? plan_nimg : x0.nimg, hw, groups, nullptr, &nch);   // chunking as the launcher will choose it
+  const int nfl = x0.nimg * (nch * groups * 2 + groups * 2);
+  auto ws = new_tmp((size_t)nfl * sizeof(float));
+  Act out = new_act(x0.nimg, x0.H, x0.W, C);
+  NrGnParams p = nr_gn_params(x0.ptr, x0.C, x0.ld, x1 ? x1->ptr : nullptr, x1 ? x1->C : 0, x1 ? x1->ld : 0, x0.nimg, hw, groups, gamma, beta, eps, silu,
+                              at<float>(ws->off), out.ptr, out.ld);
+  p.plan_nimg = plan_nimg;
+  if (getenv("NR_OP_TAPS") && keep_all && !x1) {     // debug: what the GroupNorm's input looked like when it ran
+    Act snap = new_act(x0.nimg, x0.H, x0.W, x0.C);
+    const bf16* src = x0.ptr; bf16* dst = snap.ptr; const size_t nb = (size_t)x0.rows() * x0.C * sizeof(bf16);
+    if (x0.ld == x0.C) {
+      emit([=](hipStream_t s) { launch_copy16(src, dst, nb, s); });
+      op_tap("gn_input_snapshot", snap);
+    }
+  }
+  emit([p](hipStream_t s) { NrGnParams q = p; LAUNCH_OK(nr_launch_groupnorm(&q, s)); }, NR_PROF_GROUPNORM,
+       8.0 * (double)x0.rows() * C, 2.0 * 2.0 * (double)x0.rows() * C,
+       "groupnorm nimg=" + std::to_string(x0.nimg) + " hw=" + std::to_string(x0.H * x0.W) + " C=" + std::to_string(C));
+  { NrGnParams q = p; last_op_launches(nr_groupnorm_launches(&q)); }
+  op_tap("gn", out);
+  return out;
+}
+
+Act nr_net::layernorm(const Act& x, const std::string& prefix, const float* pe, int pe_F) {
+  const float* g = wts.w_f32(prefix + ".weight", x.C);
+  const float* b = wts.w_f32(prefix + ".bias", x.C);
+  Act out = new_act(x.nimg, x.H, x.W, x.C);
+  const bf16* xp = x.ptr; bf16* op = out.ptr;
+  const int ldx = x.ld, ldo = out.ld, M = (int)x.rows(), C = x.C, hw = x.H * x.W;
+  emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_layernorm(xp, ldx, op, ldo, M, C, g, b, 1e-5f, pe, hw, pe_F, s)); },
+       NR_PROF_LAYERNORM, 8.0 * (double)M * C, 2.0 * 2.0 * (double)M * C,
+       "layernorm M=" + std::to_string(M) + " C=" + std::to_string(C));
+  op_tap("ln", out);
+  return out;
+}
+
+// mode 0 spatial self (qkv fused [M][3C]); 1 cross (q [M][C], kv [B2*ctx][2C]); 2 temporal self (qkv fused)
+Act nr_net::attention(int mode, const Act& q, const Act* kv, int C, int heads, int causal) {
+  Act out = new_act(q.nimg, q.H, q.W, C);
+  const NrAttnParams p = nr_attn_params(mode, q.ptr, kv ? kv->ptr : nullptr, out.ptr, q.ld, kv ? kv->ld : 0, out.ld, q.nimg, q.H * q.W, ctx_len, C, heads, F,
+                                        F, causal, (attn_fp8 && mode != 2) ? 1 : 0);
+  {
+    const double flops = 4.0 * (double)p.nbatch * p.heads * (double)p.Lq * p.Lk * p.d;
+    const double kvrows = mode == 1 ? (double)(p.nbatch / p.kv_div) * p.Lk : (double)p.nbatch * p.Lk;
+    const double bytes = 2.0 * ((double)p.nbatch * p.Lq * C * 2.0 + kvrows * C * 2.0);   // q + out + k + v
+    char d[160];
+    snprintf(d, sizeof(d), "attention mode=%d nbatch=%d heads=%d d=%d Lq=%d Lk=%d", mode, p.nbatch, p.heads, p.d, p.Lq, p.Lk);
+    emit([p](hipStream_t s) { LAUNCH_OK(nr_launch_attention(&p, s)); }, NR_PROF_ATTENTION, flops, bytes, d);
+    op_tap(mode == 2 ? "tattn" : (mode == 1 ? "xattn" : "sattn"), out);
+  }
+  return out;
+}
+
+const float* nr_net::temb_for(const std::string& prefix, int C) {
+  for (auto& s : temb_slots) if (s.prefix == prefix) {
+    if (s.C != C) throw NrError(NR_ERR_STATE, "temb slot size mismatch for " + prefix);
+    return temb_all + s.off;
+  }
+  throw NrError(NR_ERR_STATE, "no temb slot for " + prefix);
+}
+
+// ------------------------------------------------------------------ module builders
+// parameter names of one residual block: diffusers-style (animatediff) or sgm-style (openaimodel.py:255-312)
+nr_net::ResKeys nr_net::res_keys(const std::string& pre) const {
+  if (cfg.kind == NR_KIND_SGM_UNET)
+    return ResKeys{pre + ".in_layers.0", pre + ".in_layers.2", pre + ".out_layers.0", pre + ".out_layers.3", pre + ".skip_connection"};
+  if (cfg.kind == NR_KIND_VAE_DECODER || cfg.kind == NR_KIND_VAE_ENCODER)   // sgm/modules/diffusionmodules/model.py:94-151
+    return ResKeys{pre + ".norm1", pre + ".conv1", pre + ".norm2", pre + ".conv2", pre + ".nin_shortcut"};
+  return ResKeys{pre + ".norm1", pre + ".conv1", pre + ".norm2", pre + ".conv2", pre + ".conv_shortcut"};
+}
+
+// ResnetBlock3D.forward (resnet.py:182-212) == sgm ResBlock._forward (openaimodel.py:328-354, no up/down, no
+// scale-shift): GN+SiLU -> conv (+bias +Linear(SiLU(emb))) -> GN+SiLU -> conv (+bias) + skip(x).
+// x1 = skip tensor for the decoder concat.
+// 3x3 conv weights in the tap-inner K order of the igemm wherever Cin % 64 == 0; NR_CONV_TAP_INNER=0: tap-major
+static bool conv_tap_inner() {
+  static const bool on = env_not_0("NR_CONV_TAP_INNER");
+  return on;
+}
+Act nr_net::resnet(const Act& x0, const Act* x1, const std::string& pre, int Cout) {
+  const ResKeys k = res_keys(pre);
+  const int Cin = x0.C + (x1 ? x1->C : 0);
+  const int hw = x0.H * x0.W;
+  Act h = groupnorm(x0, x1, k.norm1, cfg.norm_eps, 1);
+  GemmOpt o1;
+  o1.bias = wts.w_f32(k.conv1 + ".bias", Cout);
+  if (cfg.kind != NR_KIND_VAE_DECODER && cfg.kind != NR_KIND_VAE_ENCODER) {   // the VAE's ResnetBlock runs with temb = None (model.py:138-139,727)
+    o1.rowvec = temb_for(pre, Cout); o1.rowvec_div = F * hw; o1.rowvec_ld = temb_total;
+  }
+  const bool ti1 = conv_tap_inner() && Cin % 64 == 0, ti2 = conv_tap_inner() && Cout % 64 == 0;
+  o1.tap_inner = ti1 ? 1 : 0;
+  Act h1 = conv(h, nullptr, wts.w_conv3(k.conv1 + ".weight", Cout, Cin, ti1), Cout, 3, 1, 0, o1);
+  h = Act();
+  Act h2 = groupnorm(h1, nullptr, k.norm2, cfg.norm_eps, 1);
+  h1 = Act();
+  Act sc;
+  const bool shortcut = wts.has(k.shortcut + ".weight");
+  if (shortcut) {
+    GemmOpt os; os.bias = wts.w_f32(k.shortcut + ".bias", Cout);
+    sc = conv(x0, x1, wts.w_linear(k.shortcut + ".weight", Cout, Cin), Cout, 1, 1, 0, os);
+  } else {
+    if (x1 || Cin != Cout) throw NrError(NR_ERR_MISSING_WEIGHT, "missing state-dict entry: " + k.shortcut + ".weight");
+    sc = x0;
+  }
+  GemmOpt o2;
+  o2.bias = wts.w_f32(k.conv2 + ".bias", Cout);
+  o2.res = &sc;
+  o2.tap_inner = ti2 ? 1 : 0;
+  Act out = conv(h2, nullptr, wts.w_conv3(k.conv2 + ".weight", Cout, Cout, ti2), Cout, 3, 1, 0, o2);
+  tap(pre, out);
+  return out;
+}
+
+// LayerNorm (+ temporal PE) -> Linear as one launch (LN folded into the igemm) or, with NR_NO_LN_FUSE=1, as the
+// layernorm kernel followed by a plain igemm (A/B and fallback path; same results to rounding).
+// Neach: rows of each stacked matrix (geglu: the inner width, the matrix has 2*Neach rows).
+Act nr_net::ln_linear(const Act& x, const std::string& ln, const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys,
+                      int Neach, bool geglu, int act, bool temporal_pe) {
+  static const char* mode = getenv("NR_LN_FUSE");            // "0" never, "1" always, unset: per shape
+  const int K = x.C;
+  const int N = (geglu ? 2 * Neach : Neach) * (int)wkeys.size();
+  // Every n-tile block of the fused GEMM recomputes the row statistics (~1-2 us per block round), so the fusion pays
+  // when the LayerNorm launch it removes costs more than that: small M (latency-bound LN) or narrow N.  Measured on
+  // BASELINE config 2 (profiles/README.md): wide GEMMs at the 32x32 / 16x16 levels are faster with the separate LN.
+  const long long M = det_rows(x.rows());
+  bool fuse = !((M >= 8192 && N >= 4 * K) || (M >= 32768 && N >= 3 * K));
+  // K = 320 on >= 4096 rows runs on the row-panel kernel (rowpanel.hip): the row statistics come from the register panel once
+  // per workgroup, so the folded LayerNorm is free there
+  static const bool rowpanel_on = env_not_0("NR_ROWPANEL");
+  if (rowpanel_on && K == 320 && M >= 4096) fuse = true;
+  // K = 640 wide projections (N >= 3 K) on 2048 .. 8192 rows run on the register-panel form of lin160.hip: statistics from the
+  // register-resident rows once per workgroup, so the fold is free there too (and the LayerNorm launch goes)
+  if (!temporal_pe && !act && nr_lin160_panel_rule((int)M, N, K) && x.rows() % 128 == 0 && x.ld % 8 == 0) fuse = true;
+  if (mode) fuse = mode[0] == '1';
+  GemmOpt o;
+  o.geglu = geglu ? 1 : 0; o.act = act;
+  if (fuse) {
+    const LnW lw = wts.w_ln_linear(wkeys, bkeys, ln, Neach, K, geglu);
+    o.bias = lw.b; o.ln_c = lw.c;
+    if (temporal_pe) {
+      o.rowvec = wts.pe_projection(wkeys, Neach, K, cfg.motion_pe_max_len);
+      o.rowvec_div = x.H * x.W; o.rowvec_ld = N; o.rowvec_mod = F;
+    }
+    return linear(x, lw.w, N, o);
+  }
+  Act n = layernorm(x, ln, temporal_pe ? wts.pe_table(K, cfg.motion_pe_max_len) : nullptr, temporal_pe ? F : 1);
+  const bf16* w;
+  if (geglu) {
+    w = wts.w_geglu(wkeys[0], Neach, K);
+    if (!bkeys.empty()) o.bias = wts.b_geglu(bkeys[0], Neach);
+  } else if (wkeys.size() > 1) {
+    w = wts.w_linear_cat(wkeys, Neach, K);
+    if (!bkeys.empty()) o.bias = wts.b_cat(bkeys, Neach);
+  } else {
+    w = wts.w_linear(wkeys[0], Neach, K);
+    if (!bkeys.empty()) o.bias = wts.w_f32(bkeys[0], Neach);
+  }
+  return linear(n, w, N, o);
+}
+
+// FeedForward(GEGLU) + residual, in place on t (motion_module_new.py:441-471,497-518)
+void nr_net::feed_forward(Act& t, const std::string& ln, const std::string& pre) {
+  const int C = t.C, inner = 4 * C;
+  Act hmid = ln_linear(t, ln, {pre + ".net.0.proj.weight"}, {pre + ".net.0.proj.bias"}, inner, true, 0, false);
+  GemmOpt o2; o2.bias = wts.w_f32(pre + ".net.2.bias", C); o2.res = &t; o2.out = &t;
+  linear(hmid, wts.w_linear(pre + ".net.2.weight", C, inner), C, o2);
+}
+
+// The block's LAST FeedForward and the transformer's proj_out as one GEMM (w_fold_ff_proj): x + proj_out(t + FF(t)) =
+// x + bc + [t | g] Wc^T with g = GEGLU(net.0(LN(t))).  Removes a launch and the write + read of the post-FF residual stream.
+// Needs C % 64 == 0 (the operand switch falls on a k-tile boundary); NR_FOLD_PROJ_OUT=0 keeps the two GEMMs.
+bool nr_net::fold_proj_out(int C) const {
+  static const bool on = env_not_0("NR_FOLD_PROJ_OUT");
+  return on && C % 64 == 0;
+}
+Act nr_net::feed_forward_proj_out(const Act& x, Act& t, const std::string& ln, const std::string& ff, const std::string& pre) {
+  const int C = t.C, inner = 4 * C;
+  if (!fold_proj_out(C)) {
+    feed_forward(t, ln, ff);
+    GemmOpt op; op.bias = wts.w_f32(pre + ".proj_out.bias", C); op.res = &x;
+    return linear(t, wts.w_linear(pre + ".proj_out.weight", C, C), C, op);
+  }
+  if (nr_ff_fused_eligible(C, det_rows(t.rows())) && t.ld == C && x.ld == C) {
+    // C = 320, >= 4096 rows: LayerNorm + GEGLU projection + the folded GEMM in ONE launch (ffpanel.hip); the 4C-wide hidden activation
+    // stays in registers; LayerNorm is applied to the register panel.  The weights travel as one pre-arranged stage stream.
+    wts.check_shape(ff + ".net.0.proj.weight", wts.need(ff + ".net.0.proj.weight"), {2 * inner, C});
+    const float* b1 = wts.b_geglu(ff + ".net.0.proj.bias", inner);
+    const float* gamma = wts.w_f32(ln + ".weight", C);
+    const float* beta = wts.w_f32(ln + ".bias", C);
+    const std::string sname = "ffs:" + ff + ".net.0.proj.weight|" + ff + ".net.2.weight|" + ff + ".net.2.bias|" + pre + ".proj_out.weight|" + pre +
+                              ".proj_out.bias";
+    // packed from the GEGLU matrix and the folded matrix; the folded matrix goes again in any case, the folded bias stays
+    bool made = false;
+    const bf16* stream = (const bf16*)wts.packed_from(sname, nr_ff_stream_bytes(C), {"geglu:" + ff + ".net.0.proj.weight"}, [&](void* d) {
+      const bf16* w1 = wts.w_geglu(ff + ".net.0.proj.weight", inner, C);
+      const FoldW fwm = wts.w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C, true);
+      LAUNCH_OK(nr_launch_ff_stream_pack(w1, fwm.w, (bf16*)d, nullptr));
+    }, &made);
+    if (made) wts.erase("foldw:" + pre + ".proj_out.weight|" + pre + ".proj_out.bias|" + ff + ".net.2.weight|" + ff + ".net.2.bias");
+    const FoldW fw = wts.w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C, false);
+    Act out = new_act(x.nimg, x.H, x.W, C);
+    const bf16* tp = t.ptr; const bf16* xp = x.ptr; bf16* op = out.ptr;
+    const int M = (int)t.rows();
+    const float* bc = fw.b;
+    char d[160];
+    snprintf(d, sizeof(d), "ff_fused M=%d C=%d (LN + GEGLU 8C + folded net.2|proj_out 5C)", M, C);
+    const int norot = det_batch ? 1 : 0;
+    emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_ff_fused(tp, C, xp, C, op, C, M, stream, gamma, beta, b1, bc, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
+         2.0 * M * (double)C * (8.0 * C + 5.0 * C), 2.0 * (3.0 * M * (double)C + 13.0 * C * (double)C), d);
+    op_tap("ff_fused", out);
+    return out;
+  }
+  Act g = ln_linear(t, ln, {ff + ".net.0.proj.weight"}, {ff + ".net.0.proj.bias"}, inner, true, 0, false);
+  const FoldW fw = wts.w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C);
+  GemmOpt op; op.bias = fw.b; op.res = &x;
+  return conv(t, &g, fw.w, C, 1, 1, 0, op);
+}
+
+// Exact classifier-free-guidance de-duplication (U-Net only, cfg_dup): the pipeline feeds cat([latents] * 2) with ONE timestep
+// (pipeline_neuroclips.py:435), so the two halves of the batch are identical until the first cross-attention reads the (different) text
+// contexts: conv_in, down_blocks[0].resnets[0] and norm / proj_in / norm1 / attn1 of down_blocks[0].attentions[0] (attention.py:256-280) are
+// evaluated on B2 / 2 samples and broadcast.  Not in deterministic-batch mode (its plan unit is the CFG pair) and not with debug taps.
+bool nr_net::cfg_dedup_active() const {
+  static const bool on = env_not_0("NR_CFG_DEDUP");      // A/B switch
+  return on && cfg_dup && cfg.kind == NR_KIND_UNET3D && B2 % 2 == 0 && B2 <= 64 && !det_batch && !keep_all && cfg.down_block_has_attn[0];
+}
+// [h; h]: the half-batch activation repeated for the second half of the batch (one gather launch)
+Act nr_net::expand_cfg(const Act& h) {
+  if (h.ld != h.C) throw NrError(NR_ERR_STATE, "expand_cfg: strided activation");
+  const int Bh = B2 / 2;
+  Act f = new_act(h.nimg * 2, h.H, h.W, h.C);
+  const long long fe = (long long)(h.nimg / Bh) * h.H * h.W * h.C;      // elements of one sample
+  const bf16* sp = h.ptr; bf16* dp = f.ptr; const int b2n = B2;
+  std::vector<int> mp(B2);
+  for (int i = 0; i < B2; ++i) mp[i] = i % Bh;
+  emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_frame_gather(sp, dp, 1, Bh, b2n, fe, mp.data(), s)); }, NR_PROF_OTHER, 0.0, 2.0 * 3.0 * (double)h.rows() * h.C,
+       "cfg broadcast rows=" + std::to_string(h.rows()) + " C=" + std::to_string(h.C));
+  return f;
+}
+
+// Transformer3DModel.forward (attention.py:95-142) with one BasicTransformerBlock (:256-300); also sgm
+// SpatialTransformer.forward (sgm/modules/attention.py:702-723) with `depth` BasicTransformerBlocks (:551-572):
+// same arithmetic and parameter names (proj_in/out are nn.Linear there: same [C][C] matrix).
+// cfg_half: x holds the first half of the batch only (cfg_dedup_active); t and x are broadcast behind the self-attention, the result is full-batch;
+// *x_full receives the broadcast input (the caller's skip connection)
+Act nr_net::spatial_transformer(const Act& x_in, const Act& ctx_bf, const std::string& pre, int depth, bool cfg_half, Act* x_full) {
+  Act x = x_in;
+  const int C = x.C;
+  const int heads = cfg.num_head_channels > 0 ? C / cfg.num_head_channels : cfg.num_heads;
+  Act hn = groupnorm(x, nullptr, pre + ".norm", 1e-6f, 0);
+  GemmOpt oi; oi.bias = wts.w_f32(pre + ".proj_in.bias", C);
+  Act t = linear(hn, wts.w_linear(pre + ".proj_in.weight", C, C), C, oi);
+  hn = Act();
+  for (int dd = 0; dd < depth; ++dd) {
+    const std::string b = pre + ".transformer_blocks." + std::to_string(dd);
+    {  // self-attention
+      Act qkv = ln_linear(t, b + ".norm1", {b + ".attn1.to_q.weight", b + ".attn1.to_k.weight", b + ".attn1.to_v.weight"}, {}, C, false, 0, false);
+      Act a = attention(0, qkv, nullptr, C, heads);
+      qkv = Act();
+      GemmOpt oo; oo.bias = wts.w_f32(b + ".attn1.to_out.0.bias", C); oo.res = &t; oo.out = &t;
+      linear(a, wts.w_linear(b + ".attn1.to_out.0.weight", C, C), C, oo);
+    }
+    if (cfg_half && dd == 0) {      // from here on the two CFG halves differ (their text contexts do)
+      t = expand_cfg(t);
+      x = expand_cfg(x);
+      if (x_full) *x_full = x;
+    }
+    if (cfg.kind != NR_KIND_SGM_UNET && !attn_fp8 && t.ld == C && nr_xattn_fused_eligible(C, heads, ctx_len, x.H * x.W, det_rows(t.rows()))) {
+      // C = 320, 8 heads, <= 80 context tokens, >= 4096 rows: the whole cross-attention block (LayerNorm, q projection, attention on the cached
+      // K | V of the clip, to_out + residual) in ONE launch that updates t in place (xattn.hip); q and the attention output never reach HBM
+      const int nctx = (int)(ctx_bf.rows() / ctx_len);      // ctx_bf is ONE "image" of B2 * ctx_len token rows
+      const Act kvs = context_kv(ctx_bf, b, C, [&](const Act& kv) {      // + the per-head LDS images of K | V
+        Act st = new_act_persistent(nctx, 1, 1, (int)(nr_xattn_kvstream_bytes(1) / sizeof(bf16)));
+        const bf16* kvp = kv.ptr; bf16* kvsp = st.ptr; const int ldkv = kv.ld, Lk = ctx_len;
+        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattn_kv_pack(kvp, ldkv, Lk, nctx, kvsp, s)); });
+        return st;
+      });
+      for (const char* wn : {".attn2.to_q.weight", ".attn2.to_out.0.weight"}) wts.check_shape(b + wn, wts.need(b + wn), {C, C});
+      const std::string sname = "xas:" + b + ".attn2.to_q.weight|" + b + ".attn2.to_out.0.weight";
+      const bf16* wstream = (const bf16*)wts.packed_from(sname, nr_xattn_wstream_bytes(), {"lin:" + b + ".attn2.to_q.weight", "lin:" + b + ".attn2.to_out.0.weight"},
+                                                         [&](void* d) {
+        const bf16* wq = wts.w_linear(b + ".attn2.to_q.weight", C, C);
+        const bf16* wo = wts.w_linear(b + ".attn2.to_out.0.weight", C, C);
+        LAUNCH_OK(nr_launch_xattn_w_pack(wq, wo, (bf16*)d, nullptr));
+      });
+      const float* gamma = wts.w_f32(b + ".norm2.weight", C);
+      const float* beta = wts.w_f32(b + ".norm2.bias", C);
+      const float* bo = wts.w_f32(b + ".attn2.to_out.0.bias", C);
+      bf16* tp = t.ptr; const bf16* kvsp = kvs.ptr;
+      const int nimg = t.nimg, hwx = x.H * x.W, ipc = F, Lk = ctx_len;
+      const double M = (double)t.rows();
+      char d[160];
+      snprintf(d, sizeof(d), "xattn_fused M=%d C=%d Lk=%d (LN, q, context attention, to_out + residual)", (int)t.rows(), C, Lk);
+      const int norot = det_batch ? 1 : 0;
+      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattn_fused(tp, nimg, hwx, ipc, nctx, Lk, wstream, kvsp, gamma, beta, bo, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
+           2.0 * M * C * 2.0 * C + 4.0 * M * (double)Lk * C, 2.0 * (2.0 * M * C + 2.0 * C * (double)C), d);
+      op_tap("xattn_fused", t);
+    } else if (cfg.kind != NR_KIND_SGM_UNET && !attn_fp8 && t.ld == C && nr_xattnw_eligible(C, heads, ctx_len, x.H * x.W, det_rows(t.rows()))) {
+      // C = 640 / 1280, 8 heads, <= 80 context tokens: LayerNorm (folded), the q projection and the attention on the cached K | V of the row's
+      // context in ONE launch per block (xattnw.hip); q never reaches HBM.  to_out + residual stays the GEMM below.
+      const int nctx = (int)(ctx_bf.rows() / ctx_len);
+      const Act kvs = context_kv(ctx_bf, b, C, [&](const Act& kv) {      // + the fragment images of K | V
+        Act st = new_act_persistent(1, 1, 1, (int)(nr_xattnw_kvstream_bytes(C, nctx) / sizeof(bf16)));
+        const bf16* kvp = kv.ptr; bf16* kvsp = st.ptr; const int ldkv = kv.ld, Lk = ctx_len, Cc = C;
+        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattnw_kv_pack(kvp, ldkv, Lk, nctx, Cc, kvsp, s)); });
+        return st;
+      });
+      const std::string nrm = b + ".norm2", wq = b + ".attn2.to_q.weight";
+      const std::string sname = "xaws:" + nrm + "|" + wq;
+      const bf16* wstream = (const bf16*)wts.packed_from(sname, nr_xattnw_wstream_bytes(C), {"lnw:" + nrm + "|" + wq + "|"}, [&](void* d) {      // from the folded [C][C] matrix
+        const LnW lwm = wts.w_ln_linear({wq}, {}, nrm, C, C, false, true);
+        LAUNCH_OK(nr_launch_xattnw_w_pack(lwm.w, C, (bf16*)d, nullptr));
+      });
+      const std::string tname = "xawt:" + nrm + "|" + wq;
+      const float* table = (const float*)wts.packed(tname, nr_xattnw_table_bytes(C), [&](void* d) {
+        const LnW lw = wts.w_ln_linear({wq}, {}, nrm, C, C, false, false);
+        LAUNCH_OK(nr_launch_xattnw_table_pack(lw.c, lw.b, C, (float*)d, nullptr));
+      });
+      if (dry) (void)wts.w_ln_linear({wq}, {}, nrm, C, C, false, false);      // shape checks in the sizing pass too
+      Act a = new_act(t.nimg, t.H, t.W, C);
+      const bf16* tp = t.ptr; bf16* ap = a.ptr; const bf16* kvsp = kvs.ptr;
+      const int nimg = t.nimg, hwx = x.H * x.W, ipc = F, Lk = ctx_len, Cc = C;
+      const double M = (double)t.rows();
+      char d[160];
+      snprintf(d, sizeof(d), "xattn_head M=%d C=%d Lk=%d (LN folded, q of 160 columns, context attention)", (int)t.rows(), C, Lk);
+      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattnw(tp, ap, nimg, hwx, ipc, nctx, Lk, Cc, wstream, kvsp, table, 1e-5f, s)); }, NR_PROF_IGEMM,
+           2.0 * M * C * (double)C + 4.0 * M * (double)Lk * C, 2.0 * (2.0 * M * C + C * (double)C), d);
+      op_tap("xattn_head", a);
+      GemmOpt oo; oo.bias = wts.w_f32(b + ".attn2.to_out.0.bias", C); oo.res = &t; oo.out = &t;
+      linear(a, wts.w_linear(b + ".attn2.to_out.0.weight", C, C), C, oo);
+    } else {  // cross-attention on the context (attention.py:100: context repeated per frame)
+      Act q = ln_linear(t, b + ".norm2", {b + ".attn2.to_q.weight"}, {}, C, false, 0, false);
+      Act kv = context_kv(ctx_bf, b, C);
+      Act a = attention(1, q, &kv, C, heads);
+      q = Act(); kv = Act();
+      GemmOpt oo; oo.bias = wts.w_f32(b + ".attn2.to_out.0.bias", C); oo.res = &t; oo.out = &t;
+      linear(a, wts.w_linear(b + ".attn2.to_out.0.weight", C, C), C, oo);
+    }
+    if (dd + 1 < depth) feed_forward(t, b + ".norm3", b + ".ff");
+  }
+  Act out = feed_forward_proj_out(x, t, pre + ".transformer_blocks." + std::to_string(depth - 1) + ".norm3",
+                                  pre + ".transformer_blocks." + std::to_string(depth - 1) + ".ff", pre);
+  tap(pre, out);
+  return out;
+}
+
+// VanillaTemporalModule -> TemporalTransformer3DModel.forward (motion_module.py:134-158)
+Act nr_net::temporal_module(const Act& x, const std::string& pre0) {
+  const std::string pre = pre0 + ".temporal_transformer";
+  const int C = x.C, heads = cfg.motion_num_heads;
+  if (F > cfg.motion_pe_max_len)
+    throw NrError(NR_ERR_ARG, "video_length " + std::to_string(F) + " exceeds temporal_position_encoding_max_len " +
+                                  std::to_string(cfg.motion_pe_max_len));
+  Act hn = groupnorm(x, nullptr, pre + ".norm", 1e-6f, 0);
+  GemmOpt oi; oi.bias = wts.w_f32(pre + ".proj_in.bias", C);
+  Act t = linear(hn, wts.w_linear(pre + ".proj_in.weight", C, C), C, oi);
+  hn = Act();
+  const std::string b = pre + ".transformer_blocks.0";
+  for (int k = 0; k < cfg.motion_num_attention_blocks; ++k) {
+    const std::string ab = b + ".attention_blocks." + std::to_string(k);
+    if (nr_tattn_fused_eligible(C, heads, F, x.H * x.W, det_rows(t.rows())) && t.ld == C) {
+      // C = 320, F = 16 or 32: the whole block (LayerNorm + PE, q|k|v, F x F attention per pixel and head, to_out + residual) in ONE launch
+      // that updates t in place (tattn.hip); q|k|v and the attention output never reach HBM
+      const std::string nrm = b + ".norms." + std::to_string(k);
+      for (const char* wn : {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"}) wts.check_shape(ab + wn, wts.need(ab + wn), {C, C});
+      const std::string sname = "tas:" + ab + ".to_q.weight|" + ab + ".to_k.weight|" + ab + ".to_v.weight|" + ab + ".to_out.0.weight";
+      const char* wn[4] = {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"};
+      const bf16* stream = (const bf16*)wts.packed_from(sname, nr_tattn_stream_bytes(), {"lin:" + ab + wn[0], "lin:" + ab + wn[1], "lin:" + ab + wn[2], "lin:" + ab + wn[3]},
+                                                        [&](void* d) {
+        const bf16* wm[4];
+        for (int i = 0; i < 4; ++i) wm[i] = wts.w_linear(ab + wn[i], C, C);
+        LAUNCH_OK(nr_launch_tattn_stream_pack(wm[0], wm[1], wm[2], wm[3], (bf16*)d, nullptr));
+      });
+      const float* gb = wts.b_ln_pe(nrm, F, C);
+      const float* gamma = wts.w_f32(nrm + ".weight", C);
+      const float* bo = wts.w_f32(ab + ".to_out.0.bias", C);
+      bf16* tp = t.ptr; const int nb2 = t.nimg / F, hw = x.H * x.W;
+      const double M = (double)t.rows();
+      char d[160];
+      snprintf(d, sizeof(d), "tattn_fused M=%d C=%d F=%d (LN+PE, q|k|v, attention, to_out + residual)", (int)t.rows(), C, F);
+      const int norot = det_batch ? 1 : 0;
+      const int Fn = F;
+      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_tattn_fused(tp, nb2, Fn, hw, stream, gamma, gb, bo, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
+           2.0 * M * C * 4.0 * C + 4.0 * (M / F) * heads * (double)F * F * (C / heads), 2.0 * (2.0 * M * C + 4.0 * C * (double)C), d);
+      op_tap("tattn_fused", t);
+      continue;
+    }
+    Act a;
+    if (nr_tattnw_eligible(C, heads, F, x.H * x.W, det_rows(t.rows())) && t.ld == C) {
+      // C = 640 / 1280, F = 16 or 32: LayerNorm + PE (folded), the q|k|v projection of one head and its F x F attention per (pixel group, head) in
+      // ONE launch (tattnw.hip); q|k|v never reach HBM.  to_out + residual stays the GEMM below.
+      const std::string nrm = b + ".norms." + std::to_string(k);
+      const std::vector<std::string> wk = {ab + ".to_q.weight", ab + ".to_k.weight", ab + ".to_v.weight"};
+      const float* rv = wts.pe_projection(wk, C, C, cfg.motion_pe_max_len);
+      const std::string sname = "taws:" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
+      const bf16* stream = (const bf16*)wts.packed_from(sname, nr_tattnw_stream_bytes(C), {"lnw:" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2] + "|"},
+                                                        [&](void* d) {      // from the folded [3C][C] matrix
+        const LnW lwm = wts.w_ln_linear(wk, {}, nrm, C, C, false, true);
+        LAUNCH_OK(nr_launch_tattnw_stream_pack(lwm.w, C, (bf16*)d, nullptr));
+      });
+      // the head-major epilogue table (LayerNorm-fold vectors + positional-encoding projections of the first F positions) the kernel stages
+      // through LDS: one per frame count a handle was planned with
+      const std::string tname = "tawe:" + std::to_string(cfg.motion_pe_max_len) + ":" + std::to_string(F) + ":" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
+      const float* table = (const float*)wts.packed(tname, nr_tattnw_table_bytes(C, F), [&](void* d) {
+        const LnW lw = wts.w_ln_linear(wk, {}, nrm, C, C, false, false);
+        LAUNCH_OK(nr_launch_tattnw_table_pack(lw.c, lw.b, rv, C, F, (float*)d, nullptr));
+      });
+      a = new_act(t.nimg, t.H, t.W, C);
+      const bf16* tp = t.ptr; bf16* ap = a.ptr;
+      const int nb2 = t.nimg / F, hw = x.H * x.W;
+      const double M = (double)t.rows();
+      char d[160];
+      snprintf(d, sizeof(d), "tattn_head M=%d C=%d F=%d (LN+PE folded, q|k|v of one head, FxF attention)", (int)t.rows(), C, F);
+      const int Fn = F;
+      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_tattnw(tp, ap, nb2, Fn, hw, C, stream, table, 1e-5f, s)); }, NR_PROF_IGEMM,
+           2.0 * M * C * 3.0 * C + 4.0 * (M / F) * heads * (double)F * F * (C / heads), 2.0 * (2.0 * M * C + 3.0 * C * (double)C), d);
+      op_tap("tattn_head", a);
+    } else {
+      // LayerNorm, then + pe[frame] (motion_module.py:212,277): both folded into the q|k|v GEMM
+      Act qkv = ln_linear(t, b + ".norms." + std::to_string(k), {ab + ".to_q.weight", ab + ".to_k.weight", ab + ".to_v.weight"}, {}, C,
+                          false, 0, true);
+      a = attention(2, qkv, nullptr, C, heads);
+    }
+    GemmOpt oo; oo.bias = wts.w_f32(ab + ".to_out.0.bias", C); oo.res = &t; oo.out = &t;
+    linear(a, wts.w_linear(ab + ".to_out.0.weight", C, C), C, oo);
+  }
+  Act out = feed_forward_proj_out(x, t, b + ".ff_norm", b + ".ff", pre);
+  tap(pre0, out);
+  return out;
+}
+
+// AttnBlock (model.py:161-201): GroupNorm -> q,k,v 1x1 convs -> single-head softmax(q k^T / sqrt(C)) v -> proj_out
+// + x.  The head dimension is the full channel count (512), beyond the flash kernels' register budget, so the
+// block is expressed as MFMA GEMMs per image: S = Q K^T (fp32 scores), row softmax -> bf16 P, O = P V.  V is
+// produced already transposed (V^T = Wv . Xn^T, i.e. the igemm with the weight as the "activation" operand); its
+// bias moves to the P V epilogue because every softmax row sums to one.
+Act nr_net::vae_attn(const Act& x, const std::string& pre) {
+  const int C = x.C, hw = x.H * x.W;
+  if (hw % 64 != 0) throw NrError(NR_ERR_UNSUPPORTED, "VAE attention: latent h*w must be a multiple of 64");
+  Act hn = groupnorm(x, nullptr, pre + ".norm", cfg.norm_eps, 0);
+  GemmOpt oq; oq.bias = wts.w_f32(pre + ".q.bias", C);
+  Act q = linear(hn, wts.w_linear(pre + ".q.weight", C, C), C, oq);
+  GemmOpt ok; ok.bias = wts.w_f32(pre + ".k.bias", C);
+  Act k = linear(hn, wts.w_linear(pre + ".k.weight", C, C), C, ok);
+  const bf16* wv = wts.w_linear(pre + ".v.weight", C, C);
+  const float* bv = wts.w_f32(pre + ".v.bias", C);
+  Act o = new_act(x.nimg, x.H, x.W, C);
+  {
+    auto vt = new_tmp((size_t)C * hw * sizeof(bf16));
+    auto sc = new_tmp((size_t)hw * hw * sizeof(float));
+    auto pr = new_tmp((size_t)hw * hw * sizeof(bf16));
+    bf16* vtp = at<bf16>(vt->off); float* scp = at<float>(sc->off); bf16* prp = at<bf16>(pr->off);
+    const float scale = 1.0f / std::sqrt((float)C);
+    for (int n = 0; n < x.nimg; ++n) {
+      const size_t off = (size_t)n * hw * C;
+      gemm_raw(wv, C, hn.ptr + off, C, hw, C, nullptr, vtp, hw, nullptr, "vae V^T");
+      gemm_raw(q.ptr + off, C, k.ptr + off, hw, hw, C, nullptr, nullptr, 0, scp, "vae QK^T");
+      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_softmax_rows(scp, prp, hw, hw, scale, s)); }, NR_PROF_ATTENTION,
+           5.0 * (double)hw * hw, 6.0 * (double)hw * hw, "softmax rows L=" + std::to_string(hw));
+      gemm_raw(prp, hw, vtp, hw, C, hw, bv, o.ptr + off, C, nullptr, "vae PV");
+    }
+  }
+  hn = Act(); q = Act(); k = Act();
+  GemmOpt op; op.bias = wts.w_f32(pre + ".proj_out.bias", C); op.res = &x;
+  Act out = linear(o, wts.w_linear(pre + ".proj_out.weight", C, C), C, op);
+  tap(pre, out);
+  return out;
+}

@@ -1,0 +1,315 @@
+// Single-op entry points of the C ABI (nr_op_*): test and tool hooks that launch ONE kernel class the way the engine's planner would, on
+// tensors in the engine's converted formats.  Host code only.
+#include "engine.h"
+
+using namespace nre;
+
+// grow-only device scratch of the op hooks (process lifetime).  Growing waits for the device first (the old buffer may still be read) and
+// returns true
+struct OpScratch { void* ptr = nullptr; size_t cap = 0; };
+static bool op_scratch(OpScratch& b, size_t need) {
+  if (need <= b.cap) return false;
+  if (b.ptr) { HIP_OK(hipDeviceSynchronize()); (void)hipFree(b.ptr); }
+  b.ptr = nullptr; b.cap = 0;
+  HIP_OK(hipMalloc(&b.ptr, need));
+  b.cap = need;
+  return true;
+}
+
+static float* op_workspace(const NrGemmParams& p) {
+  static OpScratch ws;
+  const size_t need = nr_igemm_workspace_bytes(&p);
+  op_scratch(ws, need);
+  return need ? (float*)ws.ptr : nullptr;
+}
+
+// Test / tool hooks and the panel-resident small-M kernel (smallm.hip): an eligible launch gets a fragment-major copy of its weights, packed on
+// the launch stream into a scratch buffer on EVERY call (tests: always consistent with the tensor passed in); NR_OP_FM_CACHE=1 keeps one
+// copy per weight pointer instead (timing tools that replay graphs over a pool of weights; nr_op_fm_cache_clear when the pool is freed)
+static std::map<const void*, bf16*> g_op_fm_cache;
+extern "C" void nr_op_fm_cache_clear() {
+  (void)hipDeviceSynchronize();
+  for (auto& kv : g_op_fm_cache) (void)hipFree(kv.second);
+  g_op_fm_cache.clear();
+}
+static void op_fragmajor(NrGemmParams& p, hipStream_t s) {
+  if (!nr_smallm_eligible(&p)) return;
+  const size_t need = (size_t)p.N * p.K * sizeof(bf16);
+  if (env_is_1("NR_OP_FM_CACHE")) {
+    auto it = g_op_fm_cache.find(p.w);
+    if (it == g_op_fm_cache.end()) {
+      bf16* d = nullptr;
+      HIP_OK(hipMalloc((void**)&d, need));
+      LAUNCH_OK(nr_launch_smallm_w_pack(p.w, d, p.N, p.K, s));
+      it = g_op_fm_cache.emplace(p.w, d).first;
+    }
+    p.w_fm = it->second;
+    return;
+  }
+  static OpScratch scratch;
+  op_scratch(scratch, need);
+  LAUNCH_OK(nr_launch_smallm_w_pack(p.w, scratch.ptr, p.N, p.K, s));
+  p.w_fm = (const bf16*)scratch.ptr;
+}
+
+// the engine's choice for short-K Linears on 2048..8192 rows (lin160.hip): the stage stream is packed on the launch stream on every call
+static bool op_lin160(const NrGemmParams& p, hipStream_t s) {
+  const int l1 = nr_lin160_eligible(&p);
+  if (!l1) return false;
+  static OpScratch buf;
+  op_scratch(buf, l1 == 4 ? nr_lin128q_stream_bytes(p.N, p.K) : nr_lin160_stream_bytes(p.N, p.K));
+  bf16* l160 = (bf16*)buf.ptr;
+  LAUNCH_OK(l1 == 4 ? nr_launch_lin128q_w_pack(p.w, p.N, p.K, l160, s) : nr_launch_lin160_w_pack(p.w, p.N, p.K, l160, s));
+  LAUNCH_OK(nr_launch_lin160(&p, l160, s));
+  return true;
+}
+
+extern "C" nr_status nr_op_gemm(nr_stream stream, const void* a, int32_t lda, const void* w, const float* bias,
+                                const void* res, int32_t ldr, void* out, int32_t ldo, int32_t M, int32_t N, int32_t K,
+                                int32_t geglu) {
+  NR_TRY
+  NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr, (bf16*)out, ldo);
+  p.geglu = geglu;
+  if (op_lin160(p, (hipStream_t)stream)) return NR_OK;
+  op_fragmajor(p, (hipStream_t)stream);
+  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
+  NR_CATCH
+}
+
+// two-source operand [a0 | a1] (the skip concat of unet_blocks.py:634,740 as a 1x1 GEMM; the [t | g] operand of the folded FeedForward)
+extern "C" nr_status nr_op_gemm2(nr_stream stream, const void* a0, int32_t c0, int32_t lda0, const void* a1, int32_t c1, int32_t lda1,
+                                 const void* w, const float* bias, const void* res, int32_t ldr, void* out, int32_t ldo, int32_t M, int32_t N) {
+  NR_TRY
+  NrGemmParams p = nr_gemm_params((const bf16*)a0, c0, lda0, (const bf16*)a1, c1, lda1, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr,
+                                  (bf16*)out, ldo);
+  op_fragmajor(p, (hipStream_t)stream);
+  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_ln_gemm(nr_stream stream, const void* a, int32_t lda, const void* w_scaled, const float* ln_c,
+                                   const float* bias_folded, float eps, const void* res, int32_t ldr, void* out, int32_t ldo,
+                                   int32_t M, int32_t N, int32_t K, int32_t geglu, int32_t act) {
+  NR_TRY
+  if (!ln_c) throw NrError(NR_ERR_ARG, "ln_c is required");
+  NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w_scaled, N, bias_folded, (const bf16*)res, ldr,
+                                  (bf16*)out, ldo);
+  p.geglu = geglu; p.ln_c = ln_c; p.ln_eps = eps; p.act = act;
+  if (op_lin160(p, (hipStream_t)stream)) return NR_OK;
+  op_fragmajor(p, (hipStream_t)stream);
+  LAUNCH_OK(nr_launch_igemm(&p, nullptr, (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_gemm_ex(nr_stream stream, const void* a, int32_t lda, const void* w, const float* bias, const float* ln_c,
+                                   float ln_eps, const float* rowvec, int32_t rowvec_div, int32_t rowvec_mod, int32_t rowvec_ld,
+                                   const void* res, int32_t ldr, void* out, int32_t ldo, int32_t M, int32_t N, int32_t K, int32_t geglu,
+                                   int32_t act, float out_scale) {
+  NR_TRY
+  NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr, (bf16*)out, ldo);
+  p.out_scale = out_scale; p.geglu = geglu; p.act = act;
+  p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_mod = rowvec_mod; p.rowvec_ld = rowvec_ld;
+  p.ln_c = ln_c; p.ln_eps = ln_eps;
+  op_fragmajor(p, (hipStream_t)stream);
+  LAUNCH_OK(nr_launch_igemm(&p, ln_c ? nullptr : op_workspace(p), (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_conv3x3(nr_stream stream, const void* x0, int32_t c0, const void* x1, int32_t c1, int32_t nimg,
+                                   int32_t H, int32_t W, int32_t stride, int32_t ups, const void* w, const float* bias,
+                                   const float* rowvec, int32_t rowvec_div, const void* res, void* out, int32_t Cout) {
+  NR_TRY
+  NrGemmParams p = nr_gemm_params((const bf16*)x0, c0, c0, (const bf16*)x1, c1, c1, nimg, H, W, 3, stride, ups, (const bf16*)w, Cout, bias, (const bf16*)res,
+                                  Cout, (bf16*)out, Cout);
+  p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
+  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_condembed_in(nr_stream stream, const float* cond, const float* mask, int32_t c0, int32_t nsrc, int32_t F, int32_t H,
+                                        int32_t W, const int32_t* fmap, int32_t nframes, const float* w, const float* bias, int32_t Cout,
+                                        void* out) {
+  NR_TRY
+  if (!fmap) throw NrError(NR_ERR_ARG, "fmap is null");
+  LAUNCH_OK(nr_launch_condembed_in(cond, mask, c0, nsrc, F, H, W, fmap, nframes, w, bias, Cout, (bf16*)out, (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_condembed_conv(nr_stream stream, const void* x, int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t stride,
+                                          const void* wfm, const float* bias, int32_t Cout, int32_t silu, void* out) {
+  NR_TRY
+  LAUNCH_OK(nr_launch_condembed_conv((const bf16*)x, nimg, H, W, Cin, stride, (const bf16*)wfm, bias, Cout, silu, (bf16*)out,
+                                     (hipStream_t)stream));
+  NR_CATCH
+}
+
+// as nr_op_conv3x3 (stride 1, no upsample, single source) with the weight in the tap-inner layout [Cout][Cin/64][3][3][64]
+extern "C" nr_status nr_op_conv3x3_tap_inner(nr_stream stream, const void* x0, int32_t c0, int32_t nimg, int32_t H, int32_t W, const void* w,
+                                             const float* bias, const float* rowvec, int32_t rowvec_div, const void* res, void* out,
+                                             int32_t Cout) {
+  NR_TRY
+  NrGemmParams p = nr_gemm_params((const bf16*)x0, c0, c0, nullptr, 0, 0, nimg, H, W, 3, 1, 0, (const bf16*)w, Cout, bias, (const bf16*)res, Cout, (bf16*)out,
+                                  Cout);
+  p.tap_inner = 1;
+  p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
+  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_groupnorm(nr_stream stream, const void* x0, int32_t c0, const void* x1, int32_t c1, int32_t nimg,
+                                     int32_t hw, int32_t groups, const float* gamma, const float* beta, float eps,
+                                     int32_t silu, float* partial_ws, void* out) {
+  NR_TRY
+  NrGnParams p = nr_gn_params((const bf16*)x0, c0, c0, (const bf16*)x1, c1, c1, nimg, hw, groups, gamma, beta, eps, silu, partial_ws, (bf16*)out,
+                              c0 + (x1 ? c1 : 0));
+  LAUNCH_OK(nr_launch_groupnorm(&p, (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_layernorm(nr_stream stream, const void* x, void* out, int32_t M, int32_t C, const float* gamma,
+                                     const float* beta, float eps, const float* pe, int32_t pe_hw, int32_t pe_F) {
+  NR_TRY
+  LAUNCH_OK(nr_launch_layernorm((const bf16*)x, C, (bf16*)out, C, M, C, gamma, beta, eps, pe, pe_hw > 0 ? pe_hw : 1,
+                                pe_F > 0 ? pe_F : 1, (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_op_attention(nr_stream stream, int32_t mode, const void* qp, const void* kvp, void* outp,
+                                     int32_t nimg, int32_t L, int32_t Lk, int32_t C, int32_t heads, int32_t frames,
+                                     int32_t kv_div) {
+  NR_TRY
+  const int fp8_flag = (mode & 8) ? 1 : 0;      // mode | 8: e4m3 MFMA operands (spatial / cross kernels)
+  const int causal_flag = (mode & 16) ? 1 : 0;  // mode | 16: causal mask (mode 0 only; the CLIP text encoder's form)
+  mode &= 7;
+  if (causal_flag && (mode != 0 || fp8_flag)) throw NrError(NR_ERR_ARG, "causal attention: mode 0 only");
+  if (mode > 2) throw NrError(NR_ERR_ARG, "bad attention mode");
+  // the hook's tensors are dense: q|k|v rows of 3C (modes 0 / 2), q rows of C and k|v rows of 2C (mode 1), output rows of C
+  const NrAttnParams p = nr_attn_params(mode, (const bf16*)qp, (const bf16*)kvp, (bf16*)outp, mode == 1 ? C : 3 * C, 2 * C, C, nimg, L, Lk, C, heads, frames, kv_div,
+                                        causal_flag, fp8_flag);
+  LAUNCH_OK(nr_launch_attention(&p, (hipStream_t)stream));
+  NR_CATCH
+}
+
+// ---- fused FeedForward + proj_out (ffpanel.hip), op-level entry for tests: inputs in the engine's converted formats ----
+extern "C" nr_status nr_op_ff_fused(nr_stream stream, const void* t_dev, const void* x_dev, void* out_dev, int32_t M, int32_t C,
+                                    const void* w1_geglu_dev, const float* gamma_dev, const float* beta_dev, const float* b1_geglu_dev,
+                                    const void* wc_dev, const float* bc_dev, float ln_eps) {
+  NR_TRY
+  if (!nr_ff_fused_eligible(C, 1 << 30)) throw NrError(NR_ERR_UNSUPPORTED, "the fused FeedForward kernel is built for C = 320");
+  static OpScratch buf;
+  op_scratch(buf, nr_ff_stream_bytes(C));
+  void* ws = buf.ptr;
+  // w1 == NULL: reuse the stage stream packed by the previous call (timing loops)
+  if (w1_geglu_dev) LAUNCH_OK(nr_launch_ff_stream_pack((const bf16*)w1_geglu_dev, (const bf16*)wc_dev, (bf16*)ws, (hipStream_t)stream));
+  LAUNCH_OK(nr_launch_ff_fused((const bf16*)t_dev, C, (const bf16*)x_dev, C, (bf16*)out_dev, C, M, (const bf16*)ws, gamma_dev, beta_dev,
+                               b1_geglu_dev, bc_dev, ln_eps, env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
+  NR_CATCH
+}
+
+// ---- fused temporal-attention block (tattn.hip), op-level entry for tests.  t: bf16 [nbatch * frames * hw][320], updated in place;
+// wq / wk / wv / wo: bf16 [320][320]; gamma fp32 [320]; gb fp32 [frames][320] = LayerNorm bias + positional encoding; bo fp32 [320];
+// frames = 16 or 32 ----
+extern "C" nr_status nr_op_tattn_fused_frames(nr_stream stream, void* t_dev, int32_t nbatch, int32_t frames, int32_t hw, const void* wq_dev,
+                                              const void* wk_dev, const void* wv_dev, const void* wo_dev, const float* gamma_dev,
+                                              const float* gb_dev, const float* bo_dev, float ln_eps) {
+  NR_TRY
+  if (!nr_tattn_fused_eligible(320, 8, frames, hw, 1 << 30))
+    throw NrError(NR_ERR_UNSUPPORTED, "fused temporal attention: C = 320, 8 heads, 16 or 32 frames, hw % (128 / frames) == 0");
+  static OpScratch buf;
+  op_scratch(buf, nr_tattn_stream_bytes());
+  void* ws = buf.ptr;
+  // wq == NULL: reuse the stream packed by the previous call (timing loops)
+  if (wq_dev) LAUNCH_OK(nr_launch_tattn_stream_pack((const bf16*)wq_dev, (const bf16*)wk_dev, (const bf16*)wv_dev, (const bf16*)wo_dev, (bf16*)ws,
+                                                    (hipStream_t)stream));
+  LAUNCH_OK(nr_launch_tattn_fused((bf16*)t_dev, nbatch, frames, hw, (const bf16*)ws, gamma_dev, gb_dev, bo_dev, ln_eps,
+                                  env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
+  NR_CATCH
+}
+extern "C" nr_status nr_op_xattn_fused(nr_stream stream, void* t_dev, int32_t nimg, int32_t hw, int32_t img_per_ctx, const void* wq_dev,
+                                       const void* wo_dev, const void* kv_dev, int32_t ldkv, int32_t Lk, int32_t nctx, const float* gamma_dev,
+                                       const float* beta_dev, const float* bo_dev, float ln_eps) {
+  NR_TRY
+  if (!t_dev || !kv_dev || !gamma_dev || !beta_dev || !bo_dev) throw NrError(NR_ERR_ARG, "null argument");
+  if (!nr_xattn_fused_eligible(320, 8, Lk, hw, 1 << 30) || nimg <= 0 || img_per_ctx <= 0 || nctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
+    throw NrError(NR_ERR_UNSUPPORTED, "fused cross attention: C = 320, 8 heads, Lk <= 80, hw % 128 == 0, one context per img_per_ctx images");
+  static OpScratch wbuf, kvbuf;
+  op_scratch(wbuf, nr_xattn_wstream_bytes());
+  op_scratch(kvbuf, nr_xattn_kvstream_bytes(nctx));
+  void* ws = wbuf.ptr;
+  void* kvs = kvbuf.ptr;
+  // wq == NULL: reuse the streams packed by the previous call (timing loops)
+  if (wq_dev) {
+    LAUNCH_OK(nr_launch_xattn_w_pack((const bf16*)wq_dev, (const bf16*)wo_dev, (bf16*)ws, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_xattn_kv_pack((const bf16*)kv_dev, ldkv, Lk, nctx, (bf16*)kvs, (hipStream_t)stream));
+  }
+  LAUNCH_OK(nr_launch_xattn_fused((bf16*)t_dev, nimg, hw, img_per_ctx, nctx, Lk, (const bf16*)ws, (const bf16*)kvs, gamma_dev, beta_dev, bo_dev, ln_eps,
+                                  env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
+  NR_CATCH
+}
+// ---- q projection + context attention above the C = 320 level (xattnw.hip), op-level entry for tests.  t: bf16 [nimg * hw][C] (C = 640 or 1280,
+// hw a multiple of 64); a: bf16, same shape (attention output before to_out); wq_folded: bf16 [C][C] = gamma-scaled rows of to_q; lnc / bias fp32 [C];
+// kv: bf16 [nctx * Lk][ldkv], K in columns [0, C), V in [C, 2C); image i attends to context i / img_per_ctx ----
+extern "C" nr_status nr_op_xattn_head(nr_stream stream, const void* t_dev, void* a_dev, int32_t nimg, int32_t hw, int32_t img_per_ctx, int32_t C,
+                                      const void* wq_folded_dev, const float* lnc_dev, const float* bias_dev, const void* kv_dev, int32_t ldkv, int32_t Lk,
+                                      int32_t nctx, float ln_eps) {
+  NR_TRY
+  if (!t_dev || !a_dev || !kv_dev) throw NrError(NR_ERR_ARG, "null argument");
+  if (!nr_xattnw_wstream_bytes(C) || nimg <= 0 || hw <= 0 || hw % 64 != 0 || Lk < 1 || Lk > 80 || nctx <= 0 || img_per_ctx <= 0 ||
+      (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
+    throw NrError(NR_ERR_UNSUPPORTED, "cross-attention head kernel: C = 640 or 1280, 8 heads, Lk <= 80, hw % 64 == 0, one context per img_per_ctx images");
+  static OpScratch wbuf[2], tbuf[2], kvbuf;      // weight stream and table: one per C
+  const int ci = C == 640 ? 0 : 1;
+  op_scratch(wbuf[ci], nr_xattnw_wstream_bytes(C));
+  op_scratch(tbuf[ci], nr_xattnw_table_bytes(C));
+  void* const ws = wbuf[ci].ptr;
+  void* const tbl = tbuf[ci].ptr;
+  const size_t need = nr_xattnw_kvstream_bytes(C, nctx);
+  if (op_scratch(kvbuf, need)) HIP_OK(hipMemset(kvbuf.ptr, 0, need));
+  void* kvs = kvbuf.ptr;
+  // wq_folded == NULL: reuse the streams packed by the previous call at this C (timing loops)
+  if (wq_folded_dev) {
+    if (!lnc_dev || !bias_dev) throw NrError(NR_ERR_ARG, "null argument");
+    LAUNCH_OK(nr_launch_xattnw_w_pack((const bf16*)wq_folded_dev, C, (bf16*)ws, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_xattnw_table_pack(lnc_dev, bias_dev, C, (float*)tbl, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_xattnw_kv_pack((const bf16*)kv_dev, ldkv, Lk, nctx, C, (bf16*)kvs, (hipStream_t)stream));
+  }
+  LAUNCH_OK(nr_launch_xattnw((const bf16*)t_dev, (bf16*)a_dev, nimg, hw, img_per_ctx, nctx, Lk, C, (const bf16*)ws, (const bf16*)kvs, (const float*)tbl,
+                             ln_eps, (hipStream_t)stream));
+  NR_CATCH
+}
+// ---- q|k|v projection of one head + F x F attention above the C = 320 level (tattnw.hip), op-level entry for tests.  t: bf16 [nbatch * frames * hw][C]
+// (C = 640 or 1280, frames = 16 or 32); a: bf16, same shape (attention output before to_out); w_folded: bf16 [3C][C] = gamma-scaled rows of
+// to_q | to_k | to_v; lnc / bias fp32 [3C]; rowvec fp32 [frames][3C] ----
+extern "C" nr_status nr_op_tattn_head_frames(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t frames, int32_t hw, int32_t C,
+                                             const void* w_folded_dev, const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
+  NR_TRY
+  if (!t_dev || !a_dev || !lnc_dev || !bias_dev || !rowvec_dev) throw NrError(NR_ERR_ARG, "null argument");
+  if (!nr_tattnw_stream_bytes(C) || (frames != 16 && frames != 32) || nbatch <= 0 || hw <= 0 || hw % (C == 640 ? 8 : 4) != 0)
+    throw NrError(NR_ERR_UNSUPPORTED, "temporal attention head kernel: C = 640 (hw % 8 == 0) or 1280 (hw % 4 == 0), 8 heads, 16 or 32 frames");
+  static OpScratch wbuf[2], tbuf[2][2];                                   // weight stream per C; table per [C][frames]: it is packed for one frame count
+  static int ws_frames[2] = {0, 0};                                       // the frame count of the last packing call at this C
+  const int ci = C == 640 ? 0 : 1, fi = frames == 16 ? 0 : 1;
+  op_scratch(wbuf[ci], nr_tattnw_stream_bytes(C));
+  op_scratch(tbuf[ci][fi], nr_tattnw_table_bytes(C, frames));
+  void* const w = wbuf[ci].ptr;
+  void* const tb = tbuf[ci][fi].ptr;
+  // w_folded == NULL: reuse the stream and the epilogue table packed by the previous call at this C (timing loops): same frame count only
+  if (w_folded_dev) {
+    LAUNCH_OK(nr_launch_tattnw_stream_pack((const bf16*)w_folded_dev, C, (bf16*)w, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_tattnw_table_pack(lnc_dev, bias_dev, rowvec_dev, C, frames, (float*)tb, (hipStream_t)stream));
+    ws_frames[ci] = frames;
+  } else if (ws_frames[ci] != frames) {
+    throw NrError(NR_ERR_ARG, "temporal attention head kernel: w_folded == NULL needs a previous call at this C and frame count");
+  }
+  LAUNCH_OK(nr_launch_tattnw((const bf16*)t_dev, (bf16*)a_dev, nbatch, frames, hw, C, (const bf16*)w, (const float*)tb, ln_eps, (hipStream_t)stream));
+  NR_CATCH
+}
+extern "C" nr_status nr_op_tattn_head(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t hw, int32_t C, const void* w_folded_dev,
+                                      const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
+  return nr_op_tattn_head_frames(stream, t_dev, a_dev, nbatch, 16, hw, C, w_folded_dev, lnc_dev, bias_dev, rowvec_dev, ln_eps);
+}
+extern "C" nr_status nr_op_tattn_fused(nr_stream stream, void* t_dev, int32_t nbatch, int32_t hw, const void* wq_dev, const void* wk_dev,
+                                       const void* wv_dev, const void* wo_dev, const float* gamma_dev, const float* gb_dev, const float* bo_dev,
+                                       float ln_eps) {
+  return nr_op_tattn_fused_frames(stream, t_dev, nbatch, 16, hw, wq_dev, wk_dev, wv_dev, wo_dev, gamma_dev, gb_dev, bo_dev, ln_eps);
+}

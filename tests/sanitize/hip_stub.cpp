@@ -2,19 +2,46 @@
 // host heap memory (so AddressSanitizer sees every weight-conversion upload, manifest offset and arena copy), kernel launches are no-ops
 // (nothing on this path reads kernel results on the host), streams / events / graphs are counted dummy objects.  Test infrastructure
 // only: never linked into libneurons_amd.so.
+//
+// NR_STUB_TRACE=<file> (tools/plan_equal.sh): one line per kernel launch ("L <kernel> <grid> <block> <dynamic LDS bytes>", the name as
+// registered by the kernel's translation unit), per device allocation ("M <bytes>") and per host-to-device copy ("C <bytes> <FNV-1a 64 of
+// the bytes>"): what a plan launches and every converted weight it uploads, as text that two builds of the engine can be diffed on.
 #include <hip/hip_runtime_api.h>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <string>
 
 static long g_live_allocs = 0, g_graphs = 0, g_captures = 0, g_launches = 0;
 static bool g_capturing = false;
 
+static FILE* trace() {
+  static FILE* f = getenv("NR_STUB_TRACE") ? fopen(getenv("NR_STUB_TRACE"), "w") : nullptr;
+  return f;
+}
+static std::map<const void*, std::string>& kernel_names() {      // filled by static constructors: no static-initialisation order to rely on
+  static std::map<const void*, std::string> m;
+  return m;
+}
+static unsigned long long fnv1a64(const void* p, size_t n) {
+  unsigned long long h = 0xcbf29ce484222325ull;
+  for (size_t i = 0; i < n; ++i) { h ^= ((const unsigned char*)p)[i]; h *= 0x100000001b3ull; }
+  return h;
+}
+
 extern "C" {
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
-hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); ++g_live_allocs; return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipMalloc(void** p, size_t n) {
+  if (FILE* t = trace()) fprintf(t, "M %zu\n", n);
+  *p = malloc(n ? n : 1); ++g_live_allocs; return *p ? hipSuccess : hipErrorOutOfMemory;
+}
 hipError_t hipFree(void* p) { if (p) { free(p); --g_live_allocs; } return hipSuccess; }
-hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind kind) {
+  if (FILE* t = kind == hipMemcpyHostToDevice ? trace() : nullptr) fprintf(t, "C %zu %016llx\n", n, fnv1a64(s, n));
+  memcpy(d, s, n); return hipSuccess;
+}
 hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
 hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
@@ -38,12 +65,18 @@ hipError_t hipGraphInstantiate(hipGraphExec_t* e, hipGraph_t, hipGraphNode_t*, c
 hipError_t hipGraphDestroy(hipGraph_t g) { free(g); return hipSuccess; }
 hipError_t hipGraphExecDestroy(hipGraphExec_t e) { free(e); --g_graphs; return hipSuccess; }
 hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipSuccess; }
-hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t) { ++g_launches; return hipSuccess; }
+hipError_t hipLaunchKernel(const void* fn, dim3 g, dim3 b, void**, size_t shm, hipStream_t) {
+  if (FILE* t = trace()) {
+    auto it = kernel_names().find(fn);
+    fprintf(t, "L %s %u,%u,%u %u,%u,%u %zu\n", it == kernel_names().end() ? "?" : it->second.c_str(), g.x, g.y, g.z, b.x, b.y, b.z, shm);
+  }
+  ++g_launches; return hipSuccess;
+}
 // registration / launch-configuration hooks the host side of every __global__ function references
 struct CallCfg { dim3 g, b; size_t shm; hipStream_t s; };
 static thread_local CallCfg g_cfg;
 void** __hipRegisterFatBinary(const void*) { static void* h = nullptr; return &h; }
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+void __hipRegisterFunction(void**, const void* host_fn, char*, const char* name, unsigned, void*, void*, void*, void*, int*) { kernel_names()[host_fn] = name; }
 void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
 void __hipUnregisterFatBinary(void**) {}
 hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t shm, hipStream_t s) { g_cfg = CallCfg{g, b, shm, s}; return hipSuccess; }

@@ -5,7 +5,7 @@
 #   tools/isa_equal.sh <git-rev> [extra compile flags, e.g. -DNR_STAMP]
 #
 # Exports <git-rev>'s neurons_amd/csrc and include into a temporary directory (git archive: the working tree is not touched), compiles every
-# kernel file of the Makefile's SRCS (all but engine.hip, which has no device code of its own) of both trees to device-only assembly with each
+# kernel file of the Makefile's SRCS (all but the engine*.hip files, which are host code; FILES=engine.hip compares its two small kernels) of both trees to device-only assembly with each
 # tree's own Makefile flags (CXXFLAGS, NOPK, FLAGS_<name>; read from the Makefile, not retyped here) and compares the two texts per file.
 # One line per file: "identical", or "DIFFERS" and the first differing lines.  Exit status 1 if any file differs.
 # The only normalisation: the per-compile __hip_cuid_<hex> symbol becomes a fixed token (two compiles of the same source differ in exactly that).
@@ -25,7 +25,7 @@ git -C "$root" archive "$rev" neurons_amd/csrc include | tar -x -C "$tmp/old"
 
 # a second makefile on top of the tree's own: prints its variables
 cat > "$tmp/vars.mk" <<'EOF'
-isa-srcs: ; @echo $(filter-out engine.hip,$(SRCS))
+isa-srcs: ; @echo $(filter-out engine.hip engine_weights.hip engine_layers.hip engine_nets.hip engine_ops.hip,$(SRCS))
 isa-flags-%: ; @echo $(CXXFLAGS) $(NOPK) $(FLAGS_$*)
 isa-hipcc: ; @echo $(HIPCC)
 EOF

@@ -1,0 +1,71 @@
+#!/usr/bin/env bash
+# Does the working tree's engine plan what a git revision's engine plans?  The acceptance instrument of a host-side engine refactor: the same
+# op list, workspace, converted weights (names, sizes, bytes) and kernel launches need no GPU A/B.
+#
+#   tools/plan_equal.sh <git-rev>
+#
+# Exports <git-rev>'s neurons_amd/csrc and include into a temporary directory (git archive: the working tree is not touched), builds both trees
+# host-only and without a sanitizer against the WORKING TREE's stand-in HIP runtime (tests/sanitize/hip_stub.cpp) and plan-dump driver
+# (tests/sanitize/plan_dump.cpp), runs both on the schema of tools/plan_schema.py and compares, per run, the driver's dump (op descriptions,
+# workspace and weight bytes, export manifest) and the stub's trace (every kernel launch with grid / block / LDS bytes, every device allocation,
+# size and hash of every uploaded weight).  Runs: every network at its listed shapes, then the C = 320 leaf modules once per planner switch that a
+# process reads once (NR_LN_FUSE=0, NR_FOLD_PROJ_OUT=0, NR_SMALLM=0).  One line per run: "identical", or "DIFFERS" and the first differing lines.
+# The dump must also contain every kernel class the planner can choose (a shape list that loses one is no evidence).  Exit status 1 on any of it.
+# The only normalisation: pointer values (0x...) become a fixed token.  Needs no GPU.  JOBS=<n> compiles in parallel (default 8, at most 16).
+set -euo pipefail
+
+[ $# -eq 1 ] || { echo "usage: $0 <git-rev>" >&2; exit 2; }
+rev=$1
+jobs=${JOBS:-8}; [ "$jobs" -le 16 ] || jobs=16
+root=$(git -C "$(dirname "$0")" rev-parse --show-toplevel)
+tmp=$(mktemp -d)
+trap 'rm -rf "$tmp"' EXIT
+
+mkdir -p "$tmp/old"
+git -C "$root" archive "$rev" neurons_amd/csrc include | tar -x -C "$tmp/old"
+python "$root/tools/plan_schema.py" "$tmp/schema.txt"
+
+# one tree: $1 = old | new, $2 = its root
+build_one() {
+  local srcs
+  srcs=$(cd "$2/neurons_amd/csrc" && ls ./*.hip | sed -e 's|^\./||' -e 's|\.hip$||' | tr '\n' ' ')
+  make -s -C "$root/tests/sanitize" -j"$jobs" SAN= OUT="$tmp/$1/build" SRC="$2/neurons_amd/csrc" INC="$2/include" SRCS="$srcs" "$tmp/$1/build/plan_dump" \
+    > "$tmp/$1.build.log" 2>&1 || { echo "$1: build failed" >&2; tail -n 30 "$tmp/$1.build.log" >&2; exit 1; }
+}
+build_one old "$tmp/old"
+build_one new "$root"
+
+# one run of both trees: $1 = label, $2 = networks ("" = all), rest = environment
+run_both() {
+  local label=$1 only=$2 t; shift 2
+  for t in old new; do
+    env -u NR_DETERMINISTIC_BATCH "$@" NR_STUB_TRACE="$tmp/$t.$label.trace" "$tmp/$t/build/plan_dump" "$tmp/schema.txt" $only > "$tmp/$t.$label.dump" ||
+      { echo "$t $label: plan_dump failed" >&2; exit 1; }
+    sed -E -i 's/0x[0-9a-f]+/PTR/g' "$tmp/$t.$label.dump" "$tmp/$t.$label.trace"
+  done
+}
+run_both default ""
+run_both ln_fuse_0 leaf_transformer,leaf_temporal NR_LN_FUSE=0
+run_both fold_proj_out_0 leaf_transformer,leaf_temporal NR_FOLD_PROJ_OUT=0
+run_both smallm_0 leaf_transformer,leaf_temporal NR_SMALLM=0
+
+echo "# plans of the working tree against $rev ($(git -C "$root" rev-parse --short "$rev"))"
+status=0
+for label in default ln_fuse_0 fold_proj_out_0 smallm_0; do
+  for what in dump trace; do
+    a="$tmp/old.$label.$what"; b="$tmp/new.$label.$what"
+    if cmp -s "$a" "$b"; then
+      echo "$label $what: identical ($(wc -l < "$b") lines, $(grep -c -E '^(== |L )' "$b") $([ $what = dump ] && echo plans || echo launches))"
+    else
+      echo "$label $what: DIFFERS"; status=1
+      diff "$a" "$b" | head -n 12 | sed 's/^/    /' || true
+    fi
+  done
+done
+# coverage: <rev>'s own default dump plans every kernel class
+for k in ff_fused xattn_fused xattn_head tattn_fused tattn_head 'lin160 ' 'lin160 panel' igemm groupnorm layernorm attention; do
+  n=$(grep -c -E "^op [0-9]+: $k" "$tmp/old.default.dump" || true)
+  echo "coverage '$k': $n ops in $rev's dump"
+  [ "$n" -gt 0 ] || status=1
+done
+exit $status
