@@ -472,16 +472,10 @@ int launch_attn(const NrAttnParams& p, hipStream_t stream) {
     constexpr int KSV = (DT * 16) % 32 == 16 ? DT * 16 : DT * 16 + 16;
     const size_t shm = (size_t)2 * KT2 * (KSK + KSV) * sizeof(bf16);
     static unsigned long long attr_mask = 0;       // per device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!(attr_mask >> (dev & 63) & 1ull)) {
-      (void)hipFuncSetAttribute((const void*)attn_fwd_shared_kernel<DK, DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-      (void)hipFuncSetAttribute((const void*)attn_fwd_shared_kernel<DK, DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-      if constexpr (DK == 2 && DT == 3) {
-        (void)hipFuncSetAttribute((const void*)attn_fwd_shared_kernel<DK, DT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn_fwd_shared_kernel<DK, DT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-      }
-      attr_mask |= 1ull << (dev & 63);
+    (void)nr_lds_opt_in(attr_mask, {(const void*)attn_fwd_shared_kernel<DK, DT, false>, (const void*)attn_fwd_shared_kernel<DK, DT, true>}, 100 * 1024);
+    if constexpr (DK == 2 && DT == 3) {
+      static unsigned long long attr_mask_fp8 = 0;
+      (void)nr_lds_opt_in(attr_mask_fp8, {(const void*)attn_fwd_shared_kernel<DK, DT, false, true>, (const void*)attn_fwd_shared_kernel<DK, DT, true, true>}, 100 * 1024);
     }
     const int qblocks = (p.Lq + 63) / 64;
     const unsigned blocks = (unsigned)((long long)p.nbatch * p.heads * qblocks);

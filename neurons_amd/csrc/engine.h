@@ -75,10 +75,6 @@ inline bool env_is_1(const char* name) {
   const char* v = getenv(name);
   return v && v[0] == '1';
 }
-inline bool env_not_0(const char* name) {
-  const char* v = getenv(name);
-  return !(v && v[0] == '0');
-}
 
 struct HostTensor {
   std::vector<float> data;
@@ -266,8 +262,7 @@ struct WeightStore {
   const float* w_f32(const std::string& key, int64_t n) { return w_f32(key, {n}); }
   const float* pe_table(int C, int max_len);                                                        // "pe:"
   const float* b_ln_pe(const std::string& ln, int F, int C);                                        // "tagb:"
-  const bf16* w_fragmajor(const bf16* w, int N, int K);                                             // "fm:<name of w>"
-  const bf16* w_lin160(const bf16* w, int N, int K, bool panel = false);                            // "l160:" / "l128:<name of w>"
+  const bf16* w_layout(const bf16* w, int N, int K, int layout);                                    // "fm:" / "l160:" / "l128:<name of w>" (NrWeightLayout)
 };
 
 }  // namespace nre
@@ -371,7 +366,7 @@ struct nr_net {
   T* new_scratch(size_t count) { return at<T>(arena.alloc(count * sizeof(T))); }
   // temporary fp32 scratch with lifetime of the returned handle
   std::shared_ptr<Buf> new_tmp(size_t bytes);
-  // split-K slabs of an igemm (nr_igemm_workspace_bytes; small-M / huge-K layers): scratch with the lifetime of the returned handle, null if none
+  // split-K slabs of an igemm (NrGemmRoute::ws_bytes; small-M / huge-K layers): scratch with the lifetime of the returned handle, null if none
   struct SplitK { std::shared_ptr<Buf> buf; float* ws = nullptr; };
   SplitK splitk_scratch(size_t bytes);
   void emit(std::function<void(hipStream_t)> fn, int kind = NR_PROF_OTHER, double flops = 0, double bytes = 0, const std::string& desc = std::string());

@@ -116,29 +116,21 @@ Act nr_net::conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksiz
   p.out_scale = o.scale; p.geglu = o.geglu; p.pad_tl0 = o.pad_tl0; p.act = o.act; p.ln_c = o.ln_c; p.ln_eps = 1e-5f;
   p.tap_inner = o.tap_inner;
   p.plan_m = det_batch ? (int)det_rows(p.M) : 0;
-  if (ksize == 1 && nr_smallm_eligible(&p))               // M <= 512 Linears: the panel-resident kernel reads fragment-major weights
-    p.w_fm = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : wts.w_fragmajor(w, Cout, p.K);
-  if (const int l1 = (ksize == 1 && !p.w_fm) ? nr_lin160_eligible(&p) : 0) {
-    // short-K Linear (K = 640 / 1280) on >= 2048 rows: the stage-stream kernel (lin160.hip) instead of the tiled igemm; 4 = its register-panel form
-    const bf16* stream = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : wts.w_lin160(w, Cout, p.K, l1 == 4);
-    char d[160];
-    snprintf(d, sizeof(d), "%s M=%d N=%d K=%d res=%d geglu=%d ln=%d", l1 == 4 ? "lin160 panel" : "lin160", p.M, p.N, p.K, o.res ? 1 : 0, p.geglu, p.ln_c ? 1 : 0);
-    const double bytes = 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * outC * (o.res ? 2.0 : 1.0));
-    emit([p, stream](hipStream_t s) { LAUNCH_OK(nr_launch_lin160(&p, stream, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
-    op_tap("lin160", out);
-    return out;
-  }
-  {
-    const double in_elems = (double)x0.rows() * (p.c0 + p.c1);   // every input element is needed at least once
-    const double bytes = 2.0 * (in_elems + (double)p.N * p.K + (double)p.M * outC + (o.res ? (double)p.M * outC : 0.0));
-    char d[160];
-    snprintf(d, sizeof(d), "igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0);
-    const SplitK sk = splitk_scratch(nr_igemm_workspace_bytes(&p));
-    float* ws = sk.ws;
-    emit([p, ws](hipStream_t s) { LAUNCH_OK(nr_launch_igemm(&p, ws, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
-    if (ws) last_op_launches(2);           // split-K: the igemm + its reduce kernel
-    op_tap(ksize == 3 ? "conv3" : (p.ln_c ? "lngemm" : "gemm"), out);
-  }
+  NrGemmRoute r;
+  LAUNCH_OK(nr_gemm_route(&p, &r));
+  // the weights as the chosen kernel reads them: fragment-major for the M <= 512 Linears (smallm.hip), a stage stream for the short-K Linears on >= 2048 rows (lin160.hip)
+  const bf16* wk = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : wts.w_layout(w, Cout, p.K, r.weight_layout);
+  const double in_elems = (double)x0.rows() * (p.c0 + p.c1);   // every input element is needed at least once
+  const double bytes = 2.0 * (in_elems + (double)p.N * p.K + (double)p.M * outC + (o.res ? (double)p.M * outC : 0.0));
+  const bool l160 = r.cls == NR_GEMM_LIN160;
+  char d[160];
+  if (l160) snprintf(d, sizeof(d), "%s M=%d N=%d K=%d res=%d geglu=%d ln=%d", r.lin160.form == 4 ? "lin160 panel" : "lin160", p.M, p.N, p.K, o.res ? 1 : 0, p.geglu, p.ln_c ? 1 : 0);
+  else snprintf(d, sizeof(d), "igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0);
+  const SplitK sk = splitk_scratch(r.ws_bytes);
+  float* ws = sk.ws;
+  emit([p, r, wk, ws](hipStream_t s) { LAUNCH_OK(nr_launch_gemm(&p, &r, wk, ws, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
+  if (ws) last_op_launches(2);           // split-K: the igemm + its reduce kernel
+  op_tap(l160 ? "lin160" : (ksize == 3 ? "conv3" : (p.ln_c ? "lngemm" : "gemm")), out);
   return out;
 }
 
@@ -148,11 +140,13 @@ void nr_net::gemm_raw(const bf16* a, int lda, const bf16* w, int M, int N, int K
   NrGemmParams p = nr_gemm_params(a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, w, N, bias, nullptr, 0, out, ldo);
   p.out_f32 = out32;
   p.plan_m = det_batch ? (int)det_rows(M) : 0;
-  const SplitK sk = splitk_scratch(nr_igemm_workspace_bytes(&p));
+  NrGemmRoute r;                         // W may be an activation (attention scores): only the kernels that read it as it lies
+  LAUNCH_OK(nr_gemm_route_rowmajor(&p, &r));
+  const SplitK sk = splitk_scratch(r.ws_bytes);
   float* ws = sk.ws;
   char d[160];
   snprintf(d, sizeof(d), "igemm %s M=%d N=%d K=%d", what, M, N, K);
-  emit([p, ws](hipStream_t s) { LAUNCH_OK(nr_launch_igemm(&p, ws, s)); }, NR_PROF_IGEMM, 2.0 * M * (double)N * K,
+  emit([p, r, ws](hipStream_t s) { LAUNCH_OK(nr_launch_gemm(&p, &r, p.w, ws, s)); }, NR_PROF_IGEMM, 2.0 * M * (double)N * K,
        2.0 * ((double)M * K + (double)N * K) + (out32 ? 4.0 : 2.0) * (double)M * N, d);
 }
 

@@ -383,18 +383,19 @@ void nr_net::cond_embedding(Act& x, int nd, const int* fmap_reduce, const int* f
     eo = new_act(B2 * Fe, H, W, C0);
     NrGemmParams p = nr_gemm_params(e.ptr, cl, cl, nullptr, 0, 0, Fe, H, W, 3, 1, 0, wts.w_conv3(pre + "conv_out.weight", C0, cl), C0, bo, nullptr, 0, eo.ptr, C0);
     size_t wsb = 0;                                  // split-K scratch for the largest need of any cond_batch dividing B2
+    std::vector<NrGemmRoute> routes((size_t)B2 + 1); // one route per such cond_batch
     for (int cb = 1; cb <= B2; ++cb)
-      if (B2 % cb == 0) { p.M = cb * Fe * H * W; wsb = std::max(wsb, nr_igemm_workspace_bytes(&p)); }
+      if (B2 % cb == 0) { p.M = cb * Fe * H * W; LAUNCH_OK(nr_gemm_route(&p, &routes[cb])); wsb = std::max(wsb, routes[cb].ws_bytes); }
     const SplitK sk = splitk_scratch(wsb);
     float* ws = sk.ws;
     p.M = Fe * H * W;
     char d[160];
     snprintf(d, sizeof(d), "igemm ks=3 s=1 ups=0 M=%d N=%d K=%d condembed conv_out frames=%d", p.M, p.N, p.K, Fe);
     const int hw = H * W;
-    emit([this, p, ws, Fe, hw](hipStream_t s) {
+    emit([this, p, routes, ws, Fe, hw](hipStream_t s) {
       NrGemmParams q = p;
       q.M = io.cond_batch * Fe * hw;
-      LAUNCH_OK(nr_launch_igemm(&q, ws, s));
+      LAUNCH_OK(nr_launch_gemm(&q, &routes[io.cond_batch], q.w, ws, s));
     }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, 2.0 * ((double)p.M * cl + (double)p.N * p.K + (double)p.M * C0), d);
   } else {
     eo = embed_conv(e, Fe, pre + "conv_out", C0, 1, 0, bo);
@@ -592,13 +593,15 @@ void nr_net::build() {
       const float* bias = wts.w_f32(key + ".bias", src.C);
       NrGemmParams p = nr_gemm_params(src.ptr, src.C, src.ld, nullptr, 0, 0, src.nimg, src.H, src.W, 1, 1, 0, w, src.C, bias, nullptr, 0, nullptr, src.C);   // out: at launch
       p.plan_m = det_batch ? (int)det_rows(p.M) : 0;
-      const SplitK sk = splitk_scratch(nr_igemm_workspace_bytes(&p));
+      NrGemmRoute r;                     // the epilogue scale arrives at launch: only the kernels that take any
+      LAUNCH_OK(nr_gemm_route_rowmajor(&p, &r));
+      const SplitK sk = splitk_scratch(r.ws_bytes);
       float* ws = sk.ws;
-      emit([this, p, i, is_mid, ws](hipStream_t s) {
+      emit([this, p, r, i, is_mid, ws](hipStream_t s) {
         NrGemmParams q = p;
         q.out = (bf16*)(is_mid ? io.out_mid : io.out_down[i]);
         q.out_scale = io.scale;
-        LAUNCH_OK(nr_launch_igemm(&q, ws, s));
+        LAUNCH_OK(nr_launch_gemm(&q, &r, q.w, ws, s));
       }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, 2.0 * (2.0 * p.M * (double)p.N + (double)p.N * p.K));
     }
     return;

@@ -1,6 +1,7 @@
 // Single-op entry points of the C ABI (nr_op_*): test and tool hooks that launch ONE kernel class the way the engine's planner would, on
 // tensors in the engine's converted formats.  Host code only.
 #include "engine.h"
+#include <tuple>
 
 using namespace nre;
 
@@ -16,52 +17,43 @@ static bool op_scratch(OpScratch& b, size_t need) {
   return true;
 }
 
-static float* op_workspace(const NrGemmParams& p) {
-  static OpScratch ws;
-  const size_t need = nr_igemm_workspace_bytes(&p);
-  op_scratch(ws, need);
-  return need ? (float*)ws.ptr : nullptr;
-}
-
-// Test / tool hooks and the panel-resident small-M kernel (smallm.hip): an eligible launch gets a fragment-major copy of its weights, packed on
-// the launch stream into a scratch buffer on EVERY call (tests: always consistent with the tensor passed in); NR_OP_FM_CACHE=1 keeps one
-// copy per weight pointer instead (timing tools that replay graphs over a pool of weights; nr_op_fm_cache_clear when the pool is freed)
-static std::map<const void*, bf16*> g_op_fm_cache;
+// One GEMM / conv launch the way the engine's planner would make it: route, pack, launch.  A route that names a packed weight layout (fragment-major
+// for smallm.hip, the stage streams of lin160.hip) gets that copy packed on the launch stream into a scratch buffer of its layout on EVERY call
+// (tests: always consistent with the tensor passed in); NR_OP_FM_CACHE=1 keeps one copy per (weight pointer, layout, shape) instead (timing tools
+// that replay graphs over a pool of weights; nr_op_fm_cache_clear when the pool is freed)
+static std::map<std::tuple<const void*, int, int, int>, bf16*> g_op_fm_cache;
 extern "C" void nr_op_fm_cache_clear() {
   (void)hipDeviceSynchronize();
   for (auto& kv : g_op_fm_cache) (void)hipFree(kv.second);
   g_op_fm_cache.clear();
 }
-static void op_fragmajor(NrGemmParams& p, hipStream_t s) {
-  if (!nr_smallm_eligible(&p)) return;
-  const size_t need = (size_t)p.N * p.K * sizeof(bf16);
+static const bf16* op_pack(const NrGemmParams& p, const NrGemmRoute& r, hipStream_t s) {
+  if (r.weight_layout == NR_W_ROWMAJOR || r.weight_layout == NR_W_TAP_INNER) return p.w;      // the kernel reads the matrix as the caller holds it
+  const size_t need = nr_gemm_packed_bytes(r.weight_layout, p.N, p.K);
+  if (!need) throw NrError(NR_ERR_STATE, "op_pack: shape has no packed form");
   if (env_is_1("NR_OP_FM_CACHE")) {
-    auto it = g_op_fm_cache.find(p.w);
+    auto it = g_op_fm_cache.find({p.w, r.weight_layout, p.N, p.K});
     if (it == g_op_fm_cache.end()) {
       bf16* d = nullptr;
       HIP_OK(hipMalloc((void**)&d, need));
-      LAUNCH_OK(nr_launch_smallm_w_pack(p.w, d, p.N, p.K, s));
-      it = g_op_fm_cache.emplace(p.w, d).first;
+      LAUNCH_OK(nr_launch_gemm_w_pack(r.weight_layout, p.w, p.N, p.K, d, s));
+      it = g_op_fm_cache.emplace(std::make_tuple(p.w, r.weight_layout, p.N, p.K), d).first;
     }
-    p.w_fm = it->second;
-    return;
+    return it->second;
   }
-  static OpScratch scratch;
-  op_scratch(scratch, need);
-  LAUNCH_OK(nr_launch_smallm_w_pack(p.w, scratch.ptr, p.N, p.K, s));
-  p.w_fm = (const bf16*)scratch.ptr;
+  static OpScratch scratch[2];                   // fragment-major copies | stage streams
+  OpScratch& b = scratch[r.weight_layout == NR_W_FRAGMAJOR ? 0 : 1];
+  op_scratch(b, need);
+  LAUNCH_OK(nr_launch_gemm_w_pack(r.weight_layout, p.w, p.N, p.K, (bf16*)b.ptr, s));
+  return (const bf16*)b.ptr;
 }
-
-// the engine's choice for short-K Linears on 2048..8192 rows (lin160.hip): the stage stream is packed on the launch stream on every call
-static bool op_lin160(const NrGemmParams& p, hipStream_t s) {
-  const int l1 = nr_lin160_eligible(&p);
-  if (!l1) return false;
-  static OpScratch buf;
-  op_scratch(buf, l1 == 4 ? nr_lin128q_stream_bytes(p.N, p.K) : nr_lin160_stream_bytes(p.N, p.K));
-  bf16* l160 = (bf16*)buf.ptr;
-  LAUNCH_OK(l1 == 4 ? nr_launch_lin128q_w_pack(p.w, p.N, p.K, l160, s) : nr_launch_lin160_w_pack(p.w, p.N, p.K, l160, s));
-  LAUNCH_OK(nr_launch_lin160(&p, l160, s));
-  return true;
+static void op_gemm(const NrGemmParams& p, hipStream_t s) {
+  NrGemmRoute r;
+  LAUNCH_OK(nr_gemm_route(&p, &r));
+  const bf16* wk = op_pack(p, r, s);
+  static OpScratch ws;
+  op_scratch(ws, r.ws_bytes);
+  LAUNCH_OK(nr_launch_gemm(&p, &r, wk, r.ws_bytes ? (float*)ws.ptr : nullptr, s));
 }
 
 extern "C" nr_status nr_op_gemm(nr_stream stream, const void* a, int32_t lda, const void* w, const float* bias,
@@ -70,9 +62,7 @@ extern "C" nr_status nr_op_gemm(nr_stream stream, const void* a, int32_t lda, co
   NR_TRY
   NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr, (bf16*)out, ldo);
   p.geglu = geglu;
-  if (op_lin160(p, (hipStream_t)stream)) return NR_OK;
-  op_fragmajor(p, (hipStream_t)stream);
-  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
+  op_gemm(p, (hipStream_t)stream);
   NR_CATCH
 }
 
@@ -82,8 +72,7 @@ extern "C" nr_status nr_op_gemm2(nr_stream stream, const void* a0, int32_t c0, i
   NR_TRY
   NrGemmParams p = nr_gemm_params((const bf16*)a0, c0, lda0, (const bf16*)a1, c1, lda1, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr,
                                   (bf16*)out, ldo);
-  op_fragmajor(p, (hipStream_t)stream);
-  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
+  op_gemm(p, (hipStream_t)stream);
   NR_CATCH
 }
 
@@ -95,9 +84,7 @@ extern "C" nr_status nr_op_ln_gemm(nr_stream stream, const void* a, int32_t lda,
   NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w_scaled, N, bias_folded, (const bf16*)res, ldr,
                                   (bf16*)out, ldo);
   p.geglu = geglu; p.ln_c = ln_c; p.ln_eps = eps; p.act = act;
-  if (op_lin160(p, (hipStream_t)stream)) return NR_OK;
-  op_fragmajor(p, (hipStream_t)stream);
-  LAUNCH_OK(nr_launch_igemm(&p, nullptr, (hipStream_t)stream));
+  op_gemm(p, (hipStream_t)stream);
   NR_CATCH
 }
 
@@ -110,8 +97,7 @@ extern "C" nr_status nr_op_gemm_ex(nr_stream stream, const void* a, int32_t lda,
   p.out_scale = out_scale; p.geglu = geglu; p.act = act;
   p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_mod = rowvec_mod; p.rowvec_ld = rowvec_ld;
   p.ln_c = ln_c; p.ln_eps = ln_eps;
-  op_fragmajor(p, (hipStream_t)stream);
-  LAUNCH_OK(nr_launch_igemm(&p, ln_c ? nullptr : op_workspace(p), (hipStream_t)stream));
+  op_gemm(p, (hipStream_t)stream);
   NR_CATCH
 }
 
@@ -122,7 +108,7 @@ extern "C" nr_status nr_op_conv3x3(nr_stream stream, const void* x0, int32_t c0,
   NrGemmParams p = nr_gemm_params((const bf16*)x0, c0, c0, (const bf16*)x1, c1, c1, nimg, H, W, 3, stride, ups, (const bf16*)w, Cout, bias, (const bf16*)res,
                                   Cout, (bf16*)out, Cout);
   p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
-  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
+  op_gemm(p, (hipStream_t)stream);
   NR_CATCH
 }
 
@@ -152,7 +138,7 @@ extern "C" nr_status nr_op_conv3x3_tap_inner(nr_stream stream, const void* x0, i
                                   Cout);
   p.tap_inner = 1;
   p.rowvec = rowvec; p.rowvec_div = rowvec_div > 0 ? rowvec_div : 1; p.rowvec_ld = Cout;
-  LAUNCH_OK(nr_launch_igemm(&p, op_workspace(p), (hipStream_t)stream));
+  op_gemm(p, (hipStream_t)stream);
   NR_CATCH
 }
 

@@ -197,19 +197,14 @@ std::string WeightStore::name_of(const void* p, const char* who) const {
   throw NrError(NR_ERR_STATE, std::string(who) + ": not a converted weight matrix");
 }
 
-// fragment-major copy (smallm.hip) of a converted [N][K] weight matrix; the row-major matrix stays (launches of other row counts use it)
-const bf16* WeightStore::w_fragmajor(const bf16* w, int N, int K) {
-  return (const bf16*)packed("fm:" + name_of(w, "w_fragmajor"), (size_t)N * K * sizeof(bf16),
-                             [&](void* d) { LAUNCH_OK(nr_launch_smallm_w_pack(w, d, N, K, nullptr)); });
-}
-// stage stream (lin160.hip) of a converted [N][K] weight matrix ("l128:": the 128-column layout of the register-panel kernel); the row-major
-// matrix stays (other row counts use it)
-const bf16* WeightStore::w_lin160(const bf16* w, int N, int K, bool panel) {
-  const size_t nb = panel ? nr_lin128q_stream_bytes(N, K) : nr_lin160_stream_bytes(N, K);
-  if (!nb) throw NrError(NR_ERR_STATE, "w_lin160: shape has no stage stream");
-  return (const bf16*)packed((panel ? "l128:" : "l160:") + name_of(w, "w_lin160"), nb, [&](void* d) {
-    LAUNCH_OK(panel ? nr_launch_lin128q_w_pack(w, N, K, (bf16*)d, nullptr) : nr_launch_lin160_w_pack(w, N, K, (bf16*)d, nullptr));
-  });
+// a converted [N][K] weight matrix in the layout a GEMM route names (NrWeightLayout): w itself, or its packed copy -- fragment-major (smallm.hip), the
+// stage stream of lin160.hip, the 128-column stream of its register-panel form; the row-major matrix stays (launches of other row counts use it)
+const bf16* WeightStore::w_layout(const bf16* w, int N, int K, int layout) {
+  if (layout == NR_W_ROWMAJOR || layout == NR_W_TAP_INNER) return w;
+  const size_t nb = nr_gemm_packed_bytes(layout, N, K);
+  if (!nb) throw NrError(NR_ERR_STATE, "w_layout: shape has no packed form");
+  const char* prefix = layout == NR_W_FRAGMAJOR ? "fm:" : (layout == NR_W_LIN128Q ? "l128:" : "l160:");
+  return (const bf16*)packed(prefix + name_of(w, "w_layout"), nb, [&](void* d) { LAUNCH_OK(nr_launch_gemm_w_pack(layout, w, N, K, (bf16*)d, nullptr)); });
 }
 
 const bf16* WeightStore::w_linear(const std::string& key, int N, int K) {

@@ -422,7 +422,7 @@ extern "C" void nr_ff_set_waves(int waves) { g_ff_waves = waves == 4 ? 4 : 8; }
 extern "C" size_t nr_ff_stream_bytes(int C) { return C == FF_C ? (size_t)FF_NSTAGES * FF_STAGE * sizeof(bf16) : 0; }
 
 extern "C" int nr_ff_fused_eligible(int C, long long M) {
-  static const bool off = getenv("NR_FF_FUSED") && getenv("NR_FF_FUSED")[0] == '0';   // A/B switch
+  static const bool off = !env_not_0("NR_FF_FUSED");   // A/B switch
   return !off && C == FF_C && M >= 4096;
 }
 
@@ -439,13 +439,7 @@ extern "C" int nr_launch_ff_fused(const bf16* t, int ldt, const bf16* x, int ldx
   p.t = t; p.ldt = ldt; p.x = x; p.ldx = ldx; p.out = out; p.ldo = ldo; p.M = M; p.stream = stream; p.gamma = gamma; p.beta = beta; p.b1 = b1; p.bc = bc;
   p.ln_eps = ln_eps; p.norot = norot;
   constexpr size_t shm = (size_t)FF_NS * FF_STAGE * sizeof(bf16) + (size_t)8 * FF_C * sizeof(float);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(g_ff_attr >> (dev & 63) & 1ull)) {
-    if (hipFuncSetAttribute((const void*)ff_fused_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-    if (hipFuncSetAttribute((const void*)ff_fused_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-    g_ff_attr |= 1ull << (dev & 63);
-  }
+  if (const int rc = nr_lds_opt_in(g_ff_attr, {(const void*)ff_fused_kernel<2>, (const void*)ff_fused_kernel<1>}, shm)) return rc;
   if (g_ff_waves < 0) g_ff_waves = getenv("NR_FF_WAVES") ? atoi(getenv("NR_FF_WAVES")) : 8;
   const unsigned grid = (unsigned)((M + FF_ROWS - 1) / FF_ROWS);
   if (g_ff_waves == 4) hipLaunchKernelGGL(ff_fused_kernel<2>, dim3(grid), dim3(256), shm, s, p);

@@ -535,7 +535,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(NrGemmParams p_arg, 
   nr_store8(p.out + (size_t)m * p.ldo + n, o);
 }
 
-struct Plan { int bm, bn, splitk, stages, waves; };
+typedef TiledPlan Plan;       // gemm_route.h
 
 // Tile / wave-grid / split-K choice.  Rules distilled from tools/gemm_sweep.py on MI355X (profiles/): two LDS
 // stages (2 workgroups per CU) beat a deeper ring; 8 waves help the 128x128 tile; long-K layers with few
@@ -543,7 +543,7 @@ struct Plan { int bm, bn, splitk, stages, waves; };
 Plan choose_plan(const NrGemmParams& p) {
   auto nblk = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
   const int nk = p.K / 64;
-  Plan pl;
+  Plan pl{};
   pl.splitk = 1; pl.stages = 2; pl.waves = 4;
   // 4x4-level convs (M <= 1024, K >= 8192): L2-bandwidth-bound with small tiles (every n-tile re-reads A, every m-tile
   // re-reads W), so take the biggest tile and get the parallelism from a deep deterministic split-K instead
@@ -571,7 +571,7 @@ Plan choose_plan(const NrGemmParams& p) {
   // Linears whose 64 x 160 tiling is ONE round of the chip (128-256 tiles: N = 1280 at the 8x8 level, M = 1024 / 2048) with K = 1024..3072: one
   // workgroup per CU with a 3-deep ring instead of 320-640 smaller tiles two per CU: 16.2 vs 19.2 us at M = 2048, N = K = 1280, 26.5 vs 36.3 at
   // K = 2560, 17.1 vs 20.1 LayerNorm-folded (2-deep ring there) (profiles/r05_sweep_64x160.txt, HBM-cold weights)
-  static const bool t64x160_rule = !(getenv("NR_IGEMM_T64X160") && getenv("NR_IGEMM_T64X160")[0] == '0');   // A/B switch
+  static const bool t64x160_rule = env_not_0("NR_IGEMM_T64X160");   // A/B switch
   if (t64x160_rule && p.ksize == 1 && !p.geglu && p.N % 160 == 0 && p.M > 512 && nk >= 16 && nk <= 48 && nblk(64, 160) >= 128 && nblk(64, 160) <= 256) {
     pl.bm = 64; pl.bn = 160; pl.stages = 3;
     return pl;
@@ -586,9 +586,9 @@ Plan choose_plan(const NrGemmParams& p) {
   // 4x4-level / sgm 16x16-level Linears (M <= 512): fewer blocks than CUs, every k-step waits for cold weights from HBM.
   // A 4-deep ring (3 tiles in flight) and, where the epilogue allows, 64x32 tiles (twice the blocks) measured -10 % on the
   // sgm keyframe step (tools/igemm_ab_sgm.sh); deeper rings (6, 8) and split-K + reduce were slower.
-  static const bool smallm_rule = !(getenv("NR_IGEMM_SMALLM") && getenv("NR_IGEMM_SMALLM")[0] == '0');   // A/B switch
-  static const bool wide_rule = !(getenv("NR_IGEMM_WIDE") && getenv("NR_IGEMM_WIDE")[0] == '0');         // A/B switch
-  static const bool rowwave_rule = !(getenv("NR_IGEMM_ROWWAVE") && getenv("NR_IGEMM_ROWWAVE")[0] == '0');   // A/B switch
+  static const bool smallm_rule = env_not_0("NR_IGEMM_SMALLM");   // A/B switch
+  static const bool wide_rule = env_not_0("NR_IGEMM_WIDE");         // A/B switch
+  static const bool rowwave_rule = env_not_0("NR_IGEMM_ROWWAVE");   // A/B switch
   if (smallm_rule && p.ksize == 1 && p.M <= 512 && nk >= 8) {
     pl.bm = 64; pl.bn = p.geglu ? 64 : 32; pl.waves = 4; pl.stages = 4;
     // wide GEGLU projections (N = 10240): enough 128x128 tiles for the chip, 22.4 vs 29.9 us; K = 6400 (folded net.2 + proj_out):
@@ -623,71 +623,41 @@ Plan choose_plan(const NrGemmParams& p) {
 // the shape the plan is chosen for: plan_m rows when the caller asks for batch-independent arithmetic (common.h), else the real M
 inline NrGemmParams plan_view(const NrGemmParams& p) {
   NrGemmParams q = p;
-  if (p.plan_m > 0 && p.plan_m < p.M) q.M = p.plan_m;
+  q.M = nr_plan_rows(p);
   return q;
 }
 
-// hipFuncSetAttribute is per device: one bit per device ordinal and instantiation
-inline bool attr_needed(unsigned long long& mask) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (mask & bit) return false;
-  mask |= bit;
-  return true;
-}
+typedef void (*igemm_kern_t)(NrGemmParams, int, float*, int);
 
 // returns 0 on success, 9 when the requested (tile, LayerNorm-fused) combination has no instantiation
 template <int BM, int BN, int NS, int WGM, int WGN>
-int launch_cfg(const NrGemmParams& p, unsigned grid, int splitk, float* partial, int m_fast, hipStream_t stream) {
-  const size_t shm = (size_t)NS * (BM + BN) * 64 * sizeof(bf16);
-  // LayerNorm-fused variant: instantiated for the tiles the transformer GEMMs use (nr_launch_igemm maps others onto them).
+int launch_cfg(const NrGemmParams& p, unsigned grid, const Plan& pl, float* partial, int m_fast, hipStream_t stream) {
+  size_t shm = (size_t)NS * (BM + BN) * 64 * sizeof(bf16);
+  // LayerNorm-fused variant: instantiated for the tiles the transformer GEMMs use (nr_gemm_route maps others onto them).
   // Its row-statistics exchange buffer lives in the DYNAMIC allocation behind the ring: a static __shared__ array next to
   // > 64 KiB of dynamic LDS made the first launch (and any hipGraph node captured from it) run with a short allocation.
   constexpr bool LN_OK = (NS == 2 && BM <= 128 && BN <= 128) || (NS == 4 && (BM * BN <= 64 * 64 || (BM == 128 && BN == 64))) ||
                          (BM == 128 && BN == 160 && WGN == 1 && NS <= 4) ||     // the row-wave 128x160 tile of the wide GEGLU projections
                          (BM == 64 && BN == 160 && NS <= 3);                     // the one-round tile of the N = 1280 Linears at M = 1024 / 2048
+  igemm_kern_t k = nullptr;
+  int ki = 0;                   // LayerNorm-fused | 1 + 2 lin + adma
   if (p.ln_c) {
-    if constexpr (LN_OK) {
-      const size_t shm_ln = shm + (size_t)2 * WGN * BM * sizeof(float);
-      static unsigned long long attr_ln = 0;
-      if (attr_needed(attr_ln))
-        (void)hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, NS, WGM, WGN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_ln);
-      hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, NS, WGM, WGN, true>), dim3(grid), dim3(64 * WGM * WGN), shm_ln, stream, p, splitk,
-                         partial, m_fast);
-      return 0;
-    }
-    return 9;
-  }
-  static unsigned long long attr_set = 0;
-  if (attr_needed(attr_set)) {  // > 64 KiB of dynamic LDS needs the opt-in attribute (gfx950 has 160 KiB per CU), per device
-    (void)hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    (void)hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  }
-  static const int adma_min = getenv("NR_IGEMM_ADMA_MINK") ? atoi(getenv("NR_IGEMM_ADMA_MINK")) : 24;   // k-tiles per slice; A/B switch
-  const int nk_slice = (p.K / 64) / (splitk > 1 ? splitk : 1);
-  // plain Linears (1x1, one source) on the instantiation without the conv paths (rings up to 4 deep: the ones Linears are planned with)
-  static const bool lin_on = !(getenv("NR_IGEMM_LIN") && getenv("NR_IGEMM_LIN")[0] == '0');            // A/B switch
-  if constexpr (NS <= 4) {
-    if (lin_on && p.ksize == 1 && !p.a1 && p.c1 == 0) {
-      static unsigned long long attr_lin = 0;
-      if (attr_needed(attr_lin)) {
-        (void)hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        (void)hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    if constexpr (LN_OK) { k = igemm_bf16_kernel<BM, BN, NS, WGM, WGN, true>; shm += (size_t)2 * WGN * BM * sizeof(float); }
+    else return 9;
+  } else {
+    k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true>;
+    ki = 1 + pl.adma;
+    // plain Linears (1x1, one source) on the instantiation without the conv paths (rings up to 4 deep: the ones Linears are planned with)
+    if constexpr (NS <= 4) {
+      if (pl.lin) {
+        k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false, true> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true, true>;
+        ki += 2;
       }
-      if (nk_slice >= adma_min)
-        hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true, true>), dim3(grid), dim3(64 * WGM * WGN), shm, stream, p, splitk, partial, m_fast);
-      else
-        hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false, true>), dim3(grid), dim3(64 * WGM * WGN), shm, stream, p, splitk, partial, m_fast);
-      return 0;
     }
   }
-  if (nk_slice >= adma_min)
-    hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true>), dim3(grid), dim3(64 * WGM * WGN), shm, stream, p, splitk,
-                       partial, m_fast);
-  else
-    hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false>), dim3(grid), dim3(64 * WGM * WGN), shm, stream, p, splitk,
-                       partial, m_fast);
+  static unsigned long long attr_done[5] = {};          // per instantiation
+  (void)nr_lds_opt_in(attr_done[ki], {(const void*)k}, shm);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(64 * WGM * WGN), shm, stream, p, pl.splitk, partial, m_fast);
   return 0;
 }
 
@@ -695,11 +665,11 @@ template <int BM, int BN, int WGM, int WGN>
 int launch_tile(const NrGemmParams& p, unsigned grid, const Plan& pl, float* partial, int m_fast, hipStream_t stream) {
   constexpr size_t STAGE = (size_t)(BM + BN) * 64 * sizeof(bf16);
   constexpr bool FITS4 = 4 * STAGE <= 160 * 1024;
-  if (pl.stages <= 2) return launch_cfg<BM, BN, 2, WGM, WGN>(p, grid, pl.splitk, partial, m_fast, stream);
-  if (pl.stages == 3 || !FITS4) return launch_cfg<BM, BN, 3, WGM, WGN>(p, grid, pl.splitk, partial, m_fast, stream);
-  if (pl.stages <= 4 || BM * BN > 64 * 64) return launch_cfg<BM, BN, 4, WGM, WGN>(p, grid, pl.splitk, partial, m_fast, stream);   // deep ring
-  if (pl.stages <= 6) return launch_cfg<BM, BN, 6, WGM, WGN>(p, grid, pl.splitk, partial, m_fast, stream);
-  return launch_cfg<BM, BN, 8, WGM, WGN>(p, grid, pl.splitk, partial, m_fast, stream);
+  if (pl.stages <= 2) return launch_cfg<BM, BN, 2, WGM, WGN>(p, grid, pl, partial, m_fast, stream);
+  if (pl.stages == 3 || !FITS4) return launch_cfg<BM, BN, 3, WGM, WGN>(p, grid, pl, partial, m_fast, stream);
+  if (pl.stages <= 4 || BM * BN > 64 * 64) return launch_cfg<BM, BN, 4, WGM, WGN>(p, grid, pl, partial, m_fast, stream);   // deep ring
+  if (pl.stages <= 6) return launch_cfg<BM, BN, 6, WGM, WGN>(p, grid, pl, partial, m_fast, stream);
+  return launch_cfg<BM, BN, 8, WGM, WGN>(p, grid, pl, partial, m_fast, stream);
 }
 
 // test/tuning override: NR_IGEMM_FORCE="bm,bn,splitk,stages,order" (any field <0 keeps the heuristic's choice)
@@ -728,57 +698,43 @@ void apply_override(const NrGemmParams& p, Plan& pl, int& m_fast) {
   if (ord >= 0) m_fast = ord;
 }
 
-}  // namespace
-
-// fp32 scratch (bytes) a launch of this shape needs for split-K slabs (0 if none)
-extern "C" size_t nr_igemm_workspace_bytes(const NrGemmParams* pp) {
-  if (pp->out_f32 || pp->ln_c) return 0;
-  if (nr_rowpanel_eligible(pp)) return 0;
-  if (pp->w_fm) return 0;                      // the caller chose smallm.hip when it built this description (nr_smallm_eligible)
-  if (nr_g8p_plan(pp)) return 0;
-  Plan pl = choose_plan(plan_view(*pp));
-  int mf = 0;
-  apply_override(*pp, pl, mf);
-  return pl.splitk > 1 ? (size_t)pl.splitk * pp->M * pp->N * sizeof(float) : 0;
+// tile order: the bigger operand is the one neighbouring tiles share (1: m-fast, the weights); with enough tiles both ways 8 x 8 blocks of tiles
+// (tools/gemm_sweep.py SWEEP_SET=order: never slower than either plain order, up to 12 % faster where the weights exceed one L2, and fewer L2 misses)
+int tile_order(double w_elems, double a_elems, int ntm, int ntn) {
+  static const bool grouped = env_not_0("NR_IGEMM_GROUPED");
+  static const double grouped_minw = getenv("NR_IGEMM_GROUPED_MINW") ? atof(getenv("NR_IGEMM_GROUPED_MINW")) : 3.0e6;   // weight elements (in situ: 1e6 / 3e6 / 0 = 15.85 / 15.89 / 15.80 frames/s, off 15.93; HBM 49.3 -> 44.4 GB per step at 1e6)
+  if (grouped && ntm >= 8 && ntn >= 4 && w_elems >= grouped_minw) return 8;
+  return w_elems > a_elems ? 1 : 0;
 }
 
-// Host launcher.  Returns 0 on success, nonzero on unsupported shape.  `workspace` must hold
-// nr_igemm_workspace_bytes() bytes when that is nonzero.
-extern "C" int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStream_t stream) {
-  const NrGemmParams& p = *pp;
+// the one place the kernel classes are ordered.  packed_ok: the caller can hand the kernel a packed copy of W
+int route(const NrGemmParams& p, NrGemmRoute* r, bool packed_ok) {
+  std::memset(r, 0, sizeof(*r));
+  r->weight_layout = p.tap_inner ? NR_W_TAP_INNER : NR_W_ROWMAJOR;
   const int Cin = p.c0 + p.c1;
+  // M <= 512 Linears with K a multiple of 640: the panel-resident kernel on fragment-major weights (smallm.hip)
+  if (packed_ok && smallm_plan(p, &r->smallm)) { r->cls = NR_GEMM_SMALLM; r->weight_layout = NR_W_FRAGMAJOR; return 0; }
+  // short-K Linears (K = 640 / 1280) on >= 2048 rows: the stage-stream kernel and its register-panel form (lin160.hip)
+  if (packed_ok && lin160_plan(p, &r->lin160)) { r->cls = NR_GEMM_LIN160; r->weight_layout = r->lin160.form == 4 ? NR_W_LIN128Q : NR_W_LIN160; return 0; }
   // K = 320 Linears on >= 4096 rows: the register-resident row-panel kernel (rowpanel.hip)
-  if (p.K == p.ksize * p.ksize * Cin && nr_rowpanel_eligible(pp)) return nr_launch_rowpanel(pp, stream);
-  // M <= 512 Linears with K a multiple of 640 whose weights the caller also holds fragment-major: the panel-resident kernel (smallm.hip).
-  // w_fm IS the decision (made once with nr_smallm_eligible when the description was built); a shape the kernel cannot serve is an error here
-  if (p.w_fm) return nr_launch_smallm(pp, stream);
-  if (const int nt8 = nr_g8p_plan(pp)) {
-    // tile order as below: the bigger operand is the one neighbouring tiles share; 8 x 4 blocks of tiles per XCD for weight-heavy shapes
-    const double w_e = (double)p.N * p.K;
-    const double a_e = (double)p.M * Cin;
-    int mf = w_e > a_e ? 1 : 0;
-    const int ntm_ = (p.M + 255) / 256, ntn_ = (p.N + 64 * nt8 - 1) / (64 * nt8);
-    if (ntm_ >= 8 && ntn_ >= 4 && w_e >= 3.0e6) mf = 8;
-    return nr_launch_g8p(pp, mf, stream);
+  if (p.K == p.ksize * p.ksize * Cin && rowpanel_plan(p, &r->rowpanel)) { r->cls = NR_GEMM_ROWPANEL; return 0; }
+  const double w_elems = (double)p.N * p.K;
+  if (g8p_plan(p, &r->g8p)) {
+    r->cls = NR_GEMM_G8P;
+    r->m_fast = tile_order(w_elems, (double)p.M * Cin, (p.M + 255) / 256, (p.N + 64 * r->g8p.nt - 1) / (64 * r->g8p.nt));
+    return 0;
   }
+  r->cls = NR_GEMM_TILED;
   if (p.K % 64 != 0 || Cin % 64 != 0 || p.N % 32 != 0) return 1;
   if (p.a1 && (p.c0 % 64 != 0)) return 2;
   if (p.K != p.ksize * p.ksize * Cin) return 3;
   if (p.ksize != 1 && p.ksize != 3) return 4;
   if (p.tap_inner && (p.ksize != 3 || p.stride != 1 || p.ups || p.pad_tl0 || p.a1)) return 5;
-  Plan pl = choose_plan(plan_view(p));
-  const double w_elems = (double)p.N * p.K;
+  Plan& pl = r->tiled;
+  pl = choose_plan(plan_view(p));
   const double a_elems = (double)p.M * Cin * (p.ksize == 3 ? (p.stride == 2 ? 4.0 : (p.ups ? 0.25 : 1.0)) : 1.0);
-  int m_fast = w_elems > a_elems ? 1 : 0;
-  {
-    // enough tiles both ways: 8 x 8 blocks of tiles (tools/gemm_sweep.py SWEEP_SET=order: never slower than either plain order, up to
-    // 12 % faster where the weights exceed one L2, and fewer L2 misses)
-    static const bool grouped = !(getenv("NR_IGEMM_GROUPED") && getenv("NR_IGEMM_GROUPED")[0] == '0');
-    const int ntm_ = (p.M + pl.bm - 1) / pl.bm, ntn_ = (p.N + pl.bn - 1) / pl.bn;
-    static const double grouped_minw = getenv("NR_IGEMM_GROUPED_MINW") ? atof(getenv("NR_IGEMM_GROUPED_MINW")) : 3.0e6;   // weight elements (in situ: 1e6 / 3e6 / 0 = 15.85 / 15.89 / 15.80 frames/s, off 15.93; HBM 49.3 -> 44.4 GB per step at 1e6)
-    if (grouped && ntm_ >= 8 && ntn_ >= 4 && w_elems >= grouped_minw) m_fast = 8;
-  }
-  apply_override(p, pl, m_fast);
+  r->m_fast = tile_order(w_elems, a_elems, (p.M + pl.bm - 1) / pl.bm, (p.N + pl.bn - 1) / pl.bn);
+  apply_override(p, pl, r->m_fast);
   if (p.ln_c) {      // LayerNorm-fused: every block must see the whole row (K = C) -> no split-K; supported tiles only
     if (p.ksize != 1 || p.a1 || p.out_f32) return 8;
     pl.splitk = 1;
@@ -793,6 +749,17 @@ extern "C" int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStre
     if (p.geglu) return 7;
     pl.splitk = 1;
   }
+  static const int adma_min = getenv("NR_IGEMM_ADMA_MINK") ? atoi(getenv("NR_IGEMM_ADMA_MINK")) : 24;   // k-tiles per slice; A/B switch
+  static const bool lin_on = env_not_0("NR_IGEMM_LIN");                                                  // A/B switch
+  pl.adma = (p.K / 64) / (pl.splitk > 1 ? pl.splitk : 1) >= adma_min;
+  pl.lin = lin_on && p.ksize == 1 && !p.a1 && p.c1 == 0;
+  r->ws_bytes = pl.splitk > 1 ? (size_t)pl.splitk * p.M * p.N * sizeof(float) : 0;
+  return 0;
+}
+
+// the tiled kernel as planned, then its split-K reduce
+int launch_tiled(const NrGemmParams& p, const Plan& pl, int m_fast, float* workspace, hipStream_t stream) {
+  if (pl.splitk < 1 || pl.splitk > p.K / 64 || ((p.ln_c || p.out_f32) && pl.splitk != 1)) return 9;
   if (pl.splitk > 1 && !workspace) return 6;
   float* partial = p.out_f32 ? p.out_f32 : (pl.splitk > 1 ? workspace : nullptr);
   const unsigned grid = (unsigned)(((p.M + pl.bm - 1) / pl.bm) * ((p.N + pl.bn - 1) / pl.bn) * pl.splitk);
@@ -801,8 +768,8 @@ extern "C" int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStre
   else if (pl.bm == 256 && pl.waves == 4) rc = launch_tile<256, 128, 2, 2>(p, grid, pl, partial, m_fast, stream);
   else if (pl.bm == 256) rc = launch_tile<256, 128, 4, 2>(p, grid, pl, partial, m_fast, stream);
   else if (pl.bm == 128 && pl.bn == 160 && pl.waves == 41)      // row-wave tile: rings 3 / 4 deep only (108 / 144 KiB: one workgroup per CU)
-    rc = pl.stages <= 3 ? launch_cfg<128, 160, 3, 4, 1>(p, grid, pl.splitk, partial, m_fast, stream)
-                        : launch_cfg<128, 160, 4, 4, 1>(p, grid, pl.splitk, partial, m_fast, stream);
+    rc = pl.stages <= 3 ? launch_cfg<128, 160, 3, 4, 1>(p, grid, pl, partial, m_fast, stream)
+                        : launch_cfg<128, 160, 4, 4, 1>(p, grid, pl, partial, m_fast, stream);
   else if (pl.bm == 128 && pl.bn == 160) rc = launch_tile<128, 160, 2, 2>(p, grid, pl, partial, m_fast, stream);
   else if (pl.bm == 128 && pl.bn == 128 && pl.waves == 8) rc = launch_tile<128, 128, 2, 4>(p, grid, pl, partial, m_fast, stream);
   else if (pl.bm == 128 && pl.bn == 128) rc = launch_tile<128, 128, 2, 2>(p, grid, pl, partial, m_fast, stream);
@@ -819,6 +786,42 @@ extern "C" int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStre
                        (const float*)partial);
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int nr_gemm_route(const NrGemmParams* pp, NrGemmRoute* r) { return route(*pp, r, true); }
+extern "C" int nr_gemm_route_rowmajor(const NrGemmParams* pp, NrGemmRoute* r) { return route(*pp, r, false); }
+
+// Launches what the route says; reads no environment, no mode and no eligibility rule.  Returns 0 on success, nonzero when the route does not fit
+// the launch (6: split-K planned and no workspace given)
+extern "C" int nr_launch_gemm(const NrGemmParams* pp, const NrGemmRoute* r, const bf16* packed_w, float* ws, hipStream_t stream) {
+  switch (r->cls) {
+    case NR_GEMM_SMALLM: return nr_launch_smallm(pp, &r->smallm, packed_w, stream);
+    case NR_GEMM_LIN160: return nr_launch_lin160(pp, &r->lin160, packed_w, stream);
+    case NR_GEMM_ROWPANEL: return nr_launch_rowpanel(pp, &r->rowpanel, stream);
+    case NR_GEMM_G8P: return nr_launch_g8p(pp, &r->g8p, r->m_fast, stream);
+    case NR_GEMM_TILED: return launch_tiled(*pp, r->tiled, r->m_fast, ws, stream);
+  }
+  return 9;
+}
+
+// the packed copies of a row-major [N][K] weight matrix: bytes (0: the shape has none) and the pack launch
+extern "C" size_t nr_gemm_packed_bytes(int layout, int N, int K) {
+  switch (layout) {
+    case NR_W_FRAGMAJOR: return (N % 16 == 0 && K % 32 == 0) ? (size_t)N * K * sizeof(bf16) : 0;
+    case NR_W_LIN160: return nr_lin160_stream_bytes(N, K);
+    case NR_W_LIN128Q: return nr_lin128q_stream_bytes(N, K);
+  }
+  return 0;
+}
+extern "C" int nr_launch_gemm_w_pack(int layout, const bf16* w, int N, int K, bf16* dst, hipStream_t stream) {
+  switch (layout) {
+    case NR_W_FRAGMAJOR: return nr_launch_smallm_w_pack(w, dst, N, K, stream);
+    case NR_W_LIN160: return nr_launch_lin160_w_pack(w, N, K, dst, stream);
+    case NR_W_LIN128Q: return nr_launch_lin128q_w_pack(w, N, K, dst, stream);
+  }
+  return 1;
 }
 
 #ifdef NR_STAMP

@@ -324,43 +324,31 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
   }
 }
 
-inline bool attr_needed(unsigned long long& mask) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (mask & bit) return false;
-  mask |= bit;
-  return true;
-}
-
 template <int NT, bool TAPI, int NPH>
 int launch_g8p_n(const NrGemmParams& p, int m_fast, hipStream_t stream) {
   constexpr int BN = 64 * NT;
   constexpr size_t shm = (size_t)2 * (G8_BM + BN) * 128;
   static unsigned long long attr = 0;
-  if (attr_needed(attr) &&
-      hipFuncSetAttribute((const void*)g8p_kernel<NT, TAPI, NPH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 20;
+  if (nr_lds_opt_in(attr, {(const void*)g8p_kernel<NT, TAPI, NPH>}, shm)) return 20;
   const unsigned grid = (unsigned)(((p.M + G8_BM - 1) / G8_BM) * ((p.N + BN - 1) / BN));
   hipLaunchKernelGGL((g8p_kernel<NT, TAPI, NPH>), dim3(grid), dim3(512), shm, stream, p, m_fast);
   return 0;
 }
-static int g8p_phases = -1;     // NR_G8P_PHASES: 2 (default where the instantiation exists, NT <= 4: never slower in tools/g8p_ab.py, GEGLU 1.08-1.16x
-                                // instead of 1.00-1.08x) or 4 phases per k-tile; nr_g8p_set_phases overrides
 template <int NT, bool TAPI>
-int launch_g8p(const NrGemmParams& p, int m_fast, hipStream_t stream) {
-  if (g8p_phases < 0) g8p_phases = getenv("NR_G8P_PHASES") ? atoi(getenv("NR_G8P_PHASES")) : 2;
-  if constexpr (NT <= 4) { if (g8p_phases == 2) return launch_g8p_n<NT, TAPI, 2>(p, m_fast, stream); }
+int launch_g8p(const NrGemmParams& p, int phases, int m_fast, hipStream_t stream) {
+  if constexpr (NT <= 4) { if (phases == 2) return launch_g8p_n<NT, TAPI, 2>(p, m_fast, stream); }
   return launch_g8p_n<NT, TAPI, 4>(p, m_fast, stream);
 }
 
 }  // namespace
 
-// 0 = not for this kernel; else NT (columns per tile / 64).  Pure function of the launch parameters (and of NR_G8P / NR_G8P_MIN_TILES).
+// Does this kernel take the launch, and with which NT (columns per tile / 64) and schedule?  Called by nr_gemm_route alone: the only reader of the two modes.
+static int g8p_phases = -1;     // NR_G8P_PHASES: 2 (default where the instantiation exists, NT <= 4: never slower in tools/g8p_ab.py, GEGLU 1.08-1.16x
+                                // instead of 1.00-1.08x) or 4 phases per k-tile; nr_g8p_set_phases overrides
 static int g8p_mode = -1;       // NR_G8P: 0 off (A/B), 1 heuristic (default), 2 whenever the shape is supported; nr_g8p_set_mode overrides (tests, A/B tools)
 extern "C" void nr_g8p_set_mode(int mode) { g8p_mode = mode; }
 extern "C" void nr_g8p_set_phases(int phases) { g8p_phases = phases == 2 ? 2 : 4; }
-extern "C" int nr_g8p_plan(const NrGemmParams* pp) {
-  const NrGemmParams& p = *pp;
+static int g8p_nt(const NrGemmParams& p) {
   if (g8p_mode < 0) g8p_mode = getenv("NR_G8P") ? atoi(getenv("NR_G8P")) : 1;
   const int mode = g8p_mode;
   if (!mode) return 0;
@@ -378,7 +366,7 @@ extern "C" int nr_g8p_plan(const NrGemmParams* pp) {
   if ((size_t)p.N * p.K * 2 + 4096 >= 0xffffffffull) return 0;
   if (p.lda0 % 8 != 0 || (p.a1 && p.lda1 % 8 != 0) || p.ldo % 8 != 0 || (p.res && p.ldr % 8 != 0)) return 0;
   if (p.rowvec && p.rowvec_ld % 4 != 0) return 0;
-  const long long Mp = p.plan_m > 0 && p.plan_m < p.M ? p.plan_m : p.M;     // batch-independent choice (common.h): as for one clip
+  const long long Mp = nr_plan_rows(p);                                     // batch-independent choice (common.h): as for one clip
   const long long ntm = (Mp + G8_BM - 1) / G8_BM;
   const int nk = p.K / 64;
   // Where it pays (tools/g8p_ab.py on MI355X, profiles/r04_g8p_ab_*.txt): long-K launches whose grid fills the chip in whole rounds of 256
@@ -413,16 +401,22 @@ extern "C" int nr_g8p_plan(const NrGemmParams* pp) {
   return best;
 }
 
-extern "C" int nr_launch_g8p(const NrGemmParams* pp, int m_fast, hipStream_t stream) {
+extern "C" bool g8p_plan(const NrGemmParams& p, G8pPlan* pl) {
+  pl->nt = g8p_nt(p);
+  if (g8p_phases < 0) g8p_phases = getenv("NR_G8P_PHASES") ? atoi(getenv("NR_G8P_PHASES")) : 2;
+  pl->phases = g8p_phases;
+  return pl->nt != 0;
+}
+
+extern "C" int nr_launch_g8p(const NrGemmParams* pp, const G8pPlan* pl, int m_fast, hipStream_t stream) {
   const NrGemmParams& p = *pp;
-  const int nt = nr_g8p_plan(pp);
-  if (!nt) return 21;
   const bool tapi = p.ksize == 3;
-  switch (nt) {
-    case 2: return tapi ? launch_g8p<2, true>(p, m_fast, stream) : launch_g8p<2, false>(p, m_fast, stream);
-    case 3: return tapi ? launch_g8p<3, true>(p, m_fast, stream) : launch_g8p<3, false>(p, m_fast, stream);
-    case 4: return tapi ? launch_g8p<4, true>(p, m_fast, stream) : launch_g8p<4, false>(p, m_fast, stream);
-    case 5: return tapi ? launch_g8p<5, true>(p, m_fast, stream) : launch_g8p<5, false>(p, m_fast, stream);
+  if (p.geglu && pl->nt % 2) return 21;
+  switch (pl->nt) {
+    case 2: return tapi ? launch_g8p<2, true>(p, pl->phases, m_fast, stream) : launch_g8p<2, false>(p, pl->phases, m_fast, stream);
+    case 3: return tapi ? launch_g8p<3, true>(p, pl->phases, m_fast, stream) : launch_g8p<3, false>(p, pl->phases, m_fast, stream);
+    case 4: return tapi ? launch_g8p<4, true>(p, pl->phases, m_fast, stream) : launch_g8p<4, false>(p, pl->phases, m_fast, stream);
+    case 5: return tapi ? launch_g8p<5, true>(p, pl->phases, m_fast, stream) : launch_g8p<5, false>(p, pl->phases, m_fast, stream);
   }
   return 22;
 }

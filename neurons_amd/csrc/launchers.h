@@ -3,25 +3,33 @@
 // prototype its callers see (the names are extern "C": a mismatch would otherwise link cleanly).
 #pragma once
 #include "common.h"
+#include "gemm_route.h"
 
 extern "C" {
-// gemm.hip: tiled implicit GEMM (1x1 / 3x3) and its split-K scratch
-int nr_launch_igemm(const NrGemmParams* pp, float* workspace, hipStream_t stream);
-size_t nr_igemm_workspace_bytes(const NrGemmParams* pp);
+// gemm.hip: the route of a GEMM / conv launch (gemm_route.h) and the tiled implicit GEMM (1x1 / 3x3) with its split-K scratch.
+// nr_gemm_route orders the kernel classes (smallm, lin160, row-panel, gemm8p, tiled) and is the only reader of their switches; it returns nonzero
+// for a shape no kernel serves.  nr_gemm_route_rowmajor: for a W that is no converted weight matrix (an activation as the W operand) or an epilogue
+// set at launch -- only the classes that read `w` as the caller holds it.  nr_launch_gemm launches what the route says: `packed_w` in
+// route->weight_layout (p.w itself for the unpacked layouts), `ws` of route->ws_bytes bytes
+int nr_gemm_route(const NrGemmParams* pp, NrGemmRoute* route);
+int nr_gemm_route_rowmajor(const NrGemmParams* pp, NrGemmRoute* route);
+int nr_launch_gemm(const NrGemmParams* pp, const NrGemmRoute* route, const bf16* packed_w, float* ws, hipStream_t stream);
+size_t nr_gemm_packed_bytes(int layout, int N, int K);      // 0: the shape has no such packed form
+int nr_launch_gemm_w_pack(int layout, const bf16* w, int N, int K, bf16* dst, hipStream_t stream);
 // rowpanel.hip: K = 320 row-panel GEMM
-int nr_rowpanel_eligible(const NrGemmParams* pp);
-int nr_launch_rowpanel(const NrGemmParams* pp, hipStream_t stream);
+bool rowpanel_plan(const NrGemmParams& p, RowPanelPlan* pl);
+int nr_launch_rowpanel(const NrGemmParams* pp, const RowPanelPlan* pl, hipStream_t stream);
 // gemm8p.hip: 256-row ping-pong kernel for the big launches (SparseCtrl groups, several clips per call, 32-frame clips, the VAE)
-int nr_g8p_plan(const NrGemmParams* pp);
-int nr_launch_g8p(const NrGemmParams* pp, int m_fast, hipStream_t stream);
+bool g8p_plan(const NrGemmParams& p, G8pPlan* pl);
+int nr_launch_g8p(const NrGemmParams* pp, const G8pPlan* pl, int m_fast, hipStream_t stream);
 // lin160.hip: short-K Linears (K = 640 / 1280, N % 160 == 0, >= 2048 rows) on fragment-major weights
 size_t nr_lin160_stream_bytes(int N, int K);
-int nr_lin160_eligible(const NrGemmParams* pp);
+bool lin160_plan(const NrGemmParams& p, Lin160Plan* pl);
 int nr_lin160_panel_rule(int Mp, int N, int K);
 size_t nr_lin128q_stream_bytes(int N, int K);
 int nr_launch_lin128q_w_pack(const bf16* w, int N, int K, bf16* stream, hipStream_t s);
 int nr_launch_lin160_w_pack(const bf16* w, int N, int K, bf16* stream, hipStream_t s);
-int nr_launch_lin160(const NrGemmParams* pp, const bf16* stream, hipStream_t s);
+int nr_launch_lin160(const NrGemmParams* pp, const Lin160Plan* pl, const bf16* stream, hipStream_t s);
 int nr_gn_workspace_floats(int nimg, int hw, int groups, int* pix_per_blk_out, int* nchunk_out);
 int nr_launch_groupnorm(NrGnParams* pp, hipStream_t stream);
 int nr_launch_layernorm(const bf16* x, int ldx, bf16* out, int ldo, int M, int C, const float* gamma, const float* beta,
@@ -64,8 +72,8 @@ int nr_groupnorm_launches(const NrGnParams* p);
 int nr_launch_fold_linear_pair(const float* w2, const float* w1, const float* b2, const float* b1, int C, int J, bf16* wc, float* bc,
                                hipStream_t stream);
 // smallm.hip: panel-resident kernel of the M <= 512 Linears (fragment-major weights)
-int nr_smallm_eligible(const NrGemmParams* pp);
-int nr_launch_smallm(const NrGemmParams* pp, hipStream_t stream);
+bool smallm_plan(const NrGemmParams& p, SmallmPlan* pl);
+int nr_launch_smallm(const NrGemmParams* pp, const SmallmPlan* pl, const bf16* w_fm, hipStream_t stream);
 int nr_launch_smallm_w_pack(const void* w, void* out, int N, int K, hipStream_t stream);
 // tattn.hip: one kernel per temporal-attention block of the C = 320 level
 size_t nr_xattn_wstream_bytes(void);

@@ -531,8 +531,6 @@ __global__ __launch_bounds__(256) void lin128q_w_pack_kernel(const bf16* __restr
   *(bf16x8*)(stream + (size_t)idx * 8) = *(const bf16x8*)(w + (size_t)(cb * BN + 16 * n + (lane & 15)) * K + 32 * (KPS * st + kk) + 8 * (lane >> 4));
 }
 
-unsigned long long g_l1_attr = 0;
-
 }  // namespace
 
 #ifdef NR_STAMP
@@ -546,8 +544,8 @@ extern "C" size_t nr_lin160_stream_bytes(int N, int K) { return (N % L1_BN == 0 
 // PANEL rule (rows of one clip, N, K): the LayerNorm-folded wide projections (GEGLU N = 8 C, q|k|v N = 3 C) at K = C = 640 (>= 4096 rows) / 1280 (>= 2048 rows) (NR_LIN160_PANEL_MAXM: sweep aid;
 // NR_LIN160_PANEL_K1280=0: the K-split form of the C = 1280 level off)
 extern "C" int nr_lin160_panel_rule(int Mp, int N, int K) {
-  static const bool off = (getenv("NR_LIN160") && getenv("NR_LIN160")[0] == '0') || (getenv("NR_LIN160_PANEL") && getenv("NR_LIN160_PANEL")[0] == '0');   // A/B switches
-  static const bool off1280 = getenv("NR_LIN160_PANEL_K1280") && getenv("NR_LIN160_PANEL_K1280")[0] == '0';
+  static const bool off = !env_not_0("NR_LIN160") || !env_not_0("NR_LIN160_PANEL");   // A/B switches
+  static const bool off1280 = !env_not_0("NR_LIN160_PANEL_K1280");
   static const int maxm = getenv("NR_LIN160_PANEL_MAXM") ? atoi(getenv("NR_LIN160_PANEL_MAXM")) : (1 << 30);   // no row ceiling: J = 10 blocks per workgroup amortise prologue and epilogue over any number of rounds (config 4: +1.6 %)
   if (off || Mp < 2048 || Mp > maxm || N < 3 * K) return 0;
   // K = 640 needs >= 32 row groups: at 2048 rows (the sgm keyframe model's 32 x 32 level) the best partition has 160 workgroups of 20 stages and the prologue dominates
@@ -568,35 +566,60 @@ extern "C" int nr_launch_lin128q_w_pack(const bf16* w, int N, int K, bf16* strea
   return 0;
 }
 
-extern "C" int nr_lin160_eligible(const NrGemmParams* pp) {
-  static const bool off = getenv("NR_LIN160") && getenv("NR_LIN160")[0] == '0';   // A/B switch
-  const NrGemmParams& p = *pp;
-  // PANEL: register-resident rows, W streamed
-  {
-    const int Mq = (p.plan_m > 0 && p.plan_m < p.M) ? p.plan_m : p.M;
-    if (p.ln_c && p.bias && p.ksize == 1 && p.stride == 1 && !p.ups && !p.a1 && !p.c1 && !p.rowvec && !p.act && !p.out_f32 && !p.res &&
-        p.out_scale == 1.0f && p.K == p.c0 && nr_lin160_panel_rule(Mq, p.N, p.K) && p.M % 128 == 0 && p.lda0 % 8 == 0 && p.ldo % 4 == 0 &&
-        (long long)p.M * p.ldo < (1ll << 31))          // 32-bit output offsets in the kernel: beyond that the tiled igemm serves the shape
-      return 4;
+// The forms (Lin160Plan::form) and what each needs besides the shape.  Called by nr_gemm_route alone
+extern "C" bool lin160_plan(const NrGemmParams& p, Lin160Plan* pl) {
+  static const bool off = !env_not_0("NR_LIN160");   // A/B switch
+  const int Mp = nr_plan_rows(p);                    // NR_DETERMINISTIC_BATCH: the choice is made per clip
+  *pl = Lin160Plan{0, 0, 0, 0};
+  const bool ln_wide = p.ln_c && p.bias && p.ksize == 1 && p.stride == 1 && !p.ups && !p.a1 && !p.c1 && !p.rowvec && !p.act && !p.out_f32 && !p.res &&
+                       p.out_scale == 1.0f && p.K == p.c0 && p.M % 128 == 0 && p.lda0 % 8 == 0 && p.ldo % 4 == 0;      // what PANEL and GLN share
+  // PANEL: register-resident rows, W streamed (stream = the nr_lin128q layout)
+  if (ln_wide && nr_lin160_panel_rule(Mp, p.N, p.K) &&
+      (long long)p.M * p.ldo < (1ll << 31)) {        // 32-bit output offsets in the kernel: beyond that the tiled igemm serves the shape
+    const bool ksplit = p.K == 1280;                 // K = 1280: the two waves of a SIMD split K, 64-column blocks
+    // J column blocks per workgroup (NCG = ncb / J column groups): the divisor of ncb with the fewest stage-times for the launch -- rounds of the chip x (J S stages + ~6
+    // stage-times of prologue / epilogue); ties -> the larger J
+    const int bn = ksplit ? 64 : Q_BN, ncq = p.N / bn, S = 5, nrg = p.M / 128, ns = ksplit ? 3 : Q_NS;
+    static const int j_force = getenv("NR_LIN160_PANEL_J") ? atoi(getenv("NR_LIN160_PANEL_J")) : 0;   // sweep aid
+    int J = 0; long long best = 0;
+    for (int c = 1; c <= 16 && c <= ncq; ++c) {
+      if (ncq % c != 0 || c * S < ns - 1) continue;
+      const long long wgs = (long long)nrg * (ncq / c), cost = ((wgs + 255) / 256) * (c * S + 6);
+      if (!J || cost <= best) { J = c; best = cost; }
+    }
+    if (j_force > 0 && ncq % j_force == 0 && j_force <= 16) J = j_force;
+    pl->form = 4; pl->J = J;         // J = 0 (no partition): nr_launch_lin160 reports it, as it did
+    if (J) {
+      // workgroup -> XCD: by row group (every XCD streams all of W, x crosses the fabric once) or by column group (W once or 8 / NCG times, x NCG-or-8 times): the
+      // smaller fabric traffic; by column group only where blockIdx mod 8 fixes the column group
+      static const int cg_force = getenv("NR_LIN160_PANEL_CGMAJOR") ? atoi(getenv("NR_LIN160_PANEL_CGMAJOR")) : -1;   // A/B aid
+      const int NCG = ncq / J;
+      const double wb = 2.0 * p.N * (double)p.K, xb = 2.0 * p.M * (double)p.K;
+      const bool can = NCG % 8 == 0 || 8 % NCG == 0;
+      const double by_rg = 8.0 * wb + xb;
+      const double by_cg = (NCG % 8 == 0 ? 1.0 : 8.0 / NCG) * wb + (NCG % 8 == 0 ? 8.0 : (double)NCG) * xb;
+      pl->cgmajor = (can && by_cg < by_rg) ? 1 : 0;
+      if (cg_force >= 0) pl->cgmajor = cg_force && can;
+    }
+    return true;
   }
   // GLN: the LayerNorm-folded GEGLU projection on FEW rows (the keyframe model's depth-10 levels and the 4 x 4 level of the headline: M = 512, N = 10240,
   // K = 1280): 4 x 64 workgroups = one round of the chip, each streams its 160 W rows once for 128 rows (tiled igemm: 27-32 us)
-  {
-    static const bool gln_off = getenv("NR_LIN160_GEGLU") && getenv("NR_LIN160_GEGLU")[0] == '0';
-    const int Mg = (p.plan_m > 0 && p.plan_m < p.M) ? p.plan_m : p.M;
-    if (!off && !gln_off && p.geglu && p.ln_c && p.bias && p.ksize == 1 && p.stride == 1 && !p.ups && !p.a1 && !p.c1 && !p.rowvec && !p.act && !p.out_f32 && !p.res &&
-        p.out_scale == 1.0f && p.K == p.c0 && p.K == 1280 && p.N % L1_BN == 0 && p.N >= 8192 && p.M % 128 == 0 && Mg <= 1024 && (long long)(Mg / 128) * (p.N / L1_BN) >= 192 &&
-        p.lda0 % 8 == 0 && p.ldo % 4 == 0)
-      return 2;
+  static const bool gln_on = env_not_0("NR_LIN160_GEGLU");
+  if (!off && gln_on && ln_wide && p.geglu && p.K == 1280 && p.N % L1_BN == 0 && p.N >= 8192 && Mp <= 1024 && (long long)(Mp / 128) * (p.N / L1_BN) >= 192) {
+    pl->form = 2;
+    return true;
   }
-  if (off || p.ksize != 1 || p.stride != 1 || p.ups || p.a1 || p.c1 || p.geglu || p.ln_c || p.rowvec || p.act || p.out_f32 || p.tap_inner) return 0;
+  // plain Linear (one source, no GEGLU / LayerNorm fold / row vector / activation / scale), >= 2048 rows in whole 64-row groups
+  if (off || p.ksize != 1 || p.stride != 1 || p.ups || p.a1 || p.c1 || p.geglu || p.ln_c || p.rowvec || p.act || p.out_f32 || p.tap_inner) return false;
   // K = 640 / 1280 only: the long-K folded net.2 | proj_out operand (K = 3200, built as a two-source variant and measured: 54.8 vs 55 us) gains nothing
-  if (p.out_scale != 1.0f || p.K != p.c0 || (p.K != 640 && p.K != 1280) || p.N % L1_BN != 0 || p.N > 1280) return 0;
-  const int Mp = (p.plan_m > 0 && p.plan_m < p.M) ? p.plan_m : p.M;                 // NR_DETERMINISTIC_BATCH: the choice is made per clip
-  if (p.M % 64 != 0 || Mp < 2048) return 0;
-  if (p.lda0 % 8 != 0 || p.ldo % 8 != 0 || (p.res && p.ldr % 8 != 0)) return 0;
-  if (Mp > 8192) return 0;           // one round of the chip at the headline shapes; beyond it (config 4: M = 16384 / 65536) the tiled igemm with its 2-3 resident workgroups per CU wins (profiles/r06_lin160_ab.txt)
-  return 1;
+  if (p.out_scale != 1.0f || p.K != p.c0 || (p.K != 640 && p.K != 1280) || p.N % L1_BN != 0 || p.N > 1280) return false;
+  if (p.M % 64 != 0 || Mp < 2048) return false;
+  if (p.lda0 % 8 != 0 || p.ldo % 8 != 0 || (p.res && p.ldr % 8 != 0)) return false;
+  if (Mp > 8192) return false;       // one round of the chip at the headline shapes; beyond it (config 4: M = 16384 / 65536) the tiled igemm with its 2-3 resident workgroups per CU wins (profiles/r06_lin160_ab.txt)
+  pl->form = 1;
+  pl->big = p.M % 128 == 0 && (long long)(Mp / 128) * (p.N / L1_BN) >= 256;      // 128-row tiles when they still fill the chip (and the row count allows), else 64-row tiles
+  return true;
 }
 
 extern "C" int nr_launch_lin160_w_pack(const bf16* w, int N, int K, bf16* stream, hipStream_t s) {
@@ -606,57 +629,25 @@ extern "C" int nr_launch_lin160_w_pack(const bf16* w, int N, int K, bf16* stream
   return 0;
 }
 
-extern "C" int nr_launch_lin160(const NrGemmParams* pp, const bf16* stream, hipStream_t s) {
+extern "C" int nr_launch_lin160(const NrGemmParams* pp, const Lin160Plan* pl, const bf16* stream, hipStream_t s) {
   const NrGemmParams& g = *pp;
   if (!stream) return 1;
-  const int Mp = (g.plan_m > 0 && g.plan_m < g.M) ? g.plan_m : g.M;
-  if (g.ln_c && nr_lin160_panel_rule(Mp, g.N, g.K)) {            // PANEL form (stream = the nr_lin128q layout)
-    if (!g.bias || g.M % 128 != 0 || (long long)g.M * g.ldo >= (1ll << 31)) return 1;
-    const bool ksplit = g.K == 1280;                               // K = 1280: the two waves of a SIMD split K, 64-column blocks
+  if (pl->form == 4) {                                            // PANEL form (stream = the nr_lin128q layout)
+    const bool ksplit = g.K == 1280;
+    if (!g.ln_c || !g.bias || (g.K != 640 && !ksplit) || g.M % 128 != 0 || (long long)g.M * g.ldo >= (1ll << 31)) return 1;
+    const int bn = ksplit ? 64 : Q_BN, ncq = g.N / bn, nrg = g.M / 128, ns = ksplit ? 3 : Q_NS, J = pl->J;
+    if (g.N % bn != 0 || J < 1 || J > 16 || ncq % J != 0) return 1;
     NrLin128QParams q;
     q.x = g.a0; q.lda = g.lda0; q.stream = stream; q.ln_c = g.ln_c; q.bias = g.bias; q.ln_eps = g.ln_eps; q.out = g.out; q.ldo = g.ldo; q.M = g.M; q.N = g.N; q.norot = g.plan_m > 0 ? 1 : 0;
-    // J column blocks per workgroup (NCG = ncb / J column groups): the divisor of ncb with the fewest stage-times for the launch -- rounds of the chip x (J S stages + ~6
-    // stage-times of prologue / epilogue); ties -> the larger J
-    const int bn = ksplit ? 64 : Q_BN, ncq = g.N / bn, S = 5, nrg = g.M / 128, ns = ksplit ? 3 : Q_NS;
-    static const int j_force = getenv("NR_LIN160_PANEL_J") ? atoi(getenv("NR_LIN160_PANEL_J")) : 0;   // sweep aid
-    int J = 0; long long best = 0;
-    for (int c = 1; c <= 16 && c <= ncq; ++c) {
-      if (ncq % c != 0 || c * S < ns - 1) continue;
-      const long long wgs = (long long)nrg * (ncq / c), cost = ((wgs + 255) / 256) * (c * S + 6);
-      if (!J || cost <= best) { J = c; best = cost; }
-    }
-    if (j_force > 0 && ncq % j_force == 0 && j_force <= 16) J = j_force;
-    if (!J) return 1;
-    q.J = J; q.NCG = ncq / J;
-    {
-      // workgroup -> XCD: by row group (every XCD streams all of W, x crosses the fabric once) or by column group (W once or 8 / NCG times, x NCG-or-8 times): the
-      // smaller fabric traffic; by column group only where blockIdx mod 8 fixes the column group
-      static const int cg_force = getenv("NR_LIN160_PANEL_CGMAJOR") ? atoi(getenv("NR_LIN160_PANEL_CGMAJOR")) : -1;   // A/B aid
-      const double wb = 2.0 * g.N * (double)g.K, xb = 2.0 * g.M * (double)g.K;
-      const bool can = q.NCG % 8 == 0 || 8 % q.NCG == 0;
-      const double by_rg = (nrg % 8 == 0 ? 8.0 : 8.0) * wb + xb;
-      const double by_cg = (q.NCG % 8 == 0 ? 1.0 : 8.0 / q.NCG) * wb + (q.NCG % 8 == 0 ? 8.0 : (double)q.NCG) * xb;
-      q.cgmajor = (can && by_cg < by_rg) ? 1 : 0;
-      if (cg_force >= 0) q.cgmajor = cg_force && can;
-    }
+    q.J = J; q.NCG = ncq / J; q.cgmajor = pl->cgmajor;
     const size_t shm_max = (size_t)Q_NS * Q_STAGE + 2 * 16 * Q_BN * sizeof(float);      // either form: ring [+ exchange] + the table of 16 blocks
     const size_t shm = (size_t)ns * Q_STAGE + (ksplit ? 32 * 1024 : 0) + (size_t)2 * J * bn * sizeof(float);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    static unsigned long long done = 0;
-    if (!(done >> (dev & 63) & 1ull)) {
-      const void* ks[4] = {(const void*)lin128q_kernel<20, true>, (const void*)lin128q_kernel<20, false>, (const void*)lin128q_kernel<40, true, true>, (const void*)lin128q_kernel<40, false, true>};
-      for (const void* kf : ks) if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_max) != hipSuccess) return 2;
-      done |= 1ull << (dev & 63);
-    }
-    const dim3 grid((unsigned)(nrg * q.NCG));
-    if (ksplit) {
-      if (g.geglu) hipLaunchKernelGGL((lin128q_kernel<40, true, true>), grid, dim3(512), shm, s, q);
-      else hipLaunchKernelGGL((lin128q_kernel<40, false, true>), grid, dim3(512), shm, s, q);
-    } else {
-      if (g.geglu) hipLaunchKernelGGL((lin128q_kernel<20, true>), grid, dim3(512), shm, s, q);
-      else hipLaunchKernelGGL((lin128q_kernel<20, false>), grid, dim3(512), shm, s, q);
-    }
+    typedef void (*kern_t)(NrLin128QParams);
+    static const kern_t ks[4] = {lin128q_kernel<20, true>, lin128q_kernel<20, false>, lin128q_kernel<40, true, true>, lin128q_kernel<40, false, true>};
+    static unsigned long long done[4] = {};
+    const int ki = (ksplit ? 2 : 0) + (g.geglu ? 0 : 1);
+    if (const int rc = nr_lds_opt_in(done[ki], {(const void*)ks[ki]}, shm_max)) return rc;
+    hipLaunchKernelGGL(ks[ki], dim3((unsigned)(nrg * q.NCG)), dim3(512), shm, s, q);
     return 0;
   }
   if (g.M % 64 != 0 || g.N % L1_BN != 0 || g.K % 64 != 0 || g.K / 64 < L1_NS) return 1;
@@ -664,30 +655,14 @@ extern "C" int nr_launch_lin160(const NrGemmParams* pp, const bf16* stream, hipS
   p.x = g.a0; p.lda = g.lda0; p.stream = stream; p.bias = g.bias; p.res = g.res; p.ldr = g.ldr; p.out = g.out; p.ldo = g.ldo; p.M = g.M; p.N = g.N; p.K = g.K; p.norot = g.plan_m > 0 ? 1 : 0;
   const int ncb = g.N / L1_BN;
   p.ln_c = g.ln_c; p.ln_eps = g.ln_eps;
-  if (g.geglu) {
-    if (!g.ln_c || !g.bias || g.M % 128 != 0) return 1;
-    constexpr size_t shm = (size_t)L1_NS * (L1_W_STAGE + 128 * 128);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    static unsigned long long done = 0;
-    if (!(done >> (dev & 63) & 1ull)) {
-      if (hipFuncSetAttribute((const void*)lin160_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-      done |= 1ull << (dev & 63);
-    }
-    hipLaunchKernelGGL((lin160_kernel<128, 1>), dim3((unsigned)((g.M / 128) * ncb)), dim3(512), shm, s, p);
-    return 0;
-  }
-  // 128-row tiles when they still fill the chip (and the row count allows), else 64-row tiles
-  const bool big = g.M % 128 == 0 && (long long)(Mp / 128) * ncb >= 256;
-  constexpr size_t shm128 = (size_t)L1_NS * (L1_W_STAGE + 128 * 128), shm64 = (size_t)L1_NS * (L1_W_STAGE + 64 * 128);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(g_l1_attr >> (dev & 63) & 1ull)) {
-    if (hipFuncSetAttribute((const void*)lin160_kernel<128, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm128) != hipSuccess) return 2;
-    if (hipFuncSetAttribute((const void*)lin160_kernel<64, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm64) != hipSuccess) return 2;
-    g_l1_attr |= 1ull << (dev & 63);
-  }
-  if (big) hipLaunchKernelGGL((lin160_kernel<128, 0>), dim3((unsigned)((g.M / 128) * ncb)), dim3(512), shm128, s, p);
-  else hipLaunchKernelGGL((lin160_kernel<64, 0>), dim3((unsigned)((g.M / 64) * ncb)), dim3(512), shm64, s, p);
+  const bool gln = pl->form == 2, big = gln || pl->big;
+  if (gln != (g.geglu != 0) || (gln && (!g.ln_c || !g.bias)) || (big && g.M % 128 != 0)) return 1;
+  typedef void (*kern_t)(NrLin160Params);
+  static const kern_t ks[3] = {lin160_kernel<128, 1>, lin160_kernel<128, 0>, lin160_kernel<64, 0>};
+  const int ki = gln ? 0 : (big ? 1 : 2), rows = big ? 128 : 64;
+  const size_t shm = (size_t)L1_NS * (L1_W_STAGE + rows * 128);
+  static unsigned long long done[3] = {};
+  if (const int rc = nr_lds_opt_in(done[ki], {(const void*)ks[ki]}, shm)) return rc;
+  hipLaunchKernelGGL(ks[ki], dim3((unsigned)((g.M / rows) * ncb)), dim3(512), shm, s, p);
   return 0;
 }

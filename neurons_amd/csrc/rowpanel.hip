@@ -357,44 +357,40 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(NrRowPanelParams p) {
   }
 }
 
-unsigned long long g_attr_mask = 0;   // per-device opt-in for > 64 KiB of dynamic LDS
-
 }  // namespace
 
-// shapes this kernel serves (the caller falls back to the tiled igemm otherwise)
-extern "C" int nr_rowpanel_eligible(const NrGemmParams* pp) {
-  const NrGemmParams& p = *pp;
-  static const bool off = getenv("NR_ROWPANEL") && getenv("NR_ROWPANEL")[0] == '0';   // A/B switch
-  if (off) return 0;
-  if (p.ksize != 1 || p.a1 || p.c1 != 0 || p.out_f32) return 0;
-  if (p.K != 320 || p.N % 64 != 0 || p.N > 4096 || (p.plan_m > 0 && p.plan_m < p.M ? p.plan_m : p.M) < 4096) return 0;
-  if (p.act || (p.geglu && p.rowvec)) return 0;
-  if (p.ln_c && p.rowvec && p.res) return 0;            // the one epilogue combination that does not fit 256 VGPRs (and never occurs)
-  if (p.lda0 % 8 != 0 || p.ldo % 8 != 0 || (p.res && p.ldr % 8 != 0)) return 0;
-  if (p.rowvec && (p.rowvec_div <= 0 || p.rowvec_ld % 4 != 0)) return 0;
+// shapes this kernel serves (nr_gemm_route goes on to the tiled igemm otherwise) and the workgroups per panel
+extern "C" bool rowpanel_plan(const NrGemmParams& p, RowPanelPlan* pl) {
+  static const bool on = env_not_0("NR_ROWPANEL");   // A/B switch
+  if (!on) return false;
+  if (p.ksize != 1 || p.a1 || p.c1 != 0 || p.out_f32) return false;
+  if (p.K != 320 || p.N % 64 != 0 || p.N > 4096 || nr_plan_rows(p) < 4096) return false;
+  if (p.act || (p.geglu && p.rowvec)) return false;
+  if (p.ln_c && p.rowvec && p.res) return false;            // the one epilogue combination that does not fit 256 VGPRs (and never occurs)
+  if (p.lda0 % 8 != 0 || p.ldo % 8 != 0 || (p.res && p.ldr % 8 != 0)) return false;
+  if (p.rowvec && (p.rowvec_div <= 0 || p.rowvec_ld % 4 != 0)) return false;
   const int ncol = p.geglu ? p.N / 2 : p.N;
-  if (((size_t)p.M * (size_t)(p.ldo > p.ldr ? p.ldo : p.ldr) + ncol) * 2 >= 0x7fffff00ull) return 0;   // 32-bit buffer offsets
-  return 1;
+  if (((size_t)p.M * (size_t)(p.ldo > p.ldr ? p.ldo : p.ldr) + ncol) * 2 >= 0x7fffff00ull) return false;   // 32-bit buffer offsets
+  const int mblocks = (p.M + RP_ROWS - 1) / RP_ROWS;
+  const int NC = p.N / 64;
+  int ns = (256 + mblocks - 1) / mblocks;       // fill the 256 CUs
+  if (ns > NC) ns = NC;
+  if (ns < 1) ns = 1;
+  pl->nsplit = ns;
+  return true;
 }
 
-extern "C" int nr_launch_rowpanel(const NrGemmParams* pp, hipStream_t stream) {
+extern "C" int nr_launch_rowpanel(const NrGemmParams* pp, const RowPanelPlan* pl, hipStream_t stream) {
   const NrGemmParams& g = *pp;
-  if (!nr_rowpanel_eligible(pp)) return 1;
+  if (g.K != 320 || g.N % 64 != 0 || pl->nsplit < 1 || pl->nsplit > g.N / 64) return 1;
   NrRowPanelParams p;
   p.a = g.a0; p.lda = g.lda0; p.w = g.w; p.M = g.M; p.N = g.N; p.bias = g.bias;
   p.ln_c = g.ln_c; p.ln_eps = g.ln_eps;
   p.rowvec = g.rowvec; p.rowvec_div = g.rowvec_div > 0 ? g.rowvec_div : 1; p.rowvec_mod = g.rowvec_mod; p.rowvec_ld = g.rowvec_ld;
   p.res = g.res; p.ldr = g.ldr; p.out = g.out; p.ldo = g.ldo; p.out_scale = g.out_scale; p.geglu = g.geglu; p.act = g.act;
   const int mblocks = (g.M + RP_ROWS - 1) / RP_ROWS;
-  const int NC = g.N / 64;
-  int ns = (256 + mblocks - 1) / mblocks;       // fill the 256 CUs
-  if (ns > NC) ns = NC;
-  if (ns < 1) ns = 1;
-  p.nsplit = ns;
+  p.nsplit = pl->nsplit;
   constexpr size_t shm = (size_t)(RP_NS * 5 * 64 * 64 + 8 * 2048) * sizeof(bf16);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const bool first = !(g_attr_mask >> (dev & 63) & 1ull);
   typedef void (*kern_t)(NrRowPanelParams);
   // index: LN 8 | RV 4 | RES 2 | GEGLU 1 (GEGLU never carries a row vector; LN + RV + RES does not fit 256 VGPRs and never occurs)
   static const kern_t ks[16] = {
@@ -406,13 +402,11 @@ extern "C" int nr_launch_rowpanel(const NrGemmParams* pp, hipStream_t stream) {
       rowpanel_kernel<320, true, false, true, false>,   rowpanel_kernel<320, true, false, true, true>,
       rowpanel_kernel<320, true, true, false, false>,   nullptr,
       nullptr,                                          nullptr};
-  if (first) {    // opt every instantiation of this device into > 64 KiB of dynamic LDS once
-    for (auto k : ks)
-      if (k && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-    g_attr_mask |= 1ull << (dev & 63);
-  }
-  const kern_t k = ks[(g.ln_c ? 8 : 0) | (g.rowvec ? 4 : 0) | (g.res ? 2 : 0) | (g.geglu ? 1 : 0)];
+  static unsigned long long attr_done[16] = {};          // per instantiation
+  const int ki = (g.ln_c ? 8 : 0) | (g.rowvec ? 4 : 0) | (g.res ? 2 : 0) | (g.geglu ? 1 : 0);
+  const kern_t k = ks[ki];
   if (!k) return 3;
-  hipLaunchKernelGGL(k, dim3((unsigned)(mblocks * ns)), dim3(512), shm, stream, p);
+  if (const int rc = nr_lds_opt_in(attr_done[ki], {(const void*)k}, shm)) return rc;
+  hipLaunchKernelGGL(k, dim3((unsigned)(mblocks * p.nsplit)), dim3(512), shm, stream, p);
   return 0;
 }

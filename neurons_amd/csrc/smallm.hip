@@ -322,26 +322,32 @@ __global__ __launch_bounds__(256) void smallm_w_pack_kernel(const bf16* __restri
   *(bf16x8*)(out + idx * 8) = *(const bf16x8*)(w + (size_t)(16 * Tn + (lane & 15)) * K + 32 * ks + 8 * (lane >> 4));
 }
 
-struct SmallmPlan { int nt, G, J, C; };
-
-// shapes this kernel serves and how: nt n-tiles per slab, G column groups x J slabs each, C chunks of 640 along K
-// decided: the caller already chose this kernel (w_fm set at plan time): no environment is read, only the shape rules apply, so a launch can
-// never disagree with the plan that sized its workspace
-bool smallm_plan(const NrGemmParams& p, SmallmPlan* out, bool decided) {
-  int mode = 2;
-  if (!decided) {
-    if (getenv("NR_IGEMM_FORCE")) return false;                                       // plan sweeps of the tiled igemm (tools/gemm_sweep.py)
-    const char* me = getenv("NR_SMALLM");                                             // read when the CHOICE is made (engine: plan time; nr_op_* hooks: per call)
-    mode = me ? atoi(me) : 1;                                                         // 0 off, 1 M <= 512 (default), 2 every eligible launch
-    if (!mode) return false;
+typedef void (*smallm_kern_t)(NrGemmParams, int, int);
+template <int NT> smallm_kern_t smallm_pick(bool ln, bool geglu) {
+  if constexpr (NT % 2 == 0) {
+    return ln ? (geglu ? smallm_kernel<NT, true, true> : smallm_kernel<NT, true, false>)
+              : (geglu ? smallm_kernel<NT, false, true> : smallm_kernel<NT, false, false>);
+  } else {
+    return ln ? smallm_kernel<NT, true, false> : smallm_kernel<NT, false, false>;
   }
+}
+
+}  // namespace
+
+// Shapes this kernel serves and how (SmallmPlan).  Called by nr_gemm_route alone, so the switches are read when the CHOICE is made (engine: plan
+// time; nr_op_* hooks: per call) and a launch can never disagree with the plan that packed its weights
+extern "C" bool smallm_plan(const NrGemmParams& p, SmallmPlan* out) {
+  if (getenv("NR_IGEMM_FORCE")) return false;                                         // plan sweeps of the tiled igemm (tools/gemm_sweep.py)
+  const char* me = getenv("NR_SMALLM");
+  const int mode = me ? atoi(me) : 1;                                                 // 0 off, 1 M <= 512 (default), 2 every eligible launch
+  if (!mode) return false;
   if (p.ksize != 1 || p.stride != 1 || p.ups || p.out_f32 || p.tap_inner) return false;
   if (p.a1 ? (p.c0 % 640 != 0 || p.c1 % 640 != 0 || p.lda1 % 8 != 0 || p.ln_c) : p.c1 != 0) return false;      // second source: whole 640-deep chunks
   if (p.K != p.c0 + p.c1 || p.K % 640 != 0 || p.N % 16 != 0 || p.M < 1) return false;
   if (p.lda0 % 8 != 0 || p.ldo % 4 != 0 || (p.res && p.ldr % 4 != 0)) return false;
   if (p.rowvec && (p.rowvec_div <= 0 || p.rowvec_ld % 4 != 0)) return false;
   if (p.geglu && (p.rowvec || p.res || p.act || p.out_scale != 1.0f)) return false;
-  const int Mp = (p.plan_m > 0 && p.plan_m < p.M) ? p.plan_m : p.M;                   // NR_DETERMINISTIC_BATCH: the choice is made per clip
+  const int Mp = nr_plan_rows(p);                                                     // NR_DETERMINISTIC_BATCH: the choice is made per clip
   if (mode == 1 && Mp > 512) return false;
   const int C = p.K / 640;
   if (C > 16) return false;
@@ -365,43 +371,20 @@ bool smallm_plan(const NrGemmParams& p, SmallmPlan* out, bool decided) {
   // (32-row tiles: 16 x the weight bytes over the chip), 680 KB per CU at N = 3840 against the igemm's 490 KB with 128 x 64 tiles
   // (profiles/r05_smallm_ab.txt: 0.82-1.02x); one slab per workgroup wins 1.1-1.66x.  NR_SMALLM=2 keeps them (tests, the A/B tool).
   if (mode == 1 && best.J > 1) return false;
-  if (out) *out = best;
+  *out = best;
   return true;
 }
 
-typedef void (*smallm_kern_t)(NrGemmParams, int, int);
-template <int NT> smallm_kern_t smallm_pick(bool ln, bool geglu) {
-  if constexpr (NT % 2 == 0) {
-    return ln ? (geglu ? smallm_kernel<NT, true, true> : smallm_kernel<NT, true, false>)
-              : (geglu ? smallm_kernel<NT, false, true> : smallm_kernel<NT, false, false>);
-  } else {
-    return ln ? smallm_kernel<NT, true, false> : smallm_kernel<NT, false, false>;
-  }
-}
-
-}  // namespace
-
-// The CHOICE, made once per launch description: 1 when this shape should run on the panel-resident kernel.  The caller then packs fragment-major
-// weights and sets NrGemmParams::w_fm, and nr_launch_igemm / nr_igemm_workspace_bytes follow w_fm alone (no environment read at launch time)
-extern "C" int nr_smallm_eligible(const NrGemmParams* pp) { return smallm_plan(*pp, nullptr, false) ? 1 : 0; }
-
-extern "C" int nr_launch_smallm(const NrGemmParams* pp, hipStream_t stream) {
-  const NrGemmParams& p = *pp;
-  SmallmPlan pl;
-  if (!p.w_fm || !smallm_plan(p, &pl, true)) return 1;
+extern "C" int nr_launch_smallm(const NrGemmParams* pp, const SmallmPlan* plp, const bf16* w_fm, hipStream_t stream) {
+  NrGemmParams p = *pp;
+  const SmallmPlan& pl = *plp;
+  p.w_fm = w_fm;
+  if (!w_fm || (pl.nt != 4 && pl.nt != 5) || (p.geglu && pl.nt != 4) || pl.G < 1 || pl.C != p.K / 640 || p.N != 16 * pl.nt * pl.G * pl.J) return 1;
   const bool ln = p.ln_c != nullptr, gg = p.geglu != 0;
   smallm_kern_t k = pl.nt == 5 ? smallm_pick<5>(ln, gg) : smallm_pick<4>(ln, gg);
   const size_t shm = (size_t)SM_NSLOT * SM_CHB + SM_SCRATCH;           // 140 KiB: one workgroup per CU
-  static unsigned long long attr_done[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per instantiation: one bit per device ordinal
-  {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    unsigned long long& mask = attr_done[(pl.nt == 5 ? 0 : 4) + (ln ? 2 : 0) + (gg ? 1 : 0)];
-    if (!(mask & (1ull << (dev & 63)))) {
-      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-      mask |= 1ull << (dev & 63);
-    }
-  }
+  static unsigned long long attr_done[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per instantiation
+  if (const int rc = nr_lds_opt_in(attr_done[(pl.nt == 5 ? 0 : 4) + (ln ? 2 : 0) + (gg ? 1 : 0)], {(const void*)k}, shm)) return rc;
   const unsigned grid = (unsigned)(((p.M + 31) / 32) * pl.G);
   hipLaunchKernelGGL(k, dim3(grid), dim3(128 * pl.nt), shm, stream, p, pl.J, pl.C);
   return 0;

@@ -427,7 +427,7 @@ unsigned long long g_ta_attr = 0;
 extern "C" size_t nr_tattn_stream_bytes(void) { return (size_t)TA_HEADS * TA_HEAD_BYTES; }
 
 extern "C" int nr_tattn_fused_eligible(int C, int heads, int frames, int hw, long long rows) {
-  static const bool off = getenv("NR_TATTN_FUSED") && getenv("NR_TATTN_FUSED")[0] == '0';   // A/B switch
+  static const bool off = !env_not_0("NR_TATTN_FUSED");   // A/B switch
   return !off && C == TA_C && heads == TA_HEADS && (frames == 16 || frames == 32) && hw % (TA_ROWS / frames) == 0 && rows >= 4096;
 }
 
@@ -444,13 +444,7 @@ extern "C" int nr_launch_tattn_fused(bf16* t, int nbatch, int frames, int hw, co
   p.t = t; p.hw = hw; p.nbatch = nbatch; p.stream = stream; p.gamma = gamma; p.gb = gb; p.bo = bo; p.ln_eps = ln_eps; p.norot = norot;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)TA_D);
   constexpr size_t shm = (size_t)TA_NS * TA_SLOT;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(g_ta_attr >> (dev & 63) & 1ull)) {
-    if (hipFuncSetAttribute((const void*)tattn_fused_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-    if (hipFuncSetAttribute((const void*)tattn_fused_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-    g_ta_attr |= 1ull << (dev & 63);
-  }
+  if (const int rc = nr_lds_opt_in(g_ta_attr, {(const void*)tattn_fused_kernel<16>, (const void*)tattn_fused_kernel<32>}, shm)) return rc;
   const unsigned grid = (unsigned)(nbatch * (hw / (TA_ROWS / frames)));
   if (frames == 16) hipLaunchKernelGGL(tattn_fused_kernel<16>, dim3(grid), dim3(256), shm, s, p);
   else hipLaunchKernelGGL(tattn_fused_kernel<32>, dim3(grid), dim3(256), shm, s, p);

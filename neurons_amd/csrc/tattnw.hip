@@ -488,7 +488,7 @@ extern "C" size_t nr_tattnw_stream_bytes(int C) {
 // clip) only 64 workgroups exist, each streaming a head's 1.2 MB alone: 34 us against 27 us for the q|k|v GEMM + attention core (profiles/r06_tattn_head_ab.txt).
 // frames = 32: a workgroup still owns 64 rows, so the same floor in rows is the same floor in workgroups (profiles/r08_tattn_head_f32_ab.txt)
 extern "C" int nr_tattnw_eligible(int C, int heads, int frames, int hw, long long rows) {
-  static const bool off = getenv("NR_TATTN_HEAD") && getenv("NR_TATTN_HEAD")[0] == '0';   // A/B switch
+  static const bool off = !env_not_0("NR_TATTN_HEAD");   // A/B switch
   if (off || heads != TW_HEADS || (frames != 16 && frames != 32)) return 0;
   // the same rule at both frame counts (the pixels of a 16-frame workgroup, 8 / 4, are a multiple of those of a 32-frame one, 4 / 2)
   if (C == 640) return hw % TW<80>::PIX_WG == 0;
@@ -521,17 +521,14 @@ extern "C" int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, 
 }
 
 template <int D, int F>
-static int tattnw_launch(NrTAttnWParams& p, int dev, hipStream_t s) {
+static int tattnw_launch(NrTAttnWParams& p, hipStream_t s) {
   using T = TW<D, F>;
   if (p.hw % T::PIX_WG != 0) return 1;
   const int npg = p.nbatch * (p.hw / T::PIX_WG);
   p.xcd_mode = (D == 80 && npg % 8 == 0) ? 0 : 1;
   constexpr size_t shm = (size_t)T::NS * T::STAGE;
   static unsigned long long attr = 0;        // per instantiation: devices whose dynamic-LDS limit is raised
-  if (!(attr >> (dev & 63) & 1ull)) {
-    if (hipFuncSetAttribute((const void*)tattn_head_kernel<D, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-    attr |= 1ull << (dev & 63);
-  }
+  if (const int rc = nr_lds_opt_in(attr, {(const void*)tattn_head_kernel<D, F>}, shm)) return rc;
   hipLaunchKernelGGL((tattn_head_kernel<D, F>), dim3((unsigned)(npg * TW_HEADS)), dim3(T::THREADS), shm, s, p);
   return 0;
 }
@@ -543,8 +540,6 @@ extern "C" int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int frames
   p.t = t; p.out = out; p.hw = hw; p.nbatch = nbatch; p.stream = stream; p.table = table; p.ln_eps = ln_eps;
   const int d = C / TW_HEADS;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)d);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (C == 640) return frames == 16 ? tattnw_launch<80, 16>(p, dev, s) : tattnw_launch<80, 32>(p, dev, s);
-  return frames == 16 ? tattnw_launch<160, 16>(p, dev, s) : tattnw_launch<160, 32>(p, dev, s);
+  if (C == 640) return frames == 16 ? tattnw_launch<80, 16>(p, s) : tattnw_launch<80, 32>(p, s);
+  return frames == 16 ? tattnw_launch<160, 16>(p, s) : tattnw_launch<160, 32>(p, s);
 }

@@ -418,7 +418,7 @@ extern "C" size_t nr_xattn_wstream_bytes(void) { return (size_t)XA_HEADS * XA_W_
 extern "C" size_t nr_xattn_kvstream_bytes(int nctx) { return (size_t)nctx * XA_HEADS * XA_KV_BYTES; }
 
 extern "C" int nr_xattn_fused_eligible(int C, int heads, int Lk, int hw, long long rows) {
-  static const bool off = getenv("NR_XATTN_FUSED") && getenv("NR_XATTN_FUSED")[0] == '0';   // A/B switch
+  static const bool off = !env_not_0("NR_XATTN_FUSED");   // A/B switch
   return !off && C == XA_C && heads == XA_HEADS && Lk > 0 && Lk <= XA_KEYS && hw % XA_ROWS == 0 && rows >= 4096;
 }
 
@@ -444,12 +444,7 @@ extern "C" int nr_launch_xattn_fused(bf16* t, int nimg, int hw, int img_per_ctx,
   p.gamma = gamma; p.beta = beta; p.bo = bo; p.ln_eps = ln_eps;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)XA_D);
   constexpr size_t shm = (size_t)XA_NS * XA_SLOT;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(g_xa_attr >> (dev & 63) & 1ull)) {
-    if (hipFuncSetAttribute((const void*)xattn_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-    g_xa_attr |= 1ull << (dev & 63);
-  }
+  if (const int rc = nr_lds_opt_in(g_xa_attr, {(const void*)xattn_fused_kernel}, shm)) return rc;
   const unsigned grid = (unsigned)((long long)nimg * hw / XA_ROWS);
   hipLaunchKernelGGL(xattn_fused_kernel, dim3(grid), dim3(256), shm, s, p);
   return 0;

@@ -285,7 +285,7 @@ extern "C" size_t nr_xattnw_table_bytes(int C) { return (C == 640 || C == 1280) 
 
 // rows: the launch's row count (deterministic-batch mode: one clip's)
 extern "C" int nr_xattnw_eligible(int C, int heads, int Lk, int hw, long long rows) {
-  static const bool off = getenv("NR_XATTN_HEAD") && getenv("NR_XATTN_HEAD")[0] == '0';   // A/B switch
+  static const bool off = !env_not_0("NR_XATTN_HEAD");   // A/B switch
   return !off && (C == 640 || C == 1280) && heads == XW_HEADS && Lk >= 1 && Lk <= XW_KT * 16 && hw % XW_ROWS == 0 && rows >= 2048;
 }
 
@@ -322,13 +322,7 @@ extern "C" int nr_launch_xattnw(const bf16* t, bf16* out, int nimg, int hw, int 
   const int nrg = p.nrows / XW_ROWS, ncb = C / XW_COLS;
   p.xcd_mode = nrg % 8 == 0 ? 0 : 1;
   constexpr size_t shm = (size_t)XW_NS * XW_STAGE + XW_TBL;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(g_xw_attr >> (dev & 63) & 1ull)) {
-    if (hipFuncSetAttribute((const void*)xattn_head_kernel<80>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-    if (hipFuncSetAttribute((const void*)xattn_head_kernel<160>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 2;
-    g_xw_attr |= 1ull << (dev & 63);
-  }
+  if (const int rc = nr_lds_opt_in(g_xw_attr, {(const void*)xattn_head_kernel<80>, (const void*)xattn_head_kernel<160>}, shm)) return rc;
   const unsigned grid = (unsigned)(nrg * ncb);
   if (C == 640) hipLaunchKernelGGL(xattn_head_kernel<80>, dim3(grid), dim3(256), shm, s, p);
   else hipLaunchKernelGGL(xattn_head_kernel<160>, dim3(grid), dim3(256), shm, s, p);

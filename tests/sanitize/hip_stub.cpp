@@ -6,6 +6,7 @@
 // NR_STUB_TRACE=<file> (tools/plan_equal.sh): one line per kernel launch ("L <kernel> <grid> <block> <dynamic LDS bytes>", the name as
 // registered by the kernel's translation unit), per device allocation ("M <bytes>") and per host-to-device copy ("C <bytes> <FNV-1a 64 of
 // the bytes>"): what a plan launches and every converted weight it uploads, as text that two builds of the engine can be diffed on.
+// nr_stub_note(text) puts a "# text" line of the driver's between them.
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
 #include <cstdio>
@@ -86,4 +87,5 @@ long nr_stub_live_allocs(void) { return g_live_allocs; }
 long nr_stub_live_graphs(void) { return g_graphs; }
 long nr_stub_captures(void) { return g_captures; }
 long nr_stub_launches(void) { return g_launches; }
+void nr_stub_note(const char* text) { if (FILE* t = trace()) { fprintf(t, "# %s\n", text); fflush(t); } }
 }

@@ -4,6 +4,11 @@
 // weight.  tools/plan_equal.sh builds this driver against two trees of the engine and diffs both texts: the acceptance instrument of a host-side
 // engine refactor.  Shapes of one network are planned one after another on ONE handle, so what an earlier plan left in the weight cache counts too.
 //   usage: plan_dump <schema-file> [name,name,...]     (only these networks; the switches read once per process need a run of their own)
+//          plan_dump --ops <shapes-file>               every GEMM / conv op hook (nr_op_gemm, _gemm2, _ln_gemm, _gemm_ex, _conv3x3, _conv3x3_tap_inner) at the shapes
+//                                                      of the file (tests/sanitize/op_route_shapes.txt), once per gemm8p mode 0 / 1 / 2 x NR_SMALLM unset / 0 / 2: which
+//                                                      kernel each hook launches, in the trace
+//          plan_dump --decide-once <schema-file>       the C = 1280 transformer leaf at 1024 rows planned under gemm8p mode 2 and replayed (graph off) before and after
+//                                                      nr_g8p_set_mode(1) + NR_IGEMM_FORCE: a plan launches what it was planned with (tests/test_gemm_route_host.py)
 #include "../../include/neurons_amd.h"
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +17,8 @@
 #include <map>
 #include <string>
 #include <vector>
+
+extern "C" void nr_stub_note(const char* text);
 
 struct Net { nr_net_config cfg; std::vector<std::pair<std::string, std::vector<int64_t>>> tensors; };
 
@@ -45,8 +52,9 @@ static const std::map<std::string, std::vector<Case>> g_cases = {
     {"leaf_transformer", {{{1, 2, 48, 48, 77}, PLAIN}, {{1, 2, 8, 8, 77}, PLAIN}, {{2, 2, 48, 48, 77}, PLAIN}, {{1, 4, 32, 32, 77}, PLAIN}, {{1, 2, 16, 16, 77}, PLAIN},
                           {{2, 16, 16, 16, 77}, DET_BATCH}}},
     {"leaf_temporal", {{{1, 16, 16, 16, 0}, PLAIN}, {{1, 16, 8, 8, 0}, PLAIN}, {{2, 16, 16, 16, 0}, PLAIN}, {{1, 16, 4, 8, 0}, PLAIN}, {{4, 16, 16, 16, 0}, DET_BATCH}}},
-    // C = 640: 256 / 2048 / 4096 rows and 16 frames
-    {"leaf_transformer640", {{{2, 2, 8, 8, 77}, PLAIN}, {{2, 1, 32, 32, 77}, PLAIN}, {{2, 2, 32, 32, 77}, PLAIN}, {{1, 16, 8, 8, 77}, PLAIN}, {{1, 16, 16, 16, 77}, PLAIN}}},
+    // C = 640: 256 / 2048 / 4096 rows and 16 frames; 32768 rows: the long-K (3200) folded FeedForward GEMM fills the chip with 256-row tiles (gemm8p.hip)
+    {"leaf_transformer640", {{{2, 2, 8, 8, 77}, PLAIN}, {{2, 1, 32, 32, 77}, PLAIN}, {{2, 2, 32, 32, 77}, PLAIN}, {{1, 16, 8, 8, 77}, PLAIN}, {{1, 16, 16, 16, 77}, PLAIN},
+                             {{2, 16, 32, 32, 77}, PLAIN}}},
     {"leaf_temporal640", {{{1, 16, 8, 8, 0}, PLAIN}, {{1, 8, 8, 8, 0}, PLAIN}, {{1, 16, 4, 4, 0}, PLAIN}, {{1, 16, 8, 16, 0}, PLAIN}, {{1, 16, 16, 16, 0}, PLAIN}}},
     // C = 1280: 2048 rows (and the 256 rows of the small-M kernel)
     {"leaf_transformer1280", {{{2, 1, 32, 32, 77}, PLAIN}, {{1, 16, 8, 16, 77}, PLAIN}, {{2, 2, 8, 8, 77}, PLAIN}}},
@@ -57,12 +65,10 @@ static const std::map<std::string, std::vector<Case>> g_cases = {
     {"tiny_clip", {{{2, 1, 1, 77, 0}, PLAIN}}},
 };
 
-int main(int argc, char** argv) {
-  if (argc < 2) { fprintf(stderr, "usage: plan_dump <schema-file> [name,name,...]\n"); return 1; }
-  const std::string only = argc > 2 ? std::string(",") + argv[2] + "," : std::string();
-  FILE* f = fopen(argv[1], "r");
+static std::vector<std::pair<std::string, Net>> read_schema(const char* path) {      // in file order
+  FILE* f = fopen(path, "r");
   CHECK(f, "schema file");
-  std::vector<std::pair<std::string, Net>> nets;      // in file order
+  std::vector<std::pair<std::string, Net>> nets;
   char line[4096];
   while (fgets(line, sizeof(line), f)) {
     if (line[0] == 'N') {
@@ -83,6 +89,91 @@ int main(int argc, char** argv) {
     }
   }
   fclose(f);
+  return nets;
+}
+
+// --ops: one call per line and switch setting.  Kernel launches are no-ops under the stub, so one dummy block stands in for every tensor
+static int run_ops(const char* path) {
+  FILE* f = fopen(path, "r");
+  CHECK(f, "shapes file");
+  std::vector<std::string> lines;
+  char line[512];
+  while (fgets(line, sizeof(line), f))
+    if (line[0] != '#' && line[0] != '\n') lines.emplace_back(line, strcspn(line, "\n"));
+  fclose(f);
+  alignas(256) static char blk[4096];
+  const float* fp = reinterpret_cast<const float*>(blk);
+  for (int g8p = 0; g8p <= 2; ++g8p)
+    for (const char* sm : {"", "0", "2"}) {
+      nr_g8p_set_mode(g8p);
+      if (*sm) setenv("NR_SMALLM", sm, 1); else unsetenv("NR_SMALLM");
+      nr_stub_note(("== gemm8p mode " + std::to_string(g8p) + " NR_SMALLM=" + (*sm ? sm : "unset")).c_str());
+      for (const std::string& l : lines) {
+        nr_stub_note(l.c_str());
+        char hook[32];
+        int v[12] = {0};
+        float scale = 1.f;
+        nr_status st = NR_OK;
+        if (sscanf(l.c_str(), "%31s", hook) != 1) continue;
+        const std::string h = hook;
+        if (h == "conv3x3") {
+          CHECK(sscanf(l.c_str(), "%*s %d %d %d %d %d %d %d %d %d %d %d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8, v + 9, v + 10) == 11, l.c_str());
+          st = nr_op_conv3x3(nullptr, blk, v[3], v[4] ? blk : nullptr, v[4], v[0], v[1], v[2], v[6], v[7], blk, v[8] ? fp : nullptr, v[9] ? fp : nullptr, v[9], v[10] ? blk : nullptr, blk, v[5]);
+        } else if (h == "conv3x3_tap_inner") {
+          CHECK(sscanf(l.c_str(), "%*s %d %d %d %d %d %d %d %d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7) == 8, l.c_str());
+          st = nr_op_conv3x3_tap_inner(nullptr, blk, v[3], v[0], v[1], v[2], blk, v[5] ? fp : nullptr, v[6] ? fp : nullptr, v[6], v[7] ? blk : nullptr, blk, v[4]);
+        } else {
+          CHECK(sscanf(l.c_str(), "%*s %d %d %d %d %d %d %d %d %f %d %d %d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, &scale, v + 8, v + 9, v + 10) == 12, l.c_str());
+          const int M = v[0], N = v[1], K = v[2], bias = v[3], ln = v[4], res = v[5], geglu = v[6], act = v[7], rvd = v[8], rvm = v[9], c1 = v[10];
+          const int No = geglu ? N / 2 : N;
+          if (h == "gemm") st = nr_op_gemm(nullptr, blk, K, blk, bias ? fp : nullptr, res ? blk : nullptr, No, blk, No, M, N, K, geglu);
+          else if (h == "gemm2") st = nr_op_gemm2(nullptr, blk, K - c1, K - c1, blk, c1, c1, blk, bias ? fp : nullptr, res ? blk : nullptr, N, blk, N, M, N);
+          else if (h == "ln_gemm") st = nr_op_ln_gemm(nullptr, blk, K, blk, fp, fp, 1e-5f, res ? blk : nullptr, res ? No : 0, blk, No, M, N, K, geglu, act);
+          else if (h == "gemm_ex") st = nr_op_gemm_ex(nullptr, blk, K, blk, bias ? fp : nullptr, ln ? fp : nullptr, 1e-5f, rvd ? fp : nullptr, rvd ? rvd : 1, rvm, rvd ? N : 0, res ? blk : nullptr, N, blk, N, M, N, K, 0, act, scale);
+          else CHECK(false, l.c_str());
+        }
+        if (st != NR_OK) nr_stub_note(("status " + std::to_string((int)st)).c_str());
+      }
+    }
+  return 0;
+}
+
+// --decide-once: see the usage text.  Prints the status of each replay
+static int run_decide_once(const char* schema) {
+  const auto nets = read_schema(schema);
+  const Net* n = nullptr;
+  for (auto& nn : nets) if (nn.first == "leaf_transformer1280") n = &nn.second;
+  CHECK(n, "schema has no leaf_transformer1280");
+  std::vector<float> io((size_t)8 << 20);
+  nr_net* h = nullptr;
+  OK(nr_net_create(&n->cfg, &h));
+  load_all(h, *n, 3);
+  OK(nr_net_set_graph(h, 0));
+  nr_g8p_set_mode(2);
+  OK(nr_net_plan(h, 1, 16, 8, 8, 77));
+  nr_stub_note("replay first");          // also runs the context ops (text k|v projections), which later replays skip
+  printf("replay first: status %d\n", (int)nr_leaf_forward(h, nullptr, io.data(), io.data() + (2 << 20), 77, io.data() + (4 << 20)));
+  nr_stub_note("replay planned");
+  printf("replay planned: status %d\n", (int)nr_leaf_forward(h, nullptr, io.data(), io.data() + (2 << 20), 77, io.data() + (4 << 20)));
+  nr_g8p_set_mode(1);
+  setenv("NR_IGEMM_FORCE", "64,64,4,2,0", 1);
+  nr_stub_note("replay switched");
+  printf("replay switched: status %d (%s)\n", (int)nr_leaf_forward(h, nullptr, io.data(), io.data() + (2 << 20), 77, io.data() + (4 << 20)), nr_last_error());
+  // the control: the same shape planned afresh under mode 1 takes the tiled kernel with split-K
+  unsetenv("NR_IGEMM_FORCE");
+  OK(nr_net_plan(h, 1, 16, 8, 8, 77));
+  nr_stub_note("replay control");
+  printf("replay control: status %d\n", (int)nr_leaf_forward(h, nullptr, io.data(), io.data() + (2 << 20), 77, io.data() + (4 << 20)));
+  nr_net_destroy(h);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 2) { fprintf(stderr, "usage: plan_dump <schema-file> [name,name,...] | --ops <shapes-file> | --decide-once <schema-file>\n"); return 1; }
+  if (argc == 3 && std::string(argv[1]) == "--ops") return run_ops(argv[2]);
+  if (argc == 3 && std::string(argv[1]) == "--decide-once") return run_decide_once(argv[2]);
+  const std::string only = argc > 2 ? std::string(",") + argv[2] + "," : std::string();
+  const std::vector<std::pair<std::string, Net>> nets = read_schema(argv[1]);
   const float ts[64] = {500.f, 500.f, 480.f, 480.f};
   std::vector<float> io((size_t)64 << 20);          // one host block standing in for every "device" I/O tensor
   float* sample = io.data();

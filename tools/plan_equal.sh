@@ -9,7 +9,8 @@
 # (tests/sanitize/plan_dump.cpp), runs both on the schema of tools/plan_schema.py and compares, per run, the driver's dump (op descriptions,
 # workspace and weight bytes, export manifest) and the stub's trace (every kernel launch with grid / block / LDS bytes, every device allocation,
 # size and hash of every uploaded weight).  Runs: every network at its listed shapes, then the C = 320 leaf modules once per planner switch that a
-# process reads once (NR_LN_FUSE=0, NR_FOLD_PROJ_OUT=0, NR_SMALLM=0).  One line per run: "identical", or "DIFFERS" and the first differing lines.
+# process reads once (NR_LN_FUSE=0, NR_FOLD_PROJ_OUT=0, NR_SMALLM=0), then the networks with GEMM-heavy plans once per switch of the GEMM route (NR_G8P=0 / 2,
+# NR_ROWPANEL=0, NR_LIN160=0, one NR_IGEMM_FORCE setting).  One line per run: "identical", or "DIFFERS" and the first differing lines.
 # The dump must also contain every kernel class the planner can choose (a shape list that loses one is no evidence).  Exit status 1 on any of it.
 # The only normalisation: pointer values (0x...) become a fixed token.  Needs no GPU.  JOBS=<n> compiles in parallel (default 8, at most 16).
 set -euo pipefail
@@ -48,10 +49,17 @@ run_both default ""
 run_both ln_fuse_0 leaf_transformer,leaf_temporal NR_LN_FUSE=0
 run_both fold_proj_out_0 leaf_transformer,leaf_temporal NR_FOLD_PROJ_OUT=0
 run_both smallm_0 leaf_transformer,leaf_temporal NR_SMALLM=0
+# the process-wide switches the GEMM route reads (nr_gemm_route), on the networks whose plans those kernels appear in
+gemm_nets=leaf_transformer,leaf_temporal,leaf_transformer640,leaf_temporal640,leaf_transformer1280,tiny_vae_dec
+run_both g8p_0 $gemm_nets NR_G8P=0
+run_both g8p_2 $gemm_nets NR_G8P=2
+run_both rowpanel_0 $gemm_nets NR_ROWPANEL=0
+run_both lin160_0 $gemm_nets NR_LIN160=0
+run_both igemm_force $gemm_nets NR_IGEMM_FORCE=128,64,2,3,1
 
 echo "# plans of the working tree against $rev ($(git -C "$root" rev-parse --short "$rev"))"
 status=0
-for label in default ln_fuse_0 fold_proj_out_0 smallm_0; do
+for label in default ln_fuse_0 fold_proj_out_0 smallm_0 g8p_0 g8p_2 rowpanel_0 lin160_0 igemm_force; do
   for what in dump trace; do
     a="$tmp/old.$label.$what"; b="$tmp/new.$label.$what"
     if cmp -s "$a" "$b"; then
@@ -66,6 +74,12 @@ done
 for k in ff_fused xattn_fused xattn_head tattn_fused tattn_head 'lin160 ' 'lin160 panel' igemm groupnorm layernorm attention; do
   n=$(grep -c -E "^op [0-9]+: $k" "$tmp/old.default.dump" || true)
   echo "coverage '$k': $n ops in $rev's dump"
+  [ "$n" -gt 0 ] || status=1
+done
+# ... and its default trace launches every GEMM kernel class the route can choose
+for k in smallm_kernel lin160_kernel lin128q_kernel rowpanel_kernel g8p_kernel igemm_bf16_kernel splitk_reduce_kernel; do
+  n=$(grep -c -E "^L [^ ]*$k" "$tmp/old.default.trace" || true)
+  echo "coverage '$k': $n launches in $rev's trace"
   [ "$n" -gt 0 ] || status=1
 done
 exit $status
