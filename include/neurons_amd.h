@@ -298,6 +298,15 @@ nr_status nr_unet3d_forward_after(nr_net* unet, nr_net* ctrl, int32_t slot, nr_s
  * operands (fp32 softmax statistics and accumulation).  Off by default (bf16); changing it invalidates the plan. */
 nr_status nr_net_set_attention_fp8(nr_net* h, int32_t enable);
 
+/* Weight-only OCP e4m3 storage for the Linears the small-M kernel serves (<= 512 rows, K a multiple of 640: the 4x4 level of the U-Net, the
+ * depth-10 level of the keyframe model).  Every such checkpoint matrix (LayerNorm-scaled or not) is quantised once per plan, per row n:
+ * scale 2^e[n], e[n] = ceil(log2(amax_n / 448)), codes e4m3_rne(w 2^-e[n]); the kernel widens the codes to bf16 in registers and multiplies
+ * the fp32 accumulator by the row scale, so the result equals the bf16 kernel's on the dequantised matrix bit for bit.  Matrices the engine
+ * derives as products (the folded net.2 | proj_out operand) and every other kernel class stay bf16.  A numerics variant (3 mantissa bits:
+ * ~2.6e-2 rel-L2 per Linear against the bf16-weight result); the bf16 matrices stay resident, so it saves no memory.  Off by default; a new
+ * handle takes its default from NR_W8=1; changing it invalidates the plan. */
+nr_status nr_net_set_weight_fp8(nr_net* h, int32_t enable);
+
 /* SparseCtrl: tell the engine which frames carry a condition (controlnet_cond / conditioning_mask not all zero there;
  * pipeline_neuroclips.py:447-458 fills only controlnet_image_index).  With set_noisy_sample_input_to_zero every other frame enters the
  * network as the same constant image, so down_blocks[0].resnets[0] + attentions[0] are evaluated on the conditioned frames plus ONE
@@ -376,6 +385,10 @@ void nr_op_fm_cache_clear(void);
 nr_status nr_op_gemm(nr_stream stream, const void* a_dev, int32_t lda, const void* w_dev, const float* bias_dev,
                      const void* res_dev, int32_t ldr, void* out_dev, int32_t ldo, int32_t M, int32_t N, int32_t K,
                      int32_t geglu);
+/* The e4m3 form of a bf16 [N][K] matrix as nr_net_set_weight_fp8 stores it: N K code bytes in the small-M kernel's fragment order
+ * ([N/16][K/64][64 lanes][16 bytes]), then N fp32 row scales; N % 16 == 0, K % 64 == 0, capacity >= N K + 4 N bytes.  The nr_op_gemm* hooks
+ * read NR_W8=1 per call (where NR_SMALLM is read) to run an eligible launch on this form. */
+nr_status nr_op_w8_pack(nr_stream stream, const void* w_dev, int32_t N, int32_t K, void* out_dev, int64_t capacity);
 /* out = [a0 | a1] . w^T (+bias) (+res): the two-source operand of the engine's conv(x, &skip, ...) / folded FeedForward as a 1x1 GEMM;
  * a0 [M][lda0] supplies channels [0, c0), a1 [M][lda1] channels [c0, c0 + c1); w bf16 [N][c0 + c1] */
 nr_status nr_op_gemm2(nr_stream stream, const void* a0_dev, int32_t c0, int32_t lda0, const void* a1_dev, int32_t c1, int32_t lda1,

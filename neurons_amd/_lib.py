@@ -104,6 +104,7 @@ SYMBOLS = {
     "nr_net_import_weights": (_I32, [_VP, _VP, C.c_char_p, _I64, _VP, _I64]),
     "nr_net_profile_last": (_I32, [_VP, _VP, C.POINTER(NrProfile)]),
     "nr_net_set_attention_fp8": (_I32, [_VP, _I32]),
+    "nr_net_set_weight_fp8": (_I32, [_VP, _I32]),
     "nr_net_set_deterministic_batch": (_I32, [_VP, _I32]),
     "nr_net_set_clip_samples": (_I32, [_VP, _I32]),
     "nr_net_set_cfg_pair_identical": (_I32, [_VP, _I32]),
@@ -120,6 +121,7 @@ SYMBOLS = {
     "nr_leaf_forward": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP]),
     "nr_op_fm_cache_clear": (None, []),
     "nr_op_gemm": (_I32, [_VP, _VP, _I32, _VP, _VP, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _I32]),
+    "nr_op_w8_pack": (_I32, [_VP, _VP, _I32, _I32, _VP, _I64]),
     "nr_op_gemm2": (_I32, [_VP, _VP, _I32, _I32, _VP, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _I32, _I32, _I32]),
     "nr_op_ln_gemm": (_I32, [_VP, _VP, _I32, _VP, _VP, _VP, C.c_float, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _I32, _I32]),
     "nr_op_gemm_ex": (_I32, [_VP, _VP, _I32, _VP, _VP, _VP, C.c_float, _VP, _I32, _I32, _I32, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _I32, _I32,

@@ -111,6 +111,10 @@ struct NrGemmParams {
   float ln_eps;
   int act;             // 0 none; 1 quick_gelu x*sigmoid(1.702x) (CLIP MLP), applied after bias/scale, before the residual
   int pad_tl0;         // 3x3 only: 1 = no top/left padding (bottom/right zero) — the VAE Downsample's F.pad (0,1,0,1)
+  int w8;              // REQUEST, set by the caller: 1 = this W may be read as weight-only OCP e4m3 codes with one power-of-two scale per row (opt-in
+                       // numerics variant, nr_net_set_weight_fp8 / NR_W8).  Only smallm.hip has such a form: when it takes the launch the route names
+                       // NR_W_FRAGMAJOR_E4M3, every other class ignores the request and reads bf16.  It enters no plan choice
+                       // (the field fills what was a padding hole in front of out_f32: no other offset moved)
   float* out_f32;      // non-null: write the raw fp32 accumulators to out_f32[M][N] and skip the epilogue (attention scores)
   int plan_m;          // > 0: every choice that can change the arithmetic of a row (tile -> split-K depth, row-panel eligibility) is made as if the
                        // launch had plan_m rows (the rows of ONE clip's CFG pair), so a clip's result does not depend on its neighbours in the
@@ -120,6 +124,7 @@ struct NrGemmParams {
                        // spread over the whole K loop (tap-major order: the working set of the tiles in flight exceeds the 4 MiB L2)
   const bf16* w_fm;    // non-null: the same weights in FRAGMENT-MAJOR order for smallm.hip: [N/16][K/32][64 lanes][8], lane (fr, fg) of block
                        // (T, ks) holds W[16 T + fr][32 ks + 8 fg .. + 7], so a wave's MFMA A-operand load is one contiguous KiB (nr_launch_smallm_w_pack)
+                       // With NR_W_FRAGMAJOR_E4M3 (gemm_route.h) it points at the e4m3 form instead: codes [N/16][K/64][64 lanes][16 bytes], then float scale[N]
 };
 
 __device__ __forceinline__ NrGemmParams nr_pin_params(NrGemmParams p) {
@@ -129,7 +134,7 @@ __device__ __forceinline__ NrGemmParams nr_pin_params(NrGemmParams p) {
   p.rowvec = nr_pin(p.rowvec); p.rowvec_div = nr_pin(p.rowvec_div); p.rowvec_mod = nr_pin(p.rowvec_mod); p.rowvec_ld = nr_pin(p.rowvec_ld);
   p.res = nr_pin(p.res); p.ldr = nr_pin(p.ldr); p.out = nr_pin(p.out); p.ldo = nr_pin(p.ldo); p.out_scale = nr_pin(p.out_scale);
   p.geglu = nr_pin(p.geglu); p.ln_c = nr_pin(p.ln_c); p.ln_eps = nr_pin(p.ln_eps); p.act = nr_pin(p.act); p.pad_tl0 = nr_pin(p.pad_tl0);
-  p.out_f32 = nr_pin(p.out_f32); p.tap_inner = nr_pin(p.tap_inner); p.w_fm = nr_pin(p.w_fm);
+  p.out_f32 = nr_pin(p.out_f32); p.tap_inner = nr_pin(p.tap_inner); p.w_fm = nr_pin(p.w_fm); p.w8 = nr_pin(p.w8);
   return p;
 }
 

@@ -262,7 +262,7 @@ struct WeightStore {
   const float* w_f32(const std::string& key, int64_t n) { return w_f32(key, {n}); }
   const float* pe_table(int C, int max_len);                                                        // "pe:"
   const float* b_ln_pe(const std::string& ln, int F, int C);                                        // "tagb:"
-  const bf16* w_layout(const bf16* w, int N, int K, int layout);                                    // "fm:" / "l160:" / "l128:<name of w>" (NrWeightLayout)
+  const bf16* w_layout(const bf16* w, int N, int K, int layout);                                    // "fm:" / "w8:" / "l160:" / "l128:<name of w>" (NrWeightLayout)
 };
 
 }  // namespace nre
@@ -320,6 +320,8 @@ struct nr_net {
   int cond_frames[64] = {0};
   bool cfg_dup = false;          // nr_net_set_cfg_pair_identical: the caller promises sample[b] == sample[b + B2/2] and timestep[b] == timestep[b + B2/2]
   bool attn_fp8 = false;         // nr_net_set_attention_fp8: spatial / cross attention on e4m3 MFMA operands (config 5)
+  bool w8 = false;               // nr_net_set_weight_fp8 (new handles: NR_W8=1): the Linears smallm.hip serves read their checkpoint matrices as e4m3 codes
+                                 // with one power-of-two scale per row (NrGemmParams::w8); a numerics variant, bf16 is the default
   IO io = nre::new_io();
   int n_res = 0;
   struct ResShape { int C, h, w; };
@@ -396,6 +398,7 @@ struct nr_net {
     int act = 0;             // 1: quick_gelu
     const float* ln_c = nullptr;   // LayerNorm folded into this GEMM (see w_ln_linear)
     int tap_inner = 0;       // 3x3 stride 1 single source: weights in the tap-inner layout of w_conv3(.., tap_inner)
+    bool derived_w = false;  // w is a product the engine computed (w_fold_ff_proj), not a checkpoint tensor: it stays bf16 under nr_net_set_weight_fp8
   };
   Act conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksize, int stride, int ups, const GemmOpt& o);
   Act linear(const Act& x, const bf16* w, int N, const GemmOpt& o) { return conv(x, nullptr, w, N, 1, 1, 0, o); }

@@ -241,6 +241,7 @@ extern "C" nr_status nr_net_create(const nr_net_config* cfg, nr_net** out) {
   h->cfg = *cfg;
   h->device = dev;
   h->det_batch = env_is_1("NR_DETERMINISTIC_BATCH");
+  h->w8 = env_is_1("NR_W8");
   *out = h;
   NR_CATCH
 }
@@ -380,6 +381,13 @@ extern "C" nr_status nr_net_set_attention_fp8(nr_net* h, int32_t enable) {
   NR_TRY
   if (!h) throw NrError(NR_ERR_ARG, "null handle");
   if (h->attn_fp8 != (enable != 0)) { h->attn_fp8 = enable != 0; h->planned = false; }
+  NR_CATCH
+}
+
+extern "C" nr_status nr_net_set_weight_fp8(nr_net* h, int32_t enable) {
+  NR_TRY
+  if (!h) throw NrError(NR_ERR_ARG, "null handle");
+  if (h->w8 != (enable != 0)) { h->w8 = enable != 0; h->planned = false; }
   NR_CATCH
 }
 

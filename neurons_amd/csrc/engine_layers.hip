@@ -116,16 +116,19 @@ Act nr_net::conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksiz
   p.out_scale = o.scale; p.geglu = o.geglu; p.pad_tl0 = o.pad_tl0; p.act = o.act; p.ln_c = o.ln_c; p.ln_eps = 1e-5f;
   p.tap_inner = o.tap_inner;
   p.plan_m = det_batch ? (int)det_rows(p.M) : 0;
+  p.w8 = (w8 && ksize == 1 && !o.derived_w) ? 1 : 0;      // a request: only a launch smallm.hip takes reads e4m3 weights
   NrGemmRoute r;
   LAUNCH_OK(nr_gemm_route(&p, &r));
-  // the weights as the chosen kernel reads them: fragment-major for the M <= 512 Linears (smallm.hip), a stage stream for the short-K Linears on >= 2048 rows (lin160.hip)
+  // the weights as the chosen kernel reads them: fragment-major (bf16, or e4m3 codes + row scales on request) for the M <= 512 Linears (smallm.hip), a
+  // stage stream for the short-K Linears on >= 2048 rows (lin160.hip)
   const bf16* wk = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : wts.w_layout(w, Cout, p.K, r.weight_layout);
   const double in_elems = (double)x0.rows() * (p.c0 + p.c1);   // every input element is needed at least once
   const double bytes = 2.0 * (in_elems + (double)p.N * p.K + (double)p.M * outC + (o.res ? (double)p.M * outC : 0.0));
   const bool l160 = r.cls == NR_GEMM_LIN160;
   char d[160];
   if (l160) snprintf(d, sizeof(d), "%s M=%d N=%d K=%d res=%d geglu=%d ln=%d", r.lin160.form == 4 ? "lin160 panel" : "lin160", p.M, p.N, p.K, o.res ? 1 : 0, p.geglu, p.ln_c ? 1 : 0);
-  else snprintf(d, sizeof(d), "igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0);
+  else snprintf(d, sizeof(d), "igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d%s", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0,
+                r.weight_layout == NR_W_FRAGMAJOR_E4M3 ? " w=e4m3" : "");
   const SplitK sk = splitk_scratch(r.ws_bytes);
   float* ws = sk.ws;
   emit([p, r, wk, ws](hipStream_t s) { LAUNCH_OK(nr_launch_gemm(&p, &r, wk, ws, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
@@ -371,7 +374,7 @@ Act nr_net::feed_forward_proj_out(const Act& x, Act& t, const std::string& ln, c
   }
   Act g = ln_linear(t, ln, {ff + ".net.0.proj.weight"}, {ff + ".net.0.proj.bias"}, inner, true, 0, false);
   const FoldW fw = wts.w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C);
-  GemmOpt op; op.bias = fw.b; op.res = &x;
+  GemmOpt op; op.bias = fw.b; op.res = &x; op.derived_w = true;
   return conv(t, &g, fw.w, C, 1, 1, 0, op);
 }
 

@@ -20,7 +20,8 @@ static bool op_scratch(OpScratch& b, size_t need) {
 // One GEMM / conv launch the way the engine's planner would make it: route, pack, launch.  A route that names a packed weight layout (fragment-major
 // for smallm.hip, the stage streams of lin160.hip) gets that copy packed on the launch stream into a scratch buffer of its layout on EVERY call
 // (tests: always consistent with the tensor passed in); NR_OP_FM_CACHE=1 keeps one copy per (weight pointer, layout, shape) instead (timing tools
-// that replay graphs over a pool of weights; nr_op_fm_cache_clear when the pool is freed)
+// that replay graphs over a pool of weights; nr_op_fm_cache_clear when the pool is freed).  NR_W8=1, read per call like NR_SMALLM, sets the e4m3 weight
+// request (NrGemmParams::w8) of every GEMM hook
 static std::map<std::tuple<const void*, int, int, int>, bf16*> g_op_fm_cache;
 extern "C" void nr_op_fm_cache_clear() {
   (void)hipDeviceSynchronize();
@@ -42,12 +43,14 @@ static const bf16* op_pack(const NrGemmParams& p, const NrGemmRoute& r, hipStrea
     return it->second;
   }
   static OpScratch scratch[2];                   // fragment-major copies | stage streams
-  OpScratch& b = scratch[r.weight_layout == NR_W_FRAGMAJOR ? 0 : 1];
+  OpScratch& b = scratch[(r.weight_layout == NR_W_FRAGMAJOR || r.weight_layout == NR_W_FRAGMAJOR_E4M3) ? 0 : 1];
   op_scratch(b, need);
   LAUNCH_OK(nr_launch_gemm_w_pack(r.weight_layout, p.w, p.N, p.K, (bf16*)b.ptr, s));
   return (const bf16*)b.ptr;
 }
-static void op_gemm(const NrGemmParams& p, hipStream_t s) {
+static void op_gemm(const NrGemmParams& p_arg, hipStream_t s) {
+  NrGemmParams p = p_arg;
+  p.w8 = env_is_1("NR_W8") ? 1 : 0;
   NrGemmRoute r;
   LAUNCH_OK(nr_gemm_route(&p, &r));
   const bf16* wk = op_pack(p, r, s);
@@ -63,6 +66,17 @@ extern "C" nr_status nr_op_gemm(nr_stream stream, const void* a, int32_t lda, co
   NrGemmParams p = nr_gemm_params((const bf16*)a, K, lda, nullptr, 0, 0, M, 1, 1, 1, 1, 0, (const bf16*)w, N, bias, (const bf16*)res, ldr, (bf16*)out, ldo);
   p.geglu = geglu;
   op_gemm(p, (hipStream_t)stream);
+  NR_CATCH
+}
+
+// the e4m3 form of a bf16 [N][K] matrix as smallm.hip reads it (NR_W_FRAGMAJOR_E4M3: N K code bytes, then N float row scales) into out_dev
+extern "C" nr_status nr_op_w8_pack(nr_stream stream, const void* w_dev, int32_t N, int32_t K, void* out_dev, int64_t capacity) {
+  NR_TRY
+  if (!w_dev || !out_dev) throw NrError(NR_ERR_ARG, "null argument");
+  const size_t need = nr_gemm_packed_bytes(NR_W_FRAGMAJOR_E4M3, N, K);
+  if (!need) throw NrError(NR_ERR_ARG, "e4m3 weights: N must be a multiple of 16 and K of 64");
+  if (capacity < (int64_t)need) throw NrError(NR_ERR_ARG, "output buffer too small");
+  LAUNCH_OK(nr_launch_gemm_w_pack(NR_W_FRAGMAJOR_E4M3, (const bf16*)w_dev, N, K, (bf16*)out_dev, (hipStream_t)stream));
   NR_CATCH
 }
 

@@ -197,13 +197,14 @@ std::string WeightStore::name_of(const void* p, const char* who) const {
   throw NrError(NR_ERR_STATE, std::string(who) + ": not a converted weight matrix");
 }
 
-// a converted [N][K] weight matrix in the layout a GEMM route names (NrWeightLayout): w itself, or its packed copy -- fragment-major (smallm.hip), the
-// stage stream of lin160.hip, the 128-column stream of its register-panel form; the row-major matrix stays (launches of other row counts use it)
+// a converted [N][K] weight matrix in the layout a GEMM route names (NrWeightLayout): w itself, or its packed copy -- fragment-major (smallm.hip), its
+// e4m3 form (codes + row scales), the stage stream of lin160.hip, the 128-column stream of its register-panel form; the row-major matrix stays
+// (launches of other row counts use it: the e4m3 form therefore ADDS N K + 4 N bytes per matrix, it saves no memory)
 const bf16* WeightStore::w_layout(const bf16* w, int N, int K, int layout) {
   if (layout == NR_W_ROWMAJOR || layout == NR_W_TAP_INNER) return w;
   const size_t nb = nr_gemm_packed_bytes(layout, N, K);
   if (!nb) throw NrError(NR_ERR_STATE, "w_layout: shape has no packed form");
-  const char* prefix = layout == NR_W_FRAGMAJOR ? "fm:" : (layout == NR_W_LIN128Q ? "l128:" : "l160:");
+  const char* prefix = layout == NR_W_FRAGMAJOR ? "fm:" : (layout == NR_W_FRAGMAJOR_E4M3 ? "w8:" : (layout == NR_W_LIN128Q ? "l128:" : "l160:"));
   return (const bf16*)packed(prefix + name_of(w, "w_layout"), nb, [&](void* d) { LAUNCH_OK(nr_launch_gemm_w_pack(layout, w, N, K, (bf16*)d, nullptr)); });
 }
 

@@ -713,7 +713,8 @@ int route(const NrGemmParams& p, NrGemmRoute* r, bool packed_ok) {
   r->weight_layout = p.tap_inner ? NR_W_TAP_INNER : NR_W_ROWMAJOR;
   const int Cin = p.c0 + p.c1;
   // M <= 512 Linears with K a multiple of 640: the panel-resident kernel on fragment-major weights (smallm.hip)
-  if (packed_ok && smallm_plan(p, &r->smallm)) { r->cls = NR_GEMM_SMALLM; r->weight_layout = NR_W_FRAGMAJOR; return 0; }
+  // (the e4m3 request p.w8 names the weight layout of THIS class and nothing else: smallm_plan does not see it, the classes below ignore it)
+  if (packed_ok && smallm_plan(p, &r->smallm)) { r->cls = NR_GEMM_SMALLM; r->weight_layout = p.w8 ? NR_W_FRAGMAJOR_E4M3 : NR_W_FRAGMAJOR; return 0; }
   // short-K Linears (K = 640 / 1280) on >= 2048 rows: the stage-stream kernel and its register-panel form (lin160.hip)
   if (packed_ok && lin160_plan(p, &r->lin160)) { r->cls = NR_GEMM_LIN160; r->weight_layout = r->lin160.form == 4 ? NR_W_LIN128Q : NR_W_LIN160; return 0; }
   // K = 320 Linears on >= 4096 rows: the register-resident row-panel kernel (rowpanel.hip)
@@ -797,7 +798,7 @@ extern "C" int nr_gemm_route_rowmajor(const NrGemmParams* pp, NrGemmRoute* r) { 
 // the launch (6: split-K planned and no workspace given)
 extern "C" int nr_launch_gemm(const NrGemmParams* pp, const NrGemmRoute* r, const bf16* packed_w, float* ws, hipStream_t stream) {
   switch (r->cls) {
-    case NR_GEMM_SMALLM: return nr_launch_smallm(pp, &r->smallm, packed_w, stream);
+    case NR_GEMM_SMALLM: return nr_launch_smallm(pp, &r->smallm, packed_w, r->weight_layout, stream);
     case NR_GEMM_LIN160: return nr_launch_lin160(pp, &r->lin160, packed_w, stream);
     case NR_GEMM_ROWPANEL: return nr_launch_rowpanel(pp, &r->rowpanel, stream);
     case NR_GEMM_G8P: return nr_launch_g8p(pp, &r->g8p, r->m_fast, stream);
@@ -810,6 +811,7 @@ extern "C" int nr_launch_gemm(const NrGemmParams* pp, const NrGemmRoute* r, cons
 extern "C" size_t nr_gemm_packed_bytes(int layout, int N, int K) {
   switch (layout) {
     case NR_W_FRAGMAJOR: return (N % 16 == 0 && K % 32 == 0) ? (size_t)N * K * sizeof(bf16) : 0;
+    case NR_W_FRAGMAJOR_E4M3: return (N > 0 && K > 0 && N % 16 == 0 && K % 64 == 0) ? (size_t)N * K + (size_t)N * sizeof(float) : 0;   // codes + row scales
     case NR_W_LIN160: return nr_lin160_stream_bytes(N, K);
     case NR_W_LIN128Q: return nr_lin128q_stream_bytes(N, K);
   }
@@ -818,6 +820,7 @@ extern "C" size_t nr_gemm_packed_bytes(int layout, int N, int K) {
 extern "C" int nr_launch_gemm_w_pack(int layout, const bf16* w, int N, int K, bf16* dst, hipStream_t stream) {
   switch (layout) {
     case NR_W_FRAGMAJOR: return nr_launch_smallm_w_pack(w, dst, N, K, stream);
+    case NR_W_FRAGMAJOR_E4M3: return nr_launch_smallm_w8_pack(w, dst, N, K, stream);
     case NR_W_LIN160: return nr_launch_lin160_w_pack(w, N, K, dst, stream);
     case NR_W_LIN128Q: return nr_launch_lin128q_w_pack(w, N, K, dst, stream);
   }

@@ -33,8 +33,10 @@ inline int nr_lds_opt_in(unsigned long long& mask, std::initializer_list<const v
 // in the order nr_gemm_route asks them
 enum NrGemmClass { NR_GEMM_SMALLM, NR_GEMM_LIN160, NR_GEMM_ROWPANEL, NR_GEMM_G8P, NR_GEMM_TILED, NR_GEMM_NCLASS };
 inline const char* const nr_gemm_class_name[NR_GEMM_NCLASS] = {"smallm", "lin160", "rowpanel", "gemm8p", "tiled"};
-// what the chosen kernel reads as W: the matrix as the caller holds it ([N][K], for a tap-inner 3x3 conv [N][Cin/64][9][64]) or a packed copy
-enum NrWeightLayout { NR_W_ROWMAJOR, NR_W_TAP_INNER, NR_W_FRAGMAJOR, NR_W_LIN160, NR_W_LIN128Q };
+// what the chosen kernel reads as W: the matrix as the caller holds it ([N][K], for a tap-inner 3x3 conv [N][Cin/64][9][64]) or a packed copy.
+// NR_W_FRAGMAJOR_E4M3 (smallm.hip, on request NrGemmParams::w8 only): OCP e4m3 codes [N/16][K/64][64 lanes][16 bytes] -- lane (fr, fg) of block
+// (T, kp) holds, for the k-steps 2 kp + j (j = 0, 1), the eight codes of W[16 T + fr][32 (2 kp + j) + 8 fg .. + 7] -- then float scale[N] = 2^e[n]
+enum NrWeightLayout { NR_W_ROWMAJOR, NR_W_TAP_INNER, NR_W_FRAGMAJOR, NR_W_LIN160, NR_W_LIN128Q, NR_W_FRAGMAJOR_E4M3 };
 
 // gemm.hip: tile, ring depth, wave grid (41 = 4 x 1 row waves) and split-K depth after the LayerNorm / out_f32 adjustments; adma / lin: the
 // A-operand LDS-DMA and the Linear-only instantiation

@@ -73,8 +73,9 @@ int nr_launch_fold_linear_pair(const float* w2, const float* w1, const float* b2
                                hipStream_t stream);
 // smallm.hip: panel-resident kernel of the M <= 512 Linears (fragment-major weights)
 bool smallm_plan(const NrGemmParams& p, SmallmPlan* pl);
-int nr_launch_smallm(const NrGemmParams* pp, const SmallmPlan* pl, const bf16* w_fm, hipStream_t stream);
+int nr_launch_smallm(const NrGemmParams* pp, const SmallmPlan* pl, const bf16* w_fm, int layout, hipStream_t stream);
 int nr_launch_smallm_w_pack(const void* w, void* out, int N, int K, hipStream_t stream);
+int nr_launch_smallm_w8_pack(const void* w, void* out, int N, int K, hipStream_t stream);      // NR_W_FRAGMAJOR_E4M3: codes, then the row scales
 // tattn.hip: one kernel per temporal-attention block of the C = 320 level
 size_t nr_xattn_wstream_bytes(void);
 size_t nr_xattn_kvstream_bytes(int nctx);

@@ -20,6 +20,10 @@
 //     scale / quick_gelu / residual epilogue in fragment layout, as the igemm's.
 //   * two-source operands [a0 | a1] (the skip concat as a 1x1 GEMM, the [t | g] operand of the folded net.2|proj_out): whole 640-deep chunks
 //     from either source.
+//   * opt-in e4m3 weights (NR_W_FRAGMAJOR_E4M3, smallm_w8_kernel; NrGemmParams::w8 / nr_net_set_weight_fp8): the bound below is the number of weight
+//     bytes a CU has to REQUEST, so the codes halve it: 5 contiguous 1-KiB loads per chunk and wave, each feeding two k-steps; one power-of-two scale
+//     per W row, applied to the finished accumulator.  A numerics variant (3 mantissa bits), bit-identical to the bf16 kernel on the dequantised
+//     matrix; the plan (nt, G, J, C), the grid and the LDS layout are the bf16 form's.  profiles/w8_smallm_ab.txt has the A/B.
 // Shipped plans have ONE slab per workgroup (N <= 1280 at M = 512): 1.1-1.66x the tiled igemm per launch; several slabs (N >= 1920) lose to
 // the igemm's bigger tiles and stay there (NR_SMALLM=2 keeps them for the tests).  What bounds it (profiles/r05_smallm_timeline.txt): the ISSUE
 // of 100 KB of weight loads + 40 KB of panel DMA per chunk through the CU's ~64 B/clk address path (2.2-2.5 k cycles for 320 MFMA cycles per
@@ -29,6 +33,7 @@
 #include "launchers.h"
 #include "device_prims.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -47,10 +52,33 @@ constexpr int SM_CHB = 10 * SM_SUBB;          // one 640-deep chunk of the panel
 constexpr int SM_NSLOT = 3;
 constexpr int SM_SCRATCH = 20 * 1024;         // accumulator hand-over, LayerNorm statistics, GEGLU exchange
 
-// NT: n-tiles (16 W rows) per slab = waves per wave group; LN: LayerNorm folded; GEGLU: value * gelu(gate)
-template <int NT, bool LN, bool GEGLU>
-__global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, int J, int C) {
+// eight OCP e4m3 codes (two dwords) -> the bf16x8 MFMA operand: v_cvt_pk_f32_fp8 gives two fp32 per instruction, v_perm_b32 keeps their upper halves.
+// Exact: an e4m3 value has at most 4 significant bits and its exponent range lies inside bf16's
+__device__ __forceinline__ bf16x8 smallm_e4m3_frag(unsigned c0, unsigned c1) {
+  u32x4 r;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const unsigned c = h ? c1 : c0;
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c, false);      // codes 0, 1 of the dword
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c, true);       // codes 2, 3
+    r[2 * h] = __builtin_amdgcn_perm(__float_as_uint(lo[1]), __float_as_uint(lo[0]), 0x07060302u);
+    r[2 * h + 1] = __builtin_amdgcn_perm(__float_as_uint(hi[1]), __float_as_uint(hi[0]), 0x07060302u);
+  }
+  return __builtin_bit_cast(bf16x8, r);
+}
+
+// NT: n-tiles (16 W rows) per slab = waves per wave group; LN: LayerNorm folded; GEGLU: value * gelu(gate);
+// W8: the weights are OCP e4m3 codes with one power-of-two scale per W row (NR_W_FRAGMAJOR_E4M3, opt-in).  One 16-byte load per lane then feeds
+// TWO k-steps, the two register banks hold 5 registers each, and the codes are widened to bf16 right in front of the MFMAs that read them (8 VALU
+// instructions per k-step beside its 2 MFMAs): the same bf16 MFMAs in the same order on the same operand values as the bf16 kernel run on the
+// dequantised matrix, the row scale applied to the finished accumulator -- bit-identical to that run
+// (the body of both kernel templates below: the bf16 kernels keep their names)
+template <int NT, bool LN, bool GEGLU, bool W8>
+__device__ __forceinline__ void smallm_body(NrGemmParams p_arg, int J, int C) {
   constexpr int NW = 2 * NT;                  // waves
+  constexpr int WL = W8 ? SM_KSW / 2 : SM_KSW;   // 1-KiB weight loads of one wave per chunk (SM_KSW is even: the wave groups' halves are whole k-step pairs)
+  static_assert(SM_KSW % 2 == 0, "k-steps in pairs");
+  typedef typename std::conditional<W8, u32x4, bf16x8>::type wreg_t;
   constexpr int PP = 40 / NW;                 // 1-KiB LDS-DMA pieces of a panel chunk per wave (40 per chunk)
   static_assert(40 % NW == 0, "whole pieces per wave");
   static_assert(!GEGLU || NT % 2 == 0, "value / gate n-tiles in pairs");
@@ -78,20 +106,20 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
   const int m0 = (bid - g * ntm) * 32;
   const int T = J * C;                        // steps: (slab, chunk), chunk fastest
   const bool streaming = C > SM_NSLOT;        // else the whole panel stays resident in its C slots
-  const int KB = p.K >> 5;
+  const int KB = W8 ? p.K >> 6 : p.K >> 5;    // KiB blocks per n-tile
 
-  // ---- weights: k-step ks of n-tile Tn is the KiB at ((Tn KB + ks) 64 + lane) 8 elements ----
-  const bf16* wlane = p.w_fm + ((size_t)(g * J * NT + nt) * KB + kq * SM_KSW) * 512 + lane * 8;
+  // ---- weights: k-step ks of n-tile Tn is the KiB at ((Tn KB + ks) 64 + lane) 8 elements (W8: the k-step PAIR kp, same addressing in 16-byte units) ----
+  const bf16* wlane = p.w_fm + ((size_t)(g * J * NT + nt) * KB + kq * WL) * 512 + lane * 8;
   const size_t wslab = (size_t)NT * KB * 512;                         // elements from one slab's n-tile to the next slab's
-  bf16x8 wa[SM_KSW], wb[SM_KSW];
+  wreg_t wa[WL], wb[WL];
   auto w_of = [&](int t) {                    // this wave's first KiB of step t = (slab t / C, chunk t % C)
     const int j = t / C, c = t - j * C;
-    return wlane + (size_t)j * wslab + (size_t)c * (20 * 512);
+    return wlane + (size_t)j * wslab + (size_t)c * (2 * WL * 512);
   };
-  auto issue_w = [&](bf16x8 (&w)[SM_KSW], int t) {
+  auto issue_w = [&](wreg_t (&w)[WL], int t) {
     const bf16* q = w_of(t);
 #pragma unroll
-    for (int ks = 0; ks < SM_KSW; ++ks) w[ks] = *(const bf16x8*)(q + ks * 512);
+    for (int ks = 0; ks < WL; ++ks) w[ks] = *(const wreg_t*)(q + ks * 512);
   };
 
   // ---- panel: piece q of a chunk = rows 8 (q & 3) .. + 7 of sub-tile q >> 2, lane (lr, lp) fetches the 16-byte chunk lp ^ lr of row lr ----
@@ -136,11 +164,13 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
 
   // Two register banks, two steps of weights in flight: bank t & 1 holds step t's weights and is refilled with step t + 2's, register by
   // register, right behind the MFMAs that read it (one step ahead was not enough: ~20 B/clk per CU, the tiled igemm's rate)
-  auto step = [&](bf16x8 (&wcur)[SM_KSW], int t) __attribute__((always_inline)) {
+  auto step = [&](wreg_t (&wcur)[WL], int t) __attribute__((always_inline)) {
     const bool has_next = t + 1 < T;
     if (t == 0) SM_STAMP_AT(2);
-    // this step's weights and panel chunk are older than: [the next panel chunk] + [the next step's weights]
-    if (has_next) { if (pnext) nr_wait_vmcnt<SM_KSW + PP>(); else nr_wait_vmcnt<SM_KSW>(); }
+    // this step's weights and panel chunk are older than: [the next panel chunk] + [the next step's weights]: PP pieces + WL loads, i.e.
+    // 10 + PP / 10 in the bf16 form and 5 + PP / 5 with e4m3 weights (the epilogue operands of a slab's last step, the row scales among
+    // them, are issued between the two and only make the wait stricter)
+    if (has_next) { if (pnext) nr_wait_vmcnt<WL + PP>(); else nr_wait_vmcnt<WL>(); }
     else nr_wait_vmcnt<0>();
     SM_STAMP_AT(8 + 3 * t);
     __builtin_amdgcn_s_barrier();             // every wave's pieces landed; every wave has left step t - 1 (its slot may be refilled)
@@ -153,9 +183,11 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
     const bool slab_end = c == C - 1;
     const int nq = ((g * J + j) * NT + nt) * 16 + 4 * fg;            // this lane's 4 W rows / output columns
     f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f}, cv = f32x4{0.f, 0.f, 0.f, 0.f}, rvv[2];
+    [[maybe_unused]] f32x4 sv = f32x4{1.f, 1.f, 1.f, 1.f};            // W8: 2^e of this lane's 4 W rows
     bf16x4 rr[2];
     if (slab_end && kq == 0) {                // epilogue operands, fetched behind this chunk's MFMAs
       if (p.bias) bv = *(const f32x4*)(p.bias + nq);
+      if constexpr (W8) sv = *(const f32x4*)(reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(p.w_fm) + (size_t)p.N * p.K) + nq);
       if constexpr (LN) cv = *(const f32x4*)(p.ln_c + nq);
       if constexpr (!GEGLU && !LN) {          // (LayerNorm-folded: fetched in the epilogue, the 168-register budget of 10 waves is full)
 #pragma unroll
@@ -201,9 +233,16 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
       bf16x8 (&xc)[2] = (ks & 1) ? xc2 : xa;
       bf16x8 (&xn)[2] = (ks & 1) ? xa : xc2;
       if (ks + 1 < SM_KSW) read_x(xn, ks + 1);
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wcur[ks], xc[0], acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wcur[ks], xc[1], acc[1], 0, 0, 0);
-      if (refill) wcur[ks] = *(const bf16x8*)(wref + ks * 512);
+      if constexpr (W8) {                     // register ks / 2 holds the codes of k-steps ks - (ks & 1) and + 1: refilled behind the second one
+        const bf16x8 wv = (ks & 1) ? smallm_e4m3_frag(wcur[ks >> 1][2], wcur[ks >> 1][3]) : smallm_e4m3_frag(wcur[ks >> 1][0], wcur[ks >> 1][1]);
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, xc[0], acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, xc[1], acc[1], 0, 0, 0);
+        if ((ks & 1) && refill) wcur[ks >> 1] = *(const wreg_t*)(wref + (ks >> 1) * 512);
+      } else {
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wcur[ks], xc[0], acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wcur[ks], xc[1], acc[1], 0, 0, 0);
+        if (refill) wcur[ks] = *(const wreg_t*)(wref + ks * 512);
+      }
     }
     SM_STAMP_AT(10 + 3 * t);
     if (!slab_end) return;
@@ -221,6 +260,10 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
     if (kq == 0) {
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) acc[mt] += red[(nt * 2 + mt) * 64 + lane];
+      if constexpr (W8) {                     // the row scale, on the finished accumulator and before everything else: a power of two, so exact
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) acc[mt] *= sv;
+      }
     }
     if constexpr (LN) {
       if (j == 0) {
@@ -311,6 +354,11 @@ __global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p_arg, in
   SM_STAMP_RT(7);
 }
 
+template <int NT, bool LN, bool GEGLU>
+__global__ __launch_bounds__(128 * NT) void smallm_kernel(NrGemmParams p, int J, int C) { smallm_body<NT, LN, GEGLU, false>(p, J, C); }
+template <int NT, bool LN, bool GEGLU>
+__global__ __launch_bounds__(128 * NT) void smallm_w8_kernel(NrGemmParams p, int J, int C) { smallm_body<NT, LN, GEGLU, true>(p, J, C); }
+
 // row-major [N][K] -> fragment-major [N/16][K/32][64][8]: one thread per 16-byte chunk of the destination
 __global__ __launch_bounds__(256) void smallm_w_pack_kernel(const bf16* __restrict__ w, bf16* __restrict__ out, int N, int K) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -322,6 +370,55 @@ __global__ __launch_bounds__(256) void smallm_w_pack_kernel(const bf16* __restri
   *(bf16x8*)(out + idx * 8) = *(const bf16x8*)(w + (size_t)(16 * Tn + (lane & 15)) * K + 32 * ks + 8 * (lane >> 4));
 }
 
+// row-major bf16 [N][K] -> NR_W_FRAGMAJOR_E4M3: one workgroup per n-tile (16 W rows).  Row n gets the power-of-two scale 2^e, e = ceil(log2(amax_n / 448))
+// from frexp (amax = m 2^x, 1/2 <= m < 1: amax / 448 = (m / 0.875) 2^(x - 9), so e = x - 9 up to m = 0.875 -- a ratio that IS a power of two keeps
+// it -- and x - 8 above; an all-zero row: 0), its codes are e4m3_rne(w 2^-e): the scaling is exact and |w 2^-e| <= 448, so the cast never
+// saturates (v_cvt_pk_fp8_f32: OCP e4m3fn on gfx950, round to nearest even).  Plain vector stores
+__global__ __launch_bounds__(256) void smallm_w8_pack_kernel(const bf16* __restrict__ w, unsigned char* __restrict__ out, int N, int K) {
+  __shared__ int ex[16];
+  const int T = blockIdx.x, tid = threadIdx.x;
+  {
+    const int r = tid >> 4, part = tid & 15;        // 16 threads per row
+    const bf16* row = w + (size_t)(16 * T + r) * K;
+    float amax = 0.f;
+    for (int k = part * 8; k < K; k += 128) {
+      const bf16x8 v = *(const bf16x8*)(row + k);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf((float)v[e]));
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if (part == 0) {
+      int x = 0, e = 0;
+      if (amax > 0.f) { const float m = frexpf(amax, &x); e = m > 0.875f ? x - 8 : x - 9; }
+      ex[r] = e;
+      reinterpret_cast<float*>(out + (size_t)N * K)[16 * T + r] = ldexpf(1.0f, e);
+    }
+  }
+  __syncthreads();
+  const int kb = K >> 6;
+  for (int i = tid; i < kb * 64; i += 256) {
+    const int kp = i >> 6, lane = i & 63, fr = lane & 15, fg = lane >> 4;
+    const bf16* src = w + (size_t)(16 * T + fr) * K + 64 * kp + 8 * fg;
+    const int ne = -ex[fr];
+    u32x4 q;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const bf16x8 v = *(const bf16x8*)(src + 32 * j);
+      float f[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] = ldexpf((float)v[e], ne);
+      int lo = 0, hi = 0;
+      lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+      lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+      hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+      hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+      q[2 * j] = (unsigned)lo; q[2 * j + 1] = (unsigned)hi;
+    }
+    *(u32x4*)(out + (((size_t)T * kb + kp) * 64 + lane) * 16) = q;
+  }
+}
+
 typedef void (*smallm_kern_t)(NrGemmParams, int, int);
 template <int NT> smallm_kern_t smallm_pick(bool ln, bool geglu) {
   if constexpr (NT % 2 == 0) {
@@ -329,6 +426,14 @@ template <int NT> smallm_kern_t smallm_pick(bool ln, bool geglu) {
               : (geglu ? smallm_kernel<NT, false, true> : smallm_kernel<NT, false, false>);
   } else {
     return ln ? smallm_kernel<NT, true, false> : smallm_kernel<NT, false, false>;
+  }
+}
+template <int NT> smallm_kern_t smallm_w8_pick(bool ln, bool geglu) {
+  if constexpr (NT % 2 == 0) {
+    return ln ? (geglu ? smallm_w8_kernel<NT, true, true> : smallm_w8_kernel<NT, true, false>)
+              : (geglu ? smallm_w8_kernel<NT, false, true> : smallm_w8_kernel<NT, false, false>);
+  } else {
+    return ln ? smallm_w8_kernel<NT, true, false> : smallm_w8_kernel<NT, false, false>;
   }
 }
 
@@ -375,16 +480,20 @@ extern "C" bool smallm_plan(const NrGemmParams& p, SmallmPlan* out) {
   return true;
 }
 
-extern "C" int nr_launch_smallm(const NrGemmParams* pp, const SmallmPlan* plp, const bf16* w_fm, hipStream_t stream) {
+// w_fm: the weights in `layout` = NR_W_FRAGMAJOR, or NR_W_FRAGMAJOR_E4M3 (the e4m3 instantiations: same plan, same grid, same LDS)
+extern "C" int nr_launch_smallm(const NrGemmParams* pp, const SmallmPlan* plp, const bf16* w_fm, int layout, hipStream_t stream) {
   NrGemmParams p = *pp;
   const SmallmPlan& pl = *plp;
   p.w_fm = w_fm;
+  if (layout != NR_W_FRAGMAJOR && layout != NR_W_FRAGMAJOR_E4M3) return 1;
+  const bool w8 = layout == NR_W_FRAGMAJOR_E4M3;
   if (!w_fm || (pl.nt != 4 && pl.nt != 5) || (p.geglu && pl.nt != 4) || pl.G < 1 || pl.C != p.K / 640 || p.N != 16 * pl.nt * pl.G * pl.J) return 1;
   const bool ln = p.ln_c != nullptr, gg = p.geglu != 0;
-  smallm_kern_t k = pl.nt == 5 ? smallm_pick<5>(ln, gg) : smallm_pick<4>(ln, gg);
+  smallm_kern_t k = w8 ? (pl.nt == 5 ? smallm_w8_pick<5>(ln, gg) : smallm_w8_pick<4>(ln, gg))
+                       : (pl.nt == 5 ? smallm_pick<5>(ln, gg) : smallm_pick<4>(ln, gg));
   const size_t shm = (size_t)SM_NSLOT * SM_CHB + SM_SCRATCH;           // 140 KiB: one workgroup per CU
-  static unsigned long long attr_done[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per instantiation
-  if (const int rc = nr_lds_opt_in(attr_done[(pl.nt == 5 ? 0 : 4) + (ln ? 2 : 0) + (gg ? 1 : 0)], {(const void*)k}, shm)) return rc;
+  static unsigned long long attr_done[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // per instantiation
+  if (const int rc = nr_lds_opt_in(attr_done[(w8 ? 8 : 0) + (pl.nt == 5 ? 0 : 4) + (ln ? 2 : 0) + (gg ? 1 : 0)], {(const void*)k}, shm)) return rc;
   const unsigned grid = (unsigned)(((p.M + 31) / 32) * pl.G);
   hipLaunchKernelGGL(k, dim3(grid), dim3(128 * pl.nt), shm, stream, p, pl.J, pl.C);
   return 0;
@@ -395,6 +504,13 @@ extern "C" int nr_launch_smallm_w_pack(const void* w, void* out, int N, int K, h
   if (N % 16 != 0 || K % 32 != 0) return 1;
   const size_t chunks = (size_t)N * K / 8;
   hipLaunchKernelGGL(smallm_w_pack_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, (const bf16*)w, (bf16*)out, N, K);
+  return 0;
+}
+
+// w [N][K] row-major bf16 -> out in NR_W_FRAGMAJOR_E4M3 (N K code bytes, then N float scales; N % 16 == 0, K % 64 == 0)
+extern "C" int nr_launch_smallm_w8_pack(const void* w, void* out, int N, int K, hipStream_t stream) {
+  if (N % 16 != 0 || K % 64 != 0 || N < 16 || K < 64) return 1;
+  hipLaunchKernelGGL(smallm_w8_pack_kernel, dim3((unsigned)(N / 16)), dim3(256), 0, stream, (const bf16*)w, (unsigned char*)out, N, K);
   return 0;
 }
 

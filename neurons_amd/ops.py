@@ -54,6 +54,16 @@ def gemm2(a0, a1, w, bias=None, res=None):
     return out
 
 
+def w8_pack(w):
+    """The e4m3 form of a bf16 ``[N, K]`` matrix as the small-M kernel reads it (``nr_op_w8_pack``): ``(codes, scale)`` with ``codes`` uint8
+    ``[N/16, K/64, 64, 16]`` in fragment order and ``scale`` fp32 ``[N]``; ``neurons_amd.w8.pack_reference`` is the same thing in torch."""
+    _chk_bf16(w)
+    N, K = w.shape
+    buf = torch.empty(N * K + 4 * N, dtype=torch.uint8, device=w.device)
+    _lib.check(_lib.load().nr_op_w8_pack(_stream(), _ptr(w), N, K, _ptr(buf), buf.numel()))
+    return buf[:N * K].view(N // 16, K // 64, 64, 16), buf[N * K:].view(torch.float32)
+
+
 def g8p_mode(mode):
     """0: never use the 256-row ping-pong kernel (gemm8p.hip), 1: shipped heuristic, 2: whenever the shape is supported (tests, A/B)."""
     _lib.load().nr_g8p_set_mode(int(mode))
@@ -463,6 +473,31 @@ class NativeLeaf:
     def op_descriptions(self):
         lib = _lib.load()
         return [lib.nr_net_op_desc(self._h, i).decode() for i in range(lib.nr_net_num_ops(self._h))]
+
+    def set_weight_fp8(self, flag=True):
+        """``nr_net_set_weight_fp8``: e4m3 weights for the Linears the small-M kernel serves; the next forward re-plans."""
+        _lib.check(_lib.load().nr_net_set_weight_fp8(self._h, 1 if flag else 0))
+        self._plan_key = None
+        return self
+
+    def export_weights(self):
+        """(manifest bytes, packed uint8 CUDA tensor) of every converted device buffer of the current plan."""
+        import ctypes as C
+        lib = _lib.load()
+        nbytes = C.c_int64()
+        n = lib.nr_net_export_manifest(self._h, None, 0, C.byref(nbytes))
+        if n < 0:
+            _lib.check(1)
+        buf = C.create_string_buffer(int(n))
+        lib.nr_net_export_manifest(self._h, buf, n, C.byref(nbytes))
+        arena = torch.empty(int(nbytes.value), dtype=torch.uint8, device="cuda")
+        _lib.check(lib.nr_net_export_weights(self._h, _stream(), arena.data_ptr(), arena.numel()))
+        return bytes(buf.raw[:n]), arena
+
+    def import_weights(self, manifest, arena):
+        """Adopt another leaf's converted weights (same configuration; a fresh handle: no load_state_dict before it)."""
+        _lib.check(_lib.load().nr_net_import_weights(self._h, _stream(), manifest, len(manifest), arena.data_ptr(), arena.numel()))
+        self._plan_key = None
 
     def __del__(self):
         try:

@@ -449,6 +449,14 @@ class _NativeNet:
         self._plan_key = None
         return self
 
+    def set_weight_fp8(self, flag=True):
+        """Weight-only OCP e4m3 storage (one power-of-two scale per row) for the Linears the small-M kernel serves (``nr_net_set_weight_fp8``;
+        ``neurons_amd/w8.py`` has the format).  A numerics variant: bf16 stays the default (``NR_W8=1`` turns it on for new handles); the
+        bf16 matrices stay resident, so it saves no memory.  The next forward re-plans."""
+        _lib.check(_lib.load().nr_net_set_weight_fp8(self._handle(), 1 if flag else 0))
+        self._plan_key = None
+        return self
+
     def set_deterministic_batch(self, flag=True):
         """Batch-independent arithmetic (``nr_net_set_deterministic_batch``): plan choices are made per clip, so a clip's result does not
         depend on how many clips share the call.  Default off (``NR_DETERMINISTIC_BATCH=1`` turns it on for new handles)."""
