@@ -366,7 +366,8 @@ void nr_g8p_set_mode(int32_t mode);
 /* phases per k-tile of that kernel: 2 (default; tiles of <= 256 columns only) or 4.  A/B tools and tests (env NR_G8P_PHASES). */
 void nr_g8p_set_phases(int32_t phases);
 /* waves per 128-row workgroup of the fused FeedForward kernel (ffpanel.hip): 8 (default: 16-row waves, two per SIMD) or 4 (32-row waves,
- * one per SIMD; the round-3 form).  Results are bit-identical between the two.  A/B tools and tests (env NR_FF_WAVES). */
+ * one per SIMD; the round-3 form).  Results are bit-identical between the two.  A/B tools and tests (env NR_FF_WAVES).  As nr_g8p_set_mode it sets what
+ * the NEXT launch description reads: a planned handle (and its captured graph) keeps its count until nr_net_plan; nr_op_ff_fused reads it per call. */
 void nr_ff_set_waves(int32_t waves);
 
 /* Leaf-module handles (kinds NR_KIND_LEAF_TRANSFORMER3D / NR_KIND_LEAF_TEMPORAL): Transformer3DModel.forward (attention.py:95-142) or

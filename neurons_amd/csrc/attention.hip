@@ -465,56 +465,51 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(NrAttnParams p) {
 }
 
 template <int DK, int DT>
-int launch_attn(const NrAttnParams& p, hipStream_t stream) {
-  if (p.Lq >= 48 && p.inner == 1 && !p.causal) {   // causal masking lives in the per-wave kernel only
-    // long sequences: block-shared K/V tiles
-    constexpr int KSK = DK <= 2 ? 64 : DK * 32 + 8;                              // as in the kernel
-    constexpr int KSV = (DT * 16) % 32 == 16 ? DT * 16 : DT * 16 + 16;
-    const size_t shm = (size_t)2 * KT2 * (KSK + KSV) * sizeof(bf16);
+int launch_attn(const NrAttnParams& p, const NrAttnRoute& r, hipStream_t stream) {
+  void (*k)(NrAttnParams);
+  if (r.cls == NR_ATTN_SHARED) {
     static unsigned long long attr_mask = 0;       // per device
     (void)nr_lds_opt_in(attr_mask, {(const void*)attn_fwd_shared_kernel<DK, DT, false>, (const void*)attn_fwd_shared_kernel<DK, DT, true>}, 100 * 1024);
+    k = r.fp8 ? attn_fwd_shared_kernel<DK, DT, true> : attn_fwd_shared_kernel<DK, DT, false>;
     if constexpr (DK == 2 && DT == 3) {
       static unsigned long long attr_mask_fp8 = 0;
       (void)nr_lds_opt_in(attr_mask_fp8, {(const void*)attn_fwd_shared_kernel<DK, DT, false, true>, (const void*)attn_fwd_shared_kernel<DK, DT, true, true>}, 100 * 1024);
+      if (r.ones) k = r.fp8 ? attn_fwd_shared_kernel<DK, DT, true, true> : attn_fwd_shared_kernel<DK, DT, false, true>;
     }
-    const int qblocks = (p.Lq + 63) / 64;
-    const unsigned blocks = (unsigned)((long long)p.nbatch * p.heads * qblocks);
-    if constexpr (DK == 2 && DT == 3) {
-      // d = 40: the denominator rides on the pad column of V (NR_ATTN_ROWSUM=adds keeps the VALU sums: A/B only)
-      static const bool ones = !(getenv("NR_ATTN_ROWSUM") && getenv("NR_ATTN_ROWSUM")[0] == 'a');
-      if (ones && p.d == 40) {
-        if (p.fp8) hipLaunchKernelGGL((attn_fwd_shared_kernel<DK, DT, true, true>), dim3(blocks), dim3(256), shm, stream, p);
-        else hipLaunchKernelGGL((attn_fwd_shared_kernel<DK, DT, false, true>), dim3(blocks), dim3(256), shm, stream, p);
-        return 0;
-      }
-    }
-    if (p.fp8) hipLaunchKernelGGL((attn_fwd_shared_kernel<DK, DT, true>), dim3(blocks), dim3(256), shm, stream, p);
-    else hipLaunchKernelGGL((attn_fwd_shared_kernel<DK, DT, false>), dim3(blocks), dim3(256), shm, stream, p);
-    return 0;
-  }
-  const int qtiles = (p.Lq + 15) / 16;
-  const long long total = (long long)p.nbatch * p.heads * qtiles;
-  const unsigned blocks = (unsigned)((total + 3) / 4);
-  const size_t shm = (size_t)4 * KT * vt_stride(DT) * sizeof(bf16);
-  hipLaunchKernelGGL((attn_fwd_kernel<DK, DT>), dim3(blocks), dim3(256), shm, stream, p);
+  } else k = attn_fwd_kernel<DK, DT>;
+  hipLaunchKernelGGL(k, dim3(r.grid), dim3(256), r.lds_bytes, stream, p);
   return 0;
 }
 
 }  // namespace
 
-extern "C" int nr_launch_attention(const NrAttnParams* pp, hipStream_t stream) {
+extern "C" int nr_attn_route(const NrAttnParams* pp, NrAttnRoute* r) {
   const NrAttnParams& p = *pp;
   if (p.d % 8 != 0 || p.d > 160 || p.d <= 0) return 1;
   if (p.Lq <= 0 || p.Lk <= 0 || p.nbatch <= 0) return 2;
   const int DK = (p.d + 31) / 32, DT = (p.d + 15) / 16;
-  // instantiate the head dims on the path (40, 80, 160) plus small ones used by reduced-width tests
-  if (DK == 1 && DT == 1) return launch_attn<1, 1>(p, stream);       // d = 8, 16
-  if (DK == 1 && DT == 2) return launch_attn<1, 2>(p, stream);       // d = 24, 32
-  if (DK == 2 && DT == 3) return launch_attn<2, 3>(p, stream);       // d = 40, 48
-  if (DK == 2 && DT == 4) return launch_attn<2, 4>(p, stream);       // d = 56, 64
-  if (DK == 3 && DT == 5) return launch_attn<3, 5>(p, stream);       // d = 72, 80
-  if (DK == 3 && DT == 6) return launch_attn<3, 6>(p, stream);       // d = 88, 96
-  if (DK == 4 && DT == 8) return launch_attn<4, 8>(p, stream);       // d = 120, 128
-  if (DK == 5 && DT == 10) return launch_attn<5, 10>(p, stream);     // d = 152, 160
-  return 3;
+  if (DT == 7 || DT == 9) return 3;                // d = 104 .. 112, 136 .. 144: not instantiated (nr_launch_attention)
+  *r = NrAttnRoute{};
+  r->dk = DK; r->dt = DT; r->cls = NR_ATTN_WAVE;
+  if (p.Lq >= 48 && p.inner == 1 && !p.causal) {   // long sequences: block-shared K/V tiles; causal masking lives in the per-wave kernel only
+    const int KSK = DK <= 2 ? 64 : DK * 32 + 8, KSV = vt_stride(DT);             // as in the kernel
+    r->cls = NR_ATTN_SHARED; r->fp8 = p.fp8;
+    // d = 40: the denominator rides on the pad column of V (NR_ATTN_ROWSUM=adds keeps the VALU sums: A/B only)
+    static const bool ones = !(getenv("NR_ATTN_ROWSUM") && getenv("NR_ATTN_ROWSUM")[0] == 'a');
+    r->ones = ones && p.d == 40;
+    r->lds_bytes = (size_t)2 * KT2 * (KSK + KSV) * sizeof(bf16);
+    r->grid = (unsigned)((long long)p.nbatch * p.heads * ((p.Lq + 63) / 64));
+    return 0;
+  }
+  r->lds_bytes = (size_t)4 * KT * vt_stride(DT) * sizeof(bf16);
+  r->grid = (unsigned)(((long long)p.nbatch * p.heads * ((p.Lq + 15) / 16) + 3) / 4);
+  return 0;
+}
+
+extern "C" int nr_launch_attention(const NrAttnParams* pp, const NrAttnRoute* r, hipStream_t stream) {
+  // by dt = ceil(d / 16): the head dims on the path (40, 80, 160) plus small ones used by reduced-width tests
+  static int (*const fn[11])(const NrAttnParams&, const NrAttnRoute&, hipStream_t) = {nullptr, launch_attn<1, 1>, launch_attn<1, 2>, launch_attn<2, 3>, launch_attn<2, 4>,
+                                                                                     launch_attn<3, 5>, launch_attn<3, 6>, nullptr, launch_attn<4, 8>, nullptr, launch_attn<5, 10>};
+  if (r->dt < 1 || r->dt > 10 || !fn[r->dt]) return 3;      // a route nr_attn_route does not make
+  return fn[r->dt](*pp, *r, stream);
 }

@@ -255,7 +255,7 @@ inline NrAttnParams nr_attn_params(int mode, const bf16* q, const bf16* kv, bf16
   return p;
 }
 
-// sources, shape, affine and output of a GroupNorm; the chunking (plan_nimg, pix_per_blk, nchunk) is the launcher's, `partial` its scratch
+// sources, shape, affine and output of a GroupNorm; plan_nimg is the caller's, the chunking (pix_per_blk, nchunk, finalized) the route's (nr_gn_route), `partial` its scratch
 inline NrGnParams nr_gn_params(const bf16* x0, int c0, int ld0, const bf16* x1, int c1, int ld1, int nimg, int hw, int groups, const float* gamma,
                                const float* beta, float eps, int silu, float* partial, bf16* out, int ldo) {
   NrGnParams p;

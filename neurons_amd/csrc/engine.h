@@ -420,6 +420,9 @@ struct nr_net {
   Act feed_forward_proj_out(const Act& x, Act& t, const std::string& ln, const std::string& ff, const std::string& pre);
   bool cfg_dedup_active() const;
   Act expand_cfg(const Act& h);
+  enum BlockKernel { BLOCK_UNFUSED, BLOCK_FUSED320, BLOCK_HEAD };      // a cross- / temporal-attention block on t: GEMMs + attention, the fused C = 320 kernel, the head kernel above it
+  BlockKernel cross_attn_kernel(const Act& t, int heads, int hw) const;
+  BlockKernel temporal_attn_kernel(const Act& t, int heads, int hw) const;
   Act spatial_transformer(const Act& x_in, const Act& ctx_bf, const std::string& pre, int depth = 1, bool cfg_half = false, Act* x_full = nullptr);
   Act temporal_module(const Act& x, const std::string& pre0);
   Act vae_attn(const Act& x, const std::string& pre);

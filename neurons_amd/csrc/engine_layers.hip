@@ -157,16 +157,15 @@ Act nr_net::groupnorm(const Act& x0, const Act* x1, const std::string& prefix, f
   const int C = x0.C + (x1 ? x1->C : 0);
   const float* gamma = wts.w_f32(prefix + ".weight", C);
   const float* beta = wts.w_f32(prefix + ".bias", C);
-  const int hw = x0.H * x0.W, groups = cfg.norm_num_groups;
-  const int plan_nimg = det_batch ? (int)det_rows(x0.nimg) : 0;
-  int nch = 0;
-  (void)nr_gn_workspace_floats(plan_nimg > 0 ? plan_nimg : x0.nimg, hw, groups, nullptr, &nch);   // chunking as the launcher will choose it
-  const int nfl = x0.nimg * (nch * groups * 2 + groups * 2);
-  auto ws = new_tmp((size_t)nfl * sizeof(float));
+  NrGnParams p = nr_gn_params(x0.ptr, x0.C, x0.ld, x1 ? x1->ptr : nullptr, x1 ? x1->C : 0, x1 ? x1->ld : 0, x0.nimg, x0.H * x0.W, cfg.norm_num_groups, gamma, beta,
+                              eps, silu, nullptr, nullptr, C);      // scratch and output: sized by the route below
+  if (x1) p.c1 = x1->C;      // whatever x1->ptr is in the sizing pass
+  p.plan_nimg = det_batch ? (int)det_rows(x0.nimg) : 0;
+  NrGnRoute r;
+  LAUNCH_OK(nr_gn_route(&p, &r));
+  auto ws = new_tmp((size_t)r.ws_floats * sizeof(float));
   Act out = new_act(x0.nimg, x0.H, x0.W, C);
-  NrGnParams p = nr_gn_params(x0.ptr, x0.C, x0.ld, x1 ? x1->ptr : nullptr, x1 ? x1->C : 0, x1 ? x1->ld : 0, x0.nimg, hw, groups, gamma, beta, eps, silu,
-                              at<float>(ws->off), out.ptr, out.ld);
-  p.plan_nimg = plan_nimg;
+  p.partial = at<float>(ws->off); p.out = out.ptr;
   if (getenv("NR_OP_TAPS") && keep_all && !x1) {     // debug: what the GroupNorm's input looked like when it ran
     Act snap = new_act(x0.nimg, x0.H, x0.W, x0.C);
     const bf16* src = x0.ptr; bf16* dst = snap.ptr; const size_t nb = (size_t)x0.rows() * x0.C * sizeof(bf16);
@@ -175,10 +174,10 @@ Act nr_net::groupnorm(const Act& x0, const Act* x1, const std::string& prefix, f
       op_tap("gn_input_snapshot", snap);
     }
   }
-  emit([p](hipStream_t s) { NrGnParams q = p; LAUNCH_OK(nr_launch_groupnorm(&q, s)); }, NR_PROF_GROUPNORM,
+  emit([p, r](hipStream_t s) { LAUNCH_OK(nr_launch_groupnorm(&p, &r, s)); }, NR_PROF_GROUPNORM,
        8.0 * (double)x0.rows() * C, 2.0 * 2.0 * (double)x0.rows() * C,
        "groupnorm nimg=" + std::to_string(x0.nimg) + " hw=" + std::to_string(x0.H * x0.W) + " C=" + std::to_string(C));
-  { NrGnParams q = p; last_op_launches(nr_groupnorm_launches(&q)); }
+  last_op_launches(r.launches);
   op_tap("gn", out);
   return out;
 }
@@ -201,15 +200,15 @@ Act nr_net::attention(int mode, const Act& q, const Act* kv, int C, int heads, i
   Act out = new_act(q.nimg, q.H, q.W, C);
   const NrAttnParams p = nr_attn_params(mode, q.ptr, kv ? kv->ptr : nullptr, out.ptr, q.ld, kv ? kv->ld : 0, out.ld, q.nimg, q.H * q.W, ctx_len, C, heads, F,
                                         F, causal, (attn_fp8 && mode != 2) ? 1 : 0);
-  {
-    const double flops = 4.0 * (double)p.nbatch * p.heads * (double)p.Lq * p.Lk * p.d;
-    const double kvrows = mode == 1 ? (double)(p.nbatch / p.kv_div) * p.Lk : (double)p.nbatch * p.Lk;
-    const double bytes = 2.0 * ((double)p.nbatch * p.Lq * C * 2.0 + kvrows * C * 2.0);   // q + out + k + v
-    char d[160];
-    snprintf(d, sizeof(d), "attention mode=%d nbatch=%d heads=%d d=%d Lq=%d Lk=%d", mode, p.nbatch, p.heads, p.d, p.Lq, p.Lk);
-    emit([p](hipStream_t s) { LAUNCH_OK(nr_launch_attention(&p, s)); }, NR_PROF_ATTENTION, flops, bytes, d);
-    op_tap(mode == 2 ? "tattn" : (mode == 1 ? "xattn" : "sattn"), out);
-  }
+  NrAttnRoute r;
+  LAUNCH_OK(nr_attn_route(&p, &r));
+  const double flops = 4.0 * (double)p.nbatch * p.heads * (double)p.Lq * p.Lk * p.d;
+  const double kvrows = mode == 1 ? (double)(p.nbatch / p.kv_div) * p.Lk : (double)p.nbatch * p.Lk;
+  const double bytes = 2.0 * ((double)p.nbatch * p.Lq * C * 2.0 + kvrows * C * 2.0);   // q + out + k + v
+  char d[160];
+  snprintf(d, sizeof(d), "attention mode=%d nbatch=%d heads=%d d=%d Lq=%d Lk=%d", mode, p.nbatch, p.heads, p.d, p.Lq, p.Lk);
+  emit([p, r](hipStream_t s) { LAUNCH_OK(nr_launch_attention(&p, &r, s)); }, NR_PROF_ATTENTION, flops, bytes, d);
+  op_tap(mode == 2 ? "tattn" : (mode == 1 ? "xattn" : "sattn"), out);
   return out;
 }
 
@@ -366,8 +365,8 @@ Act nr_net::feed_forward_proj_out(const Act& x, Act& t, const std::string& ln, c
     const float* bc = fw.b;
     char d[160];
     snprintf(d, sizeof(d), "ff_fused M=%d C=%d (LN + GEGLU 8C + folded net.2|proj_out 5C)", M, C);
-    const int norot = det_batch ? 1 : 0;
-    emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_ff_fused(tp, C, xp, C, op, C, M, stream, gamma, beta, b1, bc, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
+    const int norot = det_batch ? 1 : 0, waves = nr_ff_waves();
+    emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_ff_fused(tp, C, xp, C, op, C, M, stream, gamma, beta, b1, bc, 1e-5f, norot, waves, s)); }, NR_PROF_IGEMM,
          2.0 * M * (double)C * (8.0 * C + 5.0 * C), 2.0 * (3.0 * M * (double)C + 13.0 * C * (double)C), d);
     op_tap("ff_fused", out);
     return out;
@@ -400,6 +399,17 @@ Act nr_net::expand_cfg(const Act& h) {
   return f;
 }
 
+nr_net::BlockKernel nr_net::cross_attn_kernel(const Act& t, int heads, int hw) const {
+  if (cfg.kind == NR_KIND_SGM_UNET || attn_fp8 || t.ld != t.C) return BLOCK_UNFUSED;
+  if (nr_xattn_fused_eligible(t.C, heads, ctx_len, hw, det_rows(t.rows()))) return BLOCK_FUSED320;
+  return nr_xattnw_eligible(t.C, heads, ctx_len, hw, det_rows(t.rows())) ? BLOCK_HEAD : BLOCK_UNFUSED;
+}
+nr_net::BlockKernel nr_net::temporal_attn_kernel(const Act& t, int heads, int hw) const {
+  if (t.ld != t.C) return BLOCK_UNFUSED;
+  if (nr_tattn_fused_eligible(t.C, heads, F, hw, det_rows(t.rows()))) return BLOCK_FUSED320;
+  return nr_tattnw_eligible(t.C, heads, F, hw, det_rows(t.rows())) ? BLOCK_HEAD : BLOCK_UNFUSED;
+}
+
 // Transformer3DModel.forward (attention.py:95-142) with one BasicTransformerBlock (:256-300); also sgm
 // SpatialTransformer.forward (sgm/modules/attention.py:702-723) with `depth` BasicTransformerBlocks (:551-572):
 // same arithmetic and parameter names (proj_in/out are nn.Linear there: same [C][C] matrix).
@@ -427,7 +437,8 @@ Act nr_net::spatial_transformer(const Act& x_in, const Act& ctx_bf, const std::s
       x = expand_cfg(x);
       if (x_full) *x_full = x;
     }
-    if (cfg.kind != NR_KIND_SGM_UNET && !attn_fp8 && t.ld == C && nr_xattn_fused_eligible(C, heads, ctx_len, x.H * x.W, det_rows(t.rows()))) {
+    const BlockKernel xk = cross_attn_kernel(t, heads, x.H * x.W);
+    if (xk == BLOCK_FUSED320) {
       // C = 320, 8 heads, <= 80 context tokens, >= 4096 rows: the whole cross-attention block (LayerNorm, q projection, attention on the cached
       // K | V of the clip, to_out + residual) in ONE launch that updates t in place (xattn.hip); q and the attention output never reach HBM
       const int nctx = (int)(ctx_bf.rows() / ctx_len);      // ctx_bf is ONE "image" of B2 * ctx_len token rows
@@ -457,7 +468,7 @@ Act nr_net::spatial_transformer(const Act& x_in, const Act& ctx_bf, const std::s
       emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattn_fused(tp, nimg, hwx, ipc, nctx, Lk, wstream, kvsp, gamma, beta, bo, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
            2.0 * M * C * 2.0 * C + 4.0 * M * (double)Lk * C, 2.0 * (2.0 * M * C + 2.0 * C * (double)C), d);
       op_tap("xattn_fused", t);
-    } else if (cfg.kind != NR_KIND_SGM_UNET && !attn_fp8 && t.ld == C && nr_xattnw_eligible(C, heads, ctx_len, x.H * x.W, det_rows(t.rows()))) {
+    } else if (xk == BLOCK_HEAD) {
       // C = 640 / 1280, 8 heads, <= 80 context tokens: LayerNorm (folded), the q projection and the attention on the cached K | V of the row's
       // context in ONE launch per block (xattnw.hip); q never reaches HBM.  to_out + residual stays the GEMM below.
       const int nctx = (int)(ctx_bf.rows() / ctx_len);
@@ -520,7 +531,8 @@ Act nr_net::temporal_module(const Act& x, const std::string& pre0) {
   const std::string b = pre + ".transformer_blocks.0";
   for (int k = 0; k < cfg.motion_num_attention_blocks; ++k) {
     const std::string ab = b + ".attention_blocks." + std::to_string(k);
-    if (nr_tattn_fused_eligible(C, heads, F, x.H * x.W, det_rows(t.rows())) && t.ld == C) {
+    const BlockKernel tk = temporal_attn_kernel(t, heads, x.H * x.W);
+    if (tk == BLOCK_FUSED320) {
       // C = 320, F = 16 or 32: the whole block (LayerNorm + PE, q|k|v, F x F attention per pixel and head, to_out + residual) in ONE launch
       // that updates t in place (tattn.hip); q|k|v and the attention output never reach HBM
       const std::string nrm = b + ".norms." + std::to_string(k);
@@ -548,7 +560,7 @@ Act nr_net::temporal_module(const Act& x, const std::string& pre0) {
       continue;
     }
     Act a;
-    if (nr_tattnw_eligible(C, heads, F, x.H * x.W, det_rows(t.rows())) && t.ld == C) {
+    if (tk == BLOCK_HEAD) {
       // C = 640 / 1280, F = 16 or 32: LayerNorm + PE (folded), the q|k|v projection of one head and its F x F attention per (pixel group, head) in
       // ONE launch (tattnw.hip); q|k|v never reach HBM.  to_out + residual stays the GEMM below.
       const std::string nrm = b + ".norms." + std::to_string(k);

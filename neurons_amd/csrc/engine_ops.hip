@@ -162,7 +162,9 @@ extern "C" nr_status nr_op_groupnorm(nr_stream stream, const void* x0, int32_t c
   NR_TRY
   NrGnParams p = nr_gn_params((const bf16*)x0, c0, c0, (const bf16*)x1, c1, c1, nimg, hw, groups, gamma, beta, eps, silu, partial_ws, (bf16*)out,
                               c0 + (x1 ? c1 : 0));
-  LAUNCH_OK(nr_launch_groupnorm(&p, (hipStream_t)stream));
+  NrGnRoute r;      // routed per call
+  if (const int rc = nr_gn_route(&p, &r)) throw NrError(NR_ERR_UNSUPPORTED, "nr_gn_route -> " + std::to_string(rc) + ": no kernel serves this shape, nr_launch_groupnorm not called");
+  LAUNCH_OK(nr_launch_groupnorm(&p, &r, (hipStream_t)stream));
   NR_CATCH
 }
 
@@ -186,7 +188,9 @@ extern "C" nr_status nr_op_attention(nr_stream stream, int32_t mode, const void*
   // the hook's tensors are dense: q|k|v rows of 3C (modes 0 / 2), q rows of C and k|v rows of 2C (mode 1), output rows of C
   const NrAttnParams p = nr_attn_params(mode, (const bf16*)qp, (const bf16*)kvp, (bf16*)outp, mode == 1 ? C : 3 * C, 2 * C, C, nimg, L, Lk, C, heads, frames, kv_div,
                                         causal_flag, fp8_flag);
-  LAUNCH_OK(nr_launch_attention(&p, (hipStream_t)stream));
+  NrAttnRoute r;      // routed per call
+  if (const int rc = nr_attn_route(&p, &r)) throw NrError(NR_ERR_UNSUPPORTED, "nr_attn_route -> " + std::to_string(rc) + ": no kernel serves this shape, nr_launch_attention not called");
+  LAUNCH_OK(nr_launch_attention(&p, &r, (hipStream_t)stream));
   NR_CATCH
 }
 
@@ -195,14 +199,14 @@ extern "C" nr_status nr_op_ff_fused(nr_stream stream, const void* t_dev, const v
                                     const void* w1_geglu_dev, const float* gamma_dev, const float* beta_dev, const float* b1_geglu_dev,
                                     const void* wc_dev, const float* bc_dev, float ln_eps) {
   NR_TRY
-  if (!nr_ff_fused_eligible(C, 1 << 30)) throw NrError(NR_ERR_UNSUPPORTED, "the fused FeedForward kernel is built for C = 320");
+  if (!nr_ff_fused_supported(C, C, C, C)) throw NrError(NR_ERR_UNSUPPORTED, "the fused FeedForward kernel is built for C = 320");
   static OpScratch buf;
   op_scratch(buf, nr_ff_stream_bytes(C));
   void* ws = buf.ptr;
   // w1 == NULL: reuse the stage stream packed by the previous call (timing loops)
   if (w1_geglu_dev) LAUNCH_OK(nr_launch_ff_stream_pack((const bf16*)w1_geglu_dev, (const bf16*)wc_dev, (bf16*)ws, (hipStream_t)stream));
   LAUNCH_OK(nr_launch_ff_fused((const bf16*)t_dev, C, (const bf16*)x_dev, C, (bf16*)out_dev, C, M, (const bf16*)ws, gamma_dev, beta_dev,
-                               b1_geglu_dev, bc_dev, ln_eps, env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
+                               b1_geglu_dev, bc_dev, ln_eps, env_is_1("NR_DETERMINISTIC_BATCH"), nr_ff_waves(), (hipStream_t)stream));
   NR_CATCH
 }
 
@@ -213,7 +217,7 @@ extern "C" nr_status nr_op_tattn_fused_frames(nr_stream stream, void* t_dev, int
                                               const void* wk_dev, const void* wv_dev, const void* wo_dev, const float* gamma_dev,
                                               const float* gb_dev, const float* bo_dev, float ln_eps) {
   NR_TRY
-  if (!nr_tattn_fused_eligible(320, 8, frames, hw, 1 << 30))
+  if (!nr_tattn_fused_supported(320, 8, frames, hw))
     throw NrError(NR_ERR_UNSUPPORTED, "fused temporal attention: C = 320, 8 heads, 16 or 32 frames, hw % (128 / frames) == 0");
   static OpScratch buf;
   op_scratch(buf, nr_tattn_stream_bytes());
@@ -230,7 +234,7 @@ extern "C" nr_status nr_op_xattn_fused(nr_stream stream, void* t_dev, int32_t ni
                                        const float* beta_dev, const float* bo_dev, float ln_eps) {
   NR_TRY
   if (!t_dev || !kv_dev || !gamma_dev || !beta_dev || !bo_dev) throw NrError(NR_ERR_ARG, "null argument");
-  if (!nr_xattn_fused_eligible(320, 8, Lk, hw, 1 << 30) || nimg <= 0 || img_per_ctx <= 0 || nctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
+  if (!nr_xattn_fused_supported(320, 8, Lk, hw) || nimg <= 0 || img_per_ctx <= 0 || nctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
     throw NrError(NR_ERR_UNSUPPORTED, "fused cross attention: C = 320, 8 heads, Lk <= 80, hw % 128 == 0, one context per img_per_ctx images");
   static OpScratch wbuf, kvbuf;
   op_scratch(wbuf, nr_xattn_wstream_bytes());
@@ -254,8 +258,7 @@ extern "C" nr_status nr_op_xattn_head(nr_stream stream, const void* t_dev, void*
                                       int32_t nctx, float ln_eps) {
   NR_TRY
   if (!t_dev || !a_dev || !kv_dev) throw NrError(NR_ERR_ARG, "null argument");
-  if (!nr_xattnw_wstream_bytes(C) || nimg <= 0 || hw <= 0 || hw % 64 != 0 || Lk < 1 || Lk > 80 || nctx <= 0 || img_per_ctx <= 0 ||
-      (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
+  if (!nr_xattnw_supported(C, 8, Lk, hw) || nimg <= 0 || nctx <= 0 || img_per_ctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
     throw NrError(NR_ERR_UNSUPPORTED, "cross-attention head kernel: C = 640 or 1280, 8 heads, Lk <= 80, hw % 64 == 0, one context per img_per_ctx images");
   static OpScratch wbuf[2], tbuf[2], kvbuf;      // weight stream and table: one per C
   const int ci = C == 640 ? 0 : 1;
@@ -284,7 +287,7 @@ extern "C" nr_status nr_op_tattn_head_frames(nr_stream stream, const void* t_dev
                                              const void* w_folded_dev, const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
   NR_TRY
   if (!t_dev || !a_dev || !lnc_dev || !bias_dev || !rowvec_dev) throw NrError(NR_ERR_ARG, "null argument");
-  if (!nr_tattnw_stream_bytes(C) || (frames != 16 && frames != 32) || nbatch <= 0 || hw <= 0 || hw % (C == 640 ? 8 : 4) != 0)
+  if (!nr_tattnw_supported(C, 8, frames, hw) || nbatch <= 0)
     throw NrError(NR_ERR_UNSUPPORTED, "temporal attention head kernel: C = 640 (hw % 8 == 0) or 1280 (hw % 4 == 0), 8 heads, 16 or 32 frames");
   static OpScratch wbuf[2], tbuf[2][2];                                   // weight stream per C; table per [C][frames]: it is packed for one frame count
   static int ws_frames[2] = {0, 0};                                       // the frame count of the last packing call at this C

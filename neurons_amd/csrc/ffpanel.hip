@@ -414,16 +414,18 @@ __global__ __launch_bounds__(256) void ff_stream_pack_kernel(const bf16* __restr
 }
 
 unsigned long long g_ff_attr = 0;
-int g_ff_waves = -1;       // NR_FF_WAVES: 8 (default: 16-row waves, two per SIMD) or 4 (the round-3 form); nr_ff_set_waves overrides (A/B, tests)
+int g_ff_waves = -1;       // what nr_ff_waves answers: NR_FF_WAVES, 8 (default: 16-row waves, two per SIMD) or 4 (the round-3 form); nr_ff_set_waves overrides (A/B, tests)
 
 }  // namespace
 
 extern "C" void nr_ff_set_waves(int waves) { g_ff_waves = waves == 4 ? 4 : 8; }
+extern "C" int nr_ff_waves(void) { if (g_ff_waves < 0) nr_ff_set_waves(getenv("NR_FF_WAVES") ? atoi(getenv("NR_FF_WAVES")) : 8); return g_ff_waves; }
 extern "C" size_t nr_ff_stream_bytes(int C) { return C == FF_C ? (size_t)FF_NSTAGES * FF_STAGE * sizeof(bf16) : 0; }
 
-extern "C" int nr_ff_fused_eligible(int C, long long M) {
+extern "C" int nr_ff_fused_supported(int C, int ldt, int ldx, int ldo) { return C == FF_C && ldt % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0; }
+extern "C" int nr_ff_fused_eligible(int C, long long M) {      // dense rows
   static const bool off = !env_not_0("NR_FF_FUSED");   // A/B switch
-  return !off && C == FF_C && M >= 4096;
+  return !off && nr_ff_fused_supported(C, C, C, C) && M >= 4096;
 }
 
 extern "C" int nr_launch_ff_stream_pack(const bf16* w1, const bf16* wc, bf16* stream, hipStream_t s) {
@@ -433,16 +435,15 @@ extern "C" int nr_launch_ff_stream_pack(const bf16* w1, const bf16* wc, bf16* st
 }
 
 extern "C" int nr_launch_ff_fused(const bf16* t, int ldt, const bf16* x, int ldx, bf16* out, int ldo, int M, const bf16* stream,
-                                  const float* gamma, const float* beta, const float* b1, const float* bc, float ln_eps, int norot, hipStream_t s) {
-  if (M <= 0 || ldt % 8 != 0 || ldx % 8 != 0 || ldo % 8 != 0) return 1;
+                                  const float* gamma, const float* beta, const float* b1, const float* bc, float ln_eps, int norot, int waves, hipStream_t s) {
+  if (M <= 0 || !nr_ff_fused_supported(FF_C, ldt, ldx, ldo)) return 1;
   NrFFParams p;
   p.t = t; p.ldt = ldt; p.x = x; p.ldx = ldx; p.out = out; p.ldo = ldo; p.M = M; p.stream = stream; p.gamma = gamma; p.beta = beta; p.b1 = b1; p.bc = bc;
   p.ln_eps = ln_eps; p.norot = norot;
   constexpr size_t shm = (size_t)FF_NS * FF_STAGE * sizeof(bf16) + (size_t)8 * FF_C * sizeof(float);
   if (const int rc = nr_lds_opt_in(g_ff_attr, {(const void*)ff_fused_kernel<2>, (const void*)ff_fused_kernel<1>}, shm)) return rc;
-  if (g_ff_waves < 0) g_ff_waves = getenv("NR_FF_WAVES") ? atoi(getenv("NR_FF_WAVES")) : 8;
   const unsigned grid = (unsigned)((M + FF_ROWS - 1) / FF_ROWS);
-  if (g_ff_waves == 4) hipLaunchKernelGGL(ff_fused_kernel<2>, dim3(grid), dim3(256), shm, s, p);
+  if (waves == 4) hipLaunchKernelGGL(ff_fused_kernel<2>, dim3(grid), dim3(256), shm, s, p);
   else hipLaunchKernelGGL(ff_fused_kernel<1>, dim3(grid), dim3(512), shm, s, p);
   return 0;
 }

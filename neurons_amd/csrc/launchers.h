@@ -5,6 +5,14 @@
 #include "common.h"
 #include "gemm_route.h"
 
+// norm.hip, attention.hip: as nr_gemm_route, nr_gn_route / nr_attn_route decide once, are the only readers of their kernels' switches and return nonzero for a shape
+// no kernel serves.  The route of one GroupNorm: the register-resident slab kernel (gs groups per workgroup, nv 16-byte chunks per thread), the fused small-image
+// kernel (<= maxp channel pairs per thread) or the chunked stats [+ finalize] + apply passes; its kernel count and the floats `partial` must hold
+enum NrGnKind { NR_GN_SLAB, NR_GN_SMALL, NR_GN_CHUNKED };
+struct NrGnRoute { int kind, gs, nv, threads, maxp, pix_per_blk, nchunk, finalized, lds_stats, lds_apply, launches, ws_floats; };
+// attention.hip: K/V tiles per wave (short, strided or causal sequences) or shared by the block (there only: e4m3 operands, the ones column of V at d = 40)
+enum NrAttnClass { NR_ATTN_WAVE, NR_ATTN_SHARED };
+struct NrAttnRoute { int cls, dk, dt, fp8, ones; unsigned grid; size_t lds_bytes; };      // dk / dt: 32- / 16-wide tiles of the head dim
 extern "C" {
 // gemm.hip: the route of a GEMM / conv launch (gemm_route.h) and the tiled implicit GEMM (1x1 / 3x3) with its split-K scratch.
 // nr_gemm_route orders the kernel classes (smallm, lin160, row-panel, gemm8p, tiled) and is the only reader of their switches; it returns nonzero
@@ -30,11 +38,12 @@ size_t nr_lin128q_stream_bytes(int N, int K);
 int nr_launch_lin128q_w_pack(const bf16* w, int N, int K, bf16* stream, hipStream_t s);
 int nr_launch_lin160_w_pack(const bf16* w, int N, int K, bf16* stream, hipStream_t s);
 int nr_launch_lin160(const NrGemmParams* pp, const Lin160Plan* pl, const bf16* stream, hipStream_t s);
-int nr_gn_workspace_floats(int nimg, int hw, int groups, int* pix_per_blk_out, int* nchunk_out);
-int nr_launch_groupnorm(NrGnParams* pp, hipStream_t stream);
+int nr_gn_route(const NrGnParams* pp, NrGnRoute* route);
+int nr_launch_groupnorm(const NrGnParams* pp, const NrGnRoute* route, hipStream_t stream);
+int nr_attn_route(const NrAttnParams* pp, NrAttnRoute* route);
+int nr_launch_attention(const NrAttnParams* pp, const NrAttnRoute* route, hipStream_t stream);
 int nr_launch_layernorm(const bf16* x, int ldx, bf16* out, int ldo, int M, int C, const float* gamma, const float* beta,
                         float eps, const float* pe, int pe_hw, int pe_F, hipStream_t stream);
-int nr_launch_attention(const NrAttnParams* pp, hipStream_t stream);
 int nr_launch_conv_in_small(const float* s0, const float* s1, int c0, int c1, int src_batch, int nimg, int F, int H, int W,
                             const float* wT, const float* bias, const float* addend, int Cout, bf16* out, float in_scale,
                             float in_shift, hipStream_t stream);
@@ -68,7 +77,6 @@ int nr_launch_add_bf16_multi(const NrAddMulti* p, hipStream_t stream);
 int nr_launch_frame_gather(const bf16* src, bf16* dst, int B, int Fs, int Fd, long long frame_elems, const int* map, hipStream_t stream);
 int nr_launch_ncfhw_to_nhwc(const float* src, bf16* dst, int B, int C, int F, int HW, hipStream_t stream);
 int nr_launch_nhwc_to_ncfhw(const bf16* src, float* dst, int B, int C, int F, int HW, hipStream_t stream);
-int nr_groupnorm_launches(const NrGnParams* p);
 int nr_launch_fold_linear_pair(const float* w2, const float* w1, const float* b2, const float* b1, int C, int J, bf16* wc, float* bc,
                                hipStream_t stream);
 // smallm.hip: panel-resident kernel of the M <= 512 Linears (fragment-major weights)
@@ -76,15 +84,19 @@ bool smallm_plan(const NrGemmParams& p, SmallmPlan* pl);
 int nr_launch_smallm(const NrGemmParams* pp, const SmallmPlan* pl, const bf16* w_fm, int layout, hipStream_t stream);
 int nr_launch_smallm_w_pack(const void* w, void* out, int N, int K, hipStream_t stream);
 int nr_launch_smallm_w8_pack(const void* w, void* out, int N, int K, hipStream_t stream);      // NR_W_FRAGMAJOR_E4M3: codes, then the row scales
-// tattn.hip: one kernel per temporal-attention block of the C = 320 level
+// The five fused transformer kernels: X_supported = the kernel's hard shape constraints (for its launcher and its nr_op_* hook); X_eligible adds its A/B
+// switch and its row floor (for the engine's planner; rows: the launch's, one clip's under deterministic batching)
+// xattn.hip / tattn.hip: one kernel per cross- / temporal-attention block of the C = 320 level
 size_t nr_xattn_wstream_bytes(void);
 size_t nr_xattn_kvstream_bytes(int nctx);
+int nr_xattn_fused_supported(int C, int heads, int Lk, int hw);
 int nr_xattn_fused_eligible(int C, int heads, int Lk, int hw, long long rows);
 int nr_launch_xattn_w_pack(const bf16* wq, const bf16* wo, bf16* stream, hipStream_t s);
 int nr_launch_xattn_kv_pack(const bf16* kv, int ldkv, int Lk, int nctx, bf16* stream, hipStream_t s);
 int nr_launch_xattn_fused(bf16* t, int nimg, int hw, int img_per_ctx, int nctx, int Lk, const bf16* wstream, const bf16* kvstream, const float* gamma,
                           const float* beta, const float* bo, float ln_eps, int norot, hipStream_t s);
 size_t nr_tattn_stream_bytes(void);
+int nr_tattn_fused_supported(int C, int heads, int frames, int hw);
 int nr_tattn_fused_eligible(int C, int heads, int frames, int hw, long long rows);
 int nr_launch_tattn_stream_pack(const bf16* wq, const bf16* wk, const bf16* wv, const bf16* wo, bf16* stream, hipStream_t s);
 int nr_launch_tattn_fused(bf16* t, int nbatch, int frames, int hw, const bf16* stream, const float* gamma, const float* gb, const float* bo, float ln_eps,
@@ -93,6 +105,7 @@ int nr_launch_tattn_fused(bf16* t, int nbatch, int frames, int hw, const bf16* s
 size_t nr_xattnw_wstream_bytes(int C);
 size_t nr_xattnw_kvstream_bytes(int C, int nctx);
 size_t nr_xattnw_table_bytes(int C);
+int nr_xattnw_supported(int C, int heads, int Lk, int hw);
 int nr_xattnw_eligible(int C, int heads, int Lk, int hw, long long rows);
 int nr_launch_xattnw_w_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s);
 int nr_launch_xattnw_table_pack(const float* lnc, const float* bias, int C, float* table, hipStream_t s);
@@ -101,6 +114,7 @@ int nr_launch_xattnw(const bf16* t, bf16* out, int nimg, int hw, int img_per_ctx
                      const float* table, float ln_eps, hipStream_t s);
 // tattnw.hip: q|k|v projection of one head + F x F attention per (pixel group, head) above the C = 320 level (C = 640 / 1280, F = 16 / 32)
 size_t nr_tattnw_stream_bytes(int C);
+int nr_tattnw_supported(int C, int heads, int frames, int hw);
 int nr_tattnw_eligible(int C, int heads, int frames, int hw, long long rows);
 int nr_launch_tattnw_stream_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s);
 size_t nr_tattnw_table_bytes(int C, int frames);
@@ -108,10 +122,12 @@ int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, const float
 int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int frames, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s);
 // ffpanel.hip: fused FeedForward(GEGLU) + proj_out of the C = 320 level
 size_t nr_ff_stream_bytes(int C);
+int nr_ff_fused_supported(int C, int ldt, int ldx, int ldo);
 int nr_ff_fused_eligible(int C, long long M);
+int nr_ff_waves(void);      // waves per workgroup (8 or 4) of a launch described now: nr_ff_set_waves, else NR_FF_WAVES, else 8
 int nr_launch_ff_stream_pack(const bf16* w1, const bf16* wc, bf16* stream, hipStream_t s);
 int nr_launch_ff_fused(const bf16* t, int ldt, const bf16* x, int ldx, bf16* out, int ldo, int M, const bf16* stream, const float* gamma,
-                       const float* beta, const float* b1, const float* bc, float ln_eps, int norot, hipStream_t s);
+                       const float* beta, const float* b1, const float* bc, float ln_eps, int norot, int waves, hipStream_t s);
 // elementwise.hip condembed_*: SparseCtrl image-condition embedding (first conv from the fp32 planes, small-channel MFMA convs, batch / frame broadcast)
 int nr_condembed_in_supported(int cin, int Cout);
 int nr_launch_condembed_in(const float* cond, const float* mask, int c0, int nsrc, int F, int H, int W, const int* fmap, int Fe,

@@ -7,13 +7,10 @@
 //   nn.LayerNorm(dim) eps=1e-5                            attention.py:189,206,212; motion_module.py:201,207
 //   PositionalEncoding add after the temporal LayerNorm   motion_module.py:241-243,274-278
 //
-// GroupNorm is two launches: gn_stats (per image x pixel-chunk partial sums, deterministic: no
-// float atomics) and gn_apply (re-reduces the partials, folds gamma/beta/mean/rstd into a per-channel
-// scale+shift held in LDS, streams the pixels).  Both accept a channel-concat of two sources so the
-// up-block skip concat (unet_blocks.py:634,740) is never materialised for the norm.
+// GroupNorm in its general form is two launches: gn_stats (per image x pixel-chunk partial sums, deterministic: no float atomics) and gn_apply
+// (re-reduces the partials, folds gamma/beta/mean/rstd into a per-channel scale+shift held in LDS, streams the pixels); nr_gn_route prefers the
+// one-launch slab and small-image kernels.  All accept a channel-concat of two sources: the up-block skip concat (unet_blocks.py:634,740) is never materialised.
 #include "launchers.h"
-#include <cstdlib>
-
 
 namespace {
 
@@ -448,103 +445,74 @@ void launch_ln(const bf16* x, int ldx, bf16* out, int ldo, int M, int C, const f
 
 }  // namespace
 
-extern "C" int nr_gn_workspace_floats(int nimg, int hw, int groups, int* pix_per_blk_out, int* nchunk_out) {
-  // aim for >= ~16 chunks per image but at least 8 and at most 128 pixels per block (large images: many chunks,
-  // folded by gn_finalize); small batches (sgm U-Net: 2 images, VAE keyframe: 1) shrink the chunks until the streaming
-  // kernels have >= 256 blocks
-  int ppb = (hw + 15) / 16;
-  if (ppb < 8) ppb = 8;
-  if (ppb > 128) ppb = 128;
-  if (ppb > hw) ppb = hw;
-  while (ppb > 2 && (long long)nimg * ((hw + ppb - 1) / ppb) < 256) ppb = (ppb + 1) / 2;
-  const int nchunk = (hw + ppb - 1) / ppb;
-  if (pix_per_blk_out) *pix_per_blk_out = ppb;
-  if (nchunk_out) *nchunk_out = nchunk;
-  return nimg * nchunk * groups * 2 + nimg * groups * 2;
-}
-
-static int gn_launch_impl(NrGnParams* pp, hipStream_t stream, bool count_only, int* nlaunch);
-extern "C" int nr_launch_groupnorm(NrGnParams* pp, hipStream_t stream) { int n = 0; return gn_launch_impl(pp, stream, false, &n); }
-// kernels nr_launch_groupnorm enqueues for this shape (1 slab / per-group kernel, 2-3 for the chunked passes): launch accounting only
-extern "C" int nr_groupnorm_launches(const NrGnParams* pp) {
-  NrGnParams q = *pp;
-  int n = 0;
-  return gn_launch_impl(&q, nullptr, true, &n) == 0 ? n : 1;
-}
-#define GNL(...) do { ++*nlaunch; if (!count_only) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-static int gn_launch_impl(NrGnParams* pp, hipStream_t stream, bool count_only, int* nlaunch) {
-  NrGnParams p = *pp;
+extern "C" int nr_gn_route(const NrGnParams* pp, NrGnRoute* r) {
+  const NrGnParams& p = *pp;
   const int C = p.c0 + p.c1;
   const int pn = p.plan_nimg > 0 && p.plan_nimg < p.nimg ? p.plan_nimg : p.nimg;   // images the variant choices are made for (common.h)
-  if (C % 8 != 0 || C % p.groups != 0 || p.groups > 64) return 1;
-  if (p.x1 && p.c0 % 8 != 0) return 2;
-  {
-    // register-resident slab version: one read + one write (see gn_slab_kernel).  Needs >= 8 channels per group (a 16-byte chunk
-    // then touches at most two groups), 16-byte aligned slabs and concat split, and a slab of <= 512 x 32 chunks.
-    const int cg = C / p.groups;
-    static const bool noslab = getenv("NR_GN_SLAB") != nullptr && atoi(getenv("NR_GN_SLAB")) == 0;
-    if (!noslab && cg >= 8 && cg % 2 == 0 && p.c0 % 8 == 0 && p.ld0 % 8 == 0 && (p.c1 == 0 || p.ld1 % 8 == 0) && p.ldo % 8 == 0) {
-      int GS = 0;
-      for (int g = 1; g <= 8 && g <= p.groups; g *= 2) {            // smallest set whose span is a whole number of chunks
-        if (p.groups % g == 0 && (g * cg) % 8 == 0 && g * cg / 8 <= 64) { GS = g; break; }
-      }
-      // widen the slab (better line use) while the chip stays filled and the registers suffice
-      while (GS && GS * 2 <= 8 && p.groups % (GS * 2) == 0 && GS * 2 * cg / 8 <= 64 &&
-             (long long)pn * (p.groups / (GS * 2)) >= 256 &&
-             ((long long)p.hw + (512 / (GS * 2 * cg / 8)) - 1) / (512 / (GS * 2 * cg / 8)) <= 32) GS *= 2;
-      if (GS && p.hw > 64) {       // hw <= 64: the one-workgroup-per-group kernel below is as fast or faster (measured, tools/gn_ab.sh)
-        const int cpp = GS * cg / 8;
-        static const int tforce = getenv("NR_GN_T") ? atoi(getenv("NR_GN_T")) : 0;
-        // 512 threads (2 waves per SIMD); NR_GN_T=1024 measured 3-6 % slower at every shape of config 2 (tools/gn_ab.sh)
-        const int T = tforce == 1024 ? 1024 : 512;
-        const int NPL = T / cpp;
-        const int nv = (p.hw + NPL - 1) / NPL;
-        const unsigned grid = (unsigned)(p.nimg * (p.groups / GS));
-#define NR_GN_SLAB(NVV)                                                                                                  \
-  do {                                                                                                                   \
-    if (T == 1024) GNL((gn_slab_kernel<NVV, 1024>), dim3(grid), dim3(1024), 0, stream, p, GS);            \
-    else GNL((gn_slab_kernel<NVV, 512>), dim3(grid), dim3(512), 0, stream, p, GS);                        \
-    return 0;                                                                                                            \
-  } while (0)
-        if (nv <= 2) NR_GN_SLAB(2);
-        else if (nv <= 4) NR_GN_SLAB(4);
-        else if (nv <= 8) NR_GN_SLAB(8);
-        else if (nv <= 12) NR_GN_SLAB(12);
-        else if (nv <= 16) NR_GN_SLAB(16);
-#undef NR_GN_SLAB
-        // 24 / 32 chunks per thread only with 512 threads (at 1024 threads the 128-VGPR budget would spill)
-        else if (nv <= 24 && T == 512) { GNL((gn_slab_kernel<24, 512>), dim3(grid), dim3(512), 0, stream, p, GS); return 0; }
-        else if (nv <= 32 && T == 512) { GNL((gn_slab_kernel<32, 512>), dim3(grid), dim3(512), 0, stream, p, GS); return 0; }
-      }
+  if (p.hw <= 0 || C % 8 != 0 || C % p.groups != 0 || p.groups > 64) return 1;
+  if (p.c1 && p.c0 % 8 != 0) return 2;
+  const int cg = C / p.groups;
+  *r = NrGnRoute{.launches = 1};
+  // chunking of the streaming passes, for pn images: aim for >= ~16 chunks per image but at least 8 and at most 128 pixels per block (large images:
+  // many chunks, folded by gn_finalize); small batches (sgm U-Net: 2 images, VAE keyframe: 1) shrink the chunks until the kernels have >= 256 blocks
+  int ppb = std::min(std::min(std::max((p.hw + 15) / 16, 8), 128), p.hw);
+  while (ppb > 2 && (long long)pn * ((p.hw + ppb - 1) / ppb) < 256) ppb = (ppb + 1) / 2;
+  r->pix_per_blk = ppb; r->nchunk = (p.hw + ppb - 1) / ppb;
+  r->ws_floats = p.nimg * (r->nchunk * p.groups * 2 + p.groups * 2);      // `partial` (common.h), whichever kernel serves the launch
+  // register-resident slab version: one read + one write (see gn_slab_kernel).  Needs >= 8 channels per group (a 16-byte chunk
+  // then touches at most two groups), 16-byte aligned slabs and concat split, and a slab of <= 512 x 32 chunks.
+  static const bool noslab = getenv("NR_GN_SLAB") != nullptr && atoi(getenv("NR_GN_SLAB")) == 0;
+  if (!noslab && cg >= 8 && cg % 2 == 0 && p.c0 % 8 == 0 && p.ld0 % 8 == 0 && (p.c1 == 0 || p.ld1 % 8 == 0) && p.ldo % 8 == 0) {
+    int GS = 0;
+    for (int g = 1; g <= 8 && g <= p.groups && !GS; g *= 2)       // smallest set whose span is a whole number of chunks
+      if (p.groups % g == 0 && (g * cg) % 8 == 0 && g * cg / 8 <= 64) GS = g;
+    // widen the slab (better line use) while the chip stays filled and the registers suffice
+    while (GS && GS * 2 <= 8 && p.groups % (GS * 2) == 0 && GS * 2 * cg / 8 <= 64 && (long long)pn * (p.groups / (GS * 2)) >= 256 &&
+           ((long long)p.hw + (512 / (GS * 2 * cg / 8)) - 1) / (512 / (GS * 2 * cg / 8)) <= 32) GS *= 2;
+    if (GS && p.hw > 64) {       // hw <= 64: the one-workgroup-per-group kernel below is as fast or faster (measured, tools/gn_ab.sh)
+      // 512 threads (2 waves per SIMD); NR_GN_T=1024 measured 3-6 % slower at every shape of config 2 (tools/gn_ab.sh)
+      static const int T = getenv("NR_GN_T") && atoi(getenv("NR_GN_T")) == 1024 ? 1024 : 512;
+      const int NPL = T / (GS * cg / 8), nv = (p.hw + NPL - 1) / NPL;
+      // 24 / 32 chunks per thread only with 512 threads (at 1024 threads the 128-VGPR budget would spill)
+      for (int NV : {2, 4, 8, 12, 16, 24, 32})
+        if (nv <= NV && (NV <= 16 || T == 512)) { r->kind = NR_GN_SLAB; r->gs = GS; r->nv = NV; r->threads = T; return 0; }
     }
   }
-  {
-    // small images: single fused launch (needs an even channels-per-group and an even split point of the concat)
-    const int cg = C / p.groups;
-    const long long pairs = (long long)p.hw * (cg / 2);
-    static const bool small_on = env_not_0("NR_GN_SMALL");   // bisect switch (profiles/r03_race_*)
-    if (small_on && p.hw <= 64 && cg % 2 == 0 && p.c0 % 2 == 0 && pairs <= 256LL * 48) {
-      dim3 grid(p.groups, p.nimg);
-      if (pairs <= 256LL * 8) GNL((gn_fused_small_kernel<8>), grid, dim3(256), 0, stream, p);
-      else if (pairs <= 256LL * 16) GNL((gn_fused_small_kernel<16>), grid, dim3(256), 0, stream, p);
-      else GNL((gn_fused_small_kernel<48>), grid, dim3(256), 0, stream, p);
-      return 0;
-    }
+  // small images: single fused launch (needs an even channels-per-group and an even split point of the concat)
+  const long long pairs = (long long)p.hw * (cg / 2);
+  static const bool small_on = env_not_0("NR_GN_SMALL");   // bisect switch (profiles/r03_race_*)
+  if (small_on && p.hw <= 64 && cg % 2 == 0 && p.c0 % 2 == 0 && pairs <= 256LL * 48) {
+    r->kind = NR_GN_SMALL; r->maxp = pairs <= 256LL * 8 ? 8 : (pairs <= 256LL * 16 ? 16 : 48);
+    return 0;
   }
-  nr_gn_workspace_floats(pn, p.hw, p.groups, &p.pix_per_blk, &p.nchunk);     // chunking as for pn images (the engine sizes `partial` for it)
-  const int CP = C / 8;
-  const int PL = CP <= 256 ? 256 / CP : 1;
-  const size_t shm_stats = (size_t)2 * PL * C * sizeof(float);
-  const size_t shm_apply = (size_t)(2 * C + 128) * sizeof(float);
-  if (shm_stats > 60000 || shm_apply > 60000) return 3;
-  dim3 grid(p.nchunk, p.nimg);
-  p.finalized = p.nchunk > 16 ? 1 : 0;
-  GNL(gn_stats_kernel, grid, dim3(256), shm_stats, stream, p);
-  if (p.finalized) GNL(gn_finalize_kernel, dim3(p.groups, p.nimg), dim3(256), 0, stream, p);
-  GNL(gn_apply_kernel, grid, dim3(256), shm_apply, stream, p);
+  const int PL = C / 8 <= 256 ? 256 / (C / 8) : 1;      // as in gn_stats_kernel
+  r->lds_stats = 2 * PL * C * (int)sizeof(float); r->lds_apply = (2 * C + 128) * (int)sizeof(float);
+  if (r->lds_stats > 60000 || r->lds_apply > 60000) return 3;
+  r->kind = NR_GN_CHUNKED; r->finalized = r->nchunk > 16 ? 1 : 0; r->launches = 2 + r->finalized;
   return 0;
 }
-#undef GNL
+
+extern "C" int nr_launch_groupnorm(const NrGnParams* pp, const NrGnRoute* r, hipStream_t stream) {
+  NrGnParams p = *pp;      // a copy: the chunking fields are the route's
+  if (r->kind == NR_GN_SLAB) {
+    const struct { int nv; void (*k1024)(NrGnParams, int); void (*k512)(NrGnParams, int); } slab[] = {      // no 24 / 32 chunks per thread at 1024 threads
+        {2, gn_slab_kernel<2, 1024>, gn_slab_kernel<2, 512>}, {4, gn_slab_kernel<4, 1024>, gn_slab_kernel<4, 512>}, {8, gn_slab_kernel<8, 1024>, gn_slab_kernel<8, 512>},
+        {12, gn_slab_kernel<12, 1024>, gn_slab_kernel<12, 512>}, {16, gn_slab_kernel<16, 1024>, gn_slab_kernel<16, 512>}, {24, nullptr, gn_slab_kernel<24, 512>}, {32, nullptr, gn_slab_kernel<32, 512>}};
+    for (const auto& s : slab)
+      if (const auto k = r->threads == 1024 ? s.k1024 : s.k512; s.nv == r->nv && k) { hipLaunchKernelGGL(k, dim3(p.nimg * (p.groups / r->gs)), dim3(r->threads), 0, stream, p, r->gs); return 0; }
+    return 4;      // a route nr_gn_route does not make
+  } else if (r->kind == NR_GN_SMALL) {
+    const auto k = r->maxp <= 16 ? (r->maxp == 8 ? gn_fused_small_kernel<8> : gn_fused_small_kernel<16>) : gn_fused_small_kernel<48>;      // written 8, 16, 48: the order the kernels are emitted in
+    hipLaunchKernelGGL(k, dim3(p.groups, p.nimg), dim3(256), 0, stream, p);
+  } else {
+    p.pix_per_blk = r->pix_per_blk; p.nchunk = r->nchunk; p.finalized = r->finalized;
+    const dim3 grid(p.nchunk, p.nimg);
+    hipLaunchKernelGGL(gn_stats_kernel, grid, dim3(256), r->lds_stats, stream, p);
+    if (p.finalized) hipLaunchKernelGGL(gn_finalize_kernel, dim3(p.groups, p.nimg), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(gn_apply_kernel, grid, dim3(256), r->lds_apply, stream, p);
+  }
+  return 0;
+}
 
 extern "C" int nr_launch_layernorm(const bf16* x, int ldx, bf16* out, int ldo, int M, int C, const float* gamma,
                                    const float* beta, float eps, const float* pe, int pe_hw, int pe_F,

@@ -426,9 +426,10 @@ unsigned long long g_ta_attr = 0;
 
 extern "C" size_t nr_tattn_stream_bytes(void) { return (size_t)TA_HEADS * TA_HEAD_BYTES; }
 
+extern "C" int nr_tattn_fused_supported(int C, int heads, int frames, int hw) { return C == TA_C && heads == TA_HEADS && (frames == 16 || frames == 32) && hw > 0 && hw % (TA_ROWS / frames) == 0; }
 extern "C" int nr_tattn_fused_eligible(int C, int heads, int frames, int hw, long long rows) {
   static const bool off = !env_not_0("NR_TATTN_FUSED");   // A/B switch
-  return !off && C == TA_C && heads == TA_HEADS && (frames == 16 || frames == 32) && hw % (TA_ROWS / frames) == 0 && rows >= 4096;
+  return !off && nr_tattn_fused_supported(C, heads, frames, hw) && rows >= 4096;
 }
 
 extern "C" int nr_launch_tattn_stream_pack(const bf16* wq, const bf16* wk, const bf16* wv, const bf16* wo, bf16* stream, hipStream_t s) {
@@ -439,7 +440,7 @@ extern "C" int nr_launch_tattn_stream_pack(const bf16* wq, const bf16* wk, const
 
 extern "C" int nr_launch_tattn_fused(bf16* t, int nbatch, int frames, int hw, const bf16* stream, const float* gamma, const float* gb, const float* bo,
                                      float ln_eps, int norot, hipStream_t s) {
-  if (nbatch <= 0 || hw <= 0 || (frames != 16 && frames != 32) || hw % (TA_ROWS / frames) != 0) return 1;
+  if (nbatch <= 0 || !nr_tattn_fused_supported(TA_C, TA_HEADS, frames, hw)) return 1;
   NrTAttnParams p;
   p.t = t; p.hw = hw; p.nbatch = nbatch; p.stream = stream; p.gamma = gamma; p.gb = gb; p.bo = bo; p.ln_eps = ln_eps; p.norot = norot;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)TA_D);

@@ -487,13 +487,13 @@ extern "C" size_t nr_tattnw_stream_bytes(int C) {
 // rows: the launch's row count (deterministic-batch mode: one clip's).  At C = 1280 a launch needs >= 2048 rows: with 512 (the 4 x 4 level at one
 // clip) only 64 workgroups exist, each streaming a head's 1.2 MB alone: 34 us against 27 us for the q|k|v GEMM + attention core (profiles/r06_tattn_head_ab.txt).
 // frames = 32: a workgroup still owns 64 rows, so the same floor in rows is the same floor in workgroups (profiles/r08_tattn_head_f32_ab.txt)
+extern "C" int nr_tattnw_supported(int C, int heads, int frames, int hw) {
+  // the same rule at both frame counts (the pixels of a 16-frame workgroup, 8 / 4, are a multiple of those of a 32-frame one, 4 / 2)
+  return heads == TW_HEADS && (frames == 16 || frames == 32) && hw > 0 && (C == 640 ? hw % TW<80>::PIX_WG == 0 : (C == 1280 && hw % TW<160>::PIX_WG == 0));
+}
 extern "C" int nr_tattnw_eligible(int C, int heads, int frames, int hw, long long rows) {
   static const bool off = !env_not_0("NR_TATTN_HEAD");   // A/B switch
-  if (off || heads != TW_HEADS || (frames != 16 && frames != 32)) return 0;
-  // the same rule at both frame counts (the pixels of a 16-frame workgroup, 8 / 4, are a multiple of those of a 32-frame one, 4 / 2)
-  if (C == 640) return hw % TW<80>::PIX_WG == 0;
-  if (C == 1280) return hw % TW<160>::PIX_WG == 0 && rows >= 2048;
-  return 0;
+  return !off && nr_tattnw_supported(C, heads, frames, hw) && (C == 640 || rows >= 2048);
 }
 
 extern "C" int nr_launch_tattnw_stream_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s) {
@@ -523,7 +523,6 @@ extern "C" int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, 
 template <int D, int F>
 static int tattnw_launch(NrTAttnWParams& p, hipStream_t s) {
   using T = TW<D, F>;
-  if (p.hw % T::PIX_WG != 0) return 1;
   const int npg = p.nbatch * (p.hw / T::PIX_WG);
   p.xcd_mode = (D == 80 && npg % 8 == 0) ? 0 : 1;
   constexpr size_t shm = (size_t)T::NS * T::STAGE;
@@ -535,7 +534,7 @@ static int tattnw_launch(NrTAttnWParams& p, hipStream_t s) {
 
 // t, out: [nbatch * frames * hw][C]; table: nr_tattnw_table_bytes(C, frames) packed for the same frame count
 extern "C" int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int frames, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s) {
-  if (nbatch <= 0 || hw <= 0 || !nr_tattnw_stream_bytes(C) || (frames != 16 && frames != 32)) return 1;
+  if (nbatch <= 0 || !nr_tattnw_supported(C, TW_HEADS, frames, hw)) return 1;
   NrTAttnWParams p;
   p.t = t; p.out = out; p.hw = hw; p.nbatch = nbatch; p.stream = stream; p.table = table; p.ln_eps = ln_eps;
   const int d = C / TW_HEADS;

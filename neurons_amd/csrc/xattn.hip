@@ -417,9 +417,10 @@ extern "C" int nr_xattn_stamp_read(void* dst, size_t bytes, int clear) { return 
 extern "C" size_t nr_xattn_wstream_bytes(void) { return (size_t)XA_HEADS * XA_W_HEAD_BYTES; }
 extern "C" size_t nr_xattn_kvstream_bytes(int nctx) { return (size_t)nctx * XA_HEADS * XA_KV_BYTES; }
 
+extern "C" int nr_xattn_fused_supported(int C, int heads, int Lk, int hw) { return C == XA_C && heads == XA_HEADS && Lk > 0 && Lk <= XA_KEYS && hw > 0 && hw % XA_ROWS == 0; }
 extern "C" int nr_xattn_fused_eligible(int C, int heads, int Lk, int hw, long long rows) {
   static const bool off = !env_not_0("NR_XATTN_FUSED");   // A/B switch
-  return !off && C == XA_C && heads == XA_HEADS && Lk > 0 && Lk <= XA_KEYS && hw % XA_ROWS == 0 && rows >= 4096;
+  return !off && nr_xattn_fused_supported(C, heads, Lk, hw) && rows >= 4096;
 }
 
 extern "C" int nr_launch_xattn_w_pack(const bf16* wq, const bf16* wo, bf16* stream, hipStream_t s) {
@@ -437,7 +438,7 @@ extern "C" int nr_launch_xattn_kv_pack(const bf16* kv, int ldkv, int Lk, int nct
 
 extern "C" int nr_launch_xattn_fused(bf16* t, int nimg, int hw, int img_per_ctx, int nctx, int Lk, const bf16* wstream, const bf16* kvstream,
                                      const float* gamma, const float* beta, const float* bo, float ln_eps, int norot, hipStream_t s) {
-  if (nimg <= 0 || hw <= 0 || hw % XA_ROWS != 0 || img_per_ctx <= 0 || Lk <= 0 || Lk > XA_KEYS) return 1;
+  if (nimg <= 0 || img_per_ctx <= 0 || !nr_xattn_fused_supported(XA_C, XA_HEADS, Lk, hw)) return 1;
   if ((nimg + img_per_ctx - 1) / img_per_ctx > nctx) return 3;      // the kv stream holds nctx contexts: every image's context must be one of them
   NrXAttnParams p;
   p.t = t; p.hw = hw; p.nimg = nimg; p.img_per_ctx = img_per_ctx; p.Lk = Lk; p.norot = norot; p.wstream = wstream; p.kvstream = kvstream;

@@ -284,9 +284,10 @@ extern "C" size_t nr_xattnw_kvstream_bytes(int C, int nctx) { return (C == 640 |
 extern "C" size_t nr_xattnw_table_bytes(int C) { return (C == 640 || C == 1280) ? (size_t)2 * (C + 256) * sizeof(float) : 0; }
 
 // rows: the launch's row count (deterministic-batch mode: one clip's)
+extern "C" int nr_xattnw_supported(int C, int heads, int Lk, int hw) { return (C == 640 || C == 1280) && heads == XW_HEADS && Lk >= 1 && Lk <= XW_KT * 16 && hw > 0 && hw % XW_ROWS == 0; }
 extern "C" int nr_xattnw_eligible(int C, int heads, int Lk, int hw, long long rows) {
   static const bool off = !env_not_0("NR_XATTN_HEAD");   // A/B switch
-  return !off && (C == 640 || C == 1280) && heads == XW_HEADS && Lk >= 1 && Lk <= XW_KT * 16 && hw % XW_ROWS == 0 && rows >= 2048;
+  return !off && nr_xattnw_supported(C, heads, Lk, hw) && rows >= 2048;
 }
 
 extern "C" int nr_launch_xattnw_w_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s) {
@@ -313,8 +314,7 @@ extern "C" int nr_launch_xattnw_kv_pack(const bf16* kv, int ldkv, int Lk, int nc
 
 extern "C" int nr_launch_xattnw(const bf16* t, bf16* out, int nimg, int hw, int img_per_ctx, int nctx, int Lk, int C, const bf16* wstream, const bf16* kvstream,
                                 const float* table, float ln_eps, hipStream_t s) {
-  if (!nr_xattnw_wstream_bytes(C) || nimg <= 0 || hw <= 0 || hw % XW_ROWS != 0 || img_per_ctx <= 0 || Lk < 1 || Lk > XW_KT * 16) return 1;
-  if ((nimg + img_per_ctx - 1) / img_per_ctx > nctx) return 1;
+  if (!nr_xattnw_supported(C, XW_HEADS, Lk, hw) || nimg <= 0 || img_per_ctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx) return 1;
   NrXAttnWParams p;
   p.t = t; p.out = out; p.nrows = nimg * hw; p.hw = hw; p.img_per_ctx = img_per_ctx; p.Lk = Lk; p.stream = wstream; p.kvstream = kvstream; p.table = table;
   p.ln_eps = ln_eps;

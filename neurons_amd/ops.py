@@ -75,8 +75,21 @@ def g8p_phases(n):
 
 
 def ff_waves(n):
-    """8 (default) or 4 waves per workgroup of the fused FeedForward kernel (A/B; bit-identical results)."""
+    """8 (default) or 4 waves per workgroup of the fused FeedForward kernel (A/B; bit-identical results).  Read when a launch is described: the
+    op hook below does so per call, a planned handle at its next plan."""
     _lib.load().nr_ff_set_waves(int(n))
+
+
+def _ln_fold(w, gamma, beta, bias=None):
+    """LayerNorm(gamma, beta) folded into the Linear (w [N, K], bias) behind it, as engine_weights.hip's w_ln_linear does: W' = bf16(gamma * W),
+    c = row sums of W' (fp32), b' = W beta (+ bias) accumulated in fp64.  Returns (W', c, b')."""
+    wf = w.float()
+    ws = (wf * gamma.float()[None]).to(torch.bfloat16).contiguous()
+    c = ws.float().sum(dim=1).contiguous()
+    b = (wf.double() @ beta.double()).float()
+    if bias is not None:
+        b = b + bias.float()
+    return ws, c, b.contiguous()
 
 
 def ln_gemm(a, w, gamma, beta, bias=None, res=None, eps=1e-5, act=0, geglu=False):
@@ -88,13 +101,7 @@ def ln_gemm(a, w, gamma, beta, bias=None, res=None, eps=1e-5, act=0, geglu=False
     if geglu:
         w, bias = geglu_permute(w, bias)
     N = w.shape[0]
-    wf = w.float()
-    ws = (wf * gamma.float()[None]).to(torch.bfloat16).contiguous()
-    c = ws.float().sum(dim=1).contiguous()
-    b = (wf.double() @ beta.double()).float()
-    if bias is not None:
-        b = b + bias.float()
-    b = b.contiguous()
+    ws, c, b = _ln_fold(w, gamma, beta, bias)
     No = N // 2 if geglu else N
     out = torch.empty(M, No, dtype=torch.bfloat16, device=a.device)
     lib = _lib.load()
@@ -110,19 +117,10 @@ def gemm_ex(a, w, bias=None, ln=None, eps=1e-5, rowvec=None, rowvec_div=1, rowve
     _chk_f32(rowvec)
     M, K = a.shape
     N = w.shape[0]
-    wf = w.float()
-    ln_c = None
-    b = None if bias is None else bias.float().contiguous()
     if ln is not None:
-        gamma, beta = ln
-        ws = (wf * gamma.float()[None]).to(torch.bfloat16).contiguous()
-        ln_c = ws.float().sum(dim=1).contiguous()
-        b = (wf.double() @ beta.double()).float()
-        if bias is not None:
-            b = b + bias.float()
-        b = b.contiguous()
+        ws, ln_c, b = _ln_fold(w, ln[0], ln[1], bias)
     else:
-        ws = w.to(torch.bfloat16).contiguous()
+        ws, ln_c, b = w.to(torch.bfloat16).contiguous(), None, None if bias is None else bias.float().contiguous()
     out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
     lib = _lib.load()
     _lib.check(lib.nr_op_gemm_ex(_stream(), _ptr(a), K, _ptr(ws), _ptr(b), _ptr(ln_c), float(eps), _ptr(rowvec), int(rowvec_div),
@@ -363,9 +361,7 @@ def tattn_head(t, nbatch, hw, gamma, beta, wq, wk, wv, eps=1e-5, reuse_stream=Fa
         raise ValueError("tattn_head: frames must be 16 or 32")
     assert C in (640, 1280) and t.shape[0] == nbatch * F * hw
     w = torch.cat([x.float() for x in (wq, wk, wv)], 0)                                  # [3C][C]
-    wf = (w * gamma.float()[None, :]).to(torch.bfloat16).contiguous()
-    lnc = wf.float().sum(1).contiguous()
-    bias = (w.double() @ beta.double()).float().contiguous()
+    wf, lnc, bias = _ln_fold(w, gamma, beta)
     rv = (temporal_pe_table(F, C, t.device).double() @ w.double().t()).float().contiguous()   # [F][3C]
     a = torch.empty_like(t)
     _lib.check(_lib.load().nr_op_tattn_head_frames(_stream(), _ptr(t), _ptr(a), nbatch, F, hw, C, None if reuse_stream else _ptr(wf), _ptr(lnc),
@@ -396,10 +392,7 @@ def xattn_head(t, nimg, hw, img_per_ctx, gamma, beta, wq, kv, Lk, eps=1e-5, reus
     C = t.shape[1]
     assert C in (640, 1280) and t.shape[0] == nimg * hw and kv.shape[1] == 2 * C and kv.shape[0] % Lk == 0
     nctx = kv.shape[0] // Lk
-    w = wq.float()
-    wf = (w * gamma.float()[None, :]).to(torch.bfloat16).contiguous()
-    lnc = wf.float().sum(1).contiguous()
-    bias = (w.double() @ beta.double()).float().contiguous()
+    wf, lnc, bias = _ln_fold(wq, gamma, beta)
     a = torch.empty_like(t)
     _lib.check(_lib.load().nr_op_xattn_head(_stream(), _ptr(t), _ptr(a), nimg, hw, img_per_ctx, C, None if reuse_streams else _ptr(wf), _ptr(lnc), _ptr(bias),
                                             _ptr(kv), kv.shape[1], Lk, nctx, float(eps)))

@@ -9,6 +9,9 @@
 //                                                      kernel each hook launches, in the trace
 //          plan_dump --decide-once <schema-file>       the C = 1280 transformer leaf at 1024 rows planned under gemm8p mode 2 and replayed (graph off) before and after
 //                                                      nr_g8p_set_mode(1) + NR_IGEMM_FORCE: a plan launches what it was planned with (tests/test_gemm_route_host.py)
+//          plan_dump --ff-waves <schema-file>          the C = 320 temporal and transformer leaves at 4096 rows (ff_fused, tattn_fused / xattn_fused, GroupNorm, attention)
+//                                                      planned under 8 FeedForward waves and replayed (graph off) before and after nr_ff_set_waves(4), then planned
+//                                                      afresh under 4: the wave count is the plan's (tests/test_launch_routes_host.py)
 #include "../../include/neurons_amd.h"
 #include <cstdio>
 #include <cstdlib>
@@ -168,8 +171,40 @@ static int run_decide_once(const char* schema) {
   return 0;
 }
 
+// --ff-waves: see the usage text.  Prints the status of each replay
+static int run_ff_waves(const char* schema) {
+  const auto nets = read_schema(schema);
+  std::vector<float> io((size_t)8 << 20);
+  const struct { const char* net; Shape s; } leaves[] = {{"leaf_temporal", {1, 16, 16, 16, 0}}, {"leaf_transformer", {1, 4, 32, 32, 77}}};
+  for (const auto& lf : leaves) {
+    const Net* n = nullptr;
+    for (auto& nn : nets) if (nn.first == lf.net) n = &nn.second;
+    CHECK(n, "schema lacks a C = 320 leaf");
+    nr_net* h = nullptr;
+    OK(nr_net_create(&n->cfg, &h));
+    load_all(h, *n, 3);
+    OK(nr_net_set_graph(h, 0));
+    const auto replay = [&](const char* which) {
+      nr_stub_note((std::string("replay ") + which + " " + lf.net).c_str());
+      const nr_status st = nr_leaf_forward(h, nullptr, io.data(), lf.s.ctx ? io.data() + (2 << 20) : nullptr, lf.s.ctx, io.data() + (4 << 20));
+      printf("replay %s %s: status %d\n", which, lf.net, (int)st);
+    };
+    nr_ff_set_waves(8);
+    OK(nr_net_plan(h, lf.s.b, lf.s.f, lf.s.h, lf.s.w, lf.s.ctx));
+    replay("first");          // also runs the context ops, which later replays skip
+    replay("planned");
+    nr_ff_set_waves(4);
+    replay("switched");
+    OK(nr_net_plan(h, lf.s.b, lf.s.f, lf.s.h, lf.s.w, lf.s.ctx));      // the control: planned afresh under 4 waves
+    replay("control");
+    nr_net_destroy(h);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
-  if (argc < 2) { fprintf(stderr, "usage: plan_dump <schema-file> [name,name,...] | --ops <shapes-file> | --decide-once <schema-file>\n"); return 1; }
+  if (argc < 2) { fprintf(stderr, "usage: plan_dump <schema-file> [name,name,...] | --ops <shapes-file> | --decide-once <schema-file> | --ff-waves <schema-file>\n"); return 1; }
+  if (argc == 3 && std::string(argv[1]) == "--ff-waves") return run_ff_waves(argv[2]);
   if (argc == 3 && std::string(argv[1]) == "--ops") return run_ops(argv[2]);
   if (argc == 3 && std::string(argv[1]) == "--decide-once") return run_decide_once(argv[2]);
   const std::string only = argc > 2 ? std::string(",") + argv[2] + "," : std::string();

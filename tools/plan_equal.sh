@@ -10,7 +10,9 @@
 # workspace and weight bytes, export manifest) and the stub's trace (every kernel launch with grid / block / LDS bytes, every device allocation,
 # size and hash of every uploaded weight).  Runs: every network at its listed shapes, then the C = 320 leaf modules once per planner switch that a
 # process reads once (NR_LN_FUSE=0, NR_FOLD_PROJ_OUT=0, NR_SMALLM=0), then the networks with GEMM-heavy plans once per switch of the GEMM route (NR_G8P=0 / 2,
-# NR_ROWPANEL=0, NR_LIN160=0, one NR_IGEMM_FORCE setting).  One line per run: "identical", or "DIFFERS" and the first differing lines.
+# NR_ROWPANEL=0, NR_LIN160=0, one NR_IGEMM_FORCE setting), then once per switch of the GroupNorm and attention routes (NR_GN_SLAB=0, NR_GN_SMALL=0,
+# NR_GN_T=1024, NR_ATTN_ROWSUM=adds), of the fused FeedForward (NR_FF_WAVES=4, NR_FF_FUSED=0) and of the fused attention blocks (NR_TATTN_FUSED=0,
+# NR_XATTN_FUSED=0, NR_TATTN_HEAD=0, NR_XATTN_HEAD=0) on the networks whose plans contain those kernels.  One line per run: "identical", or "DIFFERS" and the first differing lines.
 # The dump must also contain every kernel class the planner can choose (a shape list that loses one is no evidence).  Exit status 1 on any of it.
 # The only normalisation: pointer values (0x...) become a fixed token.  Needs no GPU.  JOBS=<n> compiles in parallel (default 8, at most 16).
 set -euo pipefail
@@ -56,10 +58,24 @@ run_both g8p_2 $gemm_nets NR_G8P=2
 run_both rowpanel_0 $gemm_nets NR_ROWPANEL=0
 run_both lin160_0 $gemm_nets NR_LIN160=0
 run_both igemm_force $gemm_nets NR_IGEMM_FORCE=128,64,2,3,1
+# the switches nr_gn_route and nr_attn_route read, the FeedForward wave count and the A/B switches of the five fused transformer kernels
+gn_nets=tiny_unet,leaf_transformer,leaf_temporal,tiny_sgm,tiny_vae_dec,tiny_vae_enc
+leaves320=leaf_transformer,leaf_temporal
+run_both gn_slab_0 $gn_nets NR_GN_SLAB=0
+run_both gn_small_0 $gn_nets NR_GN_SMALL=0
+run_both gn_t_1024 $gn_nets NR_GN_T=1024
+run_both attn_rowsum_adds tiny_unet,leaf_transformer NR_ATTN_ROWSUM=adds
+run_both ff_waves_4 $leaves320 NR_FF_WAVES=4
+run_both ff_fused_0 $leaves320 NR_FF_FUSED=0
+run_both tattn_fused_0 leaf_temporal NR_TATTN_FUSED=0
+run_both xattn_fused_0 leaf_transformer NR_XATTN_FUSED=0
+run_both tattn_head_0 leaf_temporal640,leaf_temporal1280 NR_TATTN_HEAD=0
+run_both xattn_head_0 leaf_transformer640,leaf_transformer1280 NR_XATTN_HEAD=0
 
 echo "# plans of the working tree against $rev ($(git -C "$root" rev-parse --short "$rev"))"
 status=0
-for label in default ln_fuse_0 fold_proj_out_0 smallm_0 g8p_0 g8p_2 rowpanel_0 lin160_0 igemm_force; do
+for label in default ln_fuse_0 fold_proj_out_0 smallm_0 g8p_0 g8p_2 rowpanel_0 lin160_0 igemm_force gn_slab_0 gn_small_0 gn_t_1024 attn_rowsum_adds \
+             ff_waves_4 ff_fused_0 tattn_fused_0 xattn_fused_0 tattn_head_0 xattn_head_0; do
   for what in dump trace; do
     a="$tmp/old.$label.$what"; b="$tmp/new.$label.$what"
     if cmp -s "$a" "$b"; then
@@ -76,8 +92,9 @@ for k in ff_fused xattn_fused xattn_head tattn_fused tattn_head 'lin160 ' 'lin16
   echo "coverage '$k': $n ops in $rev's dump"
   [ "$n" -gt 0 ] || status=1
 done
-# ... and its default trace launches every GEMM kernel class the route can choose
-for k in smallm_kernel lin160_kernel lin128q_kernel rowpanel_kernel g8p_kernel igemm_bf16_kernel splitk_reduce_kernel; do
+# ... and its default trace launches every kernel class the GEMM, GroupNorm and attention routes can choose
+for k in smallm_kernel lin160_kernel lin128q_kernel rowpanel_kernel g8p_kernel igemm_bf16_kernel splitk_reduce_kernel \
+         gn_slab_kernel gn_fused_small_kernel gn_stats_kernel gn_finalize_kernel attn_fwd_kernel attn_fwd_shared_kernel; do
   n=$(grep -c -E "^L [^ ]*$k" "$tmp/old.default.trace" || true)
   echo "coverage '$k': $n launches in $rev's trace"
   [ "$n" -gt 0 ] || status=1
