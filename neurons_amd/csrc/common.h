@@ -184,6 +184,20 @@ struct NrGnParams {
   bf16* out; int ldo;               // [nimg*hw][ldo]
 };
 
+// The five fused transformer kernels: what the engine and the nr_op_* hooks describe and the launchers of launchers.h take.  Host structs only: each launcher
+// checks its X_supported rule and fills the kernel's own argument block from them.  stream / wstream / kvstream / table: as the kernel's pack launchers wrote
+// them; norot: 1 = every workgroup walks the weight stream from its start (deterministic batching); waves: per workgroup, 8 or 4 (nr_ff_waves at description time)
+struct NrFfFusedParams {      // out[M][ldo] = x + bc + [t | GEGLU(net.0(LN(t)))] Wc^T, C = 320
+  const bf16* t; int ldt; const bf16* x; int ldx; bf16* out; int ldo; int M; const bf16* stream; const float *gamma, *beta, *b1, *bc; float ln_eps; int norot, waves; };
+struct NrXattnFusedParams {   // t[nimg * hw][320] in place; image i attends to context i / img_per_ctx of the nctx in kvstream
+  bf16* t; int nimg, hw, img_per_ctx, nctx, Lk; const bf16* wstream; const bf16* kvstream; const float *gamma, *beta, *bo; float ln_eps; int norot; };
+struct NrTattnFusedParams {   // t[nbatch * frames * hw][320] in place; gb[frames][320] = LayerNorm bias + positional encoding
+  bf16* t; int nbatch, frames, hw; const bf16* stream; const float *gamma, *gb, *bo; float ln_eps; int norot; };
+struct NrXattnHeadParams {    // out[nimg * hw][C] = attention output before to_out, C = 640 / 1280
+  const bf16* t; bf16* out; int nimg, hw, img_per_ctx, nctx, Lk, C; const bf16* wstream; const bf16* kvstream; const float* table; float ln_eps; };
+struct NrTattnHeadParams {    // out[nbatch * frames * hw][C] likewise; table packed for the same frame count
+  const bf16* t; bf16* out; int nbatch, frames, hw, C; const bf16* stream; const float* table; float ln_eps; };
+
 // in-place residual adds dst[i] += src[i] of up to 16 tensors in ONE launch (the ControlNet residuals, unet.py:422-439)
 struct NrAddMulti {
   bf16* dst[16];

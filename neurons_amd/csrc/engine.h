@@ -1,12 +1,12 @@
 // Internal header of the denoiser-network engine behind the C ABI of include/neurons_amd.h: what its translation units share.
 //   engine.h            error type and macros, Arena / Act / IO, the WeightStore, the declaration of nr_net
-//   engine_weights.hip  the weight store: state dict as loaded, converted device weights, every weight converter
-//   engine_layers.hip   the plan emitters (conv, groupnorm, layernorm, attention) and the module builders up to temporal_module
+//   engine_weights.hip  the weight store: state dict as loaded, converted device weights, every weight converter, what each fused transformer kernel reads (X_weights)
+//   engine_layers.hip   the plan emitters (conv, groupnorm, layernorm, attention, one X_block per fused transformer kernel) and the module builders up to temporal_module
 //   engine_nets.hip     the network builders (U-Net / SparseCtrl, sgm U-Net, VAE decoder / encoder, CLIP, leaf modules) and plan()
 //   engine_ops.hip      the single-op test hooks (nr_op_*)
 //   engine.hip          graph-replay runtime, the C ABI, the engine's two small kernels
-// A plan idiom that is needed twice lives in ONE helper here (WeightStore::packed_from / convert / stacked / w_temb_projection, nr_net::begin_plan /
-// stage_context / context_kv / splitk_scratch); a host-side change of these files is accepted on tools/plan_equal.sh.
+// A plan idiom that is needed twice lives in ONE helper here (WeightStore::packed / convert / stacked / w_temb_projection, nr_net::begin_plan / stage_context /
+// context_kv / linear_wb / splitk_scratch, descf); a derived weight name is spelled in engine_weights.hip only; a host-side change of these files is accepted on tools/plan_equal.sh.
 #pragma once
 #include "launchers.h"
 #include "../../include/neurons_amd.h"
@@ -70,6 +70,8 @@ inline uint16_t f2bf_host(float f) {
   return (uint16_t)(u >> 16);
 }
 
+template <class... A>      // an op description: printf into a string (160 characters at the most)
+std::string descf(const char* fmt, A... a) { char d[160]; snprintf(d, sizeof(d), fmt, a...); return d; }
 // environment switches: "=1 turns it on" and "on unless =0"
 inline bool env_is_1(const char* name) {
   const char* v = getenv(name);
@@ -193,29 +195,22 @@ struct WeightStore {
     if (it != dev.end()) return it->second.ptr;
     return make();
   }
-  // a buffer a pack kernel fills on the device: fn(d) enqueues the kernel(s) on the null stream, which have run when this returns
+  // A buffer a pack kernel fills on the device: fn(d) enqueues the kernel(s) on the null stream, which have run when this returns.  inputs: converted
+  // matrices that are ONLY this pack's inputs (a fused kernel's weight stream: its launch never reads them), converted by fn.  Once the buffer exists, the
+  // inputs this call had to make are erased again: they neither stay resident nor travel in the exported arena.  An input another plan had already made stays.
   template <class Fn>
-  void* packed(const std::string& name, size_t bytes, Fn fn) {
+  void* packed(const std::string& name, size_t bytes, Fn fn, const std::vector<std::string>& inputs = {}) {
     return cached(name, [&]() {
+      std::vector<char> had;
+      for (auto& in : inputs) had.push_back(dev.count(in) != 0);
       void* d = nullptr;
       HIP_OK(hipMalloc(&d, bytes));
       try { fn(d); HIP_OK(hipDeviceSynchronize()); }
       catch (...) { (void)hipFree(d); throw; }
-      return adopt(name, d, bytes);
+      adopt(name, d, bytes);
+      for (size_t i = 0; i < inputs.size(); ++i) if (!had[i]) erase(inputs[i]);
+      return d;
     });
-  }
-  // A kernel's weight stream, packed from converted matrices that are ONLY its inputs (the fused launch never reads them): fn(d) converts them and
-  // enqueues the pack.  Once the stream exists, the inputs this call had to make are erased again: they neither stay resident nor travel in the
-  // exported arena.  An input another plan had already made stays.  *made: this call packed the stream (it was neither cached nor the sizing pass).
-  template <class Fn>
-  void* packed_from(const std::string& name, size_t bytes, const std::vector<std::string>& inputs, Fn fn, bool* made = nullptr) {
-    std::vector<char> had;
-    for (auto& in : inputs) had.push_back(dev.count(in) != 0);
-    bool did = false;
-    void* d = packed(name, bytes, [&](void* p) { fn(p); did = true; });
-    for (size_t i = 0; did && i < inputs.size(); ++i) if (!had[i]) erase(inputs[i]);
-    if (made) *made = did;
-    return d;
   }
   // The skeleton of a one-tensor converter: shape check, then (unless cached or sizing) fill(source fp32 data, `count` zeroed elements of T) and
   // upload as "<tag><key>"
@@ -247,11 +242,10 @@ struct WeightStore {
   struct Stacked { const bf16* w; const float* b; };
   Stacked w_temb_projection(const std::string& tag, const std::vector<TembSlot>& slots, const std::string& layer, int K);   // "tembw:<tag>" "tembb:<tag>"
   struct LnW { const bf16* w; const float* c; const float* b; };
-  LnW w_ln_linear(const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys, const std::string& ln, int Neach, int K, bool geglu,
-                  bool need_w = true);                                                              // "lnw:" "lnc:" "lnb:"
+  LnW w_ln_linear(const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys, const std::string& ln, int Neach, int K, bool geglu);   // "lnw:" "lnc:" "lnb:"
   const float* pe_projection(const std::vector<std::string>& wkeys, int Neach, int K, int max_len); // "perv:"
   struct FoldW { const bf16* w; const float* b; };
-  FoldW w_fold_ff_proj(const std::string& ff2, const std::string& po, int C, bool need_w = true);   // "foldw:" "foldb:"
+  FoldW w_fold_ff_proj(const std::string& ff2, const std::string& po, int C);                       // "foldw:" "foldb:"
   const bf16* w_geglu(const std::string& key, int inner, int K);                                    // "geglu:"
   const float* b_geglu(const std::string& key, int inner);                                          // "geglub:"
   const bf16* w_conv3(const std::string& key, int Cout, int Cin, bool tap_inner = false);           // "conv3:" / "conv3t:"
@@ -263,6 +257,20 @@ struct WeightStore {
   const float* pe_table(int C, int max_len);                                                        // "pe:"
   const float* b_ln_pe(const std::string& ln, int F, int C);                                        // "tagb:"
   const bf16* w_layout(const bf16* w, int N, int K, int layout);                                    // "fm:" / "w8:" / "l160:" / "l128:<name of w>" (NrWeightLayout)
+
+  // ---- what each fused transformer kernel reads (engine_weights.hip): its packed weight stream [+ epilogue table] and its fp32 vectors.  The shape checks, the
+  // stream's derived name, the pack and the converted matrices that only fed it (dropped again: the inputs of packed) live there, beside the converters they name ----
+  struct FfFusedW { const bf16* stream; const float *gamma, *beta, *b1, *bc; };
+  FfFusedW ff_fused_weights(const std::string& ln, const std::string& ff, const std::string& po, int C);                // "ffs:"   ln: LayerNorm, ff: FeedForward, po: proj_out
+  struct XattnFusedW { const bf16* wstream; const float *gamma, *beta, *bo; };
+  XattnFusedW xattn_fused_weights(const std::string& b, int C);                                                         // "xas:"   b: the transformer block
+  struct TattnFusedW { const bf16* stream; const float *gb, *gamma, *bo; };
+  TattnFusedW tattn_fused_weights(const std::string& ln, const std::string& ab, int F, int C);                          // "tas:"   ab: the attention block
+  struct HeadW { const bf16* stream; const float* table; };
+  HeadW xattn_head_weights(const std::string& ln, const std::string& wq, int C);                                        // "xaws:" "xawt:"
+  HeadW tattn_head_weights(const std::string& ln, const std::vector<std::string>& wqkv, int C, int F, int max_len);     // "taws:" "tawe:<max_len>:<F>:"
+  LnW ln_vectors(const std::vector<std::string>& wkeys, const std::string& ln, int Neach, int K);      // c / b' of a LayerNorm fold whose matrix may be gone (it fed a stream)
+  const float* fold_bias(const std::string& ff2, const std::string& po, int C);                       // bc of a FeedForward fold, likewise
 };
 
 }  // namespace nre
@@ -272,8 +280,6 @@ struct nr_net {
   using Buf = nre::Buf;
   using Act = nre::Act;
   using IO = nre::IO;
-  using LnW = nre::WeightStore::LnW;
-  using FoldW = nre::WeightStore::FoldW;
   static constexpr int NR_MAX_BATCH = nre::NR_MAX_BATCH;
 
   nr_net_config cfg;
@@ -382,9 +388,9 @@ struct nr_net {
   void begin_plan();
   Act stage_context();           // the text context fp32 -> bf16 [B2 * ctx_len][cross_dim], as a context op
   // K | V of the text context for the cross-attention of transformer block b: a persistent [.., 2C] activation written by a context op (run again
-  // only when the context changes).  pack: a further context op that re-arranges K | V for a fused kernel (allocates and returns its persistent
-  // stream); the stream is returned instead
-  Act context_kv(const Act& ctx_bf, const std::string& b, int C, const std::function<Act(const Act& kv)>& pack = nullptr);
+  // only when the context changes).  pack(kv, ldkv, stream, s): a further context op that re-arranges K | V for a fused kernel into a persistent stream
+  // of stream_bytes; the stream is returned instead
+  Act context_kv(const Act& ctx_bf, const std::string& b, int C, size_t stream_bytes = 0, const std::function<void(const bf16*, int, bf16*, hipStream_t)>& pack = nullptr);
 
   // ------------------------------------------------------------------ emitters and module builders (engine_layers.hip)
   struct GemmOpt {
@@ -402,6 +408,7 @@ struct nr_net {
   };
   Act conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksize, int stride, int ups, const GemmOpt& o);
   Act linear(const Act& x, const bf16* w, int N, const GemmOpt& o) { return conv(x, nullptr, w, N, 1, 1, 0, o); }
+  Act linear_wb(const Act& x, const std::string& key, int N, const Act* res = nullptr, Act* out = nullptr);      // linear() with <key>.weight / <key>.bias
   void gemm_raw(const bf16* a, int lda, const bf16* w, int M, int N, int K, const float* bias, bf16* out, int ldo, float* out32, const char* what);
   Act groupnorm(const Act& x0, const Act* x1, const std::string& prefix, float eps, int silu);
   Act layernorm(const Act& x, const std::string& prefix, const float* pe, int pe_F);
@@ -416,13 +423,17 @@ struct nr_net {
   Act ln_linear(const Act& x, const std::string& ln, const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys, int Neach, bool geglu,
                 int act, bool temporal_pe);
   void feed_forward(Act& t, const std::string& ln, const std::string& pre);
-  bool fold_proj_out(int C) const;
   Act feed_forward_proj_out(const Act& x, Act& t, const std::string& ln, const std::string& ff, const std::string& pre);
   bool cfg_dedup_active() const;
   Act expand_cfg(const Act& h);
   enum BlockKernel { BLOCK_UNFUSED, BLOCK_FUSED320, BLOCK_HEAD };      // a cross- / temporal-attention block on t: GEMMs + attention, the fused C = 320 kernel, the head kernel above it
   BlockKernel cross_attn_kernel(const Act& t, int heads, int hw) const;
   BlockKernel temporal_attn_kernel(const Act& t, int heads, int hw) const;
+  Act ff_fused_block(const Act& x, const Act& t, const std::string& ln, const std::string& ff, const std::string& po);      // -> out
+  void xattn_fused_block(Act& t, const Act& ctx_bf, const std::string& b, int hw);                                            // t in place
+  Act xattn_head_block(const Act& t, const Act& ctx_bf, const std::string& b, int hw);                                        // -> a, before to_out
+  void tattn_fused_block(Act& t, const std::string& nrm, const std::string& ab, int hw, int heads);                          // t in place
+  Act tattn_head_block(const Act& t, const std::string& nrm, const std::vector<std::string>& wqkv, int hw, int heads);       // -> a, before to_out
   Act spatial_transformer(const Act& x_in, const Act& ctx_bf, const std::string& pre, int depth = 1, bool cfg_half = false, Act* x_full = nullptr);
   Act temporal_module(const Act& x, const std::string& pre0);
   Act vae_attn(const Act& x, const std::string& pre);

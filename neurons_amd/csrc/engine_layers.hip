@@ -1,5 +1,5 @@
-// Plan emitters of the engine (engine.h): the arena and plan helpers, one emitter per kernel class (conv / linear, GroupNorm, LayerNorm, attention)
-// and the builders of the reference modules on top of them, through temporal_module.  The plan follows the reference module graph:
+// Plan emitters of the engine (engine.h): the arena and plan helpers, one emitter per kernel class (conv / linear, GroupNorm, LayerNorm, attention, each
+// fused transformer kernel) and the builders of the reference modules on top of them, through temporal_module.  The plan follows the reference module graph:
 //   ResnetBlock3D                       animatediff/models/resnet.py:182-212
 //   Transformer3DModel / BasicTransformerBlock   animatediff/models/attention.py:95-142,256-300
 //   TemporalTransformer3DModel / Block / VersatileAttention   animatediff/models/motion_module.py:134-158,210-222,270-329
@@ -88,13 +88,17 @@ Act nr_net::stage_context() {
   ctx_persist.push_back(ctx_bf);
   return ctx_bf;
 }
-Act nr_net::context_kv(const Act& ctx_bf, const std::string& b, int C, const std::function<Act(const Act& kv)>& pack) {
+Act nr_net::context_kv(const Act& ctx_bf, const std::string& b, int C, size_t stream_bytes, const std::function<void(const bf16*, int, bf16*, hipStream_t)>& pack) {
   building_ctx = true;
   Act kv = new_act_persistent(ctx_bf.nimg, ctx_bf.H, ctx_bf.W, 2 * C);
   GemmOpt ok; ok.out = &kv;
   linear(ctx_bf, wts.w_linear_cat({b + ".attn2.to_k.weight", b + ".attn2.to_v.weight"}, C, cfg.cross_attention_dim), 2 * C, ok);
   Act stream;
-  if (pack) stream = pack(kv);
+  if (pack) {
+    stream = new_act_persistent(1, 1, 1, (int)(stream_bytes / sizeof(bf16)));
+    const bf16* kvp = kv.ptr; bf16* sp = stream.ptr; const int ldkv = kv.ld;
+    emit([=](hipStream_t s) { pack(kvp, ldkv, sp, s); });
+  }
   building_ctx = false;
   ctx_persist.push_back(kv);
   if (pack) ctx_persist.push_back(stream);
@@ -125,16 +129,21 @@ Act nr_net::conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksiz
   const double in_elems = (double)x0.rows() * (p.c0 + p.c1);   // every input element is needed at least once
   const double bytes = 2.0 * (in_elems + (double)p.N * p.K + (double)p.M * outC + (o.res ? (double)p.M * outC : 0.0));
   const bool l160 = r.cls == NR_GEMM_LIN160;
-  char d[160];
-  if (l160) snprintf(d, sizeof(d), "%s M=%d N=%d K=%d res=%d geglu=%d ln=%d", r.lin160.form == 4 ? "lin160 panel" : "lin160", p.M, p.N, p.K, o.res ? 1 : 0, p.geglu, p.ln_c ? 1 : 0);
-  else snprintf(d, sizeof(d), "igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d%s", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0,
-                r.weight_layout == NR_W_FRAGMAJOR_E4M3 ? " w=e4m3" : "");
+  const std::string d = l160 ? descf("%s M=%d N=%d K=%d res=%d geglu=%d ln=%d", r.lin160.form == 4 ? "lin160 panel" : "lin160", p.M, p.N, p.K, o.res ? 1 : 0, p.geglu, p.ln_c ? 1 : 0)
+                             : descf("igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d%s", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0,
+                                     r.weight_layout == NR_W_FRAGMAJOR_E4M3 ? " w=e4m3" : "");
   const SplitK sk = splitk_scratch(r.ws_bytes);
   float* ws = sk.ws;
   emit([p, r, wk, ws](hipStream_t s) { LAUNCH_OK(nr_launch_gemm(&p, &r, wk, ws, s)); }, NR_PROF_IGEMM, 2.0 * p.M * (double)p.N * p.K, bytes, d);
   if (ws) last_op_launches(2);           // split-K: the igemm + its reduce kernel
   op_tap(l160 ? "lin160" : (ksize == 3 ? "conv3" : (p.ln_c ? "lngemm" : "gemm")), out);
   return out;
+}
+
+// nn.Linear / 1x1 conv `key` (<key>.weight [N][x.C], <key>.bias) on x, + res, into *out
+Act nr_net::linear_wb(const Act& x, const std::string& key, int N, const Act* res, Act* out) {
+  GemmOpt o; o.bias = wts.w_f32(key + ".bias", N); o.res = res; o.out = out;
+  return linear(x, wts.w_linear(key + ".weight", N, x.C), N, o);
 }
 
 // plain GEMM on raw pointers (the VAE's attention): out = A[M][K] . W[N][K]^T (+bias) -> bf16 [M][ldo], or raw fp32 [M][N] when out32
@@ -147,10 +156,8 @@ void nr_net::gemm_raw(const bf16* a, int lda, const bf16* w, int M, int N, int K
   LAUNCH_OK(nr_gemm_route_rowmajor(&p, &r));
   const SplitK sk = splitk_scratch(r.ws_bytes);
   float* ws = sk.ws;
-  char d[160];
-  snprintf(d, sizeof(d), "igemm %s M=%d N=%d K=%d", what, M, N, K);
   emit([p, r, ws](hipStream_t s) { LAUNCH_OK(nr_launch_gemm(&p, &r, p.w, ws, s)); }, NR_PROF_IGEMM, 2.0 * M * (double)N * K,
-       2.0 * ((double)M * K + (double)N * K) + (out32 ? 4.0 : 2.0) * (double)M * N, d);
+       2.0 * ((double)M * K + (double)N * K) + (out32 ? 4.0 : 2.0) * (double)M * N, descf("igemm %s M=%d N=%d K=%d", what, M, N, K));
 }
 
 Act nr_net::groupnorm(const Act& x0, const Act* x1, const std::string& prefix, float eps, int silu) {
@@ -205,9 +212,8 @@ Act nr_net::attention(int mode, const Act& q, const Act* kv, int C, int heads, i
   const double flops = 4.0 * (double)p.nbatch * p.heads * (double)p.Lq * p.Lk * p.d;
   const double kvrows = mode == 1 ? (double)(p.nbatch / p.kv_div) * p.Lk : (double)p.nbatch * p.Lk;
   const double bytes = 2.0 * ((double)p.nbatch * p.Lq * C * 2.0 + kvrows * C * 2.0);   // q + out + k + v
-  char d[160];
-  snprintf(d, sizeof(d), "attention mode=%d nbatch=%d heads=%d d=%d Lq=%d Lk=%d", mode, p.nbatch, p.heads, p.d, p.Lq, p.Lk);
-  emit([p, r](hipStream_t s) { LAUNCH_OK(nr_launch_attention(&p, &r, s)); }, NR_PROF_ATTENTION, flops, bytes, d);
+  emit([p, r](hipStream_t s) { LAUNCH_OK(nr_launch_attention(&p, &r, s)); }, NR_PROF_ATTENTION, flops, bytes,
+       descf("attention mode=%d nbatch=%d heads=%d d=%d Lq=%d Lk=%d", mode, p.nbatch, p.heads, p.d, p.Lq, p.Lk));
   op_tap(mode == 2 ? "tattn" : (mode == 1 ? "xattn" : "sattn"), out);
   return out;
 }
@@ -296,7 +302,7 @@ Act nr_net::ln_linear(const Act& x, const std::string& ln, const std::vector<std
   GemmOpt o;
   o.geglu = geglu ? 1 : 0; o.act = act;
   if (fuse) {
-    const LnW lw = wts.w_ln_linear(wkeys, bkeys, ln, Neach, K, geglu);
+    const auto lw = wts.w_ln_linear(wkeys, bkeys, ln, Neach, K, geglu);
     o.bias = lw.b; o.ln_c = lw.c;
     if (temporal_pe) {
       o.rowvec = wts.pe_projection(wkeys, Neach, K, cfg.motion_pe_max_len);
@@ -323,56 +329,22 @@ Act nr_net::ln_linear(const Act& x, const std::string& ln, const std::vector<std
 void nr_net::feed_forward(Act& t, const std::string& ln, const std::string& pre) {
   const int C = t.C, inner = 4 * C;
   Act hmid = ln_linear(t, ln, {pre + ".net.0.proj.weight"}, {pre + ".net.0.proj.bias"}, inner, true, 0, false);
-  GemmOpt o2; o2.bias = wts.w_f32(pre + ".net.2.bias", C); o2.res = &t; o2.out = &t;
-  linear(hmid, wts.w_linear(pre + ".net.2.weight", C, inner), C, o2);
+  linear_wb(hmid, pre + ".net.2", C, &t, &t);
 }
 
 // The block's LAST FeedForward and the transformer's proj_out as one GEMM (w_fold_ff_proj): x + proj_out(t + FF(t)) =
 // x + bc + [t | g] Wc^T with g = GEGLU(net.0(LN(t))).  Removes a launch and the write + read of the post-FF residual stream.
 // Needs C % 64 == 0 (the operand switch falls on a k-tile boundary); NR_FOLD_PROJ_OUT=0 keeps the two GEMMs.
-bool nr_net::fold_proj_out(int C) const {
-  static const bool on = env_not_0("NR_FOLD_PROJ_OUT");
-  return on && C % 64 == 0;
-}
 Act nr_net::feed_forward_proj_out(const Act& x, Act& t, const std::string& ln, const std::string& ff, const std::string& pre) {
+  static const bool fold = env_not_0("NR_FOLD_PROJ_OUT");
   const int C = t.C, inner = 4 * C;
-  if (!fold_proj_out(C)) {
+  if (!fold || C % 64 != 0) {
     feed_forward(t, ln, ff);
-    GemmOpt op; op.bias = wts.w_f32(pre + ".proj_out.bias", C); op.res = &x;
-    return linear(t, wts.w_linear(pre + ".proj_out.weight", C, C), C, op);
+    return linear_wb(t, pre + ".proj_out", C, &x);
   }
-  if (nr_ff_fused_eligible(C, det_rows(t.rows())) && t.ld == C && x.ld == C) {
-    // C = 320, >= 4096 rows: LayerNorm + GEGLU projection + the folded GEMM in ONE launch (ffpanel.hip); the 4C-wide hidden activation
-    // stays in registers; LayerNorm is applied to the register panel.  The weights travel as one pre-arranged stage stream.
-    wts.check_shape(ff + ".net.0.proj.weight", wts.need(ff + ".net.0.proj.weight"), {2 * inner, C});
-    const float* b1 = wts.b_geglu(ff + ".net.0.proj.bias", inner);
-    const float* gamma = wts.w_f32(ln + ".weight", C);
-    const float* beta = wts.w_f32(ln + ".bias", C);
-    const std::string sname = "ffs:" + ff + ".net.0.proj.weight|" + ff + ".net.2.weight|" + ff + ".net.2.bias|" + pre + ".proj_out.weight|" + pre +
-                              ".proj_out.bias";
-    // packed from the GEGLU matrix and the folded matrix; the folded matrix goes again in any case, the folded bias stays
-    bool made = false;
-    const bf16* stream = (const bf16*)wts.packed_from(sname, nr_ff_stream_bytes(C), {"geglu:" + ff + ".net.0.proj.weight"}, [&](void* d) {
-      const bf16* w1 = wts.w_geglu(ff + ".net.0.proj.weight", inner, C);
-      const FoldW fwm = wts.w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C, true);
-      LAUNCH_OK(nr_launch_ff_stream_pack(w1, fwm.w, (bf16*)d, nullptr));
-    }, &made);
-    if (made) wts.erase("foldw:" + pre + ".proj_out.weight|" + pre + ".proj_out.bias|" + ff + ".net.2.weight|" + ff + ".net.2.bias");
-    const FoldW fw = wts.w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C, false);
-    Act out = new_act(x.nimg, x.H, x.W, C);
-    const bf16* tp = t.ptr; const bf16* xp = x.ptr; bf16* op = out.ptr;
-    const int M = (int)t.rows();
-    const float* bc = fw.b;
-    char d[160];
-    snprintf(d, sizeof(d), "ff_fused M=%d C=%d (LN + GEGLU 8C + folded net.2|proj_out 5C)", M, C);
-    const int norot = det_batch ? 1 : 0, waves = nr_ff_waves();
-    emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_ff_fused(tp, C, xp, C, op, C, M, stream, gamma, beta, b1, bc, 1e-5f, norot, waves, s)); }, NR_PROF_IGEMM,
-         2.0 * M * (double)C * (8.0 * C + 5.0 * C), 2.0 * (3.0 * M * (double)C + 13.0 * C * (double)C), d);
-    op_tap("ff_fused", out);
-    return out;
-  }
+  if (nr_ff_fused_eligible(C, det_rows(t.rows())) && t.ld == C && x.ld == C) return ff_fused_block(x, t, ln, ff, pre + ".proj_out");
   Act g = ln_linear(t, ln, {ff + ".net.0.proj.weight"}, {ff + ".net.0.proj.bias"}, inner, true, 0, false);
-  const FoldW fw = wts.w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C);
+  const auto fw = wts.w_fold_ff_proj(ff + ".net.2", pre + ".proj_out", C);
   GemmOpt op; op.bias = fw.b; op.res = &x; op.derived_w = true;
   return conv(t, &g, fw.w, C, 1, 1, 0, op);
 }
@@ -410,6 +382,74 @@ nr_net::BlockKernel nr_net::temporal_attn_kernel(const Act& t, int heads, int hw
   return nr_tattnw_eligible(t.C, heads, F, hw, det_rows(t.rows())) ? BLOCK_HEAD : BLOCK_UNFUSED;
 }
 
+// ---- the five fused transformer kernels: each emitter fetches the kernel's weights (WeightStore::X_weights), fills its launch description and emits ONE op ----
+// C = 320, >= 4096 rows: LayerNorm + GEGLU projection + the folded net.2 | proj_out GEMM in ONE launch (ffpanel.hip); the 4C-wide hidden activation
+// stays in registers; LayerNorm is applied to the register panel.  The weights travel as one pre-arranged stage stream.
+Act nr_net::ff_fused_block(const Act& x, const Act& t, const std::string& ln, const std::string& ff, const std::string& po) {
+  const int C = t.C, M = (int)t.rows();
+  const auto w = wts.ff_fused_weights(ln, ff, po, C);
+  Act out = new_act(x.nimg, x.H, x.W, C);
+  const NrFfFusedParams p{.t = t.ptr, .ldt = C, .x = x.ptr, .ldx = C, .out = out.ptr, .ldo = C, .M = M, .stream = w.stream, .gamma = w.gamma, .beta = w.beta, .b1 = w.b1,
+                          .bc = w.bc, .ln_eps = 1e-5f, .norot = det_batch ? 1 : 0, .waves = nr_ff_waves()};
+  emit([p](hipStream_t s) { LAUNCH_OK(nr_launch_ff_fused(&p, s)); }, NR_PROF_IGEMM, 2.0 * M * (double)C * (8.0 * C + 5.0 * C),
+       2.0 * (3.0 * M * (double)C + 13.0 * C * (double)C), descf("ff_fused M=%d C=%d (LN + GEGLU 8C + folded net.2|proj_out 5C)", M, C));
+  op_tap("ff_fused", out);
+  return out;
+}
+// C = 320, 8 heads, <= 80 context tokens, >= 4096 rows: the whole cross-attention block (LayerNorm, q projection, attention on the cached
+// K | V of the clip, to_out + residual) in ONE launch that updates t in place (xattn.hip); q and the attention output never reach HBM
+void nr_net::xattn_fused_block(Act& t, const Act& ctx_bf, const std::string& b, int hw) {
+  const int C = t.C, nctx = (int)(ctx_bf.rows() / ctx_len), Lk = ctx_len;      // ctx_bf is ONE "image" of B2 * ctx_len token rows
+  const double M = (double)t.rows();
+  const Act kvs = context_kv(ctx_bf, b, C, nr_xattn_kvstream_bytes(nctx),      // + the per-head LDS images of K | V
+                             [=](const bf16* kv, int ldkv, bf16* st, hipStream_t s) { LAUNCH_OK(nr_launch_xattn_kv_pack(kv, ldkv, Lk, nctx, st, s)); });
+  const auto w = wts.xattn_fused_weights(b, C);
+  const NrXattnFusedParams p{.t = t.ptr, .nimg = t.nimg, .hw = hw, .img_per_ctx = F, .nctx = nctx, .Lk = Lk, .wstream = w.wstream, .kvstream = kvs.ptr, .gamma = w.gamma,
+                             .beta = w.beta, .bo = w.bo, .ln_eps = 1e-5f, .norot = det_batch ? 1 : 0};
+  emit([p](hipStream_t s) { LAUNCH_OK(nr_launch_xattn_fused(&p, s)); }, NR_PROF_IGEMM, 2.0 * M * C * 2.0 * C + 4.0 * M * (double)Lk * C,
+       2.0 * (2.0 * M * C + 2.0 * C * (double)C), descf("xattn_fused M=%d C=%d Lk=%d (LN, q, context attention, to_out + residual)", (int)t.rows(), C, Lk));
+  op_tap("xattn_fused", t);
+}
+// C = 640 / 1280, 8 heads, <= 80 context tokens: LayerNorm (folded), the q projection and the attention on the cached K | V of the row's
+// context in ONE launch per block (xattnw.hip); q never reaches HBM.  Returns the attention output: to_out + residual stays the caller's GEMM.
+Act nr_net::xattn_head_block(const Act& t, const Act& ctx_bf, const std::string& b, int hw) {
+  const int C = t.C, nctx = (int)(ctx_bf.rows() / ctx_len), Lk = ctx_len;
+  const Act kvs = context_kv(ctx_bf, b, C, nr_xattnw_kvstream_bytes(C, nctx),      // + the fragment images of K | V
+                             [=](const bf16* kv, int ldkv, bf16* st, hipStream_t s) { LAUNCH_OK(nr_launch_xattnw_kv_pack(kv, ldkv, Lk, nctx, C, st, s)); });
+  const auto w = wts.xattn_head_weights(b + ".norm2", b + ".attn2.to_q.weight", C);
+  Act a = new_act(t.nimg, t.H, t.W, C);
+  const NrXattnHeadParams p{.t = t.ptr, .out = a.ptr, .nimg = t.nimg, .hw = hw, .img_per_ctx = F, .nctx = nctx, .Lk = Lk, .C = C, .wstream = w.stream, .kvstream = kvs.ptr,
+                            .table = w.table, .ln_eps = 1e-5f};
+  const double M = (double)t.rows();
+  emit([p](hipStream_t s) { LAUNCH_OK(nr_launch_xattnw(&p, s)); }, NR_PROF_IGEMM, 2.0 * M * C * (double)C + 4.0 * M * (double)Lk * C,
+       2.0 * (2.0 * M * C + C * (double)C), descf("xattn_head M=%d C=%d Lk=%d (LN folded, q of 160 columns, context attention)", (int)t.rows(), C, Lk));
+  op_tap("xattn_head", a);
+  return a;
+}
+// C = 320, F = 16 or 32: the whole block (LayerNorm + PE, q|k|v, F x F attention per pixel and head, to_out + residual) in ONE launch
+// that updates t in place (tattn.hip); q|k|v and the attention output never reach HBM
+void nr_net::tattn_fused_block(Act& t, const std::string& nrm, const std::string& ab, int hw, int heads) {
+  const int C = t.C; const double M = (double)t.rows();
+  const auto w = wts.tattn_fused_weights(nrm, ab, F, C);
+  const NrTattnFusedParams p{.t = t.ptr, .nbatch = t.nimg / F, .frames = F, .hw = hw, .stream = w.stream, .gamma = w.gamma, .gb = w.gb, .bo = w.bo, .ln_eps = 1e-5f,
+                             .norot = det_batch ? 1 : 0};
+  emit([p](hipStream_t s) { LAUNCH_OK(nr_launch_tattn_fused(&p, s)); }, NR_PROF_IGEMM, 2.0 * M * C * 4.0 * C + 4.0 * (M / F) * heads * (double)F * F * (C / heads),
+       2.0 * (2.0 * M * C + 4.0 * C * (double)C), descf("tattn_fused M=%d C=%d F=%d (LN+PE, q|k|v, attention, to_out + residual)", (int)t.rows(), C, F));
+  op_tap("tattn_fused", t);
+}
+// C = 640 / 1280, F = 16 or 32: LayerNorm + PE (folded), the q|k|v projection of one head and its F x F attention per (pixel group, head) in
+// ONE launch (tattnw.hip); q|k|v never reach HBM.  Returns the attention output: to_out + residual stays the caller's GEMM.
+Act nr_net::tattn_head_block(const Act& t, const std::string& nrm, const std::vector<std::string>& wqkv, int hw, int heads) {
+  const int C = t.C; const double M = (double)t.rows();
+  const auto w = wts.tattn_head_weights(nrm, wqkv, C, F, cfg.motion_pe_max_len);
+  Act a = new_act(t.nimg, t.H, t.W, C);
+  const NrTattnHeadParams p{.t = t.ptr, .out = a.ptr, .nbatch = t.nimg / F, .frames = F, .hw = hw, .C = C, .stream = w.stream, .table = w.table, .ln_eps = 1e-5f};
+  emit([p](hipStream_t s) { LAUNCH_OK(nr_launch_tattnw(&p, s)); }, NR_PROF_IGEMM, 2.0 * M * C * 3.0 * C + 4.0 * (M / F) * heads * (double)F * F * (C / heads),
+       2.0 * (2.0 * M * C + 3.0 * C * (double)C), descf("tattn_head M=%d C=%d F=%d (LN+PE folded, q|k|v of one head, FxF attention)", (int)t.rows(), C, F));
+  op_tap("tattn_head", a);
+  return a;
+}
+
 // Transformer3DModel.forward (attention.py:95-142) with one BasicTransformerBlock (:256-300); also sgm
 // SpatialTransformer.forward (sgm/modules/attention.py:702-723) with `depth` BasicTransformerBlocks (:551-572):
 // same arithmetic and parameter names (proj_in/out are nn.Linear there: same [C][C] matrix).
@@ -417,20 +457,15 @@ nr_net::BlockKernel nr_net::temporal_attn_kernel(const Act& t, int heads, int hw
 // *x_full receives the broadcast input (the caller's skip connection)
 Act nr_net::spatial_transformer(const Act& x_in, const Act& ctx_bf, const std::string& pre, int depth, bool cfg_half, Act* x_full) {
   Act x = x_in;
-  const int C = x.C;
-  const int heads = cfg.num_head_channels > 0 ? C / cfg.num_head_channels : cfg.num_heads;
-  Act hn = groupnorm(x, nullptr, pre + ".norm", 1e-6f, 0);
-  GemmOpt oi; oi.bias = wts.w_f32(pre + ".proj_in.bias", C);
-  Act t = linear(hn, wts.w_linear(pre + ".proj_in.weight", C, C), C, oi);
-  hn = Act();
+  const int C = x.C, heads = cfg.num_head_channels > 0 ? C / cfg.num_head_channels : cfg.num_heads;
+  Act t = linear_wb(groupnorm(x, nullptr, pre + ".norm", 1e-6f, 0), pre + ".proj_in", C);      // norm -> proj_in
   for (int dd = 0; dd < depth; ++dd) {
     const std::string b = pre + ".transformer_blocks." + std::to_string(dd);
     {  // self-attention
       Act qkv = ln_linear(t, b + ".norm1", {b + ".attn1.to_q.weight", b + ".attn1.to_k.weight", b + ".attn1.to_v.weight"}, {}, C, false, 0, false);
       Act a = attention(0, qkv, nullptr, C, heads);
       qkv = Act();
-      GemmOpt oo; oo.bias = wts.w_f32(b + ".attn1.to_out.0.bias", C); oo.res = &t; oo.out = &t;
-      linear(a, wts.w_linear(b + ".attn1.to_out.0.weight", C, C), C, oo);
+      linear_wb(a, b + ".attn1.to_out.0", C, &t, &t);
     }
     if (cfg_half && dd == 0) {      // from here on the two CFG halves differ (their text contexts do)
       t = expand_cfg(t);
@@ -438,76 +473,16 @@ Act nr_net::spatial_transformer(const Act& x_in, const Act& ctx_bf, const std::s
       if (x_full) *x_full = x;
     }
     const BlockKernel xk = cross_attn_kernel(t, heads, x.H * x.W);
-    if (xk == BLOCK_FUSED320) {
-      // C = 320, 8 heads, <= 80 context tokens, >= 4096 rows: the whole cross-attention block (LayerNorm, q projection, attention on the cached
-      // K | V of the clip, to_out + residual) in ONE launch that updates t in place (xattn.hip); q and the attention output never reach HBM
-      const int nctx = (int)(ctx_bf.rows() / ctx_len);      // ctx_bf is ONE "image" of B2 * ctx_len token rows
-      const Act kvs = context_kv(ctx_bf, b, C, [&](const Act& kv) {      // + the per-head LDS images of K | V
-        Act st = new_act_persistent(nctx, 1, 1, (int)(nr_xattn_kvstream_bytes(1) / sizeof(bf16)));
-        const bf16* kvp = kv.ptr; bf16* kvsp = st.ptr; const int ldkv = kv.ld, Lk = ctx_len;
-        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattn_kv_pack(kvp, ldkv, Lk, nctx, kvsp, s)); });
-        return st;
-      });
-      for (const char* wn : {".attn2.to_q.weight", ".attn2.to_out.0.weight"}) wts.check_shape(b + wn, wts.need(b + wn), {C, C});
-      const std::string sname = "xas:" + b + ".attn2.to_q.weight|" + b + ".attn2.to_out.0.weight";
-      const bf16* wstream = (const bf16*)wts.packed_from(sname, nr_xattn_wstream_bytes(), {"lin:" + b + ".attn2.to_q.weight", "lin:" + b + ".attn2.to_out.0.weight"},
-                                                         [&](void* d) {
-        const bf16* wq = wts.w_linear(b + ".attn2.to_q.weight", C, C);
-        const bf16* wo = wts.w_linear(b + ".attn2.to_out.0.weight", C, C);
-        LAUNCH_OK(nr_launch_xattn_w_pack(wq, wo, (bf16*)d, nullptr));
-      });
-      const float* gamma = wts.w_f32(b + ".norm2.weight", C);
-      const float* beta = wts.w_f32(b + ".norm2.bias", C);
-      const float* bo = wts.w_f32(b + ".attn2.to_out.0.bias", C);
-      bf16* tp = t.ptr; const bf16* kvsp = kvs.ptr;
-      const int nimg = t.nimg, hwx = x.H * x.W, ipc = F, Lk = ctx_len;
-      const double M = (double)t.rows();
-      char d[160];
-      snprintf(d, sizeof(d), "xattn_fused M=%d C=%d Lk=%d (LN, q, context attention, to_out + residual)", (int)t.rows(), C, Lk);
-      const int norot = det_batch ? 1 : 0;
-      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattn_fused(tp, nimg, hwx, ipc, nctx, Lk, wstream, kvsp, gamma, beta, bo, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
-           2.0 * M * C * 2.0 * C + 4.0 * M * (double)Lk * C, 2.0 * (2.0 * M * C + 2.0 * C * (double)C), d);
-      op_tap("xattn_fused", t);
-    } else if (xk == BLOCK_HEAD) {
-      // C = 640 / 1280, 8 heads, <= 80 context tokens: LayerNorm (folded), the q projection and the attention on the cached K | V of the row's
-      // context in ONE launch per block (xattnw.hip); q never reaches HBM.  to_out + residual stays the GEMM below.
-      const int nctx = (int)(ctx_bf.rows() / ctx_len);
-      const Act kvs = context_kv(ctx_bf, b, C, [&](const Act& kv) {      // + the fragment images of K | V
-        Act st = new_act_persistent(1, 1, 1, (int)(nr_xattnw_kvstream_bytes(C, nctx) / sizeof(bf16)));
-        const bf16* kvp = kv.ptr; bf16* kvsp = st.ptr; const int ldkv = kv.ld, Lk = ctx_len, Cc = C;
-        emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattnw_kv_pack(kvp, ldkv, Lk, nctx, Cc, kvsp, s)); });
-        return st;
-      });
-      const std::string nrm = b + ".norm2", wq = b + ".attn2.to_q.weight";
-      const std::string sname = "xaws:" + nrm + "|" + wq;
-      const bf16* wstream = (const bf16*)wts.packed_from(sname, nr_xattnw_wstream_bytes(C), {"lnw:" + nrm + "|" + wq + "|"}, [&](void* d) {      // from the folded [C][C] matrix
-        const LnW lwm = wts.w_ln_linear({wq}, {}, nrm, C, C, false, true);
-        LAUNCH_OK(nr_launch_xattnw_w_pack(lwm.w, C, (bf16*)d, nullptr));
-      });
-      const std::string tname = "xawt:" + nrm + "|" + wq;
-      const float* table = (const float*)wts.packed(tname, nr_xattnw_table_bytes(C), [&](void* d) {
-        const LnW lw = wts.w_ln_linear({wq}, {}, nrm, C, C, false, false);
-        LAUNCH_OK(nr_launch_xattnw_table_pack(lw.c, lw.b, C, (float*)d, nullptr));
-      });
-      if (dry) (void)wts.w_ln_linear({wq}, {}, nrm, C, C, false, false);      // shape checks in the sizing pass too
-      Act a = new_act(t.nimg, t.H, t.W, C);
-      const bf16* tp = t.ptr; bf16* ap = a.ptr; const bf16* kvsp = kvs.ptr;
-      const int nimg = t.nimg, hwx = x.H * x.W, ipc = F, Lk = ctx_len, Cc = C;
-      const double M = (double)t.rows();
-      char d[160];
-      snprintf(d, sizeof(d), "xattn_head M=%d C=%d Lk=%d (LN folded, q of 160 columns, context attention)", (int)t.rows(), C, Lk);
-      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_xattnw(tp, ap, nimg, hwx, ipc, nctx, Lk, Cc, wstream, kvsp, table, 1e-5f, s)); }, NR_PROF_IGEMM,
-           2.0 * M * C * (double)C + 4.0 * M * (double)Lk * C, 2.0 * (2.0 * M * C + C * (double)C), d);
-      op_tap("xattn_head", a);
-      GemmOpt oo; oo.bias = wts.w_f32(b + ".attn2.to_out.0.bias", C); oo.res = &t; oo.out = &t;
-      linear(a, wts.w_linear(b + ".attn2.to_out.0.weight", C, C), C, oo);
-    } else {  // cross-attention on the context (attention.py:100: context repeated per frame)
-      Act q = ln_linear(t, b + ".norm2", {b + ".attn2.to_q.weight"}, {}, C, false, 0, false);
-      Act kv = context_kv(ctx_bf, b, C);
-      Act a = attention(1, q, &kv, C, heads);
-      q = Act(); kv = Act();
-      GemmOpt oo; oo.bias = wts.w_f32(b + ".attn2.to_out.0.bias", C); oo.res = &t; oo.out = &t;
-      linear(a, wts.w_linear(b + ".attn2.to_out.0.weight", C, C), C, oo);
+    if (xk == BLOCK_FUSED320) xattn_fused_block(t, ctx_bf, b, x.H * x.W);
+    else {
+      Act a;
+      if (xk == BLOCK_HEAD) a = xattn_head_block(t, ctx_bf, b, x.H * x.W);
+      else {  // cross-attention on the context (attention.py:100: context repeated per frame)
+        Act q = ln_linear(t, b + ".norm2", {b + ".attn2.to_q.weight"}, {}, C, false, 0, false);
+        Act kv = context_kv(ctx_bf, b, C);
+        a = attention(1, q, &kv, C, heads);
+      }
+      linear_wb(a, b + ".attn2.to_out.0", C, &t, &t);      // to_out + residual
     }
     if (dd + 1 < depth) feed_forward(t, b + ".norm3", b + ".ff");
   }
@@ -524,79 +499,21 @@ Act nr_net::temporal_module(const Act& x, const std::string& pre0) {
   if (F > cfg.motion_pe_max_len)
     throw NrError(NR_ERR_ARG, "video_length " + std::to_string(F) + " exceeds temporal_position_encoding_max_len " +
                                   std::to_string(cfg.motion_pe_max_len));
-  Act hn = groupnorm(x, nullptr, pre + ".norm", 1e-6f, 0);
-  GemmOpt oi; oi.bias = wts.w_f32(pre + ".proj_in.bias", C);
-  Act t = linear(hn, wts.w_linear(pre + ".proj_in.weight", C, C), C, oi);
-  hn = Act();
+  Act t = linear_wb(groupnorm(x, nullptr, pre + ".norm", 1e-6f, 0), pre + ".proj_in", C);      // norm -> proj_in
   const std::string b = pre + ".transformer_blocks.0";
   for (int k = 0; k < cfg.motion_num_attention_blocks; ++k) {
     const std::string ab = b + ".attention_blocks." + std::to_string(k);
+    const std::string nrm = b + ".norms." + std::to_string(k);
+    const std::vector<std::string> wqkv = {ab + ".to_q.weight", ab + ".to_k.weight", ab + ".to_v.weight"};
     const BlockKernel tk = temporal_attn_kernel(t, heads, x.H * x.W);
-    if (tk == BLOCK_FUSED320) {
-      // C = 320, F = 16 or 32: the whole block (LayerNorm + PE, q|k|v, F x F attention per pixel and head, to_out + residual) in ONE launch
-      // that updates t in place (tattn.hip); q|k|v and the attention output never reach HBM
-      const std::string nrm = b + ".norms." + std::to_string(k);
-      for (const char* wn : {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"}) wts.check_shape(ab + wn, wts.need(ab + wn), {C, C});
-      const std::string sname = "tas:" + ab + ".to_q.weight|" + ab + ".to_k.weight|" + ab + ".to_v.weight|" + ab + ".to_out.0.weight";
-      const char* wn[4] = {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"};
-      const bf16* stream = (const bf16*)wts.packed_from(sname, nr_tattn_stream_bytes(), {"lin:" + ab + wn[0], "lin:" + ab + wn[1], "lin:" + ab + wn[2], "lin:" + ab + wn[3]},
-                                                        [&](void* d) {
-        const bf16* wm[4];
-        for (int i = 0; i < 4; ++i) wm[i] = wts.w_linear(ab + wn[i], C, C);
-        LAUNCH_OK(nr_launch_tattn_stream_pack(wm[0], wm[1], wm[2], wm[3], (bf16*)d, nullptr));
-      });
-      const float* gb = wts.b_ln_pe(nrm, F, C);
-      const float* gamma = wts.w_f32(nrm + ".weight", C);
-      const float* bo = wts.w_f32(ab + ".to_out.0.bias", C);
-      bf16* tp = t.ptr; const int nb2 = t.nimg / F, hw = x.H * x.W;
-      const double M = (double)t.rows();
-      char d[160];
-      snprintf(d, sizeof(d), "tattn_fused M=%d C=%d F=%d (LN+PE, q|k|v, attention, to_out + residual)", (int)t.rows(), C, F);
-      const int norot = det_batch ? 1 : 0;
-      const int Fn = F;
-      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_tattn_fused(tp, nb2, Fn, hw, stream, gamma, gb, bo, 1e-5f, norot, s)); }, NR_PROF_IGEMM,
-           2.0 * M * C * 4.0 * C + 4.0 * (M / F) * heads * (double)F * F * (C / heads), 2.0 * (2.0 * M * C + 4.0 * C * (double)C), d);
-      op_tap("tattn_fused", t);
-      continue;
-    }
+    if (tk == BLOCK_FUSED320) { tattn_fused_block(t, nrm, ab, x.H * x.W, heads); continue; }
     Act a;
-    if (tk == BLOCK_HEAD) {
-      // C = 640 / 1280, F = 16 or 32: LayerNorm + PE (folded), the q|k|v projection of one head and its F x F attention per (pixel group, head) in
-      // ONE launch (tattnw.hip); q|k|v never reach HBM.  to_out + residual stays the GEMM below.
-      const std::string nrm = b + ".norms." + std::to_string(k);
-      const std::vector<std::string> wk = {ab + ".to_q.weight", ab + ".to_k.weight", ab + ".to_v.weight"};
-      const float* rv = wts.pe_projection(wk, C, C, cfg.motion_pe_max_len);
-      const std::string sname = "taws:" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
-      const bf16* stream = (const bf16*)wts.packed_from(sname, nr_tattnw_stream_bytes(C), {"lnw:" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2] + "|"},
-                                                        [&](void* d) {      // from the folded [3C][C] matrix
-        const LnW lwm = wts.w_ln_linear(wk, {}, nrm, C, C, false, true);
-        LAUNCH_OK(nr_launch_tattnw_stream_pack(lwm.w, C, (bf16*)d, nullptr));
-      });
-      // the head-major epilogue table (LayerNorm-fold vectors + positional-encoding projections of the first F positions) the kernel stages
-      // through LDS: one per frame count a handle was planned with
-      const std::string tname = "tawe:" + std::to_string(cfg.motion_pe_max_len) + ":" + std::to_string(F) + ":" + nrm + "|" + wk[0] + "|" + wk[1] + "|" + wk[2];
-      const float* table = (const float*)wts.packed(tname, nr_tattnw_table_bytes(C, F), [&](void* d) {
-        const LnW lw = wts.w_ln_linear(wk, {}, nrm, C, C, false, false);
-        LAUNCH_OK(nr_launch_tattnw_table_pack(lw.c, lw.b, rv, C, F, (float*)d, nullptr));
-      });
-      a = new_act(t.nimg, t.H, t.W, C);
-      const bf16* tp = t.ptr; bf16* ap = a.ptr;
-      const int nb2 = t.nimg / F, hw = x.H * x.W;
-      const double M = (double)t.rows();
-      char d[160];
-      snprintf(d, sizeof(d), "tattn_head M=%d C=%d F=%d (LN+PE folded, q|k|v of one head, FxF attention)", (int)t.rows(), C, F);
-      const int Fn = F;
-      emit([=](hipStream_t s) { LAUNCH_OK(nr_launch_tattnw(tp, ap, nb2, Fn, hw, C, stream, table, 1e-5f, s)); }, NR_PROF_IGEMM,
-           2.0 * M * C * 3.0 * C + 4.0 * (M / F) * heads * (double)F * F * (C / heads), 2.0 * (2.0 * M * C + 3.0 * C * (double)C), d);
-      op_tap("tattn_head", a);
-    } else {
-      // LayerNorm, then + pe[frame] (motion_module.py:212,277): both folded into the q|k|v GEMM
-      Act qkv = ln_linear(t, b + ".norms." + std::to_string(k), {ab + ".to_q.weight", ab + ".to_k.weight", ab + ".to_v.weight"}, {}, C,
-                          false, 0, true);
+    if (tk == BLOCK_HEAD) a = tattn_head_block(t, nrm, wqkv, x.H * x.W, heads);
+    else {  // LayerNorm, then + pe[frame] (motion_module.py:212,277): both folded into the q|k|v GEMM
+      Act qkv = ln_linear(t, nrm, wqkv, {}, C, false, 0, true);
       a = attention(2, qkv, nullptr, C, heads);
     }
-    GemmOpt oo; oo.bias = wts.w_f32(ab + ".to_out.0.bias", C); oo.res = &t; oo.out = &t;
-    linear(a, wts.w_linear(ab + ".to_out.0.weight", C, C), C, oo);
+    linear_wb(a, ab + ".to_out.0", C, &t, &t);      // to_out + residual
   }
   Act out = feed_forward_proj_out(x, t, b + ".ff_norm", b + ".ff", pre);
   tap(pre0, out);
@@ -612,10 +529,8 @@ Act nr_net::vae_attn(const Act& x, const std::string& pre) {
   const int C = x.C, hw = x.H * x.W;
   if (hw % 64 != 0) throw NrError(NR_ERR_UNSUPPORTED, "VAE attention: latent h*w must be a multiple of 64");
   Act hn = groupnorm(x, nullptr, pre + ".norm", cfg.norm_eps, 0);
-  GemmOpt oq; oq.bias = wts.w_f32(pre + ".q.bias", C);
-  Act q = linear(hn, wts.w_linear(pre + ".q.weight", C, C), C, oq);
-  GemmOpt ok; ok.bias = wts.w_f32(pre + ".k.bias", C);
-  Act k = linear(hn, wts.w_linear(pre + ".k.weight", C, C), C, ok);
+  Act q = linear_wb(hn, pre + ".q", C);
+  Act k = linear_wb(hn, pre + ".k", C);
   const bf16* wv = wts.w_linear(pre + ".v.weight", C, C);
   const float* bv = wts.w_f32(pre + ".v.bias", C);
   Act o = new_act(x.nimg, x.H, x.W, C);
@@ -635,8 +550,7 @@ Act nr_net::vae_attn(const Act& x, const std::string& pre) {
     }
   }
   hn = Act(); q = Act(); k = Act();
-  GemmOpt op; op.bias = wts.w_f32(pre + ".proj_out.bias", C); op.res = &x;
-  Act out = linear(o, wts.w_linear(pre + ".proj_out.weight", C, C), C, op);
+  Act out = linear_wb(o, pre + ".proj_out", C, &x);
   tap(pre, out);
   return out;
 }

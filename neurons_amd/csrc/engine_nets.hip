@@ -341,8 +341,7 @@ Act nr_net::embed_conv(const Act& in, int Fe, const std::string& key, int Cout, 
   const bf16* w = wts.w_condembed(key + ".weight", Cout, Cin);
   const float* b = bias ? bias : wts.w_f32(key + ".bias", Cout);
   const bf16* ip = in.ptr; bf16* op = o.ptr;
-  char d[160];
-  snprintf(d, sizeof(d), "condembed_conv Cin=%d Cout=%d s=%d H=%d W=%d frames=%d", Cin, Cout, stride, OH, OW, Fe);
+  const std::string d = descf("condembed_conv Cin=%d Cout=%d s=%d H=%d W=%d frames=%d", Cin, Cout, stride, OH, OW, Fe);
   emit([=, this](hipStream_t s) { LAUNCH_OK(nr_launch_condembed_conv(ip, io.cond_batch * Fe, Hi, Wi, Cin, stride, w, b, Cout, silu, op, s)); },
        NR_PROF_IGEMM, 2.0 * Fe * OH * OW * Cout * 9.0 * Cin, 2.0 * Fe * ((double)Hi * Wi * Cin + (double)OH * OW * Cout) + 2.0 * Cout * 9.0 * Cin, d);
   return o;
@@ -362,8 +361,7 @@ void nr_net::cond_embedding(Act& x, int nd, const int* fmap_reduce, const int* f
     const float* w = wts.w_conv_in(pre + "conv_in.weight", ch[0], cc + 1);
     const float* b = wts.w_f32(pre + "conv_in.bias", ch[0]);
     bf16* op = e.ptr; const int C = ch[0];
-    char d[160];
-    snprintf(d, sizeof(d), "condembed_in Cin=%d Cout=%d H=%d W=%d frames=%d", cc + 1, C, Hc, Wc, Fe);
+    const std::string d = descf("condembed_in Cin=%d Cout=%d H=%d W=%d frames=%d", cc + 1, C, Hc, Wc, Fe);
     emit([=, this](hipStream_t s) {
       LAUNCH_OK(nr_launch_condembed_in(io.cond, io.mask, cc, io.cond_batch, Fn, Hc, Wc, fsel.data(), Fe, w, b, C, op, s));
     }, NR_PROF_OTHER, 2.0 * Fe * Hc * Wc * C * 9.0 * (cc + 1), 4.0 * Fe * Hc * Wc * (cc + 1) + 2.0 * Fe * Hc * Wc * C, d);
@@ -389,8 +387,7 @@ void nr_net::cond_embedding(Act& x, int nd, const int* fmap_reduce, const int* f
     const SplitK sk = splitk_scratch(wsb);
     float* ws = sk.ws;
     p.M = Fe * H * W;
-    char d[160];
-    snprintf(d, sizeof(d), "igemm ks=3 s=1 ups=0 M=%d N=%d K=%d condembed conv_out frames=%d", p.M, p.N, p.K, Fe);
+    const std::string d = descf("igemm ks=3 s=1 ups=0 M=%d N=%d K=%d condembed conv_out frames=%d", p.M, p.N, p.K, Fe);
     const int hw = H * W;
     emit([this, p, routes, ws, Fe, hw](hipStream_t s) {
       NrGemmParams q = p;

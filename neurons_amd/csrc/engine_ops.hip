@@ -194,65 +194,54 @@ extern "C" nr_status nr_op_attention(nr_stream stream, int32_t mode, const void*
   NR_CATCH
 }
 
-// ---- fused FeedForward + proj_out (ffpanel.hip), op-level entry for tests: inputs in the engine's converted formats ----
-extern "C" nr_status nr_op_ff_fused(nr_stream stream, const void* t_dev, const void* x_dev, void* out_dev, int32_t M, int32_t C,
-                                    const void* w1_geglu_dev, const float* gamma_dev, const float* beta_dev, const float* b1_geglu_dev,
-                                    const void* wc_dev, const float* bc_dev, float ln_eps) {
+// ---- the five fused transformer kernels (tensors and formats: include/neurons_amd.h).  Each hook packs its streams / tables into process-lifetime scratch, fills the
+// kernel's launch description as the engine's emitter does and calls the same launcher.  A NULL weight matrix = reuse what the previous call packed (timing loops) ----
+template <class T> static T* op_packed(OpScratch& b, size_t bytes) { op_scratch(b, bytes); return (T*)b.ptr; }
+
+extern "C" nr_status nr_op_ff_fused(nr_stream stream, const void* t_dev, const void* x_dev, void* out_dev, int32_t M, int32_t C, const void* w1_geglu_dev,
+                                    const float* gamma_dev, const float* beta_dev, const float* b1_geglu_dev, const void* wc_dev, const float* bc_dev, float ln_eps) {
   NR_TRY
   if (!nr_ff_fused_supported(C, C, C, C)) throw NrError(NR_ERR_UNSUPPORTED, "the fused FeedForward kernel is built for C = 320");
   static OpScratch buf;
-  op_scratch(buf, nr_ff_stream_bytes(C));
-  void* ws = buf.ptr;
-  // w1 == NULL: reuse the stage stream packed by the previous call (timing loops)
-  if (w1_geglu_dev) LAUNCH_OK(nr_launch_ff_stream_pack((const bf16*)w1_geglu_dev, (const bf16*)wc_dev, (bf16*)ws, (hipStream_t)stream));
-  LAUNCH_OK(nr_launch_ff_fused((const bf16*)t_dev, C, (const bf16*)x_dev, C, (bf16*)out_dev, C, M, (const bf16*)ws, gamma_dev, beta_dev,
-                               b1_geglu_dev, bc_dev, ln_eps, env_is_1("NR_DETERMINISTIC_BATCH"), nr_ff_waves(), (hipStream_t)stream));
+  bf16* ws = op_packed<bf16>(buf, nr_ff_stream_bytes(C));
+  if (w1_geglu_dev) LAUNCH_OK(nr_launch_ff_stream_pack((const bf16*)w1_geglu_dev, (const bf16*)wc_dev, ws, (hipStream_t)stream));
+  const NrFfFusedParams p{.t = (const bf16*)t_dev, .ldt = C, .x = (const bf16*)x_dev, .ldx = C, .out = (bf16*)out_dev, .ldo = C, .M = M, .stream = ws, .gamma = gamma_dev,
+                          .beta = beta_dev, .b1 = b1_geglu_dev, .bc = bc_dev, .ln_eps = ln_eps, .norot = env_is_1("NR_DETERMINISTIC_BATCH"), .waves = nr_ff_waves()};
+  LAUNCH_OK(nr_launch_ff_fused(&p, (hipStream_t)stream));
   NR_CATCH
 }
-
-// ---- fused temporal-attention block (tattn.hip), op-level entry for tests.  t: bf16 [nbatch * frames * hw][320], updated in place;
-// wq / wk / wv / wo: bf16 [320][320]; gamma fp32 [320]; gb fp32 [frames][320] = LayerNorm bias + positional encoding; bo fp32 [320];
-// frames = 16 or 32 ----
-extern "C" nr_status nr_op_tattn_fused_frames(nr_stream stream, void* t_dev, int32_t nbatch, int32_t frames, int32_t hw, const void* wq_dev,
-                                              const void* wk_dev, const void* wv_dev, const void* wo_dev, const float* gamma_dev,
-                                              const float* gb_dev, const float* bo_dev, float ln_eps) {
+extern "C" nr_status nr_op_tattn_fused_frames(nr_stream stream, void* t_dev, int32_t nbatch, int32_t frames, int32_t hw, const void* wq_dev, const void* wk_dev,
+                                              const void* wv_dev, const void* wo_dev, const float* gamma_dev, const float* gb_dev, const float* bo_dev, float ln_eps) {
   NR_TRY
   if (!nr_tattn_fused_supported(320, 8, frames, hw))
     throw NrError(NR_ERR_UNSUPPORTED, "fused temporal attention: C = 320, 8 heads, 16 or 32 frames, hw % (128 / frames) == 0");
   static OpScratch buf;
-  op_scratch(buf, nr_tattn_stream_bytes());
-  void* ws = buf.ptr;
-  // wq == NULL: reuse the stream packed by the previous call (timing loops)
-  if (wq_dev) LAUNCH_OK(nr_launch_tattn_stream_pack((const bf16*)wq_dev, (const bf16*)wk_dev, (const bf16*)wv_dev, (const bf16*)wo_dev, (bf16*)ws,
-                                                    (hipStream_t)stream));
-  LAUNCH_OK(nr_launch_tattn_fused((bf16*)t_dev, nbatch, frames, hw, (const bf16*)ws, gamma_dev, gb_dev, bo_dev, ln_eps,
-                                  env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
+  bf16* ws = op_packed<bf16>(buf, nr_tattn_stream_bytes());
+  if (wq_dev) LAUNCH_OK(nr_launch_tattn_stream_pack((const bf16*)wq_dev, (const bf16*)wk_dev, (const bf16*)wv_dev, (const bf16*)wo_dev, ws, (hipStream_t)stream));
+  const NrTattnFusedParams p{.t = (bf16*)t_dev, .nbatch = nbatch, .frames = frames, .hw = hw, .stream = ws, .gamma = gamma_dev, .gb = gb_dev, .bo = bo_dev, .ln_eps = ln_eps,
+                             .norot = env_is_1("NR_DETERMINISTIC_BATCH")};
+  LAUNCH_OK(nr_launch_tattn_fused(&p, (hipStream_t)stream));
   NR_CATCH
 }
-extern "C" nr_status nr_op_xattn_fused(nr_stream stream, void* t_dev, int32_t nimg, int32_t hw, int32_t img_per_ctx, const void* wq_dev,
-                                       const void* wo_dev, const void* kv_dev, int32_t ldkv, int32_t Lk, int32_t nctx, const float* gamma_dev,
-                                       const float* beta_dev, const float* bo_dev, float ln_eps) {
+extern "C" nr_status nr_op_xattn_fused(nr_stream stream, void* t_dev, int32_t nimg, int32_t hw, int32_t img_per_ctx, const void* wq_dev, const void* wo_dev,
+                                       const void* kv_dev, int32_t ldkv, int32_t Lk, int32_t nctx, const float* gamma_dev, const float* beta_dev, const float* bo_dev,
+                                       float ln_eps) {
   NR_TRY
   if (!t_dev || !kv_dev || !gamma_dev || !beta_dev || !bo_dev) throw NrError(NR_ERR_ARG, "null argument");
   if (!nr_xattn_fused_supported(320, 8, Lk, hw) || nimg <= 0 || img_per_ctx <= 0 || nctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
     throw NrError(NR_ERR_UNSUPPORTED, "fused cross attention: C = 320, 8 heads, Lk <= 80, hw % 128 == 0, one context per img_per_ctx images");
   static OpScratch wbuf, kvbuf;
-  op_scratch(wbuf, nr_xattn_wstream_bytes());
-  op_scratch(kvbuf, nr_xattn_kvstream_bytes(nctx));
-  void* ws = wbuf.ptr;
-  void* kvs = kvbuf.ptr;
-  // wq == NULL: reuse the streams packed by the previous call (timing loops)
+  bf16* ws = op_packed<bf16>(wbuf, nr_xattn_wstream_bytes());
+  bf16* kvs = op_packed<bf16>(kvbuf, nr_xattn_kvstream_bytes(nctx));
   if (wq_dev) {
-    LAUNCH_OK(nr_launch_xattn_w_pack((const bf16*)wq_dev, (const bf16*)wo_dev, (bf16*)ws, (hipStream_t)stream));
-    LAUNCH_OK(nr_launch_xattn_kv_pack((const bf16*)kv_dev, ldkv, Lk, nctx, (bf16*)kvs, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_xattn_w_pack((const bf16*)wq_dev, (const bf16*)wo_dev, ws, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_xattn_kv_pack((const bf16*)kv_dev, ldkv, Lk, nctx, kvs, (hipStream_t)stream));
   }
-  LAUNCH_OK(nr_launch_xattn_fused((bf16*)t_dev, nimg, hw, img_per_ctx, nctx, Lk, (const bf16*)ws, (const bf16*)kvs, gamma_dev, beta_dev, bo_dev, ln_eps,
-                                  env_is_1("NR_DETERMINISTIC_BATCH"), (hipStream_t)stream));
+  const NrXattnFusedParams p{.t = (bf16*)t_dev, .nimg = nimg, .hw = hw, .img_per_ctx = img_per_ctx, .nctx = nctx, .Lk = Lk, .wstream = ws, .kvstream = kvs, .gamma = gamma_dev,
+                             .beta = beta_dev, .bo = bo_dev, .ln_eps = ln_eps, .norot = env_is_1("NR_DETERMINISTIC_BATCH")};
+  LAUNCH_OK(nr_launch_xattn_fused(&p, (hipStream_t)stream));
   NR_CATCH
 }
-// ---- q projection + context attention above the C = 320 level (xattnw.hip), op-level entry for tests.  t: bf16 [nimg * hw][C] (C = 640 or 1280,
-// hw a multiple of 64); a: bf16, same shape (attention output before to_out); wq_folded: bf16 [C][C] = gamma-scaled rows of to_q; lnc / bias fp32 [C];
-// kv: bf16 [nctx * Lk][ldkv], K in columns [0, C), V in [C, 2C); image i attends to context i / img_per_ctx ----
 extern "C" nr_status nr_op_xattn_head(nr_stream stream, const void* t_dev, void* a_dev, int32_t nimg, int32_t hw, int32_t img_per_ctx, int32_t C,
                                       const void* wq_folded_dev, const float* lnc_dev, const float* bias_dev, const void* kv_dev, int32_t ldkv, int32_t Lk,
                                       int32_t nctx, float ln_eps) {
@@ -260,59 +249,52 @@ extern "C" nr_status nr_op_xattn_head(nr_stream stream, const void* t_dev, void*
   if (!t_dev || !a_dev || !kv_dev) throw NrError(NR_ERR_ARG, "null argument");
   if (!nr_xattnw_supported(C, 8, Lk, hw) || nimg <= 0 || nctx <= 0 || img_per_ctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx)
     throw NrError(NR_ERR_UNSUPPORTED, "cross-attention head kernel: C = 640 or 1280, 8 heads, Lk <= 80, hw % 64 == 0, one context per img_per_ctx images");
-  static OpScratch wbuf[2], tbuf[2], kvbuf;      // weight stream and table: one per C
-  const int ci = C == 640 ? 0 : 1;
-  op_scratch(wbuf[ci], nr_xattnw_wstream_bytes(C));
-  op_scratch(tbuf[ci], nr_xattnw_table_bytes(C));
-  void* const ws = wbuf[ci].ptr;
-  void* const tbl = tbuf[ci].ptr;
+  static std::map<int, OpScratch> wbuf, tbuf;
+  static OpScratch kvbuf;
+  bf16* ws = op_packed<bf16>(wbuf[C], nr_xattnw_wstream_bytes(C));
+  float* tbl = op_packed<float>(tbuf[C], nr_xattnw_table_bytes(C));
   const size_t need = nr_xattnw_kvstream_bytes(C, nctx);
   if (op_scratch(kvbuf, need)) HIP_OK(hipMemset(kvbuf.ptr, 0, need));
-  void* kvs = kvbuf.ptr;
-  // wq_folded == NULL: reuse the streams packed by the previous call at this C (timing loops)
+  bf16* kvs = (bf16*)kvbuf.ptr;
   if (wq_folded_dev) {
     if (!lnc_dev || !bias_dev) throw NrError(NR_ERR_ARG, "null argument");
-    LAUNCH_OK(nr_launch_xattnw_w_pack((const bf16*)wq_folded_dev, C, (bf16*)ws, (hipStream_t)stream));
-    LAUNCH_OK(nr_launch_xattnw_table_pack(lnc_dev, bias_dev, C, (float*)tbl, (hipStream_t)stream));
-    LAUNCH_OK(nr_launch_xattnw_kv_pack((const bf16*)kv_dev, ldkv, Lk, nctx, C, (bf16*)kvs, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_xattnw_w_pack((const bf16*)wq_folded_dev, C, ws, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_xattnw_table_pack(lnc_dev, bias_dev, C, tbl, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_xattnw_kv_pack((const bf16*)kv_dev, ldkv, Lk, nctx, C, kvs, (hipStream_t)stream));
   }
-  LAUNCH_OK(nr_launch_xattnw((const bf16*)t_dev, (bf16*)a_dev, nimg, hw, img_per_ctx, nctx, Lk, C, (const bf16*)ws, (const bf16*)kvs, (const float*)tbl,
-                             ln_eps, (hipStream_t)stream));
+  const NrXattnHeadParams p{.t = (const bf16*)t_dev, .out = (bf16*)a_dev, .nimg = nimg, .hw = hw, .img_per_ctx = img_per_ctx, .nctx = nctx, .Lk = Lk, .C = C, .wstream = ws,
+                            .kvstream = kvs, .table = tbl, .ln_eps = ln_eps};
+  LAUNCH_OK(nr_launch_xattnw(&p, (hipStream_t)stream));
   NR_CATCH
 }
-// ---- q|k|v projection of one head + F x F attention above the C = 320 level (tattnw.hip), op-level entry for tests.  t: bf16 [nbatch * frames * hw][C]
-// (C = 640 or 1280, frames = 16 or 32); a: bf16, same shape (attention output before to_out); w_folded: bf16 [3C][C] = gamma-scaled rows of
-// to_q | to_k | to_v; lnc / bias fp32 [3C]; rowvec fp32 [frames][3C] ----
+// the table is packed for one frame count, so w_folded == NULL reuses the packing of the same frame count only
 extern "C" nr_status nr_op_tattn_head_frames(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t frames, int32_t hw, int32_t C,
                                              const void* w_folded_dev, const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
   NR_TRY
   if (!t_dev || !a_dev || !lnc_dev || !bias_dev || !rowvec_dev) throw NrError(NR_ERR_ARG, "null argument");
   if (!nr_tattnw_supported(C, 8, frames, hw) || nbatch <= 0)
     throw NrError(NR_ERR_UNSUPPORTED, "temporal attention head kernel: C = 640 (hw % 8 == 0) or 1280 (hw % 4 == 0), 8 heads, 16 or 32 frames");
-  static OpScratch wbuf[2], tbuf[2][2];                                   // weight stream per C; table per [C][frames]: it is packed for one frame count
-  static int ws_frames[2] = {0, 0};                                       // the frame count of the last packing call at this C
-  const int ci = C == 640 ? 0 : 1, fi = frames == 16 ? 0 : 1;
-  op_scratch(wbuf[ci], nr_tattnw_stream_bytes(C));
-  op_scratch(tbuf[ci][fi], nr_tattnw_table_bytes(C, frames));
-  void* const w = wbuf[ci].ptr;
-  void* const tb = tbuf[ci][fi].ptr;
-  // w_folded == NULL: reuse the stream and the epilogue table packed by the previous call at this C (timing loops): same frame count only
+  static std::map<int, OpScratch> wbuf;
+  static std::map<std::pair<int, int>, OpScratch> tbuf;
+  static std::map<int, int> wbuf_frames;      // the frame count of the last packing call at this C
+  bf16* w = op_packed<bf16>(wbuf[C], nr_tattnw_stream_bytes(C));
+  float* tb = op_packed<float>(tbuf[{C, frames}], nr_tattnw_table_bytes(C, frames));
   if (w_folded_dev) {
-    LAUNCH_OK(nr_launch_tattnw_stream_pack((const bf16*)w_folded_dev, C, (bf16*)w, (hipStream_t)stream));
-    LAUNCH_OK(nr_launch_tattnw_table_pack(lnc_dev, bias_dev, rowvec_dev, C, frames, (float*)tb, (hipStream_t)stream));
-    ws_frames[ci] = frames;
-  } else if (ws_frames[ci] != frames) {
+    LAUNCH_OK(nr_launch_tattnw_stream_pack((const bf16*)w_folded_dev, C, w, (hipStream_t)stream));
+    LAUNCH_OK(nr_launch_tattnw_table_pack(lnc_dev, bias_dev, rowvec_dev, C, frames, tb, (hipStream_t)stream));
+    wbuf_frames[C] = frames;
+  } else if (wbuf_frames[C] != frames) {
     throw NrError(NR_ERR_ARG, "temporal attention head kernel: w_folded == NULL needs a previous call at this C and frame count");
   }
-  LAUNCH_OK(nr_launch_tattnw((const bf16*)t_dev, (bf16*)a_dev, nbatch, frames, hw, C, (const bf16*)w, (const float*)tb, ln_eps, (hipStream_t)stream));
+  const NrTattnHeadParams p{.t = (const bf16*)t_dev, .out = (bf16*)a_dev, .nbatch = nbatch, .frames = frames, .hw = hw, .C = C, .stream = w, .table = tb, .ln_eps = ln_eps};
+  LAUNCH_OK(nr_launch_tattnw(&p, (hipStream_t)stream));
   NR_CATCH
 }
 extern "C" nr_status nr_op_tattn_head(nr_stream stream, const void* t_dev, void* a_dev, int32_t nbatch, int32_t hw, int32_t C, const void* w_folded_dev,
                                       const float* lnc_dev, const float* bias_dev, const float* rowvec_dev, float ln_eps) {
   return nr_op_tattn_head_frames(stream, t_dev, a_dev, nbatch, 16, hw, C, w_folded_dev, lnc_dev, bias_dev, rowvec_dev, ln_eps);
 }
-extern "C" nr_status nr_op_tattn_fused(nr_stream stream, void* t_dev, int32_t nbatch, int32_t hw, const void* wq_dev, const void* wk_dev,
-                                       const void* wv_dev, const void* wo_dev, const float* gamma_dev, const float* gb_dev, const float* bo_dev,
-                                       float ln_eps) {
+extern "C" nr_status nr_op_tattn_fused(nr_stream stream, void* t_dev, int32_t nbatch, int32_t hw, const void* wq_dev, const void* wk_dev, const void* wv_dev,
+                                       const void* wo_dev, const float* gamma_dev, const float* gb_dev, const float* bo_dev, float ln_eps) {
   return nr_op_tattn_fused_frames(stream, t_dev, nbatch, 16, hw, wq_dev, wk_dev, wv_dev, wo_dev, gamma_dev, gb_dev, bo_dev, ln_eps);
 }

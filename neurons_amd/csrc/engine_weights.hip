@@ -1,6 +1,6 @@
 // The weight store of an engine handle (engine.h): the state dict as loaded, the converted device weights in the layouts the kernels want
 // (bf16, tap-major conv weights, fused q|k|v, GEGLU value/gate interleave, LayerNorm folds, packed weight streams), the manifest they travel
-// between handles with, and every converter.  Host code only.
+// between handles with, every converter and the weight bundle of each fused transformer kernel.  Host code only.
 #include "engine.h"
 
 namespace nre {
@@ -22,6 +22,20 @@ std::vector<float> sinusoid_table(int max_len, int C) {
 static int geglu_src_row(int n, int inner) {
   const int q = n / 32, j = n % 32;
   return j < 16 ? q * 16 + j : inner + q * 16 + (j - 16);
+}
+
+// Derived names that a second place needs (the fused kernels' weight bundles at the end of this file name the matrices their streams are packed from):
+// spelled here only.  The one-tensor converters' are <tag><key>; part: 'w' the matrix, 'c' / 'b' its fp32 vectors
+static const char* const TAG_LIN = "lin:";
+static const char* const TAG_GEGLU = "geglu:";
+static std::string ln_name(char part, const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys, const std::string& ln) {      // "lnw:" "lnc:" "lnb:"
+  std::string name = std::string("ln") + part + ":" + ln + "|";
+  for (auto& k : wkeys) name += k + "|";
+  for (auto& k : bkeys) name += k + "|";
+  return name;
+}
+static std::string fold_name(char part, const std::string& ff2, const std::string& po) {      // "foldw:" "foldb:"
+  return std::string("fold") + part + ":" + po + ".weight|" + po + ".bias|" + ff2 + ".weight|" + ff2 + ".bias";
 }
 
 WeightStore::~WeightStore() {
@@ -210,7 +224,7 @@ const bf16* WeightStore::w_layout(const bf16* w, int N, int K, int layout) {
 
 const bf16* WeightStore::w_linear(const std::string& key, int N, int K) {
   const size_t n = (size_t)N * K;
-  return (const bf16*)convert<uint16_t>("lin:", key, {N, K}, n, [&](const float* s, uint16_t* h) { for (size_t i = 0; i < n; ++i) h[i] = f2bf_host(s[i]); });
+  return (const bf16*)convert<uint16_t>(TAG_LIN, key, {N, K}, n, [&](const float* s, uint16_t* h) { for (size_t i = 0; i < n; ++i) h[i] = f2bf_host(s[i]); });
 }
 const bf16* WeightStore::w_linear_cat(const std::vector<std::string>& keys, int Neach, int K) {
   std::string name = "cat:";
@@ -241,26 +255,19 @@ WeightStore::Stacked WeightStore::w_temb_projection(const std::string& tag, cons
 // The igemm accumulates the row statistics of x itself (gemm.hip, LNF), so no LayerNorm pass touches HBM.
 // wkeys: matrices [Neach][K] stacked along N (fused q|k|v); bkeys: their biases (empty = none);
 // geglu: single [2*Neach][K] projection with the value/gate row interleave of w_geglu.
-// need_w = false: only c / b' are wanted (the matrix was packed into a kernel's weight stream and dropped again)
 WeightStore::LnW WeightStore::w_ln_linear(const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys, const std::string& ln, int Neach,
-                                          int K, bool geglu, bool need_w) {
-  std::string name = ln + "|";
+                                          int K, bool geglu) {
   const int rows_each = geglu ? 2 * Neach : Neach;
-  for (auto& k : wkeys) { check_shape(k, need(k), {rows_each, K}); name += k + "|"; }
-  for (auto& k : bkeys) { check_shape(k, need(k), {rows_each}); name += k + "|"; }
+  for (auto& k : wkeys) check_shape(k, need(k), {rows_each, K});
+  for (auto& k : bkeys) check_shape(k, need(k), {rows_each});
   check_shape(ln + ".weight", need(ln + ".weight"), {K});
   check_shape(ln + ".bias", need(ln + ".bias"), {K});
   LnW r{nullptr, nullptr, nullptr};
   if (dry) return r;
-  const std::string nw = "lnw:" + name, nc = "lnc:" + name, nb = "lnb:" + name;
-  {
-    auto it = dev.find(nw), ic = dev.find(nc), ib = dev.find(nb);
-    if (ic != dev.end() && ib != dev.end() && (it != dev.end() || !need_w)) {
-      r.w = it != dev.end() ? (const bf16*)it->second.ptr : nullptr; r.c = (const float*)ic->second.ptr; r.b = (const float*)ib->second.ptr;
-      return r;
-    }
-    erase(nw); erase(nc); erase(nb);                               // partly present (matrix dropped after a stream pack): rebuild all three
-  }
+  const std::string nw = ln_name('w', wkeys, bkeys, ln), nc = ln_name('c', wkeys, bkeys, ln), nb = ln_name('b', wkeys, bkeys, ln);
+  auto it = dev.find(nw), ic = dev.find(nc), ib = dev.find(nb);
+  if (it != dev.end() && ic != dev.end() && ib != dev.end()) return LnW{(const bf16*)it->second.ptr, (const float*)ic->second.ptr, (const float*)ib->second.ptr};
+  erase(nw); erase(nc); erase(nb);                                 // partly present (matrix dropped after a stream pack): rebuild all three
   const HostTensor& g = data_of(ln + ".weight");
   const HostTensor& be = data_of(ln + ".bias");
   const size_t N = (size_t)rows_each * wkeys.size();
@@ -314,7 +321,7 @@ const float* WeightStore::pe_projection(const std::vector<std::string>& wkeys, i
 // FeedForward.net.2 followed by proj_out (only the residual add of the block between them) folded into one Linear over the
 // concatenated operand [t | g]: Wc = [Wpo | Wpo Wff2] ([C][5C] bf16), bc = bpo + Wpo bff2.  The C x C x 4C product runs on the device
 // in fp32 (fold_linear_pair_kernel), once per plan of new weights.
-WeightStore::FoldW WeightStore::w_fold_ff_proj(const std::string& ff2, const std::string& po, int C, bool need_w) {
+WeightStore::FoldW WeightStore::w_fold_ff_proj(const std::string& ff2, const std::string& po, int C) {
   const int J = 4 * C;
   check_shape(ff2 + ".weight", need(ff2 + ".weight"), {C, J});
   check_shape(ff2 + ".bias", need(ff2 + ".bias"), {C});
@@ -322,11 +329,9 @@ WeightStore::FoldW WeightStore::w_fold_ff_proj(const std::string& ff2, const std
   check_shape(po + ".bias", need(po + ".bias"), {C});
   FoldW r{nullptr, nullptr};
   if (dry) return r;
-  const std::string nw = "foldw:" + po + ".weight|" + po + ".bias|" + ff2 + ".weight|" + ff2 + ".bias";
-  const std::string nb = "foldb:" + po + ".weight|" + po + ".bias|" + ff2 + ".weight|" + ff2 + ".bias";
-  auto it = dev.find(nw);
-  auto itb = dev.find(nb);
-  if (itb != dev.end() && (it != dev.end() || !need_w)) { r.w = it != dev.end() ? (const bf16*)it->second.ptr : nullptr; r.b = (const float*)itb->second.ptr; return r; }
+  const std::string nw = fold_name('w', ff2, po), nb = fold_name('b', ff2, po);
+  auto it = dev.find(nw), itb = dev.find(nb);
+  if (it != dev.end() && itb != dev.end()) return FoldW{(const bf16*)it->second.ptr, (const float*)itb->second.ptr};
   if (itb != dev.end()) erase(nb);                                 // bias kept, matrix dropped after a stream pack: rebuild both
   const HostTensor& W2 = data_of(po + ".weight");
   const HostTensor& B2 = data_of(po + ".bias");
@@ -352,7 +357,7 @@ WeightStore::FoldW WeightStore::w_fold_ff_proj(const std::string& ff2, const std
 }
 // GEGLU projection [2*inner][K]: rows permuted so each 32-row group is 16 value rows then their 16 gate rows
 const bf16* WeightStore::w_geglu(const std::string& key, int inner, int K) {
-  return (const bf16*)convert<uint16_t>("geglu:", key, {2 * inner, K}, (size_t)2 * inner * K, [&](const float* s, uint16_t* h) {
+  return (const bf16*)convert<uint16_t>(TAG_GEGLU, key, {2 * inner, K}, (size_t)2 * inner * K, [&](const float* s, uint16_t* h) {
     for (int n = 0; n < 2 * inner; ++n) {
       const int src = geglu_src_row(n, inner);
       for (int k = 0; k < K; ++k) h[(size_t)n * K + k] = f2bf_host(s[(size_t)src * K + k]);
@@ -436,6 +441,84 @@ const float* WeightStore::b_ln_pe(const std::string& ln, int F, int C) {
       for (int i = 0; i < C; ++i) h[(size_t)pos * C + i] = be.data[i] + h[(size_t)pos * C + i];
     return upload(name, h.data(), h.size() * 4);
   });
+}
+
+// ------------------------------------------------------------------ the weights of the fused transformer kernels
+// c / b' of a LayerNorm fold (no biases) and bc of a FeedForward fold for a kernel whose stream holds the matrix: the vectors stay resident when
+// the matrix goes, so they alone answer; the converter (which also checks the shapes, all the sizing pass wants) only where they are missing
+WeightStore::LnW WeightStore::ln_vectors(const std::vector<std::string>& wkeys, const std::string& ln, int Neach, int K) {
+  auto ic = dev.find(ln_name('c', wkeys, {}, ln)), ib = dev.find(ln_name('b', wkeys, {}, ln));
+  if (!dry && ic != dev.end() && ib != dev.end()) return LnW{nullptr, (const float*)ic->second.ptr, (const float*)ib->second.ptr};
+  return w_ln_linear(wkeys, {}, ln, Neach, K, false);
+}
+const float* WeightStore::fold_bias(const std::string& ff2, const std::string& po, int C) {
+  auto ib = dev.find(fold_name('b', ff2, po));
+  return (!dry && ib != dev.end()) ? (const float*)ib->second.ptr : w_fold_ff_proj(ff2, po, C).b;
+}
+// ffpanel.hip: one stage stream from the GEGLU matrix and the folded net.2 | proj_out matrix
+WeightStore::FfFusedW WeightStore::ff_fused_weights(const std::string& ln, const std::string& ff, const std::string& po, int C) {
+  const int inner = 4 * C;
+  const std::string w1 = ff + ".net.0.proj.weight", ff2 = ff + ".net.2";
+  check_shape(w1, need(w1), {2 * inner, C});
+  FfFusedW r{};
+  r.b1 = b_geglu(ff + ".net.0.proj.bias", inner); r.gamma = w_f32(ln + ".weight", C); r.beta = w_f32(ln + ".bias", C);
+  bool packed_now = false;
+  r.stream = (const bf16*)packed("ffs:" + w1 + "|" + ff2 + ".weight|" + ff2 + ".bias|" + po + ".weight|" + po + ".bias", nr_ff_stream_bytes(C), [&](void* d) {
+    const bf16* wg = w_geglu(w1, inner, C);
+    LAUNCH_OK(nr_launch_ff_stream_pack(wg, w_fold_ff_proj(ff2, po, C).w, (bf16*)d, nullptr));
+    packed_now = true;
+  }, {TAG_GEGLU + w1});
+  if (packed_now) erase(fold_name('w', ff2, po));      // the folded matrix goes again in any case (also one an earlier plan had made), the folded bias stays
+  r.bc = fold_bias(ff2, po, C);
+  return r;
+}
+// xattn.hip: to_q and to_out as one stream
+WeightStore::XattnFusedW WeightStore::xattn_fused_weights(const std::string& b, int C) {
+  const std::string wq = b + ".attn2.to_q.weight", wo = b + ".attn2.to_out.0.weight";
+  for (auto& k : {wq, wo}) check_shape(k, need(k), {C, C});
+  const void* ws = packed("xas:" + wq + "|" + wo, nr_xattn_wstream_bytes(), [&](void* d) {
+    const bf16* q = w_linear(wq, C, C);
+    LAUNCH_OK(nr_launch_xattn_w_pack(q, w_linear(wo, C, C), (bf16*)d, nullptr));
+  }, {TAG_LIN + wq, TAG_LIN + wo});
+  return {.wstream = (const bf16*)ws, .gamma = w_f32(b + ".norm2.weight", C), .beta = w_f32(b + ".norm2.bias", C), .bo = w_f32(b + ".attn2.to_out.0.bias", C)};
+}
+// tattn.hip: to_q, to_k, to_v and to_out as one stream; gb = LayerNorm bias + positional encoding of the F frames
+WeightStore::TattnFusedW WeightStore::tattn_fused_weights(const std::string& ln, const std::string& ab, int F, int C) {
+  std::vector<std::string> wk, in;
+  for (const char* wn : {".to_q.weight", ".to_k.weight", ".to_v.weight", ".to_out.0.weight"}) { wk.push_back(ab + wn); in.push_back(TAG_LIN + wk.back()); }
+  for (auto& k : wk) check_shape(k, need(k), {C, C});
+  const void* ws = packed("tas:" + wk[0] + "|" + wk[1] + "|" + wk[2] + "|" + wk[3], nr_tattn_stream_bytes(), [&](void* d) {
+    const bf16* wm[4];
+    for (int i = 0; i < 4; ++i) wm[i] = w_linear(wk[i], C, C);
+    LAUNCH_OK(nr_launch_tattn_stream_pack(wm[0], wm[1], wm[2], wm[3], (bf16*)d, nullptr));
+  }, in);
+  return {.stream = (const bf16*)ws, .gb = b_ln_pe(ln, F, C), .gamma = w_f32(ln + ".weight", C), .bo = w_f32(ab + ".to_out.0.bias", C)};
+}
+// xattnw.hip: the stream from the LayerNorm-folded to_q matrix, the table from the fold's vectors
+WeightStore::HeadW WeightStore::xattn_head_weights(const std::string& ln, const std::string& wq, int C) {
+  if (dry) (void)ln_vectors({wq}, ln, C, C);      // shape checks in the sizing pass too
+  const void* ws = packed("xaws:" + ln + "|" + wq, nr_xattnw_wstream_bytes(C), [&](void* d) {
+    LAUNCH_OK(nr_launch_xattnw_w_pack(w_ln_linear({wq}, {}, ln, C, C, false).w, C, (bf16*)d, nullptr));
+  }, {ln_name('w', {wq}, {}, ln)});
+  const void* tb = packed("xawt:" + ln + "|" + wq, nr_xattnw_table_bytes(C), [&](void* d) {
+    const LnW lw = ln_vectors({wq}, ln, C, C);
+    LAUNCH_OK(nr_launch_xattnw_table_pack(lw.c, lw.b, C, (float*)d, nullptr));
+  });
+  return {(const bf16*)ws, (const float*)tb};
+}
+// tattnw.hip: the stream from the LayerNorm-folded q|k|v matrix; the head-major epilogue table (the fold's vectors + the positional-encoding projections of
+// the first F positions) the kernel stages through LDS: one per frame count a handle was planned with
+WeightStore::HeadW WeightStore::tattn_head_weights(const std::string& ln, const std::vector<std::string>& wqkv, int C, int F, int max_len) {
+  const float* rv = pe_projection(wqkv, C, C, max_len);
+  const std::string keys = ln + "|" + wqkv[0] + "|" + wqkv[1] + "|" + wqkv[2];
+  const void* ws = packed("taws:" + keys, nr_tattnw_stream_bytes(C), [&](void* d) {
+    LAUNCH_OK(nr_launch_tattnw_stream_pack(w_ln_linear(wqkv, {}, ln, C, C, false).w, C, (bf16*)d, nullptr));
+  }, {ln_name('w', wqkv, {}, ln)});
+  const void* tb = packed("tawe:" + std::to_string(max_len) + ":" + std::to_string(F) + ":" + keys, nr_tattnw_table_bytes(C, F), [&](void* d) {
+    const LnW lw = ln_vectors(wqkv, ln, C, C);
+    LAUNCH_OK(nr_launch_tattnw_table_pack(lw.c, lw.b, rv, C, F, (float*)d, nullptr));
+  });
+  return {(const bf16*)ws, (const float*)tb};
 }
 
 }  // namespace nre

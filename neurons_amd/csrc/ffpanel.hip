@@ -434,16 +434,16 @@ extern "C" int nr_launch_ff_stream_pack(const bf16* w1, const bf16* wc, bf16* st
   return 0;
 }
 
-extern "C" int nr_launch_ff_fused(const bf16* t, int ldt, const bf16* x, int ldx, bf16* out, int ldo, int M, const bf16* stream,
-                                  const float* gamma, const float* beta, const float* b1, const float* bc, float ln_eps, int norot, int waves, hipStream_t s) {
-  if (M <= 0 || !nr_ff_fused_supported(FF_C, ldt, ldx, ldo)) return 1;
+extern "C" int nr_launch_ff_fused(const NrFfFusedParams* a, hipStream_t s) {
+  const int M = a->M;
+  if (M <= 0 || !nr_ff_fused_supported(FF_C, a->ldt, a->ldx, a->ldo)) return 1;
   NrFFParams p;
-  p.t = t; p.ldt = ldt; p.x = x; p.ldx = ldx; p.out = out; p.ldo = ldo; p.M = M; p.stream = stream; p.gamma = gamma; p.beta = beta; p.b1 = b1; p.bc = bc;
-  p.ln_eps = ln_eps; p.norot = norot;
+  p.t = a->t; p.ldt = a->ldt; p.x = a->x; p.ldx = a->ldx; p.out = a->out; p.ldo = a->ldo; p.M = M; p.stream = a->stream; p.gamma = a->gamma; p.beta = a->beta; p.b1 = a->b1;
+  p.bc = a->bc; p.ln_eps = a->ln_eps; p.norot = a->norot;
   constexpr size_t shm = (size_t)FF_NS * FF_STAGE * sizeof(bf16) + (size_t)8 * FF_C * sizeof(float);
   if (const int rc = nr_lds_opt_in(g_ff_attr, {(const void*)ff_fused_kernel<2>, (const void*)ff_fused_kernel<1>}, shm)) return rc;
   const unsigned grid = (unsigned)((M + FF_ROWS - 1) / FF_ROWS);
-  if (waves == 4) hipLaunchKernelGGL(ff_fused_kernel<2>, dim3(grid), dim3(256), shm, s, p);
+  if (a->waves == 4) hipLaunchKernelGGL(ff_fused_kernel<2>, dim3(grid), dim3(256), shm, s, p);
   else hipLaunchKernelGGL(ff_fused_kernel<1>, dim3(grid), dim3(512), shm, s, p);
   return 0;
 }

@@ -1,6 +1,6 @@
-// The one declaration of every launcher, eligibility rule and size function that crosses a translation unit of this library.
-// Included by the file that defines a function and by every file that calls it, so the compiler checks each definition against the
-// prototype its callers see (the names are extern "C": a mismatch would otherwise link cleanly).
+// The one declaration of every launcher, eligibility rule and size function that crosses a translation unit of this library.  Included by the file that defines a
+// function and by every file that calls it, so the compiler checks each definition against the prototype its callers see (the names are extern "C": a mismatch would
+// otherwise link cleanly).  A long launch description is a struct of common.h, filled by field name (GEMM, GroupNorm, attention, the five fused transformer kernels).
 #pragma once
 #include "common.h"
 #include "gemm_route.h"
@@ -84,8 +84,9 @@ bool smallm_plan(const NrGemmParams& p, SmallmPlan* pl);
 int nr_launch_smallm(const NrGemmParams* pp, const SmallmPlan* pl, const bf16* w_fm, int layout, hipStream_t stream);
 int nr_launch_smallm_w_pack(const void* w, void* out, int N, int K, hipStream_t stream);
 int nr_launch_smallm_w8_pack(const void* w, void* out, int N, int K, hipStream_t stream);      // NR_W_FRAGMAJOR_E4M3: codes, then the row scales
-// The five fused transformer kernels: X_supported = the kernel's hard shape constraints (for its launcher and its nr_op_* hook); X_eligible adds its A/B
-// switch and its row floor (for the engine's planner; rows: the launch's, one clip's under deterministic batching)
+// The five fused transformer kernels: the engine's emitter (engine_layers.hip X_block) and the nr_op_* hook both fill the kernel's struct and nr_launch_X launches it,
+// nonzero for a shape the kernel does not serve.  X_supported = the kernel's hard shape constraints (for its launcher and its hook); X_eligible adds its A/B switch
+// and its row floor (for the engine's planner; rows: the launch's, one clip's under deterministic batching)
 // xattn.hip / tattn.hip: one kernel per cross- / temporal-attention block of the C = 320 level
 size_t nr_xattn_wstream_bytes(void);
 size_t nr_xattn_kvstream_bytes(int nctx);
@@ -93,14 +94,12 @@ int nr_xattn_fused_supported(int C, int heads, int Lk, int hw);
 int nr_xattn_fused_eligible(int C, int heads, int Lk, int hw, long long rows);
 int nr_launch_xattn_w_pack(const bf16* wq, const bf16* wo, bf16* stream, hipStream_t s);
 int nr_launch_xattn_kv_pack(const bf16* kv, int ldkv, int Lk, int nctx, bf16* stream, hipStream_t s);
-int nr_launch_xattn_fused(bf16* t, int nimg, int hw, int img_per_ctx, int nctx, int Lk, const bf16* wstream, const bf16* kvstream, const float* gamma,
-                          const float* beta, const float* bo, float ln_eps, int norot, hipStream_t s);
+int nr_launch_xattn_fused(const NrXattnFusedParams* pp, hipStream_t s);
 size_t nr_tattn_stream_bytes(void);
 int nr_tattn_fused_supported(int C, int heads, int frames, int hw);
 int nr_tattn_fused_eligible(int C, int heads, int frames, int hw, long long rows);
 int nr_launch_tattn_stream_pack(const bf16* wq, const bf16* wk, const bf16* wv, const bf16* wo, bf16* stream, hipStream_t s);
-int nr_launch_tattn_fused(bf16* t, int nbatch, int frames, int hw, const bf16* stream, const float* gamma, const float* gb, const float* bo, float ln_eps,
-                          int norot, hipStream_t s);
+int nr_launch_tattn_fused(const NrTattnFusedParams* pp, hipStream_t s);
 // xattnw.hip: q projection + context attention per (64 rows, 160 columns) above the C = 320 level (C = 640 / 1280, <= 80 text tokens)
 size_t nr_xattnw_wstream_bytes(int C);
 size_t nr_xattnw_kvstream_bytes(int C, int nctx);
@@ -110,8 +109,7 @@ int nr_xattnw_eligible(int C, int heads, int Lk, int hw, long long rows);
 int nr_launch_xattnw_w_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s);
 int nr_launch_xattnw_table_pack(const float* lnc, const float* bias, int C, float* table, hipStream_t s);
 int nr_launch_xattnw_kv_pack(const bf16* kv, int ldkv, int Lk, int nctx, int C, bf16* kvs, hipStream_t s);
-int nr_launch_xattnw(const bf16* t, bf16* out, int nimg, int hw, int img_per_ctx, int nctx, int Lk, int C, const bf16* wstream, const bf16* kvstream,
-                     const float* table, float ln_eps, hipStream_t s);
+int nr_launch_xattnw(const NrXattnHeadParams* pp, hipStream_t s);
 // tattnw.hip: q|k|v projection of one head + F x F attention per (pixel group, head) above the C = 320 level (C = 640 / 1280, F = 16 / 32)
 size_t nr_tattnw_stream_bytes(int C);
 int nr_tattnw_supported(int C, int heads, int frames, int hw);
@@ -119,15 +117,14 @@ int nr_tattnw_eligible(int C, int heads, int frames, int hw, long long rows);
 int nr_launch_tattnw_stream_pack(const bf16* w_folded, int C, bf16* stream, hipStream_t s);
 size_t nr_tattnw_table_bytes(int C, int frames);
 int nr_launch_tattnw_table_pack(const float* lnc, const float* bias, const float* rowvec, int C, int frames, float* table, hipStream_t s);
-int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int frames, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s);
+int nr_launch_tattnw(const NrTattnHeadParams* pp, hipStream_t s);
 // ffpanel.hip: fused FeedForward(GEGLU) + proj_out of the C = 320 level
 size_t nr_ff_stream_bytes(int C);
 int nr_ff_fused_supported(int C, int ldt, int ldx, int ldo);
 int nr_ff_fused_eligible(int C, long long M);
 int nr_ff_waves(void);      // waves per workgroup (8 or 4) of a launch described now: nr_ff_set_waves, else NR_FF_WAVES, else 8
 int nr_launch_ff_stream_pack(const bf16* w1, const bf16* wc, bf16* stream, hipStream_t s);
-int nr_launch_ff_fused(const bf16* t, int ldt, const bf16* x, int ldx, bf16* out, int ldo, int M, const bf16* stream, const float* gamma,
-                       const float* beta, const float* b1, const float* bc, float ln_eps, int norot, int waves, hipStream_t s);
+int nr_launch_ff_fused(const NrFfFusedParams* pp, hipStream_t s);
 // elementwise.hip condembed_*: SparseCtrl image-condition embedding (first conv from the fp32 planes, small-channel MFMA convs, batch / frame broadcast)
 int nr_condembed_in_supported(int cin, int Cout);
 int nr_launch_condembed_in(const float* cond, const float* mask, int c0, int nsrc, int F, int H, int W, const int* fmap, int Fe,

@@ -438,11 +438,11 @@ extern "C" int nr_launch_tattn_stream_pack(const bf16* wq, const bf16* wk, const
   return 0;
 }
 
-extern "C" int nr_launch_tattn_fused(bf16* t, int nbatch, int frames, int hw, const bf16* stream, const float* gamma, const float* gb, const float* bo,
-                                     float ln_eps, int norot, hipStream_t s) {
+extern "C" int nr_launch_tattn_fused(const NrTattnFusedParams* a, hipStream_t s) {
+  const int nbatch = a->nbatch, frames = a->frames, hw = a->hw;
   if (nbatch <= 0 || !nr_tattn_fused_supported(TA_C, TA_HEADS, frames, hw)) return 1;
   NrTAttnParams p;
-  p.t = t; p.hw = hw; p.nbatch = nbatch; p.stream = stream; p.gamma = gamma; p.gb = gb; p.bo = bo; p.ln_eps = ln_eps; p.norot = norot;
+  p.t = a->t; p.hw = hw; p.nbatch = nbatch; p.stream = a->stream; p.gamma = a->gamma; p.gb = a->gb; p.bo = a->bo; p.ln_eps = a->ln_eps; p.norot = a->norot;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)TA_D);
   constexpr size_t shm = (size_t)TA_NS * TA_SLOT;
   if (const int rc = nr_lds_opt_in(g_ta_attr, {(const void*)tattn_fused_kernel<16>, (const void*)tattn_fused_kernel<32>}, shm)) return rc;

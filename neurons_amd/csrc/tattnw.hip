@@ -533,10 +533,11 @@ static int tattnw_launch(NrTAttnWParams& p, hipStream_t s) {
 }
 
 // t, out: [nbatch * frames * hw][C]; table: nr_tattnw_table_bytes(C, frames) packed for the same frame count
-extern "C" int nr_launch_tattnw(const bf16* t, bf16* out, int nbatch, int frames, int hw, int C, const bf16* stream, const float* table, float ln_eps, hipStream_t s) {
-  if (nbatch <= 0 || !nr_tattnw_supported(C, TW_HEADS, frames, hw)) return 1;
+extern "C" int nr_launch_tattnw(const NrTattnHeadParams* a, hipStream_t s) {
+  const int frames = a->frames, C = a->C;
+  if (a->nbatch <= 0 || !nr_tattnw_supported(C, TW_HEADS, frames, a->hw)) return 1;
   NrTAttnWParams p;
-  p.t = t; p.out = out; p.hw = hw; p.nbatch = nbatch; p.stream = stream; p.table = table; p.ln_eps = ln_eps;
+  p.t = a->t; p.out = a->out; p.hw = a->hw; p.nbatch = a->nbatch; p.stream = a->stream; p.table = a->table; p.ln_eps = a->ln_eps;
   const int d = C / TW_HEADS;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)d);
   if (C == 640) return frames == 16 ? tattnw_launch<80, 16>(p, s) : tattnw_launch<80, 32>(p, s);

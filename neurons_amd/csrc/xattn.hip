@@ -436,13 +436,13 @@ extern "C" int nr_launch_xattn_kv_pack(const bf16* kv, int ldkv, int Lk, int nct
   return 0;
 }
 
-extern "C" int nr_launch_xattn_fused(bf16* t, int nimg, int hw, int img_per_ctx, int nctx, int Lk, const bf16* wstream, const bf16* kvstream,
-                                     const float* gamma, const float* beta, const float* bo, float ln_eps, int norot, hipStream_t s) {
-  if (nimg <= 0 || img_per_ctx <= 0 || !nr_xattn_fused_supported(XA_C, XA_HEADS, Lk, hw)) return 1;
-  if ((nimg + img_per_ctx - 1) / img_per_ctx > nctx) return 3;      // the kv stream holds nctx contexts: every image's context must be one of them
+extern "C" int nr_launch_xattn_fused(const NrXattnFusedParams* a, hipStream_t s) {
+  const int nimg = a->nimg, hw = a->hw, img_per_ctx = a->img_per_ctx;
+  if (nimg <= 0 || img_per_ctx <= 0 || !nr_xattn_fused_supported(XA_C, XA_HEADS, a->Lk, hw)) return 1;
+  if ((nimg + img_per_ctx - 1) / img_per_ctx > a->nctx) return 3;      // the kv stream holds nctx contexts: every image's context must be one of them
   NrXAttnParams p;
-  p.t = t; p.hw = hw; p.nimg = nimg; p.img_per_ctx = img_per_ctx; p.Lk = Lk; p.norot = norot; p.wstream = wstream; p.kvstream = kvstream;
-  p.gamma = gamma; p.beta = beta; p.bo = bo; p.ln_eps = ln_eps;
+  p.t = a->t; p.hw = hw; p.nimg = nimg; p.img_per_ctx = img_per_ctx; p.Lk = a->Lk; p.norot = a->norot; p.wstream = a->wstream; p.kvstream = a->kvstream;
+  p.gamma = a->gamma; p.beta = a->beta; p.bo = a->bo; p.ln_eps = a->ln_eps;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)XA_D);
   constexpr size_t shm = (size_t)XA_NS * XA_SLOT;
   if (const int rc = nr_lds_opt_in(g_xa_attr, {(const void*)xattn_fused_kernel}, shm)) return rc;

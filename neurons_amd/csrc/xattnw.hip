@@ -312,12 +312,12 @@ extern "C" int nr_launch_xattnw_kv_pack(const bf16* kv, int ldkv, int Lk, int nc
   return 0;
 }
 
-extern "C" int nr_launch_xattnw(const bf16* t, bf16* out, int nimg, int hw, int img_per_ctx, int nctx, int Lk, int C, const bf16* wstream, const bf16* kvstream,
-                                const float* table, float ln_eps, hipStream_t s) {
-  if (!nr_xattnw_supported(C, XW_HEADS, Lk, hw) || nimg <= 0 || img_per_ctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > nctx) return 1;
+extern "C" int nr_launch_xattnw(const NrXattnHeadParams* a, hipStream_t s) {
+  const int nimg = a->nimg, hw = a->hw, img_per_ctx = a->img_per_ctx, C = a->C;
+  if (!nr_xattnw_supported(C, XW_HEADS, a->Lk, hw) || nimg <= 0 || img_per_ctx <= 0 || (nimg + img_per_ctx - 1) / img_per_ctx > a->nctx) return 1;
   NrXAttnWParams p;
-  p.t = t; p.out = out; p.nrows = nimg * hw; p.hw = hw; p.img_per_ctx = img_per_ctx; p.Lk = Lk; p.stream = wstream; p.kvstream = kvstream; p.table = table;
-  p.ln_eps = ln_eps;
+  p.t = a->t; p.out = a->out; p.nrows = nimg * hw; p.hw = hw; p.img_per_ctx = img_per_ctx; p.Lk = a->Lk; p.stream = a->wstream; p.kvstream = a->kvstream;
+  p.table = a->table; p.ln_eps = a->ln_eps;
   p.scale_log2e = 1.4426950408889634f / sqrtf((float)(C / XW_HEADS));
   const int nrg = p.nrows / XW_ROWS, ncb = C / XW_COLS;
   p.xcd_mode = nrg % 8 == 0 ? 0 : 1;
