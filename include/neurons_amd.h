@@ -433,7 +433,9 @@ nr_status nr_op_layernorm(nr_stream stream, const void* x_dev, void* out_dev, in
                           int32_t pe_F);
 /* mode 0: spatial self ([nimg][L][3C] fused qkv), 1: cross (q [nimg][L][C], kv [nb_kv][Lk][2C], kv_div),
  * 2: temporal self (fused qkv [(b f)][hw][3C], sequence over f); mode | 8: e4m3 MFMA operands (modes 0 and 1, L >= 48);
- * mode | 16: causal mask, query i sees keys 0..i (mode 0 alone, i.e. mode == 16; with any other mode or with | 8: NR_ERR_ARG) */
+ * mode | 16: causal mask, query i sees keys 0..i (mode 0 alone, i.e. mode == 16; with any other mode or with | 8: NR_ERR_ARG).
+ * Head widths d = C / heads: multiples of 8 up to 160 except 104 .. 112 and 136 .. 144, and the wide heads 256 and 512 (modes 0 and 1 without | 8 and
+ * | 16: the VAE mid-block's single head of 512); any other combination: NR_ERR_UNSUPPORTED before anything is launched */
 nr_status nr_op_attention(nr_stream stream, int32_t mode, const void* q_dev, const void* kv_dev, void* out_dev,
                           int32_t nimg, int32_t L, int32_t Lk, int32_t C, int32_t heads, int32_t frames, int32_t kv_div);
 

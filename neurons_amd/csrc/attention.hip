@@ -464,6 +464,215 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(NrAttnParams p) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Wide heads, d = 256 / 512: the VAE's mid-block AttnBlock (one head of d = C = 512, sgm/modules/diffusionmodules/model.py:161-201) and any
+// self- / cross-attention with heads * d = C at those widths.  Arithmetic of the block-shared kernel above: bf16 operands, fp32 logits and
+// softmax statistics, P rounded to bf16 for the second product, the denominator summed in fp32 from the rounded P, fp32 accumulation, bf16 output.
+// Addressing: NrAttnParams unchanged (fused q|k|v rows, q + shared k|v with kv_div, any head count); not served: causal, fp8, inner != 1
+// (nr_attn_route).
+// Work unit: a 256-thread workgroup = 4 waves = 64 queries of one (image, head), 16 queries per wave.  K and V tiles of 32 keys are staged
+// ONCE per workgroup into LDS (row-major, 16-byte loads -> ds_write_b128, register-prefetched one tile ahead, two LDS buffers, one barrier
+// per tile): 2 x 32 x (D + 8 + D + 16) x 2 B = 131 KiB at D = 512 -> one workgroup per CU, one wave per SIMD, so the O tile of a wave
+// (D / 16 accumulator quads = 128 registers at D = 512) and the Q fragments (64) fit the 512-entry register file.  S^T = K Q^T as above,
+// so P never leaves registers; V is consumed through ds_read_b64_tr_b16.  Every lane runs every LDS read (queries >= Lq are clamped and
+// not stored, keys >= Lk are clamped rows whose probability is 0): EXEC is all ones at the transposed reads.
+// ------------------------------------------------------------------------------------------------
+constexpr int KTW = 32;       // keys per tile
+
+// LDS row strides (elements): K rows an odd number of 16-byte units (conflict-free ds_read_b128 fragments), V rows = 16 (mod 32) elements
+// so the 8 rows a half-wave touches in one ds_read_b64_tr_b16 start 8 banks apart (as attention.hip)
+__host__ __device__ constexpr int wide_ksk(int D) { return D + 8; }
+__host__ __device__ constexpr int wide_ksv(int D) { return D + 16; }
+__host__ __device__ constexpr size_t wide_lds_bytes(int D) { return (size_t)2 * KTW * (wide_ksk(D) + wide_ksv(D)) * sizeof(bf16); }
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_wide_kernel(NrAttnParams p) {
+  static_assert(D % 64 == 0, "whole 32-wide k-steps, 16-byte chunks dealt evenly to 256 threads");
+  constexpr int DK = D / 32, DT = D / 16;
+  constexpr int KSK = wide_ksk(D), KSV = wide_ksv(D);
+  constexpr int CPK = D / 8;                   // 16-byte chunks per key row
+  constexpr int CH = KTW * CPK / 256;          // chunks per thread per matrix per tile (exact)
+  constexpr int TILEK = KTW * KSK, TILEV = KTW * KSV, TILE2 = TILEK + TILEV;   // elements per buffer
+  extern __shared__ __attribute__((aligned(16))) bf16 lds[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int qblocks = (p.Lq + 63) >> 6;
+  // XCD-aware remap (bijective, as attention.hip): the query blocks of one (image, head) read their K / V through one L2
+  int bid;
+  {
+    const int nwg = gridDim.x, orig = blockIdx.x;
+    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, local = orig >> 3;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+  }
+  const int qb = bid % qblocks;
+  const int h = (bid / qblocks) % p.heads;
+  const int nb = bid / (qblocks * p.heads);
+  const int nbkv = nb / p.kv_div;
+  const long long qbase = (long long)nb * p.q_outer + (long long)h * D;          // inner == 1 (nr_attn_route)
+  const long long obase = (long long)nb * p.o_outer + (long long)h * D;
+  const long long kbase = (long long)(nbkv / p.kv_inner) * p.kv_outer + (long long)(nbkv % p.kv_inner) * p.kv_inner_stride + (long long)h * D;
+
+  const int qrow = qb * 64 + wave * 16 + c;
+  const int qrow_c = min(qrow, p.Lq - 1);
+  // Q fragments (B operand of S^T = K Q^T): lane holds Q[query c][dim 32 ks + 8 g .. + 7]
+  bf16x8 qf[DK];
+#pragma unroll
+  for (int ks = 0; ks < DK; ++ks) qf[ks] = *(const bf16x8*)(p.q + qbase + (long long)qrow_c * p.q_seq + ks * 32 + g * 8);
+
+  // staging: each thread owns CH fixed (key-in-tile, 16-byte chunk) slots; only the last, partial tile clamps the key (the clamped rows
+  // are finite data whose probabilities are exactly 0)
+  bf16x8 rk[CH], rv[CH];
+  int s_kk[CH], s_off[CH], s_lok[CH], s_lov[CH];
+#pragma unroll
+  for (int i = 0; i < CH; ++i) {
+    const int id = tid + 256 * i;
+    const int kk = id / CPK, x0 = (id - kk * CPK) << 3;
+    s_kk[i] = kk;
+    s_lok[i] = kk * KSK + x0;
+    s_lov[i] = kk * KSV + x0;
+    s_off[i] = kk * (int)p.kv_seq + x0;
+  }
+  const bf16* kb = p.k + kbase;
+  const bf16* vb = p.v + kbase;
+  const long long tile_step = (long long)KTW * p.kv_seq;
+  auto load_regs = [&](int it) {
+    const bf16* kt = kb + (long long)it * tile_step;
+    const bf16* vtp = vb + (long long)it * tile_step;
+    const int k0 = it * KTW;
+    if (k0 + KTW <= p.Lk) {
+#pragma unroll
+      for (int i = 0; i < CH; ++i) {
+        rk[i] = *(const bf16x8*)(kt + s_off[i]);
+        rv[i] = *(const bf16x8*)(vtp + s_off[i]);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < CH; ++i) {
+        const int back = max(k0 + s_kk[i] - (p.Lk - 1), 0) * (int)p.kv_seq;
+        rk[i] = *(const bf16x8*)(kt + (s_off[i] - back));
+        rv[i] = *(const bf16x8*)(vtp + (s_off[i] - back));
+      }
+    }
+  };
+  auto write_lds = [&](int buf) {
+    bf16* sk = lds + buf * TILE2;
+    bf16* sv = sk + TILEK;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      *(bf16x8*)(sk + s_lok[i]) = rk[i];
+      *(bf16x8*)(sv + s_lov[i]) = rv[i];
+    }
+  };
+
+  f32x4 acc[DT];
+#pragma unroll
+  for (int i = 0; i < DT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_i = -1e30f, l_i = 0.f;
+
+  const int ntile = (p.Lk + KTW - 1) / KTW;
+  load_regs(0);
+  write_lds(0);
+  __syncthreads();
+  const int tq = c >> 2, tp = c & 3;          // transpose-read role inside the 16-lane group
+  const float sl2 = p.scale * 1.4426950408889634f;
+  for (int it = 0; it < ntile; ++it) {
+    const int k0 = it * KTW;
+    if (it + 1 < ntile) load_regs(it + 1);
+    const bf16* sk = lds + (it & 1) * TILE2;
+    const bf16* sv = sk + TILEK;
+    // ---- S^T = K Q^T for two 16-key tiles: s[t][r] = score of key k0 + 16 t + 4 g + r and query c ----
+    f32x4 s[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < DK; ++ks) {
+        const bf16x8 kf = *(const bf16x8*)(sk + (16 * t + c) * KSK + ks * 32 + g * 8);
+        s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s[t], 0, 0, 0);
+      }
+    }
+    // softmax in the log2 domain: exp(scale s - m) = exp2(fma(s, scale log2(e), -m2)).  Keys >= Lk of the last tile score -1e30.
+    float mx = -1e30f;
+    if (k0 + KTW <= p.Lk) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) mx = fmaxf(fmaxf(fmaxf(fmaxf(mx, s[t][0]), s[t][1]), s[t][2]), s[t][3]);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = k0 + 16 * t + 4 * g + r < p.Lk ? s[t][r] : -1e30f;
+          s[t][r] = v;
+          mx = fmaxf(mx, v);
+        }
+    }
+    // Lazy running maximum, as the block-shared kernel: a query's reference only moves when the tile's maximum exceeds it by more than
+    // 2^8, so the probabilities stay <= 256 (exact in the fp32 sums, in range for bf16) and the rescale of the O tile (DT register
+    // quads) runs on the first tile and then almost never (wave-uniform skip).  If no lane's own scores exceed its query's reference by
+    // the margin, no query's tile maximum (the maximum over that query's four lanes) does.
+    constexpr float LAZY = 8.0f;
+    mx *= sl2;                                 // sl2 > 0: the max of this lane's scaled scores
+    float m_new = m_i;
+    if (__builtin_amdgcn_ballot_w64(mx > m_i + LAZY) != 0ull) {
+      mx = nr_rows_max(mx);
+      m_new = mx > m_i + LAZY ? mx : m_i;
+      const float alpha = __builtin_amdgcn_exp2f(m_i - m_new);      // 1 for the queries whose reference stays
+      l_i *= alpha;                            // a per-lane partial sum (this lane's 8 keys of every tile); the four rows are added after the loop
+#pragma unroll
+      for (int i = 0; i < DT; ++i) acc[i] *= alpha;
+      m_i = m_new;
+    }
+    float rs = 0.f;
+    bf16x8 pf;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bf16 pb = (bf16)__builtin_amdgcn_exp2f(__builtin_fmaf(s[t][r], sl2, -m_new));   // masked keys: exp2(-huge) = 0
+        rs += (float)pb;                       // the denominator sums what the second product multiplies: the ROUNDED probabilities
+        pf[t * 4 + r] = pb;
+      }
+    l_i += rs;
+    // ---- O^T += V^T P^T : A = V^T rows dv = 16 i + c, k-slot j -> key (j < 4: 4 g + j ; j >= 4: 16 + 4 g + j - 4) ----
+#pragma unroll
+    for (int i = 0; i < DT; ++i) {
+      const bf16* a0 = sv + (4 * g + tq) * KSV + 16 * i + 4 * tp;
+      const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)a0);
+      const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(a0 + 16 * KSV));
+      bf16x8 vf;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
+      acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, acc[i], 0, 0, 0);
+    }
+    if (it + 1 < ntile) write_lds((it + 1) & 1);
+    __syncthreads();
+  }
+
+  // all lanes active here; acc[i][r] = O[query c][dv = 16 i + 4 g + r]
+  const float l_all = nr_rows_sum(l_i);
+  if (qrow < p.Lq) {
+    const float inv = 1.0f / l_all;
+    bf16* op = p.out + obase + (long long)qrow * p.o_seq;
+#pragma unroll
+    for (int i = 0; i < DT; ++i) {
+      bf16x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = (bf16)(acc[i][e] * inv);
+      nr_store8(op + i * 16 + 4 * g, o);
+    }
+  }
+}
+
+template <int D>
+int launch_wide(const NrAttnParams& p, const NrAttnRoute& r, hipStream_t stream) {
+  static unsigned long long attr_mask = 0;       // per device
+  if (const int rc = nr_lds_opt_in(attr_mask, {(const void*)attn_wide_kernel<D>}, wide_lds_bytes(D))) return rc;
+  hipLaunchKernelGGL(attn_wide_kernel<D>, dim3(r.grid), dim3(256), r.lds_bytes, stream, p);
+  return 0;
+}
+
 template <int DK, int DT>
 int launch_attn(const NrAttnParams& p, const NrAttnRoute& r, hipStream_t stream) {
   void (*k)(NrAttnParams);
@@ -485,8 +694,17 @@ int launch_attn(const NrAttnParams& p, const NrAttnRoute& r, hipStream_t stream)
 
 extern "C" int nr_attn_route(const NrAttnParams* pp, NrAttnRoute* r) {
   const NrAttnParams& p = *pp;
-  if (p.d % 8 != 0 || p.d > 160 || p.d <= 0) return 1;
+  const bool wide = p.d == 256 || p.d == 512;      // attn_wide_kernel
+  if (p.d % 8 != 0 || (p.d > 160 && !wide) || p.d <= 0) return 1;
   if (p.Lq <= 0 || p.Lk <= 0 || p.nbatch <= 0) return 2;
+  if (wide) {
+    if (p.causal || p.fp8 || p.inner != 1) return 4;      // the wide kernel: bf16, unmasked, one sequence per batch entry
+    *r = NrAttnRoute{};
+    r->cls = NR_ATTN_WIDE; r->dk = p.d / 32; r->dt = p.d / 16;
+    r->lds_bytes = wide_lds_bytes(p.d);
+    r->grid = (unsigned)((long long)p.nbatch * p.heads * ((p.Lq + 63) / 64));
+    return 0;
+  }
   const int DK = (p.d + 31) / 32, DT = (p.d + 15) / 16;
   if (DT == 7 || DT == 9) return 3;                // d = 104 .. 112, 136 .. 144: not instantiated (nr_launch_attention)
   *r = NrAttnRoute{};
@@ -507,6 +725,10 @@ extern "C" int nr_attn_route(const NrAttnParams* pp, NrAttnRoute* r) {
 }
 
 extern "C" int nr_launch_attention(const NrAttnParams* pp, const NrAttnRoute* r, hipStream_t stream) {
+  if (r->cls == NR_ATTN_WIDE) {
+    if ((pp->d != 256 && pp->d != 512) || r->lds_bytes != wide_lds_bytes(pp->d)) return 3;
+    return pp->d == 256 ? launch_wide<256>(*pp, *r, stream) : launch_wide<512>(*pp, *r, stream);
+  }
   // by dt = ceil(d / 16): the head dims on the path (40, 80, 160) plus small ones used by reduced-width tests
   static int (*const fn[11])(const NrAttnParams&, const NrAttnRoute&, hipStream_t) = {nullptr, launch_attn<1, 1>, launch_attn<1, 2>, launch_attn<2, 3>, launch_attn<2, 4>,
                                                                                      launch_attn<3, 5>, launch_attn<3, 6>, nullptr, launch_attn<4, 8>, nullptr, launch_attn<5, 10>};

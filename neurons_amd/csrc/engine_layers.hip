@@ -205,8 +205,10 @@ Act nr_net::layernorm(const Act& x, const std::string& prefix, const float* pe, 
 // mode 0 spatial self (qkv fused [M][3C]); 1 cross (q [M][C], kv [B2*ctx][2C]); 2 temporal self (qkv fused)
 Act nr_net::attention(int mode, const Act& q, const Act* kv, int C, int heads, int causal) {
   Act out = new_act(q.nimg, q.H, q.W, C);
+  // e4m3 operands: the U-Net's spatial / cross attention only (nr_net_set_attention_fp8 never changed what a VAE handle computes)
+  const bool vae = cfg.kind == NR_KIND_VAE_DECODER || cfg.kind == NR_KIND_VAE_ENCODER;
   const NrAttnParams p = nr_attn_params(mode, q.ptr, kv ? kv->ptr : nullptr, out.ptr, q.ld, kv ? kv->ld : 0, out.ld, q.nimg, q.H * q.W, ctx_len, C, heads, F,
-                                        F, causal, (attn_fp8 && mode != 2) ? 1 : 0);
+                                        F, causal, (attn_fp8 && mode != 2 && !vae) ? 1 : 0);
   NrAttnRoute r;
   LAUNCH_OK(nr_attn_route(&p, &r));
   const double flops = 4.0 * (double)p.nbatch * p.heads * (double)p.Lq * p.Lk * p.d;
@@ -521,12 +523,39 @@ Act nr_net::temporal_module(const Act& x, const std::string& pre0) {
 }
 
 // AttnBlock (model.py:161-201): GroupNorm -> q,k,v 1x1 convs -> single-head softmax(q k^T / sqrt(C)) v -> proj_out
-// + x.  The head dimension is the full channel count (512), beyond the flash kernels' register budget, so the
-// block is expressed as MFMA GEMMs per image: S = Q K^T (fp32 scores), row softmax -> bf16 P, O = P V.  V is
-// produced already transposed (V^T = Wv . Xn^T, i.e. the igemm with the weight as the "activation" operand); its
-// bias moves to the P V epilogue because every softmax row sums to one.
+// + x.  The head dimension is the full channel count.  Two forms:
+//  * wide: one q|k|v Linear over all images, ONE attention launch on the wide-head flash kernel (attention.hip, NR_ATTN_WIDE: C = 256 / 512) and proj_out;
+//    any h*w, no score scratch;
+//  * GEMM sequence, per image: S = Q K^T (fp32 scores), row softmax -> bf16 P, O = P V; h*w a multiple of 64.  V is produced already transposed
+//    (V^T = Wv . Xn^T, i.e. the igemm with the weight as the "activation" operand); its bias moves to the P V epilogue because every softmax row sums to one.
+// Default: wide where the route serves C and either the GEMM sequence refuses the latent (h*w % 64 != 0) or the launch has a workgroup for every CU
+// (nimg * ceil(h*w / 64) >= 256: the 16 x 1024-token clip, 0.11 ms against 16 x 0.044 ms).  With fewer workgroups the wide kernel's time is one
+// workgroup's walk over all keys whatever the image count: at the 9216-token keyframe (144 workgroups) 0.81 ms against 0.47 ms for the GEMMs, so
+// such shapes stay on the GEMM sequence (profiles/r09_vae_attn_wide_ab.txt).  NR_VAE_ATTN_WIDE=0: never wide; =1: wide for every shape the route
+// serves.  Read when the launch is described (each plan).
+static bool vae_attn_wide(int C, int nimg, int hw) {
+  const char* sw = getenv("NR_VAE_ATTN_WIDE");
+  if (sw && sw[0] == '0') return false;
+  NrAttnParams p{};      // what the route reads of a single-head bf16 self-attention (the tensors come with the real launch, nr_net::attention)
+  p.nbatch = nimg; p.heads = 1; p.d = C; p.Lq = p.Lk = hw; p.inner = p.kv_inner = p.kv_div = 1;
+  NrAttnRoute r;
+  if (nr_attn_route(&p, &r) != 0 || r.cls != NR_ATTN_WIDE) return false;
+  if (sw && sw[0] == '1') return true;
+  return hw % 64 != 0 || r.grid >= 256u;
+}
 Act nr_net::vae_attn(const Act& x, const std::string& pre) {
   const int C = x.C, hw = x.H * x.W;
+  if (vae_attn_wide(C, x.nimg, hw)) {
+    Act hn = groupnorm(x, nullptr, pre + ".norm", cfg.norm_eps, 0);
+    GemmOpt oq; oq.bias = wts.b_cat({pre + ".q.bias", pre + ".k.bias", pre + ".v.bias"}, C);
+    Act qkv = linear(hn, wts.w_linear_cat({pre + ".q.weight", pre + ".k.weight", pre + ".v.weight"}, C, C), 3 * C, oq);
+    hn = Act();
+    Act o = attention(0, qkv, nullptr, C, 1);
+    qkv = Act();
+    Act out = linear_wb(o, pre + ".proj_out", C, &x);
+    tap(pre, out);
+    return out;
+  }
   if (hw % 64 != 0) throw NrError(NR_ERR_UNSUPPORTED, "VAE attention: latent h*w must be a multiple of 64");
   Act hn = groupnorm(x, nullptr, pre + ".norm", cfg.norm_eps, 0);
   Act q = linear_wb(hn, pre + ".q", C);

@@ -10,8 +10,9 @@
 // kernel (<= maxp channel pairs per thread) or the chunked stats [+ finalize] + apply passes; its kernel count and the floats `partial` must hold
 enum NrGnKind { NR_GN_SLAB, NR_GN_SMALL, NR_GN_CHUNKED };
 struct NrGnRoute { int kind, gs, nv, threads, maxp, pix_per_blk, nchunk, finalized, lds_stats, lds_apply, launches, ws_floats; };
-// attention.hip: K/V tiles per wave (short, strided or causal sequences) or shared by the block (there only: e4m3 operands, the ones column of V at d = 40)
-enum NrAttnClass { NR_ATTN_WAVE, NR_ATTN_SHARED };
+// attention.hip: K/V tiles per wave (short, strided or causal sequences) or shared by the block (there only: e4m3 operands, the ones column of V at d = 40);
+// NR_ATTN_WIDE: the wide heads d = 256 / 512 (bf16, not causal, inner == 1), 64 queries per workgroup on 32-key tiles
+enum NrAttnClass { NR_ATTN_WAVE, NR_ATTN_SHARED, NR_ATTN_WIDE };
 struct NrAttnRoute { int cls, dk, dt, fp8, ones; unsigned grid; size_t lds_bytes; };      // dk / dt: 32- / 16-wide tiles of the head dim
 extern "C" {
 // gemm.hip: the route of a GEMM / conv launch (gemm_route.h) and the tiled implicit GEMM (1x1 / 3x3) with its split-K scratch.

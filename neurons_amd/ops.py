@@ -241,7 +241,9 @@ def _attn_out(out, shape, like):
 
 
 def attention_self(qkv, heads, fp8=False, causal=False, out=None):
-    """qkv: [nimg, L, 3C] fused; returns [nimg, L, C].  fp8: OCP e4m3 MFMA operands (L >= 48; BASELINE config 5).
+    """qkv: [nimg, L, 3C] fused; returns [nimg, L, C].  Head widths d = C / heads: multiples of 8 up to 160 (104 .. 112 and 136 .. 144 excepted)
+    and the wide heads 256 and 512 (the VAE mid-block's single head; bf16 and unmasked only: not with fp8 or causal); any other width raises.
+    fp8: OCP e4m3 MFMA operands (L >= 48; BASELINE config 5).
     causal: query i sees keys 0..i (the CLIP text encoder's mask; not with fp8).  out: write the result into this tensor."""
     _chk_bf16(qkv)
     nimg, L, C3 = qkv.shape
@@ -253,7 +255,7 @@ def attention_self(qkv, heads, fp8=False, causal=False, out=None):
 
 
 def attention_cross(q, kv, heads, kv_div, fp8=False, out=None):
-    """q: [nimg, L, C]; kv: [nb, Lk, 2C] fused; image n attends to kv[n // kv_div].  fp8, out as in attention_self."""
+    """q: [nimg, L, C]; kv: [nb, Lk, 2C] fused; image n attends to kv[n // kv_div].  Head widths, fp8, out as in attention_self."""
     _chk_bf16(q, kv)
     nimg, L, Cc = q.shape
     Lk = kv.shape[1]
@@ -264,7 +266,8 @@ def attention_cross(q, kv, heads, kv_div, fp8=False, out=None):
 
 
 def attention_temporal(qkv, heads, frames, out=None):
-    """qkv: [(b f), hw, 3C] fused; attention runs over f for every (b, pixel); returns [(b f), hw, C].  out as in attention_self."""
+    """qkv: [(b f), hw, 3C] fused; attention runs over f for every (b, pixel); returns [(b f), hw, C].  Head widths up to 160 (the wide heads
+    256 / 512 have no temporal form).  out as in attention_self."""
     _chk_bf16(qkv)
     nimg, hw, C3 = qkv.shape
     Cc = C3 // 3
