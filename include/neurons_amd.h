@@ -412,6 +412,15 @@ nr_status nr_op_gemm_ex(nr_stream stream, const void* a_dev, int32_t lda, const 
 nr_status nr_op_conv3x3(nr_stream stream, const void* x0_dev, int32_t c0, const void* x1_dev, int32_t c1, int32_t nimg,
                         int32_t H, int32_t W, int32_t stride, int32_t ups, const void* w_dev, const float* bias_dev,
                         const float* rowvec_dev, int32_t rowvec_div, const void* res_dev, void* out_dev, int32_t Cout);
+/* The nearest-2x upsample + 3x3 conv (nr_op_conv3x3 with ups = 1, one source, stride 1) in PHASE form: four 2x2 convs on the source image, one per output
+ * parity (py, px), 4/9 of the multiply-adds.  wp_dev: bf16 [4 phases = 2 py + px][Cout][4 taps = 2 a + b][Cin] as nr_ups_phase_weights makes it;
+ * Cin % 64 == 0, Cout % 32 == 0; out [nimg][2 H][2 W][Cout]. */
+nr_status nr_op_conv3x3_ups_phase(nr_stream stream, const void* x_dev, int32_t Cin, int32_t nimg, int32_t H, int32_t W, const void* wp_dev,
+                                  const float* bias_dev, void* out_dev, int32_t Cout);
+/* HOST memory both ways: fp32 taps [Cout][3][3][Cin] -> the bf16 phase weights above (16 Cout Cin elements).  Tap (a, b) of phase (py, px) is the sum
+ * over ky in R(py, a), kx in R(px, b) of tap (ky, kx), R(0,0) = {0}, R(0,1) = {1,2}, R(1,0) = {0,1}, R(1,1) = {2}; summed in fp32, rounded once.  The
+ * engine converts its checkpoint weights with the same code. */
+nr_status nr_ups_phase_weights(const float* w_tap_host, int32_t Cout, int32_t Cin, void* out_host);
 /* SparseCtrl image-condition embedding layers (condembed_* in elementwise.hip).  nr_op_condembed_in: the first 3x3 conv + SiLU from fp32 NCFHW
  * cond [nsrc][c0][F][H][W] and mask [nsrc][1][F][H][W] (frames fmap[0..nframes), host array) to bf16 [nsrc * nframes][H][W][Cout],
  * weight fp32 [(c0 + 1) * 9][Cout], Cout 16 / 32.  nr_op_condembed_conv: 3x3 pad-1 conv (stride 1 / 2) bf16 [nimg][H][W][Cin] ->

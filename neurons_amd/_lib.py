@@ -127,6 +127,8 @@ SYMBOLS = {
     "nr_op_gemm_ex": (_I32, [_VP, _VP, _I32, _VP, _VP, _VP, C.c_float, _VP, _I32, _I32, _I32, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _I32, _I32,
                              C.c_float]),
     "nr_op_conv3x3": (_I32, [_VP, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _VP, _I32]),
+    "nr_op_conv3x3_ups_phase": (_I32, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32]),
+    "nr_ups_phase_weights": (_I32, [_VP, _I32, _I32, _VP]),
     "nr_op_condembed_in": (_I32, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, C.POINTER(_I32), _I32, _VP, _VP, _I32, _VP]),
     "nr_op_condembed_conv": (_I32, [_VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP]),
     "nr_op_conv3x3_tap_inner": (_I32, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _VP, _I32]),

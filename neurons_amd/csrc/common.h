@@ -90,7 +90,9 @@ struct NrGemmParams {
   int OH, OW;          // output spatial size
   int ksize;           // 1 or 3 (3 => pad 1)
   int stride;          // 1 or 2
-  int ups;             // 1: source is nearest-2x upsampled before the 3x3 conv
+  int ups;             // 1: source is nearest-2x upsampled before the 3x3 conv; 2: the same conv in PHASE form (tiled igemm only): four 2x2 convs on the
+                       // source, one per output parity (py, px), w = [phase 2 py + px][N][tap 2 a + b][Cin] with the 3x3 taps that read the same source
+                       // pixel summed (nr_ups_phase_pack, engine.h), K = 4 Cin; H, W, OH, OW, M as for ups = 1; no second source / res / rowvec / geglu / ln_c / out_f32
   const bf16* w;       // [N][K] bf16, K = ksize*ksize*(c0+c1), tap-major (ky,kx,c)
   int M, N, K;
   const float* bias;   // [N] fp32 or null
@@ -231,7 +233,7 @@ inline NrGemmParams nr_gemm_params(const bf16* a0, int c0, int lda0, const bf16*
   nr_conv_out_hw(H, W, ksize, stride, ups, &p.OH, &p.OW);
   p.ksize = ksize; p.stride = stride; p.ups = ups;
   p.w = w;
-  p.M = nimg * p.OH * p.OW; p.N = N; p.K = ksize * ksize * (p.c0 + p.c1);
+  p.M = nimg * p.OH * p.OW; p.N = N; p.K = (ups == 2 ? 4 : ksize * ksize) * (p.c0 + p.c1);
   p.bias = bias; p.rowvec_div = 1;
   p.res = res; p.ldr = ldr;
   p.out = out; p.ldo = ldo; p.out_scale = 1.f;

@@ -70,6 +70,26 @@ inline uint16_t f2bf_host(float f) {
   return (uint16_t)(u >> 16);
 }
 
+// Phase-form weights of a nearest-2x upsample + 3x3 conv (NrGemmParams::ups == 2) from its fp32 taps w[o][c][k] at w[o * so + c * sc + k * sk], k = 3 ky + kx:
+// out[((2 py + px) * Cout + o) * 4 + (2 a + b)][c] = bf16( sum_{ky in R(py, a)} sum_{kx in R(px, b)} w[o][c][3 ky + kx] ), R(0,0) = {0}, R(0,1) = {1, 2},
+// R(1,0) = {0, 1}, R(1,1) = {2}: the taps of output pixel (2 y + py, 2 x + px) that read source pixel (y + a + py - 1, x + b + px - 1).  Summed in fp32 in
+// the order (ky, kx) ascending, rounded once.  The one implementation: the engine's converter and the C ABI both call it
+inline void nr_ups_phase_pack(const float* w, size_t so, size_t sc, size_t sk, int Cout, int Cin, uint16_t* out) {
+  static const int lo[2][2] = {{0, 1}, {0, 2}}, hi[2][2] = {{0, 2}, {1, 2}};      // R(p, a) = [lo[p][a], hi[p][a]]
+  for (int ph = 0; ph < 4; ++ph)
+    for (int o = 0; o < Cout; ++o)
+      for (int t = 0; t < 4; ++t) {
+        const int py = ph >> 1, px = ph & 1, a = t >> 1, b = t & 1;
+        uint16_t* dst = out + (((size_t)ph * Cout + o) * 4 + t) * Cin;
+        for (int c = 0; c < Cin; ++c) {
+          float acc = 0.f;
+          for (int ky = lo[py][a]; ky <= hi[py][a]; ++ky)
+            for (int kx = lo[px][b]; kx <= hi[px][b]; ++kx) acc += w[o * so + c * sc + (size_t)(3 * ky + kx) * sk];
+          dst[c] = f2bf_host(acc);
+        }
+      }
+}
+
 template <class... A>      // an op description: printf into a string (160 characters at the most)
 std::string descf(const char* fmt, A... a) { char d[160]; snprintf(d, sizeof(d), fmt, a...); return d; }
 // environment switches: "=1 turns it on" and "on unless =0"
@@ -249,6 +269,7 @@ struct WeightStore {
   const bf16* w_geglu(const std::string& key, int inner, int K);                                    // "geglu:"
   const float* b_geglu(const std::string& key, int inner);                                          // "geglub:"
   const bf16* w_conv3(const std::string& key, int Cout, int Cin, bool tap_inner = false);           // "conv3:" / "conv3t:"
+  const bf16* w_conv3_ups_phase(const std::string& key, int Cout, int Cin);                         // "conv3up:"  [4 phases][Cout][4 taps][Cin], the taps summed in fp32
   const float* w_conv_in(const std::string& key, int Cout, int Cin);                                // "convin:"
   const bf16* w_condembed(const std::string& key, int Cout, int Cin);                               // "cefm:"
   const float* w_f32_sum(const std::string& a, const std::string& b, int64_t n);                    // "f32sum:"
@@ -326,6 +347,7 @@ struct nr_net {
   int cond_frames[64] = {0};
   bool cfg_dup = false;          // nr_net_set_cfg_pair_identical: the caller promises sample[b] == sample[b + B2/2] and timestep[b] == timestep[b + B2/2]
   bool attn_fp8 = false;         // nr_net_set_attention_fp8: spatial / cross attention on e4m3 MFMA operands (config 5)
+  int ups_phase_mode = -1;       // NR_UPS_PHASE as read when the plan began (begin_plan): 0 never the phase form, 1 every eligible upsample conv, -1 (unset) nr_ups_phase_rule
   bool w8 = false;               // nr_net_set_weight_fp8 (new handles: NR_W8=1): the Linears smallm.hip serves read their checkpoint matrices as e4m3 codes
                                  // with one power-of-two scale per row (NrGemmParams::w8); a numerics variant, bf16 is the default
   IO io = nre::new_io();
@@ -408,6 +430,9 @@ struct nr_net {
   };
   Act conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksize, int stride, int ups, const GemmOpt& o);
   Act linear(const Act& x, const bf16* w, int N, const GemmOpt& o) { return conv(x, nullptr, w, N, 1, 1, 0, o); }
+  // nearest-2x upsample + 3x3 conv `wkey` ([Cout][x.C][3][3]): on the replicated image (ups = 1, w_conv3) or as four 2x2 phase convs on the source
+  // (ups = 2, w_conv3_ups_phase), decided here once per plan (ups_phase_mode); the layer keeps only the weight form it runs with
+  Act upsample_conv(const Act& x, const std::string& wkey, int Cout, const GemmOpt& o);
   Act linear_wb(const Act& x, const std::string& key, int N, const Act* res = nullptr, Act* out = nullptr);      // linear() with <key>.weight / <key>.bias
   void gemm_raw(const bf16* a, int lda, const bf16* w, int M, int N, int K, const float* bias, bf16* out, int ldo, float* out32, const char* what);
   Act groupnorm(const Act& x0, const Act* x1, const std::string& prefix, float eps, int silu);

@@ -75,6 +75,7 @@ void nr_net::op_tap(const char* kind, const Act& a) {
 void nr_net::begin_plan() {
   ctx_persist.clear(); ops.clear(); ctx_ops.clear(); op_meta.clear(); taps.clear(); arena.reset(); parena.reset();
   ctx_dirty = true;
+  { const char* e = getenv("NR_UPS_PHASE"); ups_phase_mode = (e && e[0]) ? (e[0] != '0' ? 1 : 0) : -1; }      // per plan, never per process: two handles may differ
   temb_slots.clear(); temb_total = 0; temb_all = nullptr;
   n_res = 0; res_shapes.clear();
   t_dev = new_scratch<float>(NR_MAX_BATCH);
@@ -127,7 +128,8 @@ Act nr_net::conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksiz
   // stage stream for the short-K Linears on >= 2048 rows (lin160.hip)
   const bf16* wk = dry ? reinterpret_cast<const bf16*>(uintptr_t(16)) : wts.w_layout(w, Cout, p.K, r.weight_layout);
   const double in_elems = (double)x0.rows() * (p.c0 + p.c1);   // every input element is needed at least once
-  const double bytes = 2.0 * (in_elems + (double)p.N * p.K + (double)p.M * outC + (o.res ? (double)p.M * outC : 0.0));
+  const double w_elems = (double)p.N * p.K * (ups == 2 ? 4 : 1);   // phase form: one [N][K] matrix per phase
+  const double bytes = 2.0 * (in_elems + w_elems + (double)p.M * outC + (o.res ? (double)p.M * outC : 0.0));
   const bool l160 = r.cls == NR_GEMM_LIN160;
   const std::string d = l160 ? descf("%s M=%d N=%d K=%d res=%d geglu=%d ln=%d", r.lin160.form == 4 ? "lin160 panel" : "lin160", p.M, p.N, p.K, o.res ? 1 : 0, p.geglu, p.ln_c ? 1 : 0)
                              : descf("igemm ks=%d s=%d ups=%d M=%d N=%d K=%d geglu=%d res=%d%s", ksize, stride, ups, p.M, p.N, p.K, p.geglu, o.res ? 1 : 0,
@@ -138,6 +140,26 @@ Act nr_net::conv(const Act& x0, const Act* x1, const bf16* w, int Cout, int ksiz
   if (ws) last_op_launches(2);           // split-K: the igemm + its reduce kernel
   op_tap(l160 ? "lin160" : (ksize == 3 ? "conv3" : (p.ln_c ? "lngemm" : "gemm")), out);
   return out;
+}
+
+// Which upsample convs take the phase form when NR_UPS_PHASE is unset: M output pixels, N = Cout, Cin.  Only shapes whose line gained in every one of three
+// interleaved same-box pairs (profiles/ups_phase_ab.txt; per launch in the engine, 3x3 -> phase form):
+//   headline (+2.2-2.3 % frames/s)   M = 2048  N = Cin = 1280   75 -> 55 us      M = 8192 N = Cin = 1280   335 -> 112 us      M = 32768 N = Cin = 640   244 -> 118 us
+//   VAE round trip (+7.2-7.8 %)      M = 65536 / 262144 N = Cin = 512   0.29 -> 0.14 / 1.15 -> 0.55 ms       M = 1048576 N = Cin = 256   1.24 -> 0.64 ms
+// Not admitted: the keyframe model's 32 x 32 level (M = 8192, N = Cin = 640: 70 -> 48 us alone, but its line moved -0.05 / +0.44 / +0.11 %, inside the
+// spread) and everything unmeasured (fewer rows than the shapes above)
+static bool nr_ups_phase_rule(long long M, int N, int Cin) {
+  (void)N;
+  return Cin >= 1280 ? M >= 2048 : M >= 32768;
+}
+Act nr_net::upsample_conv(const Act& x, const std::string& wkey, int Cout, const GemmOpt& o) {
+  const int Cin = x.C;
+  const long long M = det_rows((long long)x.nimg * x.H * x.W * 4);      // NR_DETERMINISTIC_BATCH: decided on one clip's rows
+  // what nr_gemm_route takes as ups = 2: the plain conv (bias only), whole 64-channel k-tiles
+  const bool eligible = Cin % 64 == 0 && Cout % 32 == 0 && !o.res && !o.rowvec && !o.geglu && !o.ln_c && !o.tap_inner && !o.pad_tl0;
+  const bool phase = eligible && ups_phase_mode != 0 && (ups_phase_mode == 1 || nr_ups_phase_rule(M, Cout, Cin));
+  if (phase) return conv(x, nullptr, wts.w_conv3_ups_phase(wkey, Cout, Cin), Cout, 3, 1, 2, o);
+  return conv(x, nullptr, wts.w_conv3(wkey, Cout, Cin), Cout, 3, 1, 1, o);
 }
 
 // nn.Linear / 1x1 conv `key` (<key>.weight [N][x.C], <key>.bias) on x, + res, into *out

@@ -140,7 +140,7 @@ void nr_net::build_sgm() {
     if (b.up) {
       const std::string up = bp + "." + std::to_string(sub) + ".conv";
       GemmOpt o; o.bias = wts.w_f32(up + ".bias", b.Cout);
-      x = conv(x, nullptr, wts.w_conv3(up + ".weight", b.Cout, b.Cout), b.Cout, 3, 1, 1, o);
+      x = upsample_conv(x, up + ".weight", b.Cout, o);
       tap(bp + "." + std::to_string(sub), x);
     }
   }
@@ -188,7 +188,7 @@ void nr_net::build_vae() {
     for (int j = 0; j < cfg.layers_per_block + 1; ++j) x = resnet(x, nullptr, up + ".block." + std::to_string(j), Co);
     if (lev != 0) {
       GemmOpt o; o.bias = wts.w_f32(up + ".upsample.conv.bias", Co);
-      x = conv(x, nullptr, wts.w_conv3(up + ".upsample.conv.weight", Co, Co), Co, 3, 1, 1, o);   // nearest 2x + conv (model.py:67-71)
+      x = upsample_conv(x, up + ".upsample.conv.weight", Co, o);   // nearest 2x + conv (model.py:67-71)
       tap(up + ".upsample", x);
     }
   }
@@ -660,7 +660,7 @@ void nr_net::build() {
     }
     if (i != L - 1) {
       GemmOpt o; o.bias = wts.w_f32(bp + ".upsamplers.0.conv.bias", Cout);
-      x = conv(x, nullptr, wts.w_conv3(bp + ".upsamplers.0.conv.weight", Cout, Cout), Cout, 3, 1, 1, o);
+      x = upsample_conv(x, bp + ".upsamplers.0.conv.weight", Cout, o);
       tap(bp + ".upsamplers.0", x);
     }
   }

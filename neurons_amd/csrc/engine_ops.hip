@@ -126,6 +126,22 @@ extern "C" nr_status nr_op_conv3x3(nr_stream stream, const void* x0, int32_t c0,
   NR_CATCH
 }
 
+// the upsample conv in phase form (NrGemmParams::ups == 2) on phase weights; nr_op_conv3x3 with ups = 1 stays the 3x3 route on raw taps
+extern "C" nr_status nr_op_conv3x3_ups_phase(nr_stream stream, const void* x, int32_t Cin, int32_t nimg, int32_t H, int32_t W, const void* wp,
+                                             const float* bias, void* out, int32_t Cout) {
+  NR_TRY
+  if (!x || !wp || !out) throw NrError(NR_ERR_ARG, "null argument");
+  NrGemmParams p = nr_gemm_params((const bf16*)x, Cin, Cin, nullptr, 0, 0, nimg, H, W, 3, 1, 2, (const bf16*)wp, Cout, bias, nullptr, 0, (bf16*)out, Cout);
+  op_gemm(p, (hipStream_t)stream);
+  NR_CATCH
+}
+extern "C" nr_status nr_ups_phase_weights(const float* w_tap, int32_t Cout, int32_t Cin, void* out) {
+  NR_TRY
+  if (!w_tap || !out || Cout < 1 || Cin < 1) throw NrError(NR_ERR_ARG, "bad argument");
+  nr_ups_phase_pack(w_tap, (size_t)9 * Cin, 1, (size_t)Cin, Cout, Cin, (uint16_t*)out);
+  NR_CATCH
+}
+
 extern "C" nr_status nr_op_condembed_in(nr_stream stream, const float* cond, const float* mask, int32_t c0, int32_t nsrc, int32_t F, int32_t H,
                                         int32_t W, const int32_t* fmap, int32_t nframes, const float* w, const float* bias, int32_t Cout,
                                         void* out) {

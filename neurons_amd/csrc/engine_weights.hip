@@ -382,6 +382,12 @@ const bf16* WeightStore::w_conv3(const std::string& key, int Cout, int Cin, bool
         }
   });
 }
+// 3x3 conv weight [Cout][Cin][3][3] of a nearest-2x upsample conv -> its phase form [4][Cout][4][Cin] bf16 (nr_ups_phase_pack, engine.h)
+const bf16* WeightStore::w_conv3_ups_phase(const std::string& key, int Cout, int Cin) {
+  return (const bf16*)convert<uint16_t>("conv3up:", key, {Cout, Cin, 3, 3}, (size_t)16 * Cout * Cin, [&](const float* s, uint16_t* h) {
+    nr_ups_phase_pack(s, (size_t)Cin * 9, 9, 1, Cout, Cin, h);
+  });
+}
 // small-Cin conv weight [Cout][Cin][3][3] -> fp32 [Cin*9][Cout]
 const float* WeightStore::w_conv_in(const std::string& key, int Cout, int Cin) {
   return convert<float>("convin:", key, {Cout, Cin, 3, 3}, (size_t)Cin * 9 * Cout, [&](const float* s, float* h) {

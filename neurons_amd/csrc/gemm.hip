@@ -45,10 +45,17 @@ NR_STAMP_BUF(nr_stamp_buf, 512, 48);
 // LIN: the launch is a plain Linear (1x1, one source): the im2col / tap / two-source paths are compiled out.  Same arithmetic; what it buys is
 // code size: a launch starts with a cold instruction cache (tools/icache_probe.py: +0.4-1.4 us per launch when instantiations alternate, as
 // they do in the engine's graphs), and two thirds of the launches of a denoising step are Linears.  LayerNorm-folded launches are always Linears.
-template <int BM, int BN, int NS, int WGM, int WGN, bool LNF = false, bool ADMA = false, bool LIN = LNF>
+// PH: the PHASE form of a nearest-2x upsample conv (NrGemmParams::ups == 2): the 3x3 conv on the replicated image is four 2x2 convs on the source,
+// one per output parity (py, px), with the taps that read the same source pixel summed in the weights beforehand (w = [phase][N][tap][Cin], K = 4 Cin:
+// 4/9 of the multiply-adds).  Rows are phase-major: 4 x ceil(Mp / BM) row tiles, Mp = nimg H W source pixels, a tile belongs to ONE phase (= one weight
+// matrix); row (phase, r) is source pixel r on the A side and output pixel (2 y + py, 2 x + px) wherever a row index becomes an output address.
+// A template parameter, not a run-time branch: every other instantiation is compiled from the text it had.
+template <int BM, int BN, int NS, int WGM, int WGN, bool LNF = false, bool ADMA = false, bool LIN = LNF, bool PH = false>
 __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) void igemm_bf16_kernel(NrGemmParams p_arg, int splitk, float* partial, int m_fast) {
   NrGemmParams p = nr_pin_params(p_arg);
   if constexpr (LIN) { p.ksize = 1; p.stride = 1; p.ups = 0; p.a1 = nullptr; p.c1 = 0; p.tap_inner = 0; p.pad_tl0 = 0; }
+  static_assert(!PH || (!LIN && !LNF), "the phase form is a conv");
+  if constexpr (PH) { p.ksize = 3; p.stride = 1; p.ups = 2; p.a1 = nullptr; p.c1 = 0; p.tap_inner = 0; p.pad_tl0 = 0; p.geglu = 0; p.rowvec = nullptr; p.res = nullptr; }
   splitk = nr_pin(splitk); partial = nr_pin(partial); m_fast = nr_pin(m_fast);
   constexpr int BK = 64;
   constexpr int NW = WGM * WGN;
@@ -66,7 +73,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   NR_STAMP_RT(44);
   const int wm = wave / WGN, wn = wave % WGN;
   const int ntn = (p.N + BN - 1) / BN;
-  const int ntm = (p.M + BM - 1) / BM;
+  const int Mrows = PH ? p.M >> 2 : p.M;          // rows a row-tile index runs over (PH: the source pixels of one phase)
+  const int ntmp = (Mrows + BM - 1) / BM;
+  const int ntm = PH ? 4 * ntmp : ntmp;
   // XCD-aware remap (bijective): workgroups are dealt round-robin over the 8 XCDs, so give each XCD a
   // CONTIGUOUS range of logical tiles: the n-tiles that share one A row-panel then hit the same L2
   // instead of re-fetching the panel from HBM once per XCD.  Placement only affects speed.
@@ -93,7 +102,19 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     bn = nr_fdiv_small(r, gsz);
     bm = first + r - bn * gsz;
   } else if (m_fast) { bn = nr_fdiv_small(bid, ntm); bm = bid - bn * ntm; } else { bm = nr_fdiv_small(bid, ntn); bn = bid - bm * ntn; }
+  // PH: row tiles [phase * ntmp, (phase + 1) * ntmp) are one phase's, so in every tile order the tiles that share a weight matrix stay neighbours
+  const int phase = PH ? nr_fdiv_small(bm, ntmp) : 0;
+  if constexpr (PH) bm -= phase * ntmp;
+  const int ph_py = phase >> 1, ph_px = phase & 1;
   const int m0 = bm * BM, n0 = bn * BN;
+  // PH: output row (pixel index) of row r of this tile's phase
+  auto ph_out_row = [&](int r) {
+    const int hw = p.H * p.W;
+    const int n = nr_fdiv_small(r, hw);
+    const int q = r - n * hw;
+    const int y = nr_fdiv_small(q, p.W), x = q - y * p.W;
+    return (n * p.OH + 2 * y + ph_py) * p.OW + 2 * x + ph_px;
+  };
   NR_STAMP_AT(40);
   const int lr = lane >> 3;                 // row within the 8-row group
   const int lp = lane & 7;                  // physical 16-B chunk
@@ -107,9 +128,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
 #pragma unroll
   for (int j = 0; j < GA; ++j) {
     const int m = m0 + 8 * (wave * GA + j) + lr;
-    a_ok[j] = m < p.M;
+    a_ok[j] = m < Mrows;
     const int mm = a_ok[j] ? m : 0;
-    if (p.ksize == 1) {
+    if constexpr (PH) {      // (image, y, x) of the SOURCE pixel
+      const int hw = p.H * p.W;
+      const int n = nr_fdiv_small(mm, hw);
+      const int r = mm - n * hw;
+      a_pix[j] = n; a_oy[j] = nr_fdiv_small(r, p.W); a_ox[j] = r - a_oy[j] * p.W;
+    } else if (p.ksize == 1) {
       a_pix[j] = mm; a_oy[j] = 0; a_ox[j] = 0;
     } else {
       const int ohw = p.OH * p.OW;
@@ -162,7 +188,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     for (int j = 0; j < GB; ++j) {
       const int n = n0 + 8 * (wave * GB + j) + lr;
       const bool ok = n < p.N;
-      wp[j] = ok ? p.w + (size_t)n * p.K + kbase + lchunk : zsrc;
+      wp[j] = ok ? p.w + ((size_t)phase * p.N + n) * p.K + kbase + lchunk : zsrc;
       winc[j] = ok ? BK : 0;
     }
   }
@@ -182,7 +208,17 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     const bf16* src; int ld;
     if (st_c < p.c0) { src = p.a0 + st_c; ld = p.lda0; } else { src = p.a1 + (st_c - p.c0); ld = p.lda1; }
     src += lchunk;
-    if (p.ksize == 1) {
+    if constexpr (PH) {      // tap (a, b) of phase (py, px) reads source pixel (y + a + py - 1, x + b + px - 1), zero outside the source
+      const int dy = (st_tap >> 1) + ph_py - 1, dx = (st_tap & 1) + ph_px - 1;
+#pragma unroll
+      for (int j = 0; j < GA; ++j) {
+        const int iy = a_oy[j] + dy, ix = a_ox[j] + dx;
+        const bool ok = a_ok[j] && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+        const size_t pix = ((size_t)a_pix[j] * p.H + iy) * p.W + ix;
+        ap[j] = ok ? src + pix * ld : zsrc;
+        ainc[j] = ok ? BK : 0;
+      }
+    } else if (p.ksize == 1) {
 #pragma unroll
       for (int j = 0; j < GA; ++j) {
         ap[j] = a_ok[j] ? src + (size_t)a_pix[j] * ld : zsrc;
@@ -236,7 +272,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     if (st_c == Cin) { st_c = 0; st_tap += 1; resetup = true; }
     else if (p.c1 > 0 && st_c == p.c0) resetup = true;
     if (resetup) {
-      if (st_tap < p.ksize * p.ksize) setup_rows();
+      if (st_tap < (PH ? 4 : p.ksize * p.ksize)) setup_rows();
     } else {
 #pragma unroll
       for (int j = 0; j < GA; ++j) ap[j] += ainc[j];
@@ -370,12 +406,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
 #pragma unroll
     for (int j = 0; j < MT; ++j) {
       const int m = m0 + wm * WM + j * 16 + fr;
-      if (m >= p.M) continue;
+      if (m >= Mrows) continue;
+      const int ms = PH ? phase * Mrows + m : m;      // the slabs stay dense: [slice][phase * Mp + r][N]
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
         const int n = n0 + wn * WN + i * 16 + 4 * fg;
         if (n >= p.N) continue;
-        nr_store16f(slab + (size_t)m * p.N + n, acc[i][j]);
+        nr_store16f(slab + (size_t)ms * p.N + n, acc[i][j]);
       }
     }
     return;
@@ -422,7 +459,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     for (int idx = tid; idx < BM * c8n; idx += NTH) {
       const int row = idx / c8n, c8 = idx - row * c8n;
       const int m = m0 + row, n = nb0 + c8 * 8;
-      if (m >= p.M || n >= nout) continue;
+      if (m >= Mrows || n >= nout) continue;
       f32x4 va = *(const f32x4*)(sC + row * BN + (((2 * c8) ^ (row & 7)) << 2));
       f32x4 vb = *(const f32x4*)(sC + row * BN + (((2 * c8 + 1) ^ (row & 7)) << 2));
       if (!p.geglu) {
@@ -445,7 +482,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
       bf16x8 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) { o[e] = (bf16)va[e]; o[4 + e] = (bf16)vb[e]; }
-      nr_store16(p.out + (size_t)m * p.ldo + n, o);
+      nr_store16(p.out + (size_t)(PH ? ph_out_row(m) : m) * p.ldo + n, o);
     }
 #ifdef NR_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -457,7 +494,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
 #pragma unroll
   for (int j = 0; j < MT; ++j) {
     const int m = m0 + wm * WM + j * 16 + fr;
-    if (m >= p.M) continue;
+    if (m >= Mrows) continue;
+    const size_t mo = PH ? ph_out_row(m) : m;
     const float* rv = p.rowvec ? p.rowvec + nr_rowvec_row(p, m) : nullptr;
     if (!p.geglu) {
 #pragma unroll
@@ -480,7 +518,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
         bf16x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
-        nr_store8(p.out + (size_t)m * p.ldo + n, o);
+        nr_store8(p.out + mo * p.ldo + n, o);
       }
     } else {
       if constexpr (NT % 2 == 0) {
@@ -498,14 +536,16 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
           bf16x4 o;
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = (bf16)(v[e] * gelu_erf_fast(g[e]));
-          nr_store8(p.out + (size_t)m * p.ldo + oc, o);
+          nr_store8(p.out + mo * p.ldo + oc, o);
         }
       }
     }
   }
 }
 
-// out[m][n] = epilogue( sum_s partial[s][m][n] ), 4 consecutive n per thread
+// out[m][n] = epilogue( sum_s partial[s][m][n] ), 4 consecutive n per thread.  PH: slab row m = phase * Mp + r of a phase-form launch goes to the
+// output pixel of (phase, r) (igemm_bf16_kernel); such a launch has neither rowvec nor res
+template <bool PH>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(NrGemmParams p_arg, int splitk, const float* __restrict__ partial) {
   const NrGemmParams p = nr_pin_params(p_arg);
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -532,7 +572,15 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(NrGemmParams p_arg, 
   bf16x4 o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
-  nr_store8(p.out + (size_t)m * p.ldo + n, o);
+  size_t mo = (size_t)m;
+  if constexpr (PH) {
+    const int Mp = p.M >> 2, hw = p.H * p.W;
+    const int phase = m / Mp, r = m - phase * Mp;
+    const int img = r / hw, q = r - img * hw;
+    const int y = q / p.W, x = q - y * p.W;
+    mo = (size_t)(img * p.OH + 2 * y + (phase >> 1)) * p.OW + 2 * x + (phase & 1);
+  }
+  nr_store8(p.out + mo * p.ldo + n, o);
 }
 
 typedef TiledPlan Plan;       // gemm_route.h
@@ -540,11 +588,52 @@ typedef TiledPlan Plan;       // gemm_route.h
 // Tile / wave-grid / split-K choice.  Rules distilled from tools/gemm_sweep.py on MI355X (profiles/): two LDS
 // stages (2 workgroups per CU) beat a deeper ring; 8 waves help the 128x128 tile; long-K layers with few
 // tiles gain 1.3-1.7x from split-K; 128x160 only pays for N = 320.
+// the (tile, waves) pairs the phase form (NrGemmParams::ups == 2) is instantiated for, all with the two-stage ring
+constexpr bool phase_tile(int bm, int bn, int waves) {
+  return (bm == 128 && bn == 160 && waves == 4) || (bm == 128 && bn == 128 && waves == 8) || (bm == 128 && bn == 64 && waves == 4) ||
+         (bm == 64 && bn == 64 && waves == 4) || (bm == 256 && bn == 128 && waves == 8);
+}
+// row tiles of a launch: the phase form tiles each of its four phases (M / 4 source pixels) on its own
+inline long long row_tiles(const NrGemmParams& p, int bm) { return p.ups == 2 ? 4ll * ((p.M / 4 + bm - 1) / bm) : (p.M + bm - 1) / bm; }
+
+// Phase-form upsample convs: four GEMMs of M / 4 rows and K = 4 Cin that share one launch, so the rules of choose_plan keyed on nk >= 128 (K = 9 Cin)
+// do not fire.  Per shape by NR_IGEMM_FORCE sweeps of the op (HBM-cold weights, profiles/ups_phase_ab.txt; us per launch, the 3x3 form beside it):
+//   M = 2048  N = 1280 K = 5120  (3x3: 72-82)    128x160 split-K 4: 50.5   split-K 2: 55   one slice: 87   128x128: 62-77   128x64: 61-72   64x64: 67-79
+//   M = 8192  N = 1280 K = 5120  (3x3: 322)      128x160 one slice (512 tiles, one round): 108   two slices: 132   128x128: 140-163   128x64: 148   256x128: 201
+//   M = 32768 N = 640  K = 2560  (3x3: 231-240)  128x160: 109   128x128: 115   128x64: 135   256x128: 139
+//   N = 512 / 256 (the VAE: no 160-column tiling)  128x128 8 waves: 140 / 551 / 640 against 256x128: 156 / 610 / 774 (3x3: 292 / 1153 / 1241)
+// The split-K rule for under-filled grids below is choose_plan's reasoning, not a measurement of this form.
+Plan choose_plan_phase(const NrGemmParams& p) {
+  auto nblk = [&](int bm, int bn) { return row_tiles(p, bm) * ((p.N + bn - 1) / bn); };
+  const int nk = p.K / 64;
+  Plan pl{};
+  pl.splitk = 1; pl.stages = 2; pl.waves = 4;
+  // N a multiple of 160: the 128 x 160 tile on every measured shape; four K slices where the four phases of <= 2048 rows leave 128 tiles of a long K
+  if (p.N % 160 == 0) {
+    pl.bm = 128; pl.bn = 160;
+    if (p.M <= 2048 && nk >= 64) { pl.splitk = 4; return pl; }
+  } else {
+    const bool n128 = p.N % 128 == 0 || p.N >= 960;
+    if (n128 && nblk(128, 128) >= 400) { pl.bm = 128; pl.bn = 128; pl.waves = 8; }
+    else if (nblk(128, 64) >= 256) { pl.bm = 128; pl.bn = 64; }
+    else { pl.bm = 64; pl.bn = 64; }
+  }
+  // under-filled grids with a K worth cutting: deterministic split-K as in choose_plan (every slice keeps >= 16 k-tiles, <= 4 slabs)
+  const long long tiles = nblk(pl.bm, pl.bn);
+  if (tiles < 512 && nk >= 64) {
+    int s_ = (int)((1024 + tiles - 1) / tiles);
+    if (s_ > nk / 16) s_ = nk / 16;
+    if (s_ > 4) s_ = 4;
+    pl.splitk = s_ < 1 ? 1 : s_;
+  }
+  return pl;
+}
 Plan choose_plan(const NrGemmParams& p) {
   auto nblk = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
   const int nk = p.K / 64;
   Plan pl{};
   pl.splitk = 1; pl.stages = 2; pl.waves = 4;
+  if (p.ups == 2) return choose_plan_phase(p);
   // 4x4-level convs (M <= 1024, K >= 8192): L2-bandwidth-bound with small tiles (every n-tile re-reads A, every m-tile
   // re-reads W), so take the biggest tile and get the parallelism from a deep deterministic split-K instead
   if (!p.geglu && p.M <= 1024 && nk >= 128 && p.N % 160 == 0) {
@@ -640,10 +729,16 @@ int launch_cfg(const NrGemmParams& p, unsigned grid, const Plan& pl, float* part
                          (BM == 128 && BN == 160 && WGN == 1 && NS <= 4) ||     // the row-wave 128x160 tile of the wide GEGLU projections
                          (BM == 64 && BN == 160 && NS <= 3);                     // the one-round tile of the N = 1280 Linears at M = 1024 / 2048
   igemm_kern_t k = nullptr;
-  int ki = 0;                   // LayerNorm-fused | 1 + 2 lin + adma
+  int ki = 0;                   // LayerNorm-fused | 1 + 2 lin + adma | 5 + adma phase form
   if (p.ln_c) {
     if constexpr (LN_OK) { k = igemm_bf16_kernel<BM, BN, NS, WGM, WGN, true>; shm += (size_t)2 * WGN * BM * sizeof(float); }
     else return 9;
+  } else if (p.ups == 2) {
+    // phase form: instantiated for the two-stage tiles choose_plan_phase picks from (the route maps every other request onto them)
+    if constexpr (phase_tile(BM, BN, WGM * WGN) && NS == 2) {
+      k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false, false, true> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true, false, true>;
+      ki = 5 + pl.adma;
+    } else return 9;
   } else {
     k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true>;
     ki = 1 + pl.adma;
@@ -655,7 +750,7 @@ int launch_cfg(const NrGemmParams& p, unsigned grid, const Plan& pl, float* part
       }
     }
   }
-  static unsigned long long attr_done[5] = {};          // per instantiation
+  static unsigned long long attr_done[7] = {};          // per instantiation
   (void)nr_lds_opt_in(attr_done[ki], {(const void*)k}, shm);
   hipLaunchKernelGGL(k, dim3(grid), dim3(64 * WGM * WGN), shm, stream, p, pl.splitk, partial, m_fast);
   return 0;
@@ -712,15 +807,24 @@ int route(const NrGemmParams& p, NrGemmRoute* r, bool packed_ok) {
   std::memset(r, 0, sizeof(*r));
   r->weight_layout = p.tap_inner ? NR_W_TAP_INNER : NR_W_ROWMAJOR;
   const int Cin = p.c0 + p.c1;
+  // the phase form of an upsample conv (ups == 2, w = [4 phases][N][4 taps][Cin], K = 4 Cin): the tiled kernel only, and only the plain conv --
+  // 10: a field the form has no path for (second source, stride, tap_inner, pad_tl0, geglu, ln_c, out_f32; res / rowvec: their rows are not
+  // mapped to output pixels); 11: the geometry is not a 2x upsample of H x W
+  const bool phase = p.ups == 2;
+  if (phase) {
+    r->cls = NR_GEMM_TILED;
+    if (p.ksize != 3 || p.stride != 1 || p.a1 || p.c1 || p.tap_inner || p.pad_tl0 || p.geglu || p.ln_c || p.out_f32 || p.res || p.rowvec) return 10;
+    if (p.H < 1 || p.W < 1 || p.OH != 2 * p.H || p.OW != 2 * p.W || p.M < 4 || p.M % (p.OH * p.OW) != 0) return 11;
+  } else if (p.ups != 0 && p.ups != 1) return 11;
   // M <= 512 Linears with K a multiple of 640: the panel-resident kernel on fragment-major weights (smallm.hip)
   // (the e4m3 request p.w8 names the weight layout of THIS class and nothing else: smallm_plan does not see it, the classes below ignore it)
-  if (packed_ok && smallm_plan(p, &r->smallm)) { r->cls = NR_GEMM_SMALLM; r->weight_layout = p.w8 ? NR_W_FRAGMAJOR_E4M3 : NR_W_FRAGMAJOR; return 0; }
+  if (!phase && packed_ok && smallm_plan(p, &r->smallm)) { r->cls = NR_GEMM_SMALLM; r->weight_layout = p.w8 ? NR_W_FRAGMAJOR_E4M3 : NR_W_FRAGMAJOR; return 0; }
   // short-K Linears (K = 640 / 1280) on >= 2048 rows: the stage-stream kernel and its register-panel form (lin160.hip)
-  if (packed_ok && lin160_plan(p, &r->lin160)) { r->cls = NR_GEMM_LIN160; r->weight_layout = r->lin160.form == 4 ? NR_W_LIN128Q : NR_W_LIN160; return 0; }
+  if (!phase && packed_ok && lin160_plan(p, &r->lin160)) { r->cls = NR_GEMM_LIN160; r->weight_layout = r->lin160.form == 4 ? NR_W_LIN128Q : NR_W_LIN160; return 0; }
   // K = 320 Linears on >= 4096 rows: the register-resident row-panel kernel (rowpanel.hip)
-  if (p.K == p.ksize * p.ksize * Cin && rowpanel_plan(p, &r->rowpanel)) { r->cls = NR_GEMM_ROWPANEL; return 0; }
+  if (!phase && p.K == p.ksize * p.ksize * Cin && rowpanel_plan(p, &r->rowpanel)) { r->cls = NR_GEMM_ROWPANEL; return 0; }
   const double w_elems = (double)p.N * p.K;
-  if (g8p_plan(p, &r->g8p)) {
+  if (!phase && g8p_plan(p, &r->g8p)) {
     r->cls = NR_GEMM_G8P;
     r->m_fast = tile_order(w_elems, (double)p.M * Cin, (p.M + 255) / 256, (p.N + 64 * r->g8p.nt - 1) / (64 * r->g8p.nt));
     return 0;
@@ -728,14 +832,22 @@ int route(const NrGemmParams& p, NrGemmRoute* r, bool packed_ok) {
   r->cls = NR_GEMM_TILED;
   if (p.K % 64 != 0 || Cin % 64 != 0 || p.N % 32 != 0) return 1;
   if (p.a1 && (p.c0 % 64 != 0)) return 2;
-  if (p.K != p.ksize * p.ksize * Cin) return 3;
+  if (p.K != (phase ? 4 : p.ksize * p.ksize) * Cin) return 3;
   if (p.ksize != 1 && p.ksize != 3) return 4;
   if (p.tap_inner && (p.ksize != 3 || p.stride != 1 || p.ups || p.pad_tl0 || p.a1)) return 5;
   Plan& pl = r->tiled;
   pl = choose_plan(plan_view(p));
   const double a_elems = (double)p.M * Cin * (p.ksize == 3 ? (p.stride == 2 ? 4.0 : (p.ups ? 0.25 : 1.0)) : 1.0);
-  r->m_fast = tile_order(w_elems, a_elems, (p.M + pl.bm - 1) / pl.bm, (p.N + pl.bn - 1) / pl.bn);
+  // (phase form: w_elems is ONE phase's matrix and the order is chosen on one phase's row tiles; bands of 8 row tiles must not straddle two phases)
+  const int ntm1 = (int)(phase ? row_tiles(p, pl.bm) / 4 : row_tiles(p, pl.bm));
+  r->m_fast = tile_order(w_elems, a_elems, ntm1, (p.N + pl.bn - 1) / pl.bn);
   apply_override(p, pl, r->m_fast);
+  if (phase) {      // what the form is instantiated for: two stages, the tiles of phase_tile
+    pl.stages = 2;
+    if (pl.bm == 256 || (pl.bm == 128 && pl.bn == 128)) pl.waves = 8; else pl.waves = 4;
+    if (!phase_tile(pl.bm, pl.bn, pl.waves)) { pl.bm = 128; pl.bn = 128; pl.waves = 8; }
+    if (r->m_fast >= 2 && (row_tiles(p, pl.bm) / 4) % r->m_fast != 0) r->m_fast = w_elems > a_elems ? 1 : 0;
+  }
   if (p.ln_c) {      // LayerNorm-fused: every block must see the whole row (K = C) -> no split-K; supported tiles only
     if (p.ksize != 1 || p.a1 || p.out_f32) return 8;
     pl.splitk = 1;
@@ -763,7 +875,7 @@ int launch_tiled(const NrGemmParams& p, const Plan& pl, int m_fast, float* works
   if (pl.splitk < 1 || pl.splitk > p.K / 64 || ((p.ln_c || p.out_f32) && pl.splitk != 1)) return 9;
   if (pl.splitk > 1 && !workspace) return 6;
   float* partial = p.out_f32 ? p.out_f32 : (pl.splitk > 1 ? workspace : nullptr);
-  const unsigned grid = (unsigned)(((p.M + pl.bm - 1) / pl.bm) * ((p.N + pl.bn - 1) / pl.bn) * pl.splitk);
+  const unsigned grid = (unsigned)(row_tiles(p, pl.bm) * ((p.N + pl.bn - 1) / pl.bn) * pl.splitk);
   int rc;
   if (pl.bm == 256 && pl.bn == 160) rc = launch_tile<256, 160, 2, 2>(p, grid, pl, partial, m_fast, stream);
   else if (pl.bm == 256 && pl.waves == 4) rc = launch_tile<256, 128, 2, 2>(p, grid, pl, partial, m_fast, stream);
@@ -783,8 +895,8 @@ int launch_tiled(const NrGemmParams& p, const Plan& pl, int m_fast, float* works
   if (rc) return rc;      // no instantiation for this (tile, LayerNorm-fused) request: fail loudly, never skip the launch
   if (pl.splitk > 1) {
     const long long total = (long long)p.M * (p.N / 4);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, pl.splitk,
-                       (const float*)partial);
+    hipLaunchKernelGGL(p.ups == 2 ? splitk_reduce_kernel<true> : splitk_reduce_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p,
+                       pl.splitk, (const float*)partial);
   }
   return 0;
 }

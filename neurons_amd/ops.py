@@ -165,6 +165,29 @@ def conv3x3(x0, w, bias=None, x1=None, stride=1, ups=False, rowvec=None, rowvec_
     return out
 
 
+def ups_phase_weights(w_tap):
+    """3x3 taps [Cout, 3, 3, Cin] (any float dtype, any device) -> the phase weights of conv3x3_ups_phase: bf16 [4, Cout, 4, Cin] on the CPU,
+    phase = 2 py + px, tap = 2 a + b; the taps that read the same source pixel are summed in fp32 and rounded once (the engine's converter code)."""
+    Cout, _, _, Cin = w_tap.shape
+    src = w_tap.detach().to("cpu", torch.float32).contiguous()
+    out = torch.empty(4, Cout, 4, Cin, dtype=torch.bfloat16)
+    _lib.check(_lib.load().nr_ups_phase_weights(src.data_ptr(), Cout, Cin, out.data_ptr()))
+    return out
+
+
+def conv3x3_ups_phase(x, w_tap, bias=None):
+    """nearest-2x upsample + 3x3 conv (pad 1) as four 2x2 phase convs on the source: x [nimg, H, W, Cin] bf16, w_tap [Cout, 3, 3, Cin] (the taps
+    conv3x3 takes), bias fp32 [Cout]; returns [nimg, 2H, 2W, Cout] bf16.  conv3x3(ups=True) is the same conv on the replicated image."""
+    _chk_bf16(x)
+    _chk_f32(bias)
+    nimg, H, W, Cin = x.shape
+    Cout = w_tap.shape[0]
+    wp = ups_phase_weights(w_tap).to(x.device)
+    out = torch.empty(nimg, 2 * H, 2 * W, Cout, dtype=torch.bfloat16, device=x.device)
+    _lib.check(_lib.load().nr_op_conv3x3_ups_phase(_stream(), _ptr(x), Cin, nimg, H, W, _ptr(wp), _ptr(bias), _ptr(out), Cout))
+    return out
+
+
 def condembed_pack(w):
     """3x3 conv weight [Cout, Cin, 3, 3] -> the fragment-major bf16 layout of condembed_conv: [Cout/16][KS][64][8], KS = ceil(9 Cin / 32),
     lane (fr, g) of block (T, ks) holding W[16 T + fr][32 ks + 8 g .. + 7], K index = tap * Cin + c, zero-padded beyond 9 Cin."""
