@@ -97,6 +97,17 @@ __device__ __forceinline__ s16x4 nr_pack4(const f32x4& v) {
   return __builtin_bit_cast(s16x4, b);
 }
 
+// eight values (float[8] or a bf16x8 fragment: whatever converts to float) -> eight OCP e4m3 codes (v_cvt_pk_fp8_f32: e4m3fn on gfx950,
+// round to nearest even, saturating), element e in byte e: the 64-bit operand of the fp8 MFMAs, or two dwords of a packed weight
+template <class V> __device__ __forceinline__ unsigned long long nr_e4m3x8(const V& v) {
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)v[0], (float)v[1], lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)v[2], (float)v[3], lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)v[4], (float)v[5], hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)v[6], (float)v[7], hi, true);
+  return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+}
+
 // acc += A B (16 x 16 x 32 bf16) with the accumulator PINNED in the AGPR half of the register file ("+a": vDst = SrcC = an AGPR quad):
 // the out tiles of xattn.hip and tattn.hip.  Left to hipcc the 160 accumulator registers of the out tile live in VGPRs between the heads
 // and every group of MFMAs is bracketed by v_accvgpr copies (xattn: 478 copies for 200 MFMAs, the o stage at 37 instead of 16 cycles per
@@ -128,6 +139,16 @@ __device__ __forceinline__ void nr_mfma_results(f32x4& acc) { asm volatile("s_no
 // ----------------------------------------------------------------------------------------------
 // Epilogue and index helpers
 // ----------------------------------------------------------------------------------------------
+
+// XCD-aware remap of blockIdx.x over gridDim.x (bijective): workgroups are dealt round-robin over the 8 XCDs, so give each XCD a
+// CONTIGUOUS range of logical ids: the workgroups that share an operand (the n-tiles of one A row-panel, the query blocks of one head)
+// then hit the same L2 instead of re-fetching it from HBM once per XCD.  Placement only affects speed.  Each caller says what its
+// neighbouring ids share.
+__device__ __forceinline__ int nr_xcd_bid() {
+  const int nwg = gridDim.x, orig = blockIdx.x;
+  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, local = orig >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+}
 
 // a / d for d > 0 through the float reciprocal with one correction step: exact for 0 <= a < 2^24 and a quotient < 2^22.  The tile-index
 // and im2col-row arithmetic of the igemm prologue used ~10 integer (two of them 64-bit) divisions = 2,300-3,100 of the 4,400-4,900

@@ -76,15 +76,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   const int Mrows = PH ? p.M >> 2 : p.M;          // rows a row-tile index runs over (PH: the source pixels of one phase)
   const int ntmp = (Mrows + BM - 1) / BM;
   const int ntm = PH ? 4 * ntmp : ntmp;
-  // XCD-aware remap (bijective): workgroups are dealt round-robin over the 8 XCDs, so give each XCD a
-  // CONTIGUOUS range of logical tiles: the n-tiles that share one A row-panel then hit the same L2
-  // instead of re-fetching the panel from HBM once per XCD.  Placement only affects speed.
-  int bid;
-  {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, local = orig >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-  }
+  int bid = nr_xcd_bid();                         // the n-tiles that share one A row-panel share an L2
   const int slice = splitk > 1 ? nr_fdiv_small(bid, ntn * ntm) : 0;
   bid -= slice * ntn * ntm;
   // tile order inside an XCD's range: the operand that is re-used by neighbouring tiles should be the BIG

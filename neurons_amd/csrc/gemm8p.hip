@@ -50,12 +50,7 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave >> 2, wn = wave & 3;             // M half (= stagger group), N quarter
   const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + G8_BM - 1) / G8_BM;
-  int bid;
-  {                                                    // XCD-contiguous tile ranges (bijective), as gemm.hip
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, local = orig >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-  }
+  const int bid = nr_xcd_bid();                        // the tiles of one operand panel share an L2, as gemm.hip
   int bm, bn;
   if (m_fast >= 2) {
     const int G = m_fast;

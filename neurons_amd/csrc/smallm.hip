@@ -95,12 +95,7 @@ __device__ __forceinline__ void smallm_body(NrGemmParams p_arg, int J, int C) {
   const int fr = lane & 15, fg = lane >> 4;
   const int lr = lane >> 3, lp = lane & 7;
   const int ntm = (p.M + 31) >> 5;
-  int bid;
-  {   // XCD-aware remap (bijective): consecutive ids on one XCD, so the row tiles that share a column group's weights share an L2
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, local = orig >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-  }
+  const int bid = nr_xcd_bid();               // the row tiles that share a column group's weights share an L2
   // (an 8 row-tile x 4 column-group block per XCD instead of 16 x 2 -- less panel, more weights fetched per XCD -- was worth 1-2 % at K >= 5120 only)
   const int g = bid / ntm;                    // column group: slabs g J .. g J + J - 1
   const int m0 = (bid - g * ntm) * 32;
@@ -408,12 +403,8 @@ __global__ __launch_bounds__(256) void smallm_w8_pack_kernel(const bf16* __restr
       float f[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] = ldexpf((float)v[e], ne);
-      int lo = 0, hi = 0;
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-      q[2 * j] = (unsigned)lo; q[2 * j + 1] = (unsigned)hi;
+      const unsigned long long c = nr_e4m3x8(f);
+      q[2 * j] = (unsigned)c; q[2 * j + 1] = (unsigned)(c >> 32);
     }
     *(u32x4*)(out + (((size_t)T * kb + kp) * 64 + lane) * 16) = q;
   }

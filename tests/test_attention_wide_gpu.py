@@ -1,4 +1,4 @@
-"""The wide-head attention kernel (attn_wide_kernel of attention.hip, d = 256 / 512) through neurons_amd.ops: the VAE mid-block shape class (one head of
+"""The wide-head attention kernel (the WideHead instantiations of attn_fwd_shared_kernel in attention.hip, d = 256 / 512) through neurons_amd.ops: the VAE mid-block shape class (one head of
 d = 512 over h*w tokens), a strided two-head cross-attention at d = 256, the rescale of a non-empty accumulator, batch independence and
 the calls the wide route refuses.
 

@@ -104,6 +104,31 @@ PARENT = [
     (_self(2, 77, 8, 160, causal=1), (NR_ATTN_WAVE, 5, 10, 0, 0, 20, 4 * 32 * 176 * 2)),
     (_temporal(32, 64, 16, 8, 40), (NR_ATTN_WAVE, 2, 3, 0, 0, 2 * 64 * 8 // 4, 4 * 32 * 48 * 2)),
     (_temporal(32, 64, 16, 8, 160), (NR_ATTN_WAVE, 5, 10, 0, 0, 2 * 64 * 8 // 4, 4 * 32 * 176 * 2)),
+    # every other instantiated dt (1, 2, 4, 6, 8) once per class, and a second width of dt = 3, 5, 10: the numbers the rule answered while the
+    # route still retyped the kernels' LDS strides (recorded from that commit's nr_attn_route)
+    (_self(2, 1024, 8, 16), (NR_ATTN_SHARED, 1, 1, 0, 0, 256, 20480)),
+    (_self(2, 40, 8, 16), (NR_ATTN_WAVE, 1, 1, 0, 0, 12, 4096)),
+    (_self(2, 100, 8, 8, fp8=1), (NR_ATTN_SHARED, 1, 1, 1, 0, 32, 20480)),
+    (_self(2, 1024, 8, 32), (NR_ATTN_SHARED, 1, 2, 0, 0, 256, 28672)),
+    (_self(2, 40, 8, 32), (NR_ATTN_WAVE, 1, 2, 0, 0, 12, 12288)),
+    (_self(2, 1024, 8, 24), (NR_ATTN_SHARED, 1, 2, 0, 0, 256, 28672)),
+    (_self(2, 1024, 8, 48), (NR_ATTN_SHARED, 2, 3, 0, 0, 256, 28672)),
+    (_self(2, 40, 8, 48), (NR_ATTN_WAVE, 2, 3, 0, 0, 12, 12288)),
+    (_self(2, 1024, 8, 64), (NR_ATTN_SHARED, 2, 4, 0, 0, 256, 36864)),
+    (_self(2, 40, 8, 64), (NR_ATTN_WAVE, 2, 4, 0, 0, 12, 20480)),
+    (_self(2, 100, 8, 56, fp8=1), (NR_ATTN_SHARED, 2, 4, 1, 0, 32, 36864)),
+    (_self(2, 1024, 8, 72), (NR_ATTN_SHARED, 3, 5, 0, 0, 256, 47104)),
+    (_self(2, 40, 8, 72), (NR_ATTN_WAVE, 3, 5, 0, 0, 12, 20480)),
+    (_self(2, 1024, 8, 96), (NR_ATTN_SHARED, 3, 6, 0, 0, 256, 55296)),
+    (_self(2, 40, 8, 96), (NR_ATTN_WAVE, 3, 6, 0, 0, 12, 28672)),
+    (_self(2, 100, 8, 88, fp8=1), (NR_ATTN_SHARED, 3, 6, 1, 0, 32, 55296)),
+    (_self(2, 1024, 8, 128), (NR_ATTN_SHARED, 4, 8, 0, 0, 256, 71680)),
+    (_self(2, 40, 8, 128), (NR_ATTN_WAVE, 4, 8, 0, 0, 12, 36864)),
+    (_self(2, 100, 8, 120, fp8=1), (NR_ATTN_SHARED, 4, 8, 1, 0, 32, 71680)),
+    (_self(2, 1024, 8, 152), (NR_ATTN_SHARED, 5, 10, 0, 0, 256, 88064)),
+    (_self(2, 40, 8, 152), (NR_ATTN_WAVE, 5, 10, 0, 0, 12, 45056)),
+    (_self(2, 100, 1, 256), (NR_ATTN_WIDE, 8, 16, 0, 0, 4, 68608)),
+    (_self(2, 100, 1, 512), (NR_ATTN_WIDE, 16, 32, 0, 0, 4, 134144)),
 ]
 
 

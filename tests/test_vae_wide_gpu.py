@@ -1,5 +1,5 @@
 """GPU: the full-width first-stage decoder / encoder (mid-block attention with one head of d = 512) on the wide-head attention kernel
-(attn_wide_kernel of attention.hip), at latents the GEMM sequence refuses (6 x 6, 10 x 12: h*w no multiple of 64), where the kernel is the
+(attn_fwd_shared_kernel<WideHead<512>> of attention.hip), at latents the GEMM sequence refuses (6 x 6, 10 x 12: h*w no multiple of 64), where the kernel is the
 default, and at latents the GEMM sequence also serves (8 x 8), where the kernel runs under NR_VAE_ATTN_WIDE=1 (the default there stays the
 GEMM sequence until a launch has a workgroup for every CU; the switch is read each time a plan is built).
 

@@ -9,7 +9,8 @@
 # tree's own Makefile flags (CXXFLAGS, NOPK, FLAGS_<name>; read from the Makefile, not retyped here) and compares the two texts per file.
 # One line per file: "identical", or "DIFFERS" and the first differing lines.  Exit status 1 if any file differs.
 # The only normalisation: the per-compile __hip_cuid_<hex> symbol becomes a fixed token (two compiles of the same source differ in exactly that).
-# Needs no GPU.  JOBS=<n> compiles in parallel (default 8, at most 16); FILES="a.hip b.hip" compares only those.
+# Needs no GPU.  JOBS=<n> compiles in parallel (default 8, at most 16); FILES="a.hip b.hip" compares only those; KEEP=<dir> keeps both sets of
+# assembly as <dir>/old and <dir>/new (tools/isa_kernels.py compares a file per kernel when a refactor renames or reorders its kernels).
 set -euo pipefail
 
 [ $# -ge 1 ] || { echo "usage: $0 <git-rev> [extra compile flags]" >&2; exit 2; }
@@ -48,6 +49,8 @@ for f in $srcs; do
   [ -f "$tmp/old/neurons_amd/csrc/$f" ] && printf '%s\0%s\0%s\0' old "$tmp/old/neurons_amd/csrc" "$f"
   printf '%s\0%s\0%s\0' new "$root/neurons_amd/csrc" "$f"
 done | xargs -0 -n 3 -P "$jobs" bash -c 'compile_one "$@"' _
+
+if [ -n "${KEEP:-}" ]; then mkdir -p "$KEEP" && cp -r "$tmp/asm/old" "$tmp/asm/new" "$KEEP/"; fi
 
 echo "# device assembly of the working tree against $rev ($(git -C "$root" rev-parse --short "$rev"))${extra:+, extra flags: $extra}"
 status=0
