@@ -24,6 +24,7 @@
 #include "device_prims.h"
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 namespace {
 
@@ -577,14 +578,54 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(NrGemmParams p_arg, 
 
 typedef TiledPlan Plan;       // gemm_route.h
 
+// THE instantiations of igemm_bf16_kernel: one row per (tile, wave grid) with the ring depths NS compiled for the conv / Linear forms (per depth: builtin
+// DMA and ADMA, and up to LIN_MAX_RING deep the LIN form of both), for the LayerNorm-folded form (one kernel per depth) and whether the phase form
+// exists (ADMA or not, always PHASE_RING deep).  The route's legalisation (legalise) and the launcher's dispatch (launch_exact) are both generated from
+// this table and nothing else names a tile or a depth: a plan is routable exactly when it is launchable.  160 kernels.
+constexpr unsigned rings(std::initializer_list<int> ns) { unsigned m = 0; for (int n : ns) m |= 1u << n; return m; }
+constexpr bool has_ring(unsigned set, int ns) { return ns >= 0 && ns < 32 && (set >> ns & 1); }
+struct TileRow {
+  int bm, bn, wgm, wgn;
+  unsigned ns, ns_ln;      // ring depths of the conv / Linear forms | of the LayerNorm-folded form (bit NS)
+  bool phase;
+  constexpr int waves() const { return wgn == 1 ? 41 : wgm * wgn; }      // TiledPlan::waves (41 = 4 x 1 row waves)
+  // dynamic LDS: the ring, and behind it the row-statistics exchange of the LayerNorm-folded form
+  constexpr size_t lds_bytes(int NS, bool ln) const { return (size_t)NS * (bm + bn) * 64 * sizeof(bf16) + (ln ? (size_t)2 * wgn * bm * sizeof(float) : 0); }
+};
+constexpr int RING_MIN = 2, RING_MAX = 8, LIN_MAX_RING = 4, PHASE_RING = 2;
+constexpr TileRow TILES[] = {
+    {256, 160, 2, 2, rings({2, 3}), 0, false},
+    {256, 128, 2, 2, rings({2, 3}), 0, false},
+    {256, 128, 4, 2, rings({2, 3}), 0, true},
+    {128, 160, 4, 1, rings({3, 4}), rings({3, 4}), false},      // row-wave tile of the wide GEGLU projections: 108 / 144 KiB, one workgroup per CU
+    {128, 160, 2, 2, rings({2, 3, 4}), 0, true},
+    {128, 128, 2, 4, rings({2, 3, 4}), rings({2}), true},
+    {128, 128, 2, 2, rings({2, 3, 4}), rings({2}), false},
+    {128, 64, 4, 2, rings({2, 3, 4}), rings({2, 4}), false},
+    {128, 64, 2, 2, rings({2, 3, 4}), rings({2, 4}), true},
+    {64, 160, 2, 2, rings({2, 3, 4}), rings({2, 3}), false},    // one-round tile of the N = 1280 Linears at M = 1024 / 2048
+    {64, 64, 2, 2, rings({2, 3, 4, 6, 8}), rings({2, 4}), true},      // depths 6 / 8: tools/shortk_sweep.py
+    {64, 32, 2, 2, rings({2, 3, 4, 6, 8}), rings({2, 4}), false},
+};
+constexpr int NTILES = sizeof(TILES) / sizeof(TILES[0]), NRINGS = RING_MAX - RING_MIN + 1;
+constexpr bool table_fits_lds() {
+  for (const TileRow& t : TILES)
+    for (int ns = 0; ns < 32; ++ns)
+      if ((has_ring(t.ns, ns) && (ns < RING_MIN || ns > RING_MAX || t.lds_bytes(ns, false) > 160 * 1024)) ||
+          (has_ring(t.ns_ln, ns) && (!has_ring(t.ns, ns) || t.lds_bytes(ns, true) > 160 * 1024)) || (t.phase && !has_ring(t.ns, PHASE_RING))) return false;
+  return true;
+}
+static_assert(table_fits_lds(), "every ring is RING_MIN .. RING_MAX deep and fits the 160 KiB of a CU's LDS; a LayerNorm-folded depth and the phase depth are depths of the tile");
+// the row of a tile with this wave count (0: any), among the rows with the phase form when `phase`
+constexpr const TileRow* find_row(int bm, int bn, int waves, bool phase = false) {
+  for (const TileRow& t : TILES)
+    if (t.bm == bm && t.bn == bn && (waves == 0 || t.waves() == waves) && (!phase || t.phase)) return &t;
+  return nullptr;
+}
+
 // Tile / wave-grid / split-K choice.  Rules distilled from tools/gemm_sweep.py on MI355X (profiles/): two LDS
 // stages (2 workgroups per CU) beat a deeper ring; 8 waves help the 128x128 tile; long-K layers with few
 // tiles gain 1.3-1.7x from split-K; 128x160 only pays for N = 320.
-// the (tile, waves) pairs the phase form (NrGemmParams::ups == 2) is instantiated for, all with the two-stage ring
-constexpr bool phase_tile(int bm, int bn, int waves) {
-  return (bm == 128 && bn == 160 && waves == 4) || (bm == 128 && bn == 128 && waves == 8) || (bm == 128 && bn == 64 && waves == 4) ||
-         (bm == 64 && bn == 64 && waves == 4) || (bm == 256 && bn == 128 && waves == 8);
-}
 // row tiles of a launch: the phase form tiles each of its four phases (M / 4 source pixels) on its own
 inline long long row_tiles(const NrGemmParams& p, int bm) { return p.ups == 2 ? 4ll * ((p.M / 4 + bm - 1) / bm) : (p.M + bm - 1) / bm; }
 
@@ -710,56 +751,71 @@ inline NrGemmParams plan_view(const NrGemmParams& p) {
 
 typedef void (*igemm_kern_t)(NrGemmParams, int, float*, int);
 
-// returns 0 on success, 9 when the requested (tile, LayerNorm-fused) combination has no instantiation
-template <int BM, int BN, int NS, int WGM, int WGN>
-int launch_cfg(const NrGemmParams& p, unsigned grid, const Plan& pl, float* partial, int m_fast, hipStream_t stream) {
-  size_t shm = (size_t)NS * (BM + BN) * 64 * sizeof(bf16);
-  // LayerNorm-fused variant: instantiated for the tiles the transformer GEMMs use (nr_gemm_route maps others onto them).
-  // Its row-statistics exchange buffer lives in the DYNAMIC allocation behind the ring: a static __shared__ array next to
-  // > 64 KiB of dynamic LDS made the first launch (and any hipGraph node captured from it) run with a short allocation.
-  constexpr bool LN_OK = (NS == 2 && BM <= 128 && BN <= 128) || (NS == 4 && (BM * BN <= 64 * 64 || (BM == 128 && BN == 64))) ||
-                         (BM == 128 && BN == 160 && WGN == 1 && NS <= 4) ||     // the row-wave 128x160 tile of the wide GEGLU projections
-                         (BM == 64 && BN == 160 && NS <= 3);                     // the one-round tile of the N = 1280 Linears at M = 1024 / 2048
+// The instantiation (row I of TILES, ring depth NS) of the form the request and the plan name.  Returns 0; 9 when the table has none (nothing is launched);
+// 2 when the runtime refuses the LDS opt-in
+template <int I, int NS>
+int launch_inst(const NrGemmParams& p, unsigned grid, const Plan& pl, float* partial, int m_fast, hipStream_t stream) {
+  constexpr TileRow T = TILES[I];
+  constexpr int BM = T.bm, BN = T.bn, WGM = T.wgm, WGN = T.wgn;
+  const bool ln = p.ln_c != nullptr, plain = !ln && p.ups != 2;
   igemm_kern_t k = nullptr;
-  int ki = 0;                   // LayerNorm-fused | 1 + 2 lin + adma | 5 + adma phase form
-  if (p.ln_c) {
-    if constexpr (LN_OK) { k = igemm_bf16_kernel<BM, BN, NS, WGM, WGN, true>; shm += (size_t)2 * WGN * BM * sizeof(float); }
-    else return 9;
-  } else if (p.ups == 2) {
-    // phase form: instantiated for the two-stage tiles choose_plan_phase picks from (the route maps every other request onto them)
-    if constexpr (phase_tile(BM, BN, WGM * WGN) && NS == 2) {
-      k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false, false, true> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true, false, true>;
-      ki = 5 + pl.adma;
-    } else return 9;
-  } else {
-    k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true>;
-    ki = 1 + pl.adma;
-    // plain Linears (1x1, one source) on the instantiation without the conv paths (rings up to 4 deep: the ones Linears are planned with)
-    if constexpr (NS <= 4) {
-      if (pl.lin) {
-        k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false, true> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true, true>;
-        ki += 2;
-      }
-    }
-  }
+  int ki = 0;                   // LayerNorm-folded | 1 + 2 lin + adma | 5 + adma phase form
+  // LayerNorm-folded: its row-statistics exchange buffer lives in the DYNAMIC allocation behind the ring (TileRow::lds_bytes): a static __shared__ array
+  // next to > 64 KiB of dynamic LDS made the first launch (and any hipGraph node captured from it) run with a short allocation.
+  if constexpr (has_ring(T.ns_ln, NS))
+    if (ln) k = igemm_bf16_kernel<BM, BN, NS, WGM, WGN, true>;
+  if constexpr (T.phase && NS == PHASE_RING)
+    if (p.ups == 2 && !ln) { k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false, false, true> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true, false, true>; ki = 5 + pl.adma; }
+  if constexpr (has_ring(T.ns, NS))
+    if (plain && !pl.lin) { k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true>; ki = 1 + pl.adma; }
+  if constexpr (has_ring(T.ns, NS) && NS <= LIN_MAX_RING)      // plain Linears (1x1, one source) on the instantiation without the conv paths
+    if (plain && pl.lin) { k = !pl.adma ? igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, false, true> : igemm_bf16_kernel<BM, BN, NS, WGM, WGN, false, true, true>; ki = 3 + pl.adma; }
+  if (!k) return 9;
+  const size_t shm = T.lds_bytes(NS, ln);
   static unsigned long long attr_done[7] = {};          // per instantiation
-  (void)nr_lds_opt_in(attr_done[ki], {(const void*)k}, shm);
+  if (const int rc = nr_lds_opt_in(attr_done[ki], {(const void*)k}, shm)) return rc;
   hipLaunchKernelGGL(k, dim3(grid), dim3(64 * WGM * WGN), shm, stream, p, pl.splitk, partial, m_fast);
   return 0;
 }
-
-template <int BM, int BN, int WGM, int WGN>
-int launch_tile(const NrGemmParams& p, unsigned grid, const Plan& pl, float* partial, int m_fast, hipStream_t stream) {
-  constexpr size_t STAGE = (size_t)(BM + BN) * 64 * sizeof(bf16);
-  constexpr bool FITS4 = 4 * STAGE <= 160 * 1024;
-  if (pl.stages <= 2) return launch_cfg<BM, BN, 2, WGM, WGN>(p, grid, pl, partial, m_fast, stream);
-  if (pl.stages == 3 || !FITS4) return launch_cfg<BM, BN, 3, WGM, WGN>(p, grid, pl, partial, m_fast, stream);
-  if (pl.stages <= 4 || BM * BN > 64 * 64) return launch_cfg<BM, BN, 4, WGM, WGN>(p, grid, pl, partial, m_fast, stream);   // deep ring
-  if (pl.stages <= 6) return launch_cfg<BM, BN, 6, WGM, WGN>(p, grid, pl, partial, m_fast, stream);
-  return launch_cfg<BM, BN, 8, WGM, WGN>(p, grid, pl, partial, m_fast, stream);
+// the exact lookup of (bm, bn, waves, stages) in TILES x [RING_MIN, RING_MAX]; J = row * NRINGS + depth - RING_MIN.  Never a neighbour: 9 when nothing matches
+template <size_t... J>
+int launch_exact(std::index_sequence<J...>, const NrGemmParams& p, unsigned grid, const Plan& pl, float* partial, int m_fast, hipStream_t stream) {
+  int rc = 9;
+  const auto is = [&](const TileRow& t, int ns) { return pl.bm == t.bm && pl.bn == t.bn && pl.waves == t.waves() && pl.stages == ns; };
+  (void)((is(TILES[J / NRINGS], RING_MIN + (int)(J % NRINGS)) &&
+          ((rc = launch_inst<(int)(J / NRINGS), RING_MIN + (int)(J % NRINGS)>(p, grid, pl, partial, m_fast, stream)), true)) || ...);
+  return rc;
 }
 
-// test/tuning override: NR_IGEMM_FORCE="bm,bn,splitk,stages,order" (any field <0 keeps the heuristic's choice)
+// smallest depth of the set not below the request, else the deepest
+constexpr int pick_ring(unsigned set, int want) {
+  int deepest = 0;
+  for (int ns = RING_MIN; ns <= RING_MAX; ++ns)
+    if (has_ring(set, ns)) { if (ns >= want) return ns; deepest = ns; }
+  return deepest;
+}
+// The one step from the plan the heuristics and NR_IGEMM_FORCE ask for to a row and ring of TILES that exist for the request's form (plain, LayerNorm-folded,
+// phase): afterwards (bm, bn, waves, stages) is what runs.  Returns 9 for a tile the table does not have
+int legalise(const NrGemmParams& p, Plan& pl) {
+  const bool ln = p.ln_c != nullptr, phase = p.ups == 2;
+  const bool row_wave = pl.waves == 41;          // as planned, whatever tile NR_IGEMM_FORCE then named
+  if (ln && pl.bn == 32) pl.bn = 64;             // every n-tile recomputes the row statistics: keep the n-tiles wide
+  if (!find_row(pl.bm, pl.bn, 0)) return 9;
+  const TileRow* t = phase ? find_row(pl.bm, pl.bn, 0, true) : find_row(pl.bm, pl.bn, pl.waves);      // phase form: the tile's phase row, whatever its wave grid
+  if (!t && !phase) t = find_row(pl.bm, pl.bn, 4);             // a wave grid the tile is not built with: its 2 x 2 one (every tile has it)
+  if (!t || (ln && !t->ns_ln)) t = find_row(128, 128, 8);      // a tile the form is not built for: 128 x 128 on 8 waves
+  pl.bm = t->bm; pl.bn = t->bn; pl.waves = t->waves();
+  if (phase) pl.stages = PHASE_RING;
+  // LayerNorm-folded: a depth the form is not built with falls back to the two-stage ring (two workgroups per CU), NOT to the next deeper one; a row-wave
+  // plan (one workgroup per CU, no two-stage ring) follows the rule of the plain forms
+  else if (ln) pl.stages = row_wave || has_ring(t->ns_ln, pl.stages) ? pick_ring(t->ns_ln, pl.stages) : 2;
+  else pl.stages = pick_ring(t->ns, pl.stages);
+  return 0;
+}
+
+// test/tuning override: NR_IGEMM_FORCE="bm,bn,splitk,stages,order,waves" (a field < 0 or left out keeps the heuristic's choice): a tile of TILES (both
+// fields or neither), K slices, ring depth 2 .. 8, tile order (0 n-fast, 1 m-fast, 8 grouped), waves 4 / 8 / 41 (41: the row-wave grid of 128 x 160).  What
+// it names goes through legalise like any plan, so the route records and the launcher runs the nearest instantiation of the request's form
 void apply_override(const NrGemmParams& p, Plan& pl, int& m_fast) {
   const char* e = getenv("NR_IGEMM_FORCE");
   if (!e) return;
@@ -773,8 +829,7 @@ void apply_override(const NrGemmParams& p, Plan& pl, int& m_fast) {
   int bm = -1, bn = -1, sk = -1, st = -1, ord = -1, wv = -1;
   sscanf(e, "%d,%d,%d,%d,%d,%d", &bm, &bn, &sk, &st, &ord, &wv);
   if (bm > 0 && bn > 0) {
-    const bool ok = (bm == 128 && (bn == 160 || bn == 128 || bn == 64)) || (bm == 64 && (bn == 64 || bn == 32 || bn == 160)) || (bm == 256 && (bn == 128 || bn == 160));
-    if (ok && !(p.geglu && ((bn == 160 && !(bm == 128 && wv == 41)) || bn == 32))) { pl.bm = bm; pl.bn = bn; }
+    if (find_row(bm, bn, 0) && !(p.geglu && ((bn == 160 && !(bm == 128 && wv == 41)) || bn == 32))) { pl.bm = bm; pl.bn = bn; }
   }
   if (wv == 4 || wv == 8) pl.waves = wv;
   if (pl.bm == 256 && pl.bn == 128 && wv != 4) pl.waves = 8;
@@ -834,22 +889,12 @@ int route(const NrGemmParams& p, NrGemmRoute* r, bool packed_ok) {
   const int ntm1 = (int)(phase ? row_tiles(p, pl.bm) / 4 : row_tiles(p, pl.bm));
   r->m_fast = tile_order(w_elems, a_elems, ntm1, (p.N + pl.bn - 1) / pl.bn);
   apply_override(p, pl, r->m_fast);
-  if (phase) {      // what the form is instantiated for: two stages, the tiles of phase_tile
-    pl.stages = 2;
-    if (pl.bm == 256 || (pl.bm == 128 && pl.bn == 128)) pl.waves = 8; else pl.waves = 4;
-    if (!phase_tile(pl.bm, pl.bn, pl.waves)) { pl.bm = 128; pl.bn = 128; pl.waves = 8; }
-    if (r->m_fast >= 2 && (row_tiles(p, pl.bm) / 4) % r->m_fast != 0) r->m_fast = w_elems > a_elems ? 1 : 0;
-  }
-  if (p.ln_c) {      // LayerNorm-fused: every block must see the whole row (K = C) -> no split-K; supported tiles only
+  if (p.ln_c) {      // LayerNorm-fused: every block must see the whole row (K = C) -> no split-K
     if (p.ksize != 1 || p.a1 || p.out_f32) return 8;
     pl.splitk = 1;
-    if (pl.bn == 32) pl.bn = 64;             // every n-tile recomputes the row statistics: keep the n-tiles wide
-    const bool t64x160 = pl.bm == 64 && pl.bn == 160;
-    if (!(pl.stages == 4 && (pl.bm * pl.bn <= 64 * 64 || (pl.bm == 128 && pl.bn == 64))) && pl.waves != 41 && !(t64x160 && pl.stages <= 3)) pl.stages = 2;
-    if (pl.bm > 128) { pl.bm = 128; pl.bn = 128; pl.waves = 8; }
-    if (pl.bn > 128 && !(pl.bm == 128 && pl.bn == 160 && pl.waves == 41) && !t64x160) { pl.bm = 128; pl.bn = 128; pl.waves = 8; }
-    if (pl.waves == 41 && pl.stages > 4) pl.stages = 4;
   }
+  if (legalise(p, pl)) return 9;
+  if (phase && r->m_fast >= 2 && (row_tiles(p, pl.bm) / 4) % r->m_fast != 0) r->m_fast = w_elems > a_elems ? 1 : 0;
   if (p.out_f32) {   // raw fp32 result: the kernel's slab path with a single K slice, no reduce pass
     if (p.geglu) return 7;
     pl.splitk = 1;
@@ -858,6 +903,8 @@ int route(const NrGemmParams& p, NrGemmRoute* r, bool packed_ok) {
   static const bool lin_on = env_not_0("NR_IGEMM_LIN");                                                  // A/B switch
   pl.adma = (p.K / 64) / (pl.splitk > 1 ? pl.splitk : 1) >= adma_min;
   pl.lin = lin_on && p.ksize == 1 && !p.a1 && p.c1 == 0;
+  if (pl.stages > LIN_MAX_RING) pl.lin = 0;       // the Linear-only instantiation exists for the rings Linears are planned with
+  if (p.ln_c) { pl.adma = 0; pl.lin = 1; }        // the LayerNorm-folded form is one instantiation per ring: builtin DMA, a Linear by construction
   r->ws_bytes = pl.splitk > 1 ? (size_t)pl.splitk * p.M * p.N * sizeof(float) : 0;
   return 0;
 }
@@ -868,23 +915,8 @@ int launch_tiled(const NrGemmParams& p, const Plan& pl, int m_fast, float* works
   if (pl.splitk > 1 && !workspace) return 6;
   float* partial = p.out_f32 ? p.out_f32 : (pl.splitk > 1 ? workspace : nullptr);
   const unsigned grid = (unsigned)(row_tiles(p, pl.bm) * ((p.N + pl.bn - 1) / pl.bn) * pl.splitk);
-  int rc;
-  if (pl.bm == 256 && pl.bn == 160) rc = launch_tile<256, 160, 2, 2>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 256 && pl.waves == 4) rc = launch_tile<256, 128, 2, 2>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 256) rc = launch_tile<256, 128, 4, 2>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 128 && pl.bn == 160 && pl.waves == 41)      // row-wave tile: rings 3 / 4 deep only (108 / 144 KiB: one workgroup per CU)
-    rc = pl.stages <= 3 ? launch_cfg<128, 160, 3, 4, 1>(p, grid, pl, partial, m_fast, stream)
-                        : launch_cfg<128, 160, 4, 4, 1>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 128 && pl.bn == 160) rc = launch_tile<128, 160, 2, 2>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 128 && pl.bn == 128 && pl.waves == 8) rc = launch_tile<128, 128, 2, 4>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 128 && pl.bn == 128) rc = launch_tile<128, 128, 2, 2>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 128 && pl.bn == 64 && pl.waves == 8) rc = launch_tile<128, 64, 4, 2>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 128 && pl.bn == 64) rc = launch_tile<128, 64, 2, 2>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 64 && pl.bn == 160) rc = launch_tile<64, 160, 2, 2>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 64 && pl.bn == 32) rc = launch_tile<64, 32, 2, 2>(p, grid, pl, partial, m_fast, stream);
-  else if (pl.bm == 64 && pl.bn == 64) rc = launch_tile<64, 64, 2, 2>(p, grid, pl, partial, m_fast, stream);
-  else rc = 9;            // no such tile: never launch another one on a grid computed for this one
-  if (rc) return rc;      // no instantiation for this (tile, LayerNorm-fused) request: fail loudly, never skip the launch
+  // no such instantiation (9) or no LDS opt-in (2): fail loudly, never launch a neighbour on a grid computed for this tile
+  if (const int rc = launch_exact(std::make_index_sequence<NTILES * NRINGS>{}, p, grid, pl, partial, m_fast, stream)) return rc;
   if (pl.splitk > 1) {
     const long long total = (long long)p.M * (p.N / 4);
     hipLaunchKernelGGL(p.ups == 2 ? splitk_reduce_kernel<true> : splitk_reduce_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p,

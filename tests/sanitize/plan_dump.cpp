@@ -12,7 +12,12 @@
 //          plan_dump --ff-waves <schema-file>          the C = 320 temporal and transformer leaves at 4096 rows (ff_fused, tattn_fused / xattn_fused, GroupNorm, attention)
 //                                                      planned under 8 FeedForward waves and replayed (graph off) before and after nr_ff_set_waves(4), then planned
 //                                                      afresh under 4: the wave count is the plan's (tests/test_launch_routes_host.py)
+//          plan_dump --force-sweep                     the tiled igemm under every NR_IGEMM_FORCE string of bm {64, 128, 256} x bn {32, 64, 128, 160} x stages 2 .. 8 x
+//                                                      waves {-1, 4, 8, 41}: per string one small call of each request kind (Linear, GEGLU Linear, LayerNorm-folded
+//                                                      Linear plain and GEGLU, 3x3 conv, two-source 3x3 conv, phase-form upsample conv) through its op hook, with
+//                                                      the route's tiled plan as a note in front of the launch lines (tests/test_igemm_table_host.py)
 #include "../../include/neurons_amd.h"
+#include "launchers.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -141,6 +146,57 @@ static int run_ops(const char* path) {
   return 0;
 }
 
+// --force-sweep: see the usage text.  M <= 512 rows, so of the five GEMM classes only smallm could claim a call, and it steps aside under NR_IGEMM_FORCE.
+// The note is nr_gemm_route on the NrGemmParams the hook builds from the same arguments (engine_ops.hip); a hook that fails adds a "status" note
+static int run_force_sweep() {
+  alignas(256) static char blk[4096];
+  const bf16* b = reinterpret_cast<const bf16*>(blk);
+  bf16* o = reinterpret_cast<bf16*>(blk);
+  const float* fp = reinterpret_cast<const float*>(blk);
+  const int M = 320, N = 320, K = 256, H = 16, Cin = 64;      // Linears: 320 rows; convs: one 16 x 16 image (the phase form: 8 x 8 -> 16 x 16)
+  struct Kind { const char* name; NrGemmParams p; std::function<nr_status()> hook; };
+  std::vector<Kind> kinds;
+  const auto linear = [&](const char* name, int geglu, bool ln) {
+    const int Nw = geglu ? 2 * N : N;
+    NrGemmParams p = nr_gemm_params(b, K, K, nullptr, 0, 0, M, 1, 1, 1, 1, 0, b, Nw, fp, b, N, o, N);
+    p.geglu = geglu;
+    if (ln) { p.ln_c = fp; p.ln_eps = 1e-5f; }
+    kinds.push_back({name, p, [=]() { return ln ? nr_op_ln_gemm(nullptr, blk, K, blk, fp, fp, 1e-5f, blk, N, blk, N, M, Nw, K, geglu, 0)
+                                                 : nr_op_gemm(nullptr, blk, K, blk, fp, blk, N, blk, N, M, Nw, K, geglu); }});
+  };
+  linear("linear", 0, false);
+  linear("geglu", 1, false);
+  linear("ln_linear", 0, true);
+  linear("ln_geglu", 1, true);
+  for (int c1 : {0, 2 * Cin}) {      // two sources of 128 channels: K = 2304, long enough for the heuristic's split-K (and its reduce launch)
+    const int c0 = c1 ? c1 : Cin;
+    NrGemmParams p = nr_gemm_params(b, c0, c0, c1 ? b : nullptr, c1, c1, 1, H, H, 3, 1, 0, b, N, fp, nullptr, N, o, N);
+    kinds.push_back({c1 ? "conv3x3_2src" : "conv3x3", p, [=]() { return nr_op_conv3x3(nullptr, blk, c0, c1 ? blk : nullptr, c1, 1, H, H, 1, 0, blk, fp, nullptr, 0, nullptr, blk, N); }});
+  }
+  kinds.push_back({"conv3x3_ups_phase", nr_gemm_params(b, Cin, Cin, nullptr, 0, 0, 1, H / 2, H / 2, 3, 1, 2, b, N, fp, nullptr, 0, o, N),
+                   [=]() { return nr_op_conv3x3_ups_phase(nullptr, blk, Cin, 1, H / 2, H / 2, blk, fp, blk, N); }});
+  for (int bm : {64, 128, 256})
+    for (int bn : {32, 64, 128, 160})
+      for (int st = 2; st <= 8; ++st)
+        for (int wv : {-1, 4, 8, 41}) {
+          const std::string force = std::to_string(bm) + "," + std::to_string(bn) + ",-1," + std::to_string(st) + ",-1," + std::to_string(wv);
+          setenv("NR_IGEMM_FORCE", force.c_str(), 1);
+          for (const Kind& k : kinds) {
+            NrGemmRoute r;
+            const int rc = nr_gemm_route(&k.p, &r);
+            const TiledPlan& t = r.tiled;
+            char note[256];
+            snprintf(note, sizeof(note), "route %s force=%s status=%d class=%s bm=%d bn=%d splitk=%d stages=%d waves=%d adma=%d lin=%d", k.name, force.c_str(), rc,
+                     nr_gemm_class_name[r.cls], t.bm, t.bn, t.splitk, t.stages, t.waves, t.adma, t.lin);
+            nr_stub_note(note);
+            const nr_status st_hook = k.hook();
+            if (st_hook != NR_OK) nr_stub_note(("status " + std::to_string((int)st_hook)).c_str());
+          }
+        }
+  unsetenv("NR_IGEMM_FORCE");
+  return 0;
+}
+
 // --decide-once: see the usage text.  Prints the status of each replay
 static int run_decide_once(const char* schema) {
   const auto nets = read_schema(schema);
@@ -203,7 +259,8 @@ static int run_ff_waves(const char* schema) {
 }
 
 int main(int argc, char** argv) {
-  if (argc < 2) { fprintf(stderr, "usage: plan_dump <schema-file> [name,name,...] | --ops <shapes-file> | --decide-once <schema-file> | --ff-waves <schema-file>\n"); return 1; }
+  if (argc < 2) { fprintf(stderr, "usage: plan_dump <schema-file> [name,name,...] | --ops <shapes-file> | --decide-once <schema-file> | --ff-waves <schema-file> | --force-sweep\n"); return 1; }
+  if (argc == 2 && std::string(argv[1]) == "--force-sweep") return run_force_sweep();
   if (argc == 3 && std::string(argv[1]) == "--ff-waves") return run_ff_waves(argv[2]);
   if (argc == 3 && std::string(argv[1]) == "--ops") return run_ops(argv[2]);
   if (argc == 3 && std::string(argv[1]) == "--decide-once") return run_decide_once(argv[2]);

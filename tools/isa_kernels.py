@@ -73,15 +73,18 @@ def main():
     for n, b in new.items():
         partners = by_text.get(hashlib.sha1(normalised(n, b).encode()).hexdigest())
         if partners:
-            matched.add(partners[0])
-            print(f"identical  {names[n]}  ==  {names[partners[0]]}")
+            partner = n if n in partners else partners[0]      # the kernel of the same name (same template arguments) where it is one of them
+            matched.add(partner)
+            print(f"identical  {names[n]}  ==  {names[partner]}")
         else:
             differing += 1
             print(f"DIFFERS    {names[n]}\n           new: {figures(b)}")
     for n, b in old.items():
         if n not in matched:
             print(f"unmatched  {names[n]} (old)\n           old: {figures(b)}")
-    print(f"# {len(new) - differing} of {len(new)} kernels identical to a kernel of {sys.argv[1]}")
+    same_name = sum(1 for n in new if n in matched)
+    print(f"# {len(new) - differing} of {len(new)} kernels identical to a kernel of {sys.argv[1]} ({same_name} to the one of the same name); "
+          f"{len(old) - len(matched)} of its {len(old)} kernels have no partner")
     sys.exit(1 if differing else 0)
 
 

@@ -12,7 +12,8 @@
 # process reads once (NR_LN_FUSE=0, NR_FOLD_PROJ_OUT=0, NR_SMALLM=0), then the networks with GEMM-heavy plans once per switch of the GEMM route (NR_G8P=0 / 2,
 # NR_ROWPANEL=0, NR_LIN160=0, one NR_IGEMM_FORCE setting), then once per switch of the GroupNorm and attention routes (NR_GN_SLAB=0, NR_GN_SMALL=0,
 # NR_GN_T=1024, NR_ATTN_ROWSUM=adds), of the fused FeedForward (NR_FF_WAVES=4, NR_FF_FUSED=0) and of the fused attention blocks (NR_TATTN_FUSED=0,
-# NR_XATTN_FUSED=0, NR_TATTN_HEAD=0, NR_XATTN_HEAD=0) on the networks whose plans contain those kernels.  One line per run: "identical", or "DIFFERS" and the first differing lines.
+# NR_XATTN_FUSED=0, NR_TATTN_HEAD=0, NR_XATTN_HEAD=0) on the networks whose plans contain those kernels, then the op hooks (plan_dump --ops: the whole trace) and the
+# NR_IGEMM_FORCE sweep of the tiled igemm (plan_dump --force-sweep: the launch lines only; the route notes between them are counted).  One line per run: "identical", or "DIFFERS" and the first differing lines.
 # The dump must also contain every kernel class the planner can choose (a shape list that loses one is no evidence).  Exit status 1 on any of it.
 # The only normalisation: pointer values (0x...) become a fixed token.  Needs no GPU.  JOBS=<n> compiles in parallel (default 8, at most 16).
 set -euo pipefail
@@ -71,6 +72,15 @@ run_both tattn_fused_0 leaf_temporal NR_TATTN_FUSED=0
 run_both xattn_fused_0 leaf_transformer NR_XATTN_FUSED=0
 run_both tattn_head_0 leaf_temporal640,leaf_temporal1280 NR_TATTN_HEAD=0
 run_both xattn_head_0 leaf_transformer640,leaf_transformer1280 NR_XATTN_HEAD=0
+# the GEMM / conv op hooks at the shapes of tests/sanitize/op_route_shapes.txt, and the tiled igemm under the NR_IGEMM_FORCE sweep of plan_dump --force-sweep
+for t in old new; do
+  env -u NR_DETERMINISTIC_BATCH -u NR_IGEMM_FORCE NR_STUB_TRACE="$tmp/$t.ops.trace" "$tmp/$t/build/plan_dump" --ops "$root/tests/sanitize/op_route_shapes.txt" > /dev/null ||
+    { echo "$t ops: plan_dump failed" >&2; exit 1; }
+  env -u NR_DETERMINISTIC_BATCH NR_STUB_TRACE="$tmp/$t.sweep.trace" "$tmp/$t/build/plan_dump" --force-sweep > /dev/null || { echo "$t sweep: plan_dump failed" >&2; exit 1; }
+  sed -E -i 's/0x[0-9a-f]+/PTR/g' "$tmp/$t.ops.trace" "$tmp/$t.sweep.trace"
+  grep '^L ' "$tmp/$t.sweep.trace" > "$tmp/$t.sweep.launches"
+  grep '^# ' "$tmp/$t.sweep.trace" > "$tmp/$t.sweep.notes"
+done
 
 echo "# plans of the working tree against $rev ($(git -C "$root" rev-parse --short "$rev"))"
 status=0
@@ -86,6 +96,17 @@ for label in default ln_fuse_0 fold_proj_out_0 smallm_0 g8p_0 g8p_2 rowpanel_0 l
     fi
   done
 done
+for what in ops.trace sweep.launches; do
+  a="$tmp/old.$what"; b="$tmp/new.$what"
+  if cmp -s "$a" "$b"; then
+    echo "${what/./ }: identical ($(wc -l < "$b") lines, $(grep -c '^L ' "$b") launches)"
+  else
+    echo "${what/./ }: DIFFERS"; status=1
+    diff "$a" "$b" | head -n 12 | sed 's/^/    /' || true
+  fi
+done
+# the sweep's route notes may differ where $rev's route recorded a plan its launcher then changed: counted, not judged
+echo "sweep notes: $(diff "$tmp/old.sweep.notes" "$tmp/new.sweep.notes" | grep -c '^>' || true) of $(wc -l < "$tmp/new.sweep.notes") differ from $rev's"
 # coverage: <rev>'s own default dump plans every kernel class
 for k in ff_fused xattn_fused xattn_head tattn_fused tattn_head 'lin160 ' 'lin160 panel' igemm groupnorm layernorm attention; do
   n=$(grep -c -E "^op [0-9]+: $k" "$tmp/old.default.dump" || true)
