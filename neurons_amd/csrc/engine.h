@@ -6,7 +6,7 @@
 //   engine_ops.hip      the single-op test hooks (nr_op_*)
 //   engine.hip          graph-replay runtime, the C ABI, the engine's two small kernels
 // A plan idiom that is needed twice lives in ONE helper here (WeightStore::packed / convert / stacked / w_temb_projection, nr_net::begin_plan / stage_context /
-// context_kv / linear_wb / splitk_scratch, descf); a derived weight name is spelled in engine_weights.hip only; a host-side change of these files is accepted on tools/plan_equal.sh.
+// context_kv / linear_wb / splitk_scratch / stem / head / downsample_conv / time_embedding / frame_gather, descf); a derived weight name is spelled in engine_weights.hip only; a host-side change of these files is accepted on tools/plan_equal.sh.
 #pragma once
 #include "launchers.h"
 #include "../../include/neurons_amd.h"
@@ -439,7 +439,7 @@ struct nr_net {
   Act layernorm(const Act& x, const std::string& prefix, const float* pe, int pe_F);
   Act attention(int mode, const Act& q, const Act* kv, int C, int heads, int causal = 0);
   using TembSlot = nre::TembSlot;
-  std::vector<TembSlot> temb_slots;   // filled by a pre-pass over the topology
+  std::vector<TembSlot> temb_slots;   // add_temb_slot: one per ResBlock, before time_embedding
   float* temb_all = nullptr;          // [B2][temb_total]
   const float* temb_for(const std::string& prefix, int C);
   struct ResKeys { std::string norm1, conv1, norm2, conv2, shortcut; };
@@ -464,7 +464,26 @@ struct nr_net {
   Act vae_attn(const Act& x, const std::string& pre);
 
   // ------------------------------------------------------------------ networks (engine_nets.hip)
-  void enumerate_resnets(std::vector<TembSlot>& out) const;
+  // emitters the builders share.  What the 4-channel stem reads is resolved when the op launches: io.sample (`batch` samples; affine: x * io.in_scale + io.in_shift),
+  // io.cond + io.mask (C + 1 planes of io.cond_batch condition images), or a plan-time buffer such as the VAE decoder's post_quant output
+  struct StemIn { enum { SAMPLE, COND, BUFFER } from; int C, batch; const float* buf = nullptr; bool affine = false; };
+  std::function<void(hipStream_t)> stem(const StemIn& in, const std::string& key, const Act& out, const char* addend_key = nullptr);
+  void head(const Act& x, const std::string& norm, const std::string& conv, int Cout, const char* quant = nullptr);
+  Act downsample_conv(const Act& x, const std::string& key, const std::string& tap_name, int pad_tl0 = 0);
+  void add_temb_slot(const std::string& prefix, int C) { temb_slots.push_back(TembSlot{prefix, temb_total, C}); temb_total += C; }
+  void time_embedding(const std::string& l1, const std::string& l2, const char* label, const std::string& tag, const std::string& layer);
+  // the identical-frame evaluation (n_cond_frames): the n distinct frames to evaluate and, per frame, which of them it equals; empty = off
+  struct FrameDedup { std::vector<int> reduce, expand; int n() const { return (int)reduce.size(); } };
+  FrameDedup identical_frames() const;
+  Act frame_gather(const Act& x, int Fs, const std::vector<int>& map);
+  Act embed_conv(const Act& in, int Fe, const std::string& key, int Cout, int stride, int silu, const float* bias);
+  void cond_embedding(Act& x, const FrameDedup& fd);
+  // the builders: one per network kind, each in the order of its reference forward()
+  struct Trunk { Act x, ctx; std::vector<Act> skips; };      // mid-block output, bf16 text context, the n_res down-block residuals
+  Trunk down_mid();
+  void residual_adds(const Trunk& t);
+  void build_unet3d();
+  void build_sparsectrl();
   struct SgmLayout {
     struct In { int idx; int kind; int level; int Cout; };          // kind 0 conv_in, 1 res(+attn), 2 downsample
     struct Out { int idx; int level; int Cout; bool attn; bool up; };
@@ -477,9 +496,7 @@ struct nr_net {
   void build_vae_enc();
   void build_clip();
   void build_leaf();
-  Act embed_conv(const Act& in, int Fe, const std::string& key, int Cout, int stride, int silu, const float* bias);
-  void cond_embedding(Act& x, int nd, const int* fmap_reduce, const int* fmap_expand);
-  void build();
+  void build();                  // dispatch on cfg.kind
   void plan(int batch, int frames, int h, int w, int ctxl);
 
   // ------------------------------------------------------------------ runtime (engine.hip)

@@ -56,6 +56,11 @@ static const std::map<std::string, std::vector<Case>> g_cases = {
                    {{2, 8, 8, 8, 77}, DEBUG_TAPS}, {{2, 8, 8, 8, 77}, CFG_PAIR}}},
     {"tiny_ctrl", {{{2, 8, 8, 8, 77}, PLAIN}, {{8, 8, 8, 8, 77}, PLAIN}, {{2, 8, 8, 8, 77}, COND_FRAME0}}},
     {"tiny_ctrl_image", {{{2, 8, 8, 8, 77}, PLAIN}, {{2, 8, 8, 8, 77}, COND_FRAME0}}},
+    // the noisy sample not zeroed (conv_in(sample) + the embedding), a motion module in the mid block, 17 residual adds (one launch each)
+    {"tiny_ctrl_noisy", {{{2, 8, 8, 8, 77}, PLAIN}, {{4, 8, 8, 8, 77}, PLAIN}}},
+    {"tiny_ctrl_image_noisy", {{{2, 8, 8, 8, 77}, PLAIN}}},
+    {"tiny_unet_midmotion", {{{2, 8, 8, 8, 77}, PLAIN}}},
+    {"tiny_unet_lpb3", {{{2, 8, 8, 8, 77}, PLAIN}}},
     // C = 320: 4608 / 128 / 9216 rows (the dry-run's), 4096 and 512 rows
     {"leaf_transformer", {{{1, 2, 48, 48, 77}, PLAIN}, {{1, 2, 8, 8, 77}, PLAIN}, {{2, 2, 48, 48, 77}, PLAIN}, {{1, 4, 32, 32, 77}, PLAIN}, {{1, 2, 16, 16, 77}, PLAIN},
                           {{2, 16, 16, 16, 77}, DET_BATCH}}},

@@ -120,4 +120,10 @@ for k in smallm_kernel lin160_kernel lin128q_kernel rowpanel_kernel g8p_kernel i
   echo "coverage '$k': $n launches in $rev's trace"
   [ "$n" -gt 0 ] || status=1
 done
+# ... and the default dump plans the networks that reach the builders' rarer branches (noisy sample not zeroed, mid-block motion module, one add per residual)
+for k in tiny_ctrl_noisy tiny_ctrl_image_noisy tiny_unet_midmotion tiny_unet_lpb3; do
+  n=$(grep -c "^== $k plan " "$tmp/old.default.dump" || true)
+  echo "coverage '$k': $n plans in $rev's dump"
+  [ "$n" -gt 0 ] || status=1
+done
 exit $status
