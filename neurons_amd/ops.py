@@ -29,27 +29,39 @@ def _chk_f32(*ts):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), (t.dtype, t.shape)
 
 
-def gemm(a, w, bias=None, res=None, geglu=False):
-    """out[M, N(or N/2)] = a[M, K] @ w[N, K]^T (+bias) (+res) ; geglu expects the value/gate-interleaved weight."""
+def _out_tensor(out, shape, like):
+    """The result tensor of an op: a fresh one, or the caller's (contiguous bf16 of the result shape on the inputs' device)."""
+    if out is None:
+        return torch.empty(*shape, dtype=torch.bfloat16, device=like.device)
+    _chk_bf16(out)
+    if tuple(out.shape) != tuple(shape) or out.device != like.device:
+        raise ValueError(f"out: expected a bf16 tensor of shape {tuple(shape)} on {like.device}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def gemm(a, w, bias=None, res=None, geglu=False, out=None):
+    """out[M, N(or N/2)] = a[M, K] @ w[N, K]^T (+bias) (+res) ; geglu expects the value/gate-interleaved weight.
+    out: write the result into this tensor."""
     _chk_bf16(a, w, res)
     _chk_f32(bias)
     M, K = a.shape
     N = w.shape[0]
-    out = torch.empty(M, N // 2 if geglu else N, dtype=torch.bfloat16, device=a.device)
+    out = _out_tensor(out, (M, N // 2 if geglu else N), a)
     lib = _lib.load()
     _lib.check(lib.nr_op_gemm(_stream(), _ptr(a), K, _ptr(w), _ptr(bias), _ptr(res), out.shape[1], _ptr(out),
                               out.shape[1], M, N, K, 1 if geglu else 0))
     return out
 
 
-def gemm2(a0, a1, w, bias=None, res=None):
-    """out[M, N] = cat([a0, a1], dim=1) @ w[N, c0 + c1]^T (+bias) (+res) without materialising the concat (engine: two-source igemm)."""
+def gemm2(a0, a1, w, bias=None, res=None, out=None):
+    """out[M, N] = cat([a0, a1], dim=1) @ w[N, c0 + c1]^T (+bias) (+res) without materialising the concat (engine: two-source igemm).
+    out as in gemm."""
     _chk_bf16(a0, a1, w, res)
     _chk_f32(bias)
     M, c0 = a0.shape
     c1 = a1.shape[1]
     N = w.shape[0]
-    out = torch.empty(M, N, dtype=torch.bfloat16, device=a0.device)
+    out = _out_tensor(out, (M, N), a0)
     _lib.check(_lib.load().nr_op_gemm2(_stream(), _ptr(a0), c0, c0, _ptr(a1), c1, c1, _ptr(w), _ptr(bias), _ptr(res), N, _ptr(out), N, M, N))
     return out
 
@@ -92,10 +104,10 @@ def _ln_fold(w, gamma, beta, bias=None):
     return ws, c, b.contiguous()
 
 
-def ln_gemm(a, w, gamma, beta, bias=None, res=None, eps=1e-5, act=0, geglu=False):
+def ln_gemm(a, w, gamma, beta, bias=None, res=None, eps=1e-5, act=0, geglu=False, out=None):
     """out = Linear(LayerNorm(a)) with the LayerNorm folded into the GEMM (engine: ln_linear).  The folding of gamma / beta
     into (w_scaled, ln_c, bias_folded) is done here on the host exactly as engine.hip's w_ln_linear does.  ``geglu``: w is a GEGLU projection
-    [value(inner) | gate(inner)] (rows re-ordered here to the engine's 16 / 16 interleave); out = value * gelu(gate), inner columns."""
+    [value(inner) | gate(inner)] (rows re-ordered here to the engine's 16 / 16 interleave); out = value * gelu(gate), inner columns.  out as in gemm."""
     _chk_bf16(a, res)
     M, K = a.shape
     if geglu:
@@ -103,7 +115,7 @@ def ln_gemm(a, w, gamma, beta, bias=None, res=None, eps=1e-5, act=0, geglu=False
     N = w.shape[0]
     ws, c, b = _ln_fold(w, gamma, beta, bias)
     No = N // 2 if geglu else N
-    out = torch.empty(M, No, dtype=torch.bfloat16, device=a.device)
+    out = _out_tensor(out, (M, No), a)
     lib = _lib.load()
     _lib.check(lib.nr_op_ln_gemm(_stream(), _ptr(a), K, _ptr(ws), _ptr(c), _ptr(b), float(eps), _ptr(res), No, _ptr(out), No, M, N, K, 1 if geglu else 0,
                                  int(act)))
@@ -138,9 +150,10 @@ def geglu_permute(w, b):
     return w[src].contiguous(), (None if b is None else b[src].contiguous())
 
 
-def conv3x3(x0, w, bias=None, x1=None, stride=1, ups=False, rowvec=None, rowvec_div=1, res=None, tap_inner=False):
+def conv3x3(x0, w, bias=None, x1=None, stride=1, ups=False, rowvec=None, rowvec_div=1, res=None, tap_inner=False, out=None):
     """x0/x1: [nimg, H, W, C] bf16; w: [Cout, 3, 3, Cin] bf16 (tap-major); returns [nimg, OH, OW, Cout].
-    tap_inner: run the engine's ResnetBlock form (stride 1, one source): the weight is re-arranged here to [Cout][Cin/64][3][3][64]."""
+    tap_inner: run the engine's ResnetBlock form (stride 1, one source): the weight is re-arranged here to [Cout][Cin/64][3][3][64].
+    out: write the result into this tensor (either form)."""
     _chk_bf16(x0, x1, w, res)
     _chk_f32(bias, rowvec)
     nimg, H, W, c0 = x0.shape
@@ -149,7 +162,7 @@ def conv3x3(x0, w, bias=None, x1=None, stride=1, ups=False, rowvec=None, rowvec_
             raise ValueError("tap_inner: stride 1, no upsample, one source, Cin % 64 == 0")
         Cout = w.shape[0]
         wt = w.reshape(Cout, 9, c0 // 64, 64).permute(0, 2, 1, 3).contiguous()
-        out = torch.empty(nimg, H, W, Cout, dtype=torch.bfloat16, device=x0.device)
+        out = _out_tensor(out, (nimg, H, W, Cout), x0)
         _lib.check(_lib.load().nr_op_conv3x3_tap_inner(_stream(), _ptr(x0), c0, nimg, H, W, _ptr(wt), _ptr(bias), _ptr(rowvec), rowvec_div,
                                                         _ptr(res), _ptr(out), Cout))
         return out
@@ -158,7 +171,7 @@ def conv3x3(x0, w, bias=None, x1=None, stride=1, ups=False, rowvec=None, rowvec_
     OH, OW = (2 * H, 2 * W) if ups else (H, W)
     if stride == 2:
         OH, OW = (OH - 1) // 2 + 1, (OW - 1) // 2 + 1
-    out = torch.empty(nimg, OH, OW, Cout, dtype=torch.bfloat16, device=x0.device)
+    out = _out_tensor(out, (nimg, OH, OW, Cout), x0)
     lib = _lib.load()
     _lib.check(lib.nr_op_conv3x3(_stream(), _ptr(x0), c0, _ptr(x1), c1, nimg, H, W, stride, 1 if ups else 0, _ptr(w),
                                  _ptr(bias), _ptr(rowvec), rowvec_div, _ptr(res), _ptr(out), Cout))
@@ -175,15 +188,16 @@ def ups_phase_weights(w_tap):
     return out
 
 
-def conv3x3_ups_phase(x, w_tap, bias=None):
+def conv3x3_ups_phase(x, w_tap, bias=None, out=None):
     """nearest-2x upsample + 3x3 conv (pad 1) as four 2x2 phase convs on the source: x [nimg, H, W, Cin] bf16, w_tap [Cout, 3, 3, Cin] (the taps
-    conv3x3 takes), bias fp32 [Cout]; returns [nimg, 2H, 2W, Cout] bf16.  conv3x3(ups=True) is the same conv on the replicated image."""
+    conv3x3 takes), bias fp32 [Cout]; returns [nimg, 2H, 2W, Cout] bf16.  conv3x3(ups=True) is the same conv on the replicated image.
+    out: write the result into this tensor."""
     _chk_bf16(x)
     _chk_f32(bias)
     nimg, H, W, Cin = x.shape
     Cout = w_tap.shape[0]
     wp = ups_phase_weights(w_tap).to(x.device)
-    out = torch.empty(nimg, 2 * H, 2 * W, Cout, dtype=torch.bfloat16, device=x.device)
+    out = _out_tensor(out, (nimg, 2 * H, 2 * W, Cout), x)
     _lib.check(_lib.load().nr_op_conv3x3_ups_phase(_stream(), _ptr(x), Cin, nimg, H, W, _ptr(wp), _ptr(bias), _ptr(out), Cout))
     return out
 
@@ -253,16 +267,6 @@ def layernorm(x, gamma, beta, eps=1e-5, pe=None, pe_hw=1, pe_F=1):
     return out
 
 
-def _attn_out(out, shape, like):
-    """The result tensor of an attention op: a fresh one, or the caller's (contiguous bf16 of the result shape on the inputs' device)."""
-    if out is None:
-        return torch.empty(*shape, dtype=torch.bfloat16, device=like.device)
-    _chk_bf16(out)
-    if tuple(out.shape) != tuple(shape) or out.device != like.device:
-        raise ValueError(f"out: expected a bf16 tensor of shape {tuple(shape)} on {like.device}, got {tuple(out.shape)} on {out.device}")
-    return out
-
-
 def attention_self(qkv, heads, fp8=False, causal=False, out=None):
     """qkv: [nimg, L, 3C] fused; returns [nimg, L, C].  Head widths d = C / heads: multiples of 8 up to 160 (104 .. 112 and 136 .. 144 excepted)
     and the wide heads 256 and 512 (the VAE mid-block's single head; bf16 and unmasked only: not with fp8 or causal); any other width raises.
@@ -271,7 +275,7 @@ def attention_self(qkv, heads, fp8=False, causal=False, out=None):
     _chk_bf16(qkv)
     nimg, L, C3 = qkv.shape
     Cc = C3 // 3
-    out = _attn_out(out, (nimg, L, Cc), qkv)
+    out = _out_tensor(out, (nimg, L, Cc), qkv)
     lib = _lib.load()
     _lib.check(lib.nr_op_attention(_stream(), (8 if fp8 else 0) | (16 if causal else 0), _ptr(qkv), None, _ptr(out), nimg, L, L, Cc, heads, 1, 1))
     return out
@@ -282,7 +286,7 @@ def attention_cross(q, kv, heads, kv_div, fp8=False, out=None):
     _chk_bf16(q, kv)
     nimg, L, Cc = q.shape
     Lk = kv.shape[1]
-    out = _attn_out(out, (nimg, L, Cc), q)
+    out = _out_tensor(out, (nimg, L, Cc), q)
     lib = _lib.load()
     _lib.check(lib.nr_op_attention(_stream(), 9 if fp8 else 1, _ptr(q), _ptr(kv), _ptr(out), nimg, L, Lk, Cc, heads, 1, kv_div))
     return out
@@ -294,7 +298,7 @@ def attention_temporal(qkv, heads, frames, out=None):
     _chk_bf16(qkv)
     nimg, hw, C3 = qkv.shape
     Cc = C3 // 3
-    out = _attn_out(out, (nimg, hw, Cc), qkv)
+    out = _out_tensor(out, (nimg, hw, Cc), qkv)
     lib = _lib.load()
     _lib.check(lib.nr_op_attention(_stream(), 2, _ptr(qkv), None, _ptr(out), nimg, hw, frames, Cc, heads, frames, 1))
     return out

@@ -3,7 +3,8 @@ string that names it (the route reads the variable per call), against the fp32 t
 tests/test_ops_gpu.py::test_gemm_bias_res / ::test_gemm_geglu.  Ring depth 2 for the eleven regular tiles, 3 for the row-wave tile.
 M = 300, N = 352, K = 256: a row tail for 64 / 128 / 256-row tiles, a column tail for every bn, four k-tiles; too few rows and the wrong K for the
 other four GEMM classes.  The row-wave tile can only be forced for a GEGLU projection: N = 640 there, bias only (the GEGLU epilogue has no residual).
-That the forced string arrives at the instantiation it names is tests/test_igemm_table_host.py's subject."""
+That the forced string arrives at the instantiation it names is tests/test_igemm_table_host.py's subject.  The other forms of the kernel (conv,
+two sources, ADMA, deeper rings, LayerNorm-folded, phase, split-K, tile orders) are computed bit-exactly in tests/test_igemm_forms_gpu.py."""
 import os
 import sys
 

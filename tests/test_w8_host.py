@@ -6,6 +6,7 @@ import ctypes as C
 import pytest
 import torch
 
+from igemm_forms import NrGemmParams, NrGemmRoute      # the ctypes mirrors of common.h / gemm_route.h
 from neurons_amd import _lib, w8
 
 # NrWeightLayout / NrGemmClass of neurons_amd/csrc/gemm_route.h
@@ -106,18 +107,6 @@ def test_pack_reference_puts_every_code_where_the_kernel_reads_it():
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # the built library through ctypes: sizes and the route (host functions; nothing here touches a device)
 # ---------------------------------------------------------------------------------------------------------------------------------------
-class NrGemmParams(C.Structure):      # neurons_amd/csrc/common.h
-    _fields_ = [("a0", C.c_void_p), ("a1", C.c_void_p), ("c0", C.c_int), ("c1", C.c_int), ("lda0", C.c_int), ("lda1", C.c_int), ("H", C.c_int),
-                ("W", C.c_int), ("OH", C.c_int), ("OW", C.c_int), ("ksize", C.c_int), ("stride", C.c_int), ("ups", C.c_int), ("w", C.c_void_p),
-                ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("bias", C.c_void_p), ("rowvec", C.c_void_p), ("rowvec_div", C.c_int),
-                ("rowvec_mod", C.c_int), ("rowvec_ld", C.c_int), ("res", C.c_void_p), ("ldr", C.c_int), ("out", C.c_void_p), ("ldo", C.c_int),
-                ("out_scale", C.c_float), ("geglu", C.c_int), ("ln_c", C.c_void_p), ("ln_eps", C.c_float), ("act", C.c_int), ("pad_tl0", C.c_int),
-                ("w8", C.c_int), ("out_f32", C.c_void_p), ("plan_m", C.c_int), ("tap_inner", C.c_int), ("w_fm", C.c_void_p)]
-
-
-class NrGemmRoute(C.Structure):       # neurons_amd/csrc/gemm_route.h
-    _fields_ = [("cls", C.c_int), ("weight_layout", C.c_int), ("m_fast", C.c_int), ("ws_bytes", C.c_size_t), ("tiled", C.c_int * 7),
-                ("smallm", C.c_int * 4), ("lin160", C.c_int * 4), ("rowpanel", C.c_int * 1), ("g8p", C.c_int * 2)]
 
 
 @pytest.fixture()
