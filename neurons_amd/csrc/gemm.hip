@@ -536,6 +536,327 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   }
 }
 
+// K-PAIR form of the 128 x 160 tile (TiledPlan::waves == 82): the two K slices (2 j, 2 j + 1) of an S-slice plan in ONE 512-thread workgroup.  Waves
+// 0-3 and 4-7 are two K groups; each is the 2 x 2 wave grid of igemm_bf16_kernel<128, 160, 2, 2, 2, false, true> on the same output tile, with its own
+// two-stage ring (2 x 2 x 36 KiB = the LDS two free workgroups of that kernel hold on a CU), its own running pointers and its own 20 accumulator tiles, and
+// group g covers exactly the k-tiles slice 2 j + g has there.  After the loop group 1 hands its accumulators to group 0 through the (dead) ring, group 0
+// adds them -- slice 2 j first, the order of splitk_reduce_kernel -- and runs the direct epilogue (nslab == 1: no slab, no reduce launch) or writes
+// slab j of nslab = S / 2.  Same partial sums in the same order as the S-slice plan when nslab == 1.
+// Loop: waves w and w + 4 share a SIMD, and s_barrier is workgroup-wide: with both groups in igemm_bf16_kernel's one-barrier loop they wait together and
+// issue their MFMAs together (measured 10-35 % slower than two free workgroups, profiles/kpair_ab.txt).  So the loop takes two barriers per k-tile and
+// group 1 runs half an iteration late: after barrier 2 t group 0 reads the fragments of its tile t and issues the DMA of tile t + 1 while group 1 multiplies
+// its tile t - 1; after barrier 2 t + 1 the roles swap -- a matrix segment beside a memory segment on every SIMD (gemm8p.hip's stagger with the groups
+// splitting K instead of M).  Each group's "my tile has landed" wait sits in front of the barrier that opens its own load segment; a group that runs out
+// of k-tiles (the slices differ by one when 2 nslab does not divide the k-tiles) keeps arriving at the barriers.
+// LIN: as igemm_bf16_kernel.  TAPI: the tap-inner K order of a one-source stride-1 conv; a template parameter because the rows' state of the two K orders
+// together (centre byte offsets and tap masks | pixel coordinates) does not fit beside 80 accumulator and 72 fragment registers in the 256 a wave has.
+template <bool LIN, bool TAPI>
+__global__ __launch_bounds__(512, 1) void igemm_kpair_kernel(NrGemmParams p_arg, int nslab, float* partial, int m_fast) {
+  NrGemmParams p = nr_pin_params(p_arg);
+  static_assert(!(LIN && TAPI), "the tap-inner order is a conv's");
+  p.ups = 0;
+  if constexpr (LIN) { p.ksize = 1; p.stride = 1; p.a1 = nullptr; p.c1 = 0; p.pad_tl0 = 0; }
+  if constexpr (TAPI) { p.ksize = 3; p.stride = 1; p.a1 = nullptr; p.c1 = 0; p.pad_tl0 = 0; }
+  nslab = nr_pin(nslab); partial = nr_pin(partial); m_fast = nr_pin(m_fast);
+  constexpr int BM = 128, BN = 160, BK = 64, WGN = 2, NW = 4;      // per K group
+  constexpr int WM = 64, WN = 80, MT = WM / 16, NT = WN / 16;
+  constexpr int GA = BM / (8 * NW), GB = BN / (8 * NW);
+  constexpr int TILE = (BM + BN) * BK;               // elements per LDS buffer
+  extern __shared__ __attribute__((aligned(16))) bf16 smem[];   // 2 groups x 2 stages x TILE elements
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int grp = __builtin_amdgcn_readfirstlane(tid >> 8);            // K group
+  const int wave = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);      // wave within the group
+  NR_STAMP_AT(0);
+  NR_STAMP_RT(44);
+  const int wm = wave / WGN, wn = wave % WGN;
+  const int ntn = (p.N + BN - 1) / BN;
+  const int ntm = (p.M + BM - 1) / BM;
+  int bid = nr_xcd_bid();
+  const int pair = nslab > 1 ? nr_fdiv_small(bid, ntn * ntm) : 0;
+  bid -= pair * ntn * ntm;
+  int bm, bn;      // the tile orders of igemm_bf16_kernel
+  if (m_fast >= 2) {
+    const int G = m_fast;
+    const int band = nr_fdiv_small(bid, G * ntn);
+    const int first = band * G;
+    const int gsz = min(G, ntm - first);
+    const int r = bid - band * G * ntn;
+    bn = nr_fdiv_small(r, gsz);
+    bm = first + r - bn * gsz;
+  } else if (m_fast) { bn = nr_fdiv_small(bid, ntm); bm = bid - bn * ntm; } else { bm = nr_fdiv_small(bid, ntn); bn = bid - bm * ntn; }
+  const int m0 = bm * BM, n0 = bn * BN;
+  const int lr = lane >> 3;                 // row within the 8-row group
+  const int lp = lane & 7;                  // physical 16-B chunk
+  const int lchunk = (lp ^ lr) << 3;        // logical chunk (elements) this lane must fetch
+  const int Cin = p.c0 + p.c1;
+
+  // ---- per-lane A rows: group g = wave*GA + j, tile row = 8*g + lr ----
+  int a_pix[GA], a_oy[GA], a_ox[GA];
+  bool a_ok[GA];
+#pragma unroll
+  for (int j = 0; j < GA; ++j) {
+    const int m = m0 + 8 * (wave * GA + j) + lr;
+    a_ok[j] = m < p.M;
+    const int mm = a_ok[j] ? m : 0;
+    if (p.ksize == 1) {
+      a_pix[j] = mm; a_oy[j] = 0; a_ox[j] = 0;
+    } else {
+      const int ohw = p.OH * p.OW;
+      const int n = nr_fdiv_small(mm, ohw);
+      const int r = mm - n * ohw;
+      a_pix[j] = n; a_oy[j] = nr_fdiv_small(r, p.OW); a_ox[j] = r - a_oy[j] * p.OW;
+    }
+  }
+  const bf16* zsrc = (const bf16*)nr_zero16;
+  constexpr bool tap_inner = TAPI;
+  long long a_cbyte[GA];
+  unsigned a_tapmask[GA];
+  if constexpr (tap_inner) {
+#pragma unroll
+    for (int j = 0; j < GA; ++j) {
+      a_cbyte[j] = (((long long)a_pix[j] * p.H + a_oy[j]) * p.W + a_ox[j]) * p.lda0 * (long long)sizeof(bf16);
+      unsigned msk = 0;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int iy = a_oy[j] + t / 3 - 1, ix = a_ox[j] + t % 3 - 1;
+        if (a_ok[j] && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) msk |= 1u << t;
+      }
+      a_tapmask[j] = msk;
+    }
+  }
+
+  // the k-tiles of slice 2 pair + grp of the 2 nslab slices, and how many the sibling group has (the groups take the same number of barriers)
+  const int nk_total = p.K / BK;
+  const int S = 2 * nslab, slice = 2 * pair + grp;
+  const int kt_begin = nr_fdiv_small(nk_total * slice, S), kt_end = nr_fdiv_small(nk_total * (slice + 1), S);
+  const int nmine = kt_end - kt_begin;
+  const int nsib = nr_fdiv_small(nk_total * ((slice ^ 1) + 1), S) - nr_fdiv_small(nk_total * (slice ^ 1), S);
+  const int nmax = max(nmine, nsib);
+
+  // ---- running source pointers of the NEXT k-tile to stage (igemm_bf16_kernel) ----
+  const bf16* ap[GA];
+  const bf16* wp[GB];
+  int st_tap, st_c;
+  {
+    const int kbase = kt_begin * BK;
+    if constexpr (tap_inner) { const int q9 = nr_fdiv_small(kt_begin, 9); st_tap = kt_begin - 9 * q9; st_c = q9 * BK; }
+    else { st_tap = p.ksize == 3 ? nr_fdiv_small(kbase, Cin) : 0; st_c = kbase - st_tap * Cin; }
+#pragma unroll
+    for (int j = 0; j < GB; ++j) {
+      // a W row past N feeds only columns that are never stored: it reads the last row instead of the zero word, so every row advances alike
+      const int n = min(n0 + 8 * (wave * GB + j) + lr, p.N - 1);
+      wp[j] = p.w + (size_t)n * p.K + kbase + lchunk;
+    }
+  }
+  auto setup_rows_tap_inner = [&]() {
+    const int ky = st_tap / 3, kx = st_tap - ky * 3;
+    const long long delta = ((long long)(ky - 1) * p.W + (kx - 1)) * p.lda0 * (long long)sizeof(bf16);
+    const char* base = reinterpret_cast<const char*>(p.a0 + st_c + lchunk) + delta;
+#pragma unroll
+    for (int j = 0; j < GA; ++j) {
+      const bool ok = (a_tapmask[j] >> st_tap) & 1u;
+      ap[j] = ok ? reinterpret_cast<const bf16*>(base + a_cbyte[j]) : zsrc;
+    }
+  };
+  auto setup_rows = [&]() {
+    if constexpr (tap_inner) { setup_rows_tap_inner(); return; }
+    const bf16* src; int ld;
+    if (st_c < p.c0) { src = p.a0 + st_c; ld = p.lda0; } else { src = p.a1 + (st_c - p.c0); ld = p.lda1; }
+    src += lchunk;
+    if (p.ksize == 1) {
+#pragma unroll
+      for (int j = 0; j < GA; ++j) {
+        ap[j] = a_ok[j] ? src + (size_t)a_pix[j] * ld : zsrc;
+      }
+    } else {
+      const int ky = st_tap / 3, kx = st_tap - ky * 3;
+#pragma unroll
+      for (int j = 0; j < GA; ++j) {
+        const int iy = a_oy[j] * p.stride + ky - (p.pad_tl0 ? 0 : 1);
+        const int ix = a_ox[j] * p.stride + kx - (p.pad_tl0 ? 0 : 1);
+        const bool ok = a_ok[j] && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+        const size_t pix = ((size_t)a_pix[j] * p.H + iy) * p.W + ix;
+        ap[j] = ok ? src + pix * ld : zsrc;
+      }
+    }
+  };
+  setup_rows();
+
+  bf16* ring = smem + grp * 2 * TILE;      // this group's two buffers
+  auto stage = [&](int buf) {
+    bf16* sA = ring + buf * TILE;
+    bf16* sB = sA + BM * BK;
+    const unsigned la = nr_lds_addr(sA + wave * GA * 8 * BK), lb = nr_lds_addr(sB + wave * GB * 8 * BK);
+#pragma unroll
+    for (int j = 0; j < GA; ++j) nr_glds16(ap[j], la + (unsigned)(j * 8 * BK * (int)sizeof(bf16)));
+#pragma unroll
+    for (int j = 0; j < GB; ++j) nr_glds16(wp[j], lb + (unsigned)(j * 8 * BK * (int)sizeof(bf16)));
+    // advance to the next k-tile
+#pragma unroll
+    for (int j = 0; j < GB; ++j) wp[j] += BK;
+    if constexpr (tap_inner) {
+      st_tap += 1;
+      if (st_tap == 9) { st_tap = 0; st_c += BK; }
+      setup_rows_tap_inner();
+      return;
+    }
+    st_c += BK;
+    bool resetup = false;
+    if (st_c == Cin) { st_c = 0; st_tap += 1; resetup = true; }
+    else if (p.c1 > 0 && st_c == p.c0) resetup = true;
+    if (resetup) {
+      if (st_tap < p.ksize * p.ksize) setup_rows();
+    } else {
+#pragma unroll
+      for (int j = 0; j < GA; ++j) ap[j] += ap[j] != zsrc ? BK : 0;      // a row on the zero word (padding, M tail) stays there
+    }
+  };
+
+  f32x4 acc[NT][MT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int fr = lane & 15, fg = lane >> 4;
+  bf16x8 wf[2][NT], xf[2][MT];
+  // the fragments of k-step ks of the tile in buffer `buf`
+  auto read_frags = [&](int buf, int ks) {
+    const bf16* sA = ring + buf * TILE;
+    const bf16* sB = sA + BM * BK;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      const int row = wn * WN + i * 16 + fr;
+      wf[ks][i] = *(const bf16x8*)(sB + row * BK + (((4 * ks + fg) ^ (row & 7)) << 3));
+    }
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+      const int row = wm * WM + j * 16 + fr;
+      xf[ks][j] = *(const bf16x8*)(sA + row * BK + (((4 * ks + fg) ^ (row & 7)) << 3));
+    }
+  };
+  auto multiply = [&]() {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][i], xf[ks][j], acc[i][j], 0, 0, 0);
+  };
+  // a workgroup-wide barrier no MFMA, LDS access or DMA issue moves across
+  auto barrier = [&]() {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  // the load segment of tile t: its fragments into registers, the DMA of tile t + 1 into the buffer whose fragments (tile t - 1) every wave of the group
+  // consumed in the multiply segment one barrier earlier
+  auto load_tile = [&](int t) {
+    if (t < nmine) {
+      read_frags(t & 1, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (t + 1 < nmine) stage((t & 1) ^ 1);
+      __builtin_amdgcn_sched_barrier(0);
+      read_frags(t & 1, 1);
+    }
+  };
+  if (nmine > 0) stage(0);
+  NR_STAMP_AT(1);
+  if (grp == 0) {
+    for (int t = 0; t < nmax; ++t) {
+      if (t < nmine) nr_wait_vmcnt<0>();      // tile t of this group has landed
+      barrier();
+      if (t < 18) NR_STAMP_AT(4 + 2 * t);
+      load_tile(t);                           // ... beside group 1's MFMAs of its tile t - 1
+      barrier();
+      if (t < 18) NR_STAMP_AT(5 + 2 * t);
+      if (t < nmine) multiply();              // ... beside group 1's load segment of its tile t
+    }
+  } else {
+    for (int t = 0; t < nmax; ++t) {
+      barrier();
+      if (t > 0 && t - 1 < nmine) multiply();
+      if (t < nmine) nr_wait_vmcnt<0>();
+      barrier();
+      load_tile(t);
+    }
+    if (nmax - 1 < nmine) multiply();
+  }
+  NR_STAMP_AT(2);
+
+  // ---- acc(slice 2 pair) + acc(slice 2 pair + 1): group 1 -> LDS in lane order (20 x 256 x 16 B = 80 KiB of the 144 KiB ring) -> group 0 ----
+  f32x4* xch = reinterpret_cast<f32x4*>(smem);
+  const int t256 = tid & 255;
+  barrier();                                   // both groups are done with their rings
+  if (grp == 1) {
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+      for (int j = 0; j < MT; ++j) xch[(i * MT + j) * 256 + t256] = acc[i][j];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // s_barrier waits for no counter: the stores have reached the LDS before group 0 is let through
+  }
+  barrier();
+  if (grp == 1) return;
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) acc[i][j] = acc[i][j] + xch[(i * MT + j) * 256 + t256];
+
+  // ---- epilogue of group 0: lane holds out[m = ..+fr][n = ..+4*fg + r], r = 0..3 (the slab / direct paths of igemm_bf16_kernel) ----
+  if (partial) {
+    float* slab = partial + (size_t)pair * p.M * p.N;
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+      const int m = m0 + wm * WM + j * 16 + fr;
+      if (m >= p.M) continue;
+#pragma unroll
+      for (int i = 0; i < NT; ++i) {
+        const int n = n0 + wn * WN + i * 16 + 4 * fg;
+        if (n >= p.N) continue;
+        nr_store16f(slab + (size_t)m * p.N + n, acc[i][j]);
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < MT; ++j) {
+    const int m = m0 + wm * WM + j * 16 + fr;
+    if (m >= p.M) continue;
+    const float* rv = p.rowvec ? p.rowvec + nr_rowvec_row(p, m) : nullptr;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      const int n = n0 + wn * WN + i * 16 + 4 * fg;
+      if (n >= p.N) continue;
+      f32x4 v = acc[i][j];
+      if (p.bias) { const f32x4 b = *(const f32x4*)(p.bias + n); v += b; }
+      if (rv) { const f32x4 t = *(const f32x4*)(rv + n); v += t; }
+      v *= p.out_scale;
+      if (p.act == 1) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
+      }
+      if (p.res) {
+        const bf16x4 r = *(const bf16x4*)(p.res + (size_t)m * p.ldr + n);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] += (float)r[e];
+      }
+      bf16x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
+      nr_store8(p.out + (size_t)m * p.ldo + n, o);
+    }
+  }
+#ifdef NR_STAMP
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+  NR_STAMP_AT(3);
+  NR_STAMP_RT(45);
+}
+
 // out[m][n] = epilogue( sum_s partial[s][m][n] ), 4 consecutive n per thread.  PH: slab row m = phase * Mp + r of a phase-form launch goes to the
 // output pixel of (phase, r) (igemm_bf16_kernel); such a launch has neither rowvec nor res
 template <bool PH>
@@ -661,7 +982,7 @@ Plan choose_plan_phase(const NrGemmParams& p) {
   }
   return pl;
 }
-Plan choose_plan(const NrGemmParams& p) {
+Plan choose_plan_slices(const NrGemmParams& p) {
   auto nblk = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
   const int nk = p.K / 64;
   Plan pl{};
@@ -742,6 +1063,42 @@ Plan choose_plan(const NrGemmParams& p) {
   return pl;
 }
 
+constexpr int KPAIR_WAVES = 82;      // TiledPlan::waves of a K-pair plan: 8 waves as 2 K groups; its splitk counts the slabs written (1: none)
+// THE test of a K-pair plan, asked by the rule, the override, the legalisation and the launcher: a form igemm_kpair_kernel is built for -- a plain conv or
+// Linear (no LayerNorm fold, GEGLU, upsample gather of either form or raw fp32 result) -- on the 128 x 160 tile, at least one k-tile per K group
+inline bool kpair_ok(const NrGemmParams& p, const Plan& pl) {
+  return pl.waves == KPAIR_WAVES && !p.ln_c && !p.geglu && !p.ups && !p.out_f32 && pl.bm == 128 && pl.bn == 160 && pl.splitk >= 1 && 2 * pl.splitk <= p.K / 64;
+}
+// a K-pair plan as the plan on free workgroups that computes the same sums: one slice per K group
+inline void kpair_undo(Plan& pl) { if (pl.waves == KPAIR_WAVES) { pl.waves = 4; pl.splitk *= 2; } }
+
+// choose_plan_slices, and where that is the two-stage 128 x 160 tile with an even number of K slices on a form the K-pair kernel has: the slices in
+// pairs, one 8-wave workgroup per pair and half the slabs (none, and no reduce launch, for two slices).  Same LDS, waves per SIMD and bytes in flight
+// per CU.  Admitted by measurement (us per launch, HBM-cold weights, slices on free workgroups -> K pairs; profiles/kpair_ab.txt):
+//   M = 8192 N = 640   3x3 K = 5760 tap-inner 80 -> 77    K = 11520 two-source 134 -> 129    K = 17280 two-source 182 -> 182
+//   M = 2048 N = 1280  3x3 K = 11520 tap-inner 75 -> 69   stride 2 77 -> 69   K = 23040 two-source 129 -> 126   Linear K = 6400 48.8 -> 45.1
+//   M = 512  N = 1280  3x3 K = 23040 (16 slices -> 8 pairs) 52 -> 44
+// Kept out: M = 512, K = 11520 (8 slices -> 4 pairs: 128 workgroups leave half the CUs idle, 35.7 -> 39.3), hence the full-round condition; the
+// replicated upsample gather (ups == 1), whose routes tests/test_ups_phase_host.py records.
+// The one-slice M = 8192, N = 640, K = 3200 Linears (one 4-wave workgroup per CU on 128 x 64 tiles, no second wave on a SIMD) run as one pair per 128 x 160
+// tile, one round of the chip: 44.3 -> 40.2 us (two free slices + reduce: 47.0).  No other one-slice shape was measured, so none is admitted.
+Plan choose_plan(const NrGemmParams& p) {
+  const Plan pl = choose_plan_slices(p);
+  static const bool kpair_rule = env_not_0("NR_IGEMM_KPAIR");      // A/B switch
+  if (!kpair_rule) return pl;
+  const long long tiles = (long long)((p.M + 127) / 128) * ((p.N + 159) / 160);
+  Plan kp = pl;
+  kp.waves = KPAIR_WAVES;
+  if (pl.bm == 128 && pl.bn == 160 && pl.waves == 4 && pl.stages == 2 && pl.splitk >= 2 && pl.splitk % 2 == 0) {
+    kp.splitk = pl.splitk / 2;
+    if (tiles * kp.splitk >= 256 && kpair_ok(p, kp)) return kp;
+  } else if (p.ksize == 1 && pl.bm == 128 && pl.bn == 64 && pl.waves == 4 && pl.stages == 2 && pl.splitk == 1 && p.N == 640 && p.K == 3200 && tiles == 256) {
+    kp.bm = 128; kp.bn = 160;      // the one measured shape (M in 8065 .. 8192) on the plan it was measured against, no other
+    if (kpair_ok(p, kp)) return kp;
+  }
+  return pl;
+}
+
 // the shape the plan is chosen for: plan_m rows when the caller asks for batch-independent arithmetic (common.h), else the real M
 inline NrGemmParams plan_view(const NrGemmParams& p) {
   NrGemmParams q = p;
@@ -787,6 +1144,16 @@ int launch_exact(std::index_sequence<J...>, const NrGemmParams& p, unsigned grid
   return rc;
 }
 
+// igemm_kpair_kernel: the K pairs of a 128 x 160 plan (waves == 82), pl.splitk slabs.  Returns 0; 2 when the runtime refuses the LDS opt-in
+int launch_kpair(const NrGemmParams& p, unsigned grid, const Plan& pl, float* partial, int m_fast, hipStream_t stream) {
+  const igemm_kern_t k = pl.lin ? igemm_kpair_kernel<true, false> : (p.tap_inner ? igemm_kpair_kernel<false, true> : igemm_kpair_kernel<false, false>);
+  const size_t shm = (size_t)2 * 2 * (128 + 160) * 64 * sizeof(bf16);      // two groups x two stages
+  static unsigned long long attr_done[3] = {};          // per instantiation
+  if (const int rc = nr_lds_opt_in(attr_done[pl.lin ? 0 : (p.tap_inner ? 1 : 2)], {(const void*)k}, shm)) return rc;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(512), shm, stream, p, pl.splitk, partial, m_fast);
+  return 0;
+}
+
 // smallest depth of the set not below the request, else the deepest
 constexpr int pick_ring(unsigned set, int want) {
   int deepest = 0;
@@ -799,6 +1166,10 @@ constexpr int pick_ring(unsigned set, int want) {
 int legalise(const NrGemmParams& p, Plan& pl) {
   const bool ln = p.ln_c != nullptr, phase = p.ups == 2;
   const bool row_wave = pl.waves == 41;          // as planned, whatever tile NR_IGEMM_FORCE then named
+  if (pl.waves == KPAIR_WAVES) {                 // the K-pair kernel: one tile, one ring (the rule and the override only ever name it where kpair_ok holds)
+    pl.stages = 2;
+    return kpair_ok(p, pl) ? 0 : 9;
+  }
   if (ln && pl.bn == 32) pl.bn = 64;             // every n-tile recomputes the row statistics: keep the n-tiles wide
   if (!find_row(pl.bm, pl.bn, 0)) return 9;
   const TileRow* t = phase ? find_row(pl.bm, pl.bn, 0, true) : find_row(pl.bm, pl.bn, pl.waves);      // phase form: the tile's phase row, whatever its wave grid
@@ -814,7 +1185,8 @@ int legalise(const NrGemmParams& p, Plan& pl) {
 }
 
 // test/tuning override: NR_IGEMM_FORCE="bm,bn,splitk,stages,order,waves" (a field < 0 or left out keeps the heuristic's choice): a tile of TILES (both
-// fields or neither), K slices, ring depth 2 .. 8, tile order (0 n-fast, 1 m-fast, 8 grouped), waves 4 / 8 / 41 (41: the row-wave grid of 128 x 160).  What
+// fields or neither), K slices, ring depth 2 .. 8, tile order (0 n-fast, 1 m-fast, 8 grouped), waves 4 / 8 / 41 / 82 (41: the row-wave grid of 128 x 160;
+// 82: its K-pair kernel, the K-slices field then counts slabs).  What
 // it names goes through legalise like any plan, so the route records and the launcher runs the nearest instantiation of the request's form
 void apply_override(const NrGemmParams& p, Plan& pl, int& m_fast) {
   const char* e = getenv("NR_IGEMM_FORCE");
@@ -828,6 +1200,7 @@ void apply_override(const NrGemmParams& p, Plan& pl, int& m_fast) {
   if (const char* f = getenv("NR_IGEMM_FORCE_K")) if (p.K != atoi(f)) return;
   int bm = -1, bn = -1, sk = -1, st = -1, ord = -1, wv = -1;
   sscanf(e, "%d,%d,%d,%d,%d,%d", &bm, &bn, &sk, &st, &ord, &wv);
+  kpair_undo(pl);      // a K-pair plan only where the sixth field names it: every other field means what it meant
   if (bm > 0 && bn > 0) {
     if (find_row(bm, bn, 0) && !(p.geglu && ((bn == 160 && !(bm == 128 && wv == 41)) || bn == 32))) { pl.bm = bm; pl.bn = bn; }
   }
@@ -836,6 +1209,14 @@ void apply_override(const NrGemmParams& p, Plan& pl, int& m_fast) {
   if (pl.bn == 160 || pl.bm == 64) pl.waves = 4;
   if (wv == 41 && pl.bm == 128 && pl.bn == 160) pl.waves = 41;      // 4 x 1 waves (32 x 160 each): the row-wave tile
   if (sk > 0 && !p.geglu) { const int nk = p.K / 64; pl.splitk = sk > nk ? nk : sk; }
+  // 82: the K-pair kernel on the 128 x 160 tile; the third field is then the number of slabs (1: none), each the sum of two K slices
+  if (wv == KPAIR_WAVES) {
+    Plan kp = pl;
+    kp.waves = KPAIR_WAVES;
+    if (sk <= 0) kp.splitk = pl.splitk >= 2 ? pl.splitk / 2 : 1;      // no slab count named: the planned slices in pairs
+    if (2 * kp.splitk > p.K / 64) kp.splitk = p.K / 128;
+    if (kpair_ok(p, kp)) pl = kp;
+  }
   if (st >= 2 && st <= 8) pl.stages = st;
   if (ord >= 0) m_fast = ord;
 }
@@ -901,7 +1282,7 @@ int route(const NrGemmParams& p, NrGemmRoute* r, bool packed_ok) {
   }
   static const int adma_min = getenv("NR_IGEMM_ADMA_MINK") ? atoi(getenv("NR_IGEMM_ADMA_MINK")) : 24;   // k-tiles per slice; A/B switch
   static const bool lin_on = env_not_0("NR_IGEMM_LIN");                                                  // A/B switch
-  pl.adma = (p.K / 64) / (pl.splitk > 1 ? pl.splitk : 1) >= adma_min;
+  pl.adma = pl.waves == KPAIR_WAVES || (p.K / 64) / (pl.splitk > 1 ? pl.splitk : 1) >= adma_min;      // the K-pair kernel: asm DMA only
   pl.lin = lin_on && p.ksize == 1 && !p.a1 && p.c1 == 0;
   if (pl.stages > LIN_MAX_RING) pl.lin = 0;       // the Linear-only instantiation exists for the rings Linears are planned with
   if (p.ln_c) { pl.adma = 0; pl.lin = 1; }        // the LayerNorm-folded form is one instantiation per ring: builtin DMA, a Linear by construction
@@ -912,11 +1293,14 @@ int route(const NrGemmParams& p, NrGemmRoute* r, bool packed_ok) {
 // the tiled kernel as planned, then its split-K reduce
 int launch_tiled(const NrGemmParams& p, const Plan& pl, int m_fast, float* workspace, hipStream_t stream) {
   if (pl.splitk < 1 || pl.splitk > p.K / 64 || ((p.ln_c || p.out_f32) && pl.splitk != 1)) return 9;
+  const bool kpair = pl.waves == KPAIR_WAVES;
+  if (kpair && !(kpair_ok(p, pl) && pl.stages == 2)) return 9;
   if (pl.splitk > 1 && !workspace) return 6;
   float* partial = p.out_f32 ? p.out_f32 : (pl.splitk > 1 ? workspace : nullptr);
   const unsigned grid = (unsigned)(row_tiles(p, pl.bm) * ((p.N + pl.bn - 1) / pl.bn) * pl.splitk);
   // no such instantiation (9) or no LDS opt-in (2): fail loudly, never launch a neighbour on a grid computed for this tile
-  if (const int rc = launch_exact(std::make_index_sequence<NTILES * NRINGS>{}, p, grid, pl, partial, m_fast, stream)) return rc;
+  if (const int rc = kpair ? launch_kpair(p, grid, pl, partial, m_fast, stream)
+                           : launch_exact(std::make_index_sequence<NTILES * NRINGS>{}, p, grid, pl, partial, m_fast, stream)) return rc;
   if (pl.splitk > 1) {
     const long long total = (long long)p.M * (p.N / 4);
     hipLaunchKernelGGL(p.ups == 2 ? splitk_reduce_kernel<true> : splitk_reduce_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p,

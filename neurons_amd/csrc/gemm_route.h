@@ -38,8 +38,9 @@ inline const char* const nr_gemm_class_name[NR_GEMM_NCLASS] = {"smallm", "lin160
 // (T, kp) holds, for the k-steps 2 kp + j (j = 0, 1), the eight codes of W[16 T + fr][32 (2 kp + j) + 8 fg .. + 7] -- then float scale[N] = 2^e[n]
 enum NrWeightLayout { NR_W_ROWMAJOR, NR_W_TAP_INNER, NR_W_FRAGMAJOR, NR_W_LIN160, NR_W_LIN128Q, NR_W_FRAGMAJOR_E4M3 };
 
-// gemm.hip: tile, ring depth, wave grid (41 = 4 x 1 row waves) and split-K depth after the LayerNorm / out_f32 adjustments; adma / lin: the
-// A-operand LDS-DMA and the Linear-only instantiation
+// gemm.hip: tile, ring depth, wave grid (41 = 4 x 1 row waves; 82 = the K-pair kernel of the 128 x 160 tile: 8 waves as two K groups) and split-K depth
+// after the LayerNorm / out_f32 adjustments; adma / lin: the A-operand LDS-DMA and the Linear-only instantiation.  waves == 82: splitk is the number of
+// fp32 slabs written (1: none, no reduce launch), each the sum of TWO K slices, and ws_bytes follows from it
 struct TiledPlan { int bm, bn, splitk, stages, waves, adma, lin; };
 // smallm.hip: nt n-tiles per slab, G column groups x J slabs each, C chunks of 640 along K
 struct SmallmPlan { int nt, G, J, C; };

@@ -15,12 +15,14 @@
 # NR_XATTN_FUSED=0, NR_TATTN_HEAD=0, NR_XATTN_HEAD=0) on the networks whose plans contain those kernels, then the op hooks (plan_dump --ops: the whole trace) and the
 # NR_IGEMM_FORCE sweep of the tiled igemm (plan_dump --force-sweep: the launch lines only; the route notes between them are counted).  One line per run: "identical", or "DIFFERS" and the first differing lines.
 # The dump must also contain every kernel class the planner can choose (a shape list that loses one is no evidence).  Exit status 1 on any of it.
+# DIFF_LINES=<n> prints the first n lines of every differing run instead of 12.
 # The only normalisation: pointer values (0x...) become a fixed token.  Needs no GPU.  JOBS=<n> compiles in parallel (default 8, at most 16).
 set -euo pipefail
 
 [ $# -eq 1 ] || { echo "usage: $0 <git-rev>" >&2; exit 2; }
 rev=$1
 jobs=${JOBS:-8}; [ "$jobs" -le 16 ] || jobs=16
+difflines=${DIFF_LINES:-12}      # lines of each differing run that are printed (DIFF_LINES=1000000: the whole diff list)
 root=$(git -C "$(dirname "$0")" rev-parse --show-toplevel)
 tmp=$(mktemp -d)
 trap 'rm -rf "$tmp"' EXIT
@@ -92,7 +94,7 @@ for label in default ln_fuse_0 fold_proj_out_0 smallm_0 g8p_0 g8p_2 rowpanel_0 l
       echo "$label $what: identical ($(wc -l < "$b") lines, $(grep -c -E '^(== |L )' "$b") $([ $what = dump ] && echo plans || echo launches))"
     else
       echo "$label $what: DIFFERS"; status=1
-      diff "$a" "$b" | head -n 12 | sed 's/^/    /' || true
+      diff "$a" "$b" | head -n "$difflines" | sed 's/^/    /' || true
     fi
   done
 done
@@ -102,7 +104,7 @@ for what in ops.trace sweep.launches; do
     echo "${what/./ }: identical ($(wc -l < "$b") lines, $(grep -c '^L ' "$b") launches)"
   else
     echo "${what/./ }: DIFFERS"; status=1
-    diff "$a" "$b" | head -n 12 | sed 's/^/    /' || true
+    diff "$a" "$b" | head -n "$difflines" | sed 's/^/    /' || true
   fi
 done
 # the sweep's route notes may differ where $rev's route recorded a plan its launcher then changed: counted, not judged
