@@ -222,6 +222,28 @@ nr_status nr_gaussian_sample(nr_stream stream, const float* moments_dev, const f
 nr_status nr_edm_cfg_euler_step(nr_stream stream, const float* net_dev, const float* x_dev, float* x_out_dev, int64_t n,
                                 float cfg_scale, float sigma_quantized, float sigma, float sigma_next);
 
+/* replaces the start of sgm img2img, do_img2img between the encoder and the sampler (generative_models/sgm/inference/helpers.py:276-291; with
+ * skip_encode it is the start utils.unclip_recon forms, utils.py:324-335), in one launch.  Per element of sample b:
+ *   z      = z_in                                                         (NR_IMG2IMG_LATENT: skip_encode, the caller holds a latent)
+ *          = (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps_enc) * z_scale   (NR_IMG2IMG_MOMENTS: encode_first_stage's posterior sample times
+ *                                                                          scale_factor, read from the encoder's moments as nr_gaussian_sample does)
+ *   noise' = noise + offset_noise_level * offset[b]                       (offset_dev NULL or level 0: noise' = noise)
+ *   out    = (z + noise' * sigma0) / sqrt(1 + sigma0^2)
+ * sigma0 is the first entry of the (pruned) sigma table.  The division is the ONLY one: EulerEDMSampler multiplies by sqrt(1 + sigma0^2) again
+ * on entry (sampling.py:52), so the result goes to the sampler as it is.
+ *   z_in_dev    fp32 [batch][n_per_sample]      (LATENT; unread and may be NULL in MOMENTS; out_dev may alias it)
+ *   moments_dev fp32 [batch][2][n_per_sample]   (MOMENTS: mean | logvar per sample, nr_vae_encode's output; may be NULL in LATENT)
+ *   eps_enc_dev fp32 [batch][n_per_sample]      (MOMENTS: the posterior draw; may be NULL in LATENT)
+ *   noise_dev   fp32 [batch][n_per_sample], offset_dev fp32 [batch] or NULL, out_dev fp32 [batch][n_per_sample]
+ * All draws are the caller's (RNG order is the caller's contract).  No allocation; 16-byte accesses when every base is 16-byte aligned (any
+ * n_per_sample), scalar otherwise.  NR_ERR_ARG before any launch: a null tensor the mode reads, batch or n_per_sample <= 0, sigma0 < 0 or not
+ * finite, a non-finite z_scale or offset_noise_level, an unknown mode. */
+#define NR_IMG2IMG_LATENT 0
+#define NR_IMG2IMG_MOMENTS 1
+nr_status nr_edm_img2img_start(nr_stream stream, const float* z_in_dev, const float* moments_dev, const float* eps_enc_dev, const float* noise_dev,
+                               const float* offset_dev, float* out_dev, int64_t batch, int64_t n_per_sample, float z_scale, float sigma0,
+                               float offset_noise_level, int32_t mode);
+
 /* replaces one iteration of BrainDiffusionPrior.p_sample_loop_ddpm (model_variants/BrainModel_neurons.py:324-341,363-389) behind the network
  * call, i.e. DiffusionPrior.p_mean_variance + the ancestral update of dalle2-pytorch 1.15.6 (requirements.txt:11; NOT vendored: parity
  * unpinned): [pred = null + (pred - null) * cond_scale]; x_start = pred (mode 0, predict_x_start: the NEURONS prior) | sqrt(ac) x -

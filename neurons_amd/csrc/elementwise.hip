@@ -381,6 +381,65 @@ __global__ void edm_cfg_euler_kernel(const float* __restrict__ net, const float*
   x_out[i] = xv + d * (sigma_next - sigma);
 }
 
+// sgm img2img start (see nr_edm_img2img_start in include/neurons_amd.h): one element of sample b.  `m` is the element's latent in mode 0 and
+// the posterior mean in mode 1 (then `lv` / `e` are its logvar and the encoder draw)
+template <int MODE>
+__device__ __forceinline__ float img2img_start_one(float m, float lv, float e, float nz, float off, float z_scale, float sigma0, float den) {
+  float z = m;
+  if (MODE == 1) z = (m + expf(0.5f * fminf(fmaxf(lv, -30.f), 20.f)) * e) * z_scale;
+  return (z + (nz + off) * sigma0) / den;
+}
+
+// src = z_in (mode 0, may alias out: every thread reads its own elements before it writes them) or the moments [batch][2][nps] (mode 1).
+// VEC: four consecutive elements of the flat [batch * nps] index per thread; such a group may straddle a sample boundary when nps % 4 != 0, so the
+// sample index (offset scalar o[b], moments row) is formed per element, and the moments are loaded as vectors only when nps % 4 == 0.
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(256) void edm_img2img_start_kernel(const float* src, const float* __restrict__ eps_enc,
+                                                                const float* __restrict__ noise, const float* __restrict__ offset, float* out,
+                                                                long long total, long long nps, float z_scale, float sigma0, float den,
+                                                                float offset_level) {
+  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * (VEC ? 4 : 1);
+  if (i0 >= total) return;
+  if (VEC && i0 + 4 <= total) {
+    const f32x4 nz = *(const f32x4*)(noise + i0);
+    f32x4 m, lv = {0.f, 0.f, 0.f, 0.f}, e = {0.f, 0.f, 0.f, 0.f}, off = {0.f, 0.f, 0.f, 0.f};
+    const long long b0 = i0 / nps;
+    if (MODE == 0) {
+      m = *(const f32x4*)(src + i0);
+    } else {
+      e = *(const f32x4*)(eps_enc + i0);
+      if ((nps & 3) == 0) {
+        m = *(const f32x4*)(src + i0 + b0 * nps);
+        lv = *(const f32x4*)(src + i0 + b0 * nps + nps);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const long long b = (i0 + k) / nps;
+          m[k] = src[i0 + k + b * nps];
+          lv[k] = src[i0 + k + b * nps + nps];
+        }
+      }
+    }
+    if (offset) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) off[k] = offset_level * offset[(i0 + k) / nps];
+    }
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = img2img_start_one<MODE>(m[k], lv[k], e[k], nz[k], off[k], z_scale, sigma0, den);
+    *(f32x4*)(out + i0) = o;
+    return;
+  }
+  const long long i1 = VEC ? total : i0 + 1;      // the ragged tail (VEC) or this thread's one element
+  for (long long i = i0; i < i1; ++i) {
+    const long long b = i / nps;
+    const float off = offset ? offset_level * offset[b] : 0.f;
+    const float m = MODE == 0 ? src[i] : src[i + b * nps];
+    const float lv = MODE == 0 ? 0.f : src[i + b * nps + nps];
+    out[i] = img2img_start_one<MODE>(m, lv, MODE == 0 ? 0.f : eps_enc[i], noise[i], off, z_scale, sigma0, den);
+  }
+}
+
 __global__ void add_bf16_kernel(const bf16* __restrict__ a, const bf16* __restrict__ b, bf16* __restrict__ out,
                                 long long n8) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -614,6 +673,35 @@ extern "C" int nr_launch_edm_cfg_euler(const float* net, const float* x, float* 
                                        float sigma_q, float sigma, float sigma_next, hipStream_t stream) {
   hipLaunchKernelGGL(edm_cfg_euler_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, net, x, x_out, total,
                      scale, sigma_q, sigma, sigma_next);
+  return 0;
+}
+
+namespace {
+template <int MODE>
+void launch_img2img_start(const float* src, const float* eps_enc, const float* noise, const float* offset, float* out, long long total,
+                          long long nps, float z_scale, float sigma0, float den, float offset_level, hipStream_t stream) {
+  // 16-byte accesses need every vector-loaded base 16-byte aligned (the per-sample offset scalars are read one at a time)
+  const uintptr_t bases = (uintptr_t)src | (uintptr_t)eps_enc | (uintptr_t)noise | (uintptr_t)out;
+  if ((bases & 15) == 0) {
+    const long long threads = (total + 3) / 4;
+    hipLaunchKernelGGL((edm_img2img_start_kernel<MODE, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, src, eps_enc, noise,
+                       offset, out, total, nps, z_scale, sigma0, den, offset_level);
+  } else {
+    hipLaunchKernelGGL((edm_img2img_start_kernel<MODE, false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, eps_enc, noise,
+                       offset, out, total, nps, z_scale, sigma0, den, offset_level);
+  }
+}
+}  // namespace
+
+// mode 0: src = z_in; mode 1: src = moments, eps_enc the encoder draw.  offset == nullptr: no offset noise.  den = sqrt(1 + sigma0^2).
+extern "C" int nr_launch_edm_img2img_start(const float* src, const float* eps_enc, const float* noise, const float* offset, float* out,
+                                           long long batch, long long nps, float z_scale, float sigma0, float den, float offset_level, int mode,
+                                           hipStream_t stream) {
+  if (mode < 0 || mode > 1 || batch <= 0 || nps <= 0) return 1;
+  const long long total = batch * nps;
+  if ((total + 255) / 256 > 0x7fffffffLL) return 2;
+  if (mode == 0) launch_img2img_start<0>(src, nullptr, noise, offset, out, total, nps, z_scale, sigma0, den, offset_level, stream);
+  else launch_img2img_start<1>(src, eps_enc, noise, offset, out, total, nps, z_scale, sigma0, den, offset_level, stream);
   return 0;
 }
 

@@ -689,6 +689,24 @@ extern "C" nr_status nr_edm_cfg_euler_step(nr_stream stream, const float* net_de
   NR_CATCH
 }
 
+extern "C" nr_status nr_edm_img2img_start(nr_stream stream, const float* z_in_dev, const float* moments_dev, const float* eps_enc_dev,
+                                          const float* noise_dev, const float* offset_dev, float* out_dev, int64_t batch, int64_t n_per_sample,
+                                          float z_scale, float sigma0, float offset_noise_level, int32_t mode) {
+  NR_TRY
+  if (mode != NR_IMG2IMG_LATENT && mode != NR_IMG2IMG_MOMENTS) throw NrError(NR_ERR_ARG, "unknown mode (NR_IMG2IMG_LATENT / NR_IMG2IMG_MOMENTS)");
+  if (!noise_dev || !out_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
+  if (mode == NR_IMG2IMG_LATENT ? !z_in_dev : (!moments_dev || !eps_enc_dev)) throw NrError(NR_ERR_ARG, "null tensor argument for this mode");
+  if (batch <= 0 || n_per_sample <= 0 || batch > INT64_MAX / 2 / n_per_sample) throw NrError(NR_ERR_ARG, "batch / n_per_sample out of range");
+  // !(..) form: a NaN fails it too
+  if (!(sigma0 >= 0.f) || !std::isfinite(sigma0)) throw NrError(NR_ERR_ARG, "sigma0 must be finite and >= 0");
+  if (!std::isfinite(offset_noise_level) || !std::isfinite(z_scale)) throw NrError(NR_ERR_ARG, "non-finite scalar argument");
+  const float den = (float)std::sqrt(1.0 + (double)sigma0 * (double)sigma0);
+  const bool use_offset = offset_dev && offset_noise_level != 0.f;
+  LAUNCH_OK(nr_launch_edm_img2img_start(mode == NR_IMG2IMG_LATENT ? z_in_dev : moments_dev, eps_enc_dev, noise_dev, use_offset ? offset_dev : nullptr,
+                                        out_dev, batch, n_per_sample, z_scale, sigma0, den, offset_noise_level, mode, (hipStream_t)stream));
+  NR_CATCH
+}
+
 extern "C" nr_status nr_prior_p_sample_step(nr_stream stream, const float* pred_dev, const float* pred_null_dev, const float* x_dev,
                                             const float* noise_dev, float* x_out_dev, float* x_start_out_dev, int64_t n, float cond_scale,
                                             int32_t mode, int32_t clamp, double alpha_cumprod_t, double alpha_cumprod_prev, double beta_t) {

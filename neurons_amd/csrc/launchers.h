@@ -63,6 +63,8 @@ int nr_launch_linear_small(const float* x, int M, int K, const bf16* W, const fl
                            float* y, const float* addend, hipStream_t stream);
 int nr_launch_edm_cfg_euler(const float* net, const float* x, float* x_out, long long total, float scale, float sigma_q,
                             float sigma, float sigma_next, hipStream_t stream);
+int nr_launch_edm_img2img_start(const float* src, const float* eps_enc, const float* noise, const float* offset, float* out, long long batch,
+                                long long nps, float z_scale, float sigma0, float den, float offset_level, int mode, hipStream_t stream);
 int nr_launch_cfg_combine(const float* eps, float* out, long long total, float guidance, hipStream_t stream);
 int nr_launch_cfg_ddim_step(const float* eps, const float* x, float* x_out, long long total, float guidance, int do_cfg,
                             float sqrt_at, float sqrt_1mat, float sqrt_ap, float sqrt_1map, hipStream_t stream);

@@ -10,7 +10,11 @@
                              nr_edm_cfg_euler_step; a foreign closure gets the reference's loop, statement for statement
   NativeDiffusionEngine    ~ sgm/models/diffusion.py DiffusionEngine, the attributes utils.unclip_recon (utils.py:302-350) and
                              recon_keyframe_neurons_enhance.py:300-324 touch: the drop-in boundary of the keyframe path
-  unclip_sample            ~ the sampling part of utils.unclip_recon (:308-340), on explicit z / noise tensors
+  unclip_sample            ~ the sampling part of utils.unclip_recon (:308-340), on explicit z / noise tensors; ``init`` / ``strength``
+                             start it from an image instead of pure noise (the img2img reading of utils.py:308)
+  Img2ImgDiscretizationWrapper, do_img2img
+                           ~ sgm/inference/helpers.py:77-98,243-305: the pruned sigma table and the img2img call; the noised start
+                             (posterior sample, offset noise, sigma0, 1 / sqrt(1 + sigma0^2)) is the HIP kernel nr_edm_img2img_start
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -242,6 +246,33 @@ class LegacyDDPMDiscretization:
         return sigmas.to(device)
 
 
+class Img2ImgDiscretizationWrapper:
+    """``Img2ImgDiscretizationWrapper`` (sgm/inference/helpers.py:77-98): wraps a discretization and keeps the LAST
+    ``max(int(strength * len(sigmas)), 1)`` entries of whatever it returns (appended zero included), so the sampler starts part-way down the
+    schedule.  ``strength = 1`` hands the wrapped table through; ``strength = 0`` leaves the one-entry table ``[0]``: no step at all.  The
+    pruned table is a suffix of the full one, so a native network meets only (sigma, c_in) values the full schedule has too."""
+
+    def __init__(self, discretization, strength: float = 1.0):
+        self.discretization = discretization
+        self.strength = strength
+        assert 0.0 <= self.strength <= 1.0
+
+    def __call__(self, *args, **kwargs):
+        sigmas = self.discretization(*args, **kwargs)          # large first, then decreasing
+        keep = max(int(self.strength * len(sigmas)), 1)
+        if keep >= len(sigmas):
+            return sigmas
+        sigmas = torch.flip(sigmas, (0,))
+        sigmas = sigmas[:keep]
+        return torch.flip(sigmas, (0,))
+
+
+def _unwrapped_discretization(discretization):
+    while isinstance(discretization, Img2ImgDiscretizationWrapper):
+        discretization = discretization.discretization
+    return discretization
+
+
 class EpsScaling:
     """denoiser_scaling.py:29-37: (c_skip, c_out, c_in, c_noise) = (1, -sigma, 1 / sqrt(sigma^2 + 1), sigma)."""
 
@@ -424,7 +455,8 @@ class EulerEDMSampler:
         self.num_steps = num_steps
         self.guider = VanillaCFG(scale)
         self.discretization = discretization or LegacyDDPMDiscretization()
-        self.denoiser = DiscreteDenoiser(discretization=self.discretization)     # host scalars of the fused path
+        # host scalars of the fused path: the 1000-entry table the network is evaluated on, never an img2img-pruned one
+        self.denoiser = DiscreteDenoiser(discretization=_unwrapped_discretization(self.discretization))
         self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = s_churn, s_tmin, s_tmax, s_noise
         self.verbose = verbose
         self.device = device
@@ -509,20 +541,23 @@ class NativeDiffusionEngine:
         .denoiser              DiscreteDenoiser (EpsScaling)             denoiser(model, x, sigma, c)               denoiser.py:23-75
         .sampler               EulerEDMSampler + VanillaCFG              sampler(denoiser_fn, x, cond=, uc=); .discretization(n); .num_steps
         .first_stage_model     NativeVAEDecoder                          decode_first_stage(z)                      diffusion.py:118-135
+        .first_stage_encoder   NativeVAEEncoder (same ddconfig)          encode_first_stage(x[, noise])             diffusion.py:137-150
         .ema_scope()           no-op context (use_ema is False in unclip6.yaml; diffusion.py:198-210)
         .eval() / .requires_grad_() / .to(device) / .load_state_dict(ckpt["state_dict"])
 
     ``load_state_dict`` takes the checkpoint's key names: ``model.diffusion_model.*`` -> the U-Net, ``first_stage_model.{decoder,
-    post_quant_conv}.*`` -> the decoder; ``conditioner.*`` (open_clip embedders, not called by unclip_recon), ``denoiser.sigmas`` (regenerated),
-    ``first_stage_model.{encoder,quant_conv,loss}.*`` and ``model_ema.*`` are ignored."""
+    post_quant_conv}.*`` -> the decoder, ``first_stage_model.{encoder,quant_conv}.*`` -> the encoder (optional as a whole: a checkpoint
+    without them loads, and only ``encode_first_stage`` then raises); ``conditioner.*`` (open_clip embedders, not called by unclip_recon),
+    ``denoiser.sigmas`` (regenerated), ``first_stage_model.loss.*`` and ``model_ema.*`` are ignored."""
 
     def __init__(self, network_config: Optional[SGMUNetConfig] = None, first_stage_config=None, num_steps: int = 38, scale: float = 5.0,
                  scale_factor: float = 0.18215, disable_first_stage_autocast: bool = True, use_ema: bool = False, **ignored):
-        from .vae import NativeVAEDecoder, VAEDecoderConfig
+        from .vae import NativeVAEDecoder, NativeVAEEncoder, VAEDecoderConfig
         if use_ema:
             raise NotImplementedError("use_ema: inference checkpoints carry the EMA weights already (unclip6.yaml has no EMA)")
         self.model = NativeOpenAIWrapper(NativeSGMUNet(network_config or SGMUNetConfig()))
         self.first_stage_model = NativeVAEDecoder(first_stage_config or VAEDecoderConfig())
+        self.first_stage_encoder = NativeVAEEncoder(self.first_stage_model.config)       # same ddconfig as the decoder
         disc = LegacyDDPMDiscretization()
         self.denoiser = DiscreteDenoiser(discretization=disc)
         self.sampler = EulerEDMSampler(num_steps=num_steps, scale=scale, discretization=disc)
@@ -557,6 +592,7 @@ class NativeDiffusionEngine:
     def to(self, device=None, dtype=None):
         self.model.to(device)
         self.first_stage_model.to(device)
+        self.first_stage_encoder.to(device)
         return self
 
     @property
@@ -564,7 +600,7 @@ class NativeDiffusionEngine:
         return self.model.diffusion_model.device
 
     def load_state_dict(self, state_dict, strict=True):
-        unet_sd, vae_sd, ignored, unexpected = {}, {}, [], []
+        unet_sd, vae_sd, enc_sd, ignored, unexpected = {}, {}, {}, [], []
         for k, v in state_dict.items():
             if k.startswith("model.diffusion_model."):
                 unet_sd[k[len("model.diffusion_model."):]] = v
@@ -572,6 +608,8 @@ class NativeDiffusionEngine:
                 kk = k[len("first_stage_model."):]
                 if kk.startswith("decoder.") or kk.startswith("post_quant_conv."):
                     vae_sd[kk] = v
+                elif kk.startswith("encoder.") or kk.startswith("quant_conv."):
+                    enc_sd[kk] = v
                 else:
                     ignored.append(k)
             elif k.startswith(("conditioner.", "denoiser.", "model_ema.", "loss_fn.")):
@@ -580,8 +618,10 @@ class NativeDiffusionEngine:
                 unexpected.append(k)
         m1, u1 = self.model.diffusion_model.load_state_dict(unet_sd, strict=False)
         m2, u2 = self.first_stage_model.load_state_dict(vae_sd, strict=False)
-        missing = ["model.diffusion_model." + k for k in m1] + ["first_stage_model." + k for k in m2]
-        unexpected += ["model.diffusion_model." + k for k in u1] + ["first_stage_model." + k for k in u2]
+        # the encoder half is optional as a WHOLE (a decoder-only checkpoint serves every txt2img caller); given in part, the rest is missing
+        m3, u3 = self.first_stage_encoder.load_state_dict(enc_sd, strict=False) if enc_sd else ([], [])
+        missing = ["model.diffusion_model." + k for k in m1] + ["first_stage_model." + k for k in m2 + m3]
+        unexpected += ["model.diffusion_model." + k for k in u1] + ["first_stage_model." + k for k in u2 + u3]
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict for NativeDiffusionEngine:\n\tMissing key(s): {missing[:8]}"
                                f"{'...' if len(missing) > 8 else ''}\n\tUnexpected key(s): {unexpected[:8]}")
@@ -591,20 +631,156 @@ class NativeDiffusionEngine:
     def decode_first_stage(self, z):
         return self.first_stage_model.decode_first_stage(z, scale_factor=self.scale_factor)
 
+    def _encoder(self):
+        if not self.first_stage_encoder._loaded:
+            raise RuntimeError("NativeDiffusionEngine: the checkpoint held no first_stage_model.encoder.* / quant_conv.* tensors; "
+                               "img2img from an image needs them (there is no fallback encoder)")
+        return self.first_stage_encoder
+
+    @torch.no_grad()
+    def encode_first_stage_moments(self, x):
+        """``first_stage_model.encoder`` -> ``quant_conv`` (autoencoder.py:468-483): x [n][3][H][W] in [-1, 1] on the GPU -> the posterior's
+        fp32 moments (mean | logvar) [n][2z][H/8][W/8], what ``nr_edm_img2img_start`` reads in its moments mode."""
+        return self._encoder().moments(x)
+
+    @torch.no_grad()
+    def encode_first_stage(self, x, noise: Optional[torch.Tensor] = None):
+        """``DiffusionEngine.encode_first_stage`` (diffusion.py:137-150) over ``AutoencodingEngineLegacy.encode`` (autoencoder.py:468-488):
+        the regularizer is ``DiagonalGaussianRegularizer`` with its default ``sample=True`` (autoencoder.py:508-520, regularizers/__init__.py:13-31),
+        so the latent is a posterior SAMPLE, ``scale_factor * (mean + std * eps)``, not the mode.  ``noise`` is that eps [n][z][H/8][W/8];
+        ``None`` draws it where and when the reference does: ``torch.randn(mean.shape)`` on the host from the global generator, after the encoder
+        ran (distributions.py:38-42)."""
+        moments = self.encode_first_stage_moments(x)
+        from .vae import DiagonalGaussianDistribution
+        post = DiagonalGaussianDistribution(moments)
+        if noise is None:
+            return post.sample(scale=self.scale_factor, host_draw=True)
+        if tuple(noise.shape) != tuple(post.mean.shape):
+            raise ValueError(f"noise must have the latent's shape {tuple(post.mean.shape)}, got {tuple(noise.shape)}")
+        return post._draw(_f32_cuda(noise, "noise"), self.scale_factor)
+
+
+def _f32_cuda(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: CUDA (ROCm) tensors required; there is no CPU fallback")
+    return t.to(torch.float32).contiguous()
+
+
+def edm_img2img_start(noise, sigma0: float, z: Optional[torch.Tensor] = None, moments: Optional[torch.Tensor] = None,
+                      enc_noise: Optional[torch.Tensor] = None, z_scale: float = 1.0, offset: Optional[torch.Tensor] = None,
+                      offset_noise_level: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The noised, pre-scaled start of sgm img2img (helpers.py:276-291) in ONE HIP launch (``nr_edm_img2img_start``):
+    ``(z + (noise + level * offset[b]) * sigma0) / sqrt(1 + sigma0^2)`` with ``z`` given (skip_encode) or formed from the encoder's
+    ``moments`` and the posterior draw ``enc_noise`` as ``(mean + std * enc_noise) * z_scale``.  ``out`` may be ``z`` itself."""
+    if (z is None) == (moments is None):
+        raise ValueError("pass exactly one of z (a latent) and moments (the encoder's output, with enc_noise)")
+    noise = _f32_cuda(noise, "noise")
+    n = noise.shape[0]
+    nps = noise.numel() // max(n, 1)
+    if z is not None:
+        src = z if out is z else _f32_cuda(z, "z")
+        if out is z and (not z.is_cuda or z.dtype != torch.float32 or not z.is_contiguous()):
+            raise ValueError("in-place start needs a contiguous fp32 CUDA latent")
+        if tuple(src.shape) != tuple(noise.shape):
+            raise ValueError(f"z {tuple(src.shape)} and noise {tuple(noise.shape)} differ in shape")
+        mode, eps = _lib.NR_IMG2IMG_LATENT, None
+    else:
+        src = _f32_cuda(moments, "moments")
+        if enc_noise is None:
+            raise ValueError("moments need enc_noise, the posterior draw")
+        eps = _f32_cuda(enc_noise, "enc_noise")
+        if src.shape[0] != n or src.numel() != 2 * noise.numel() or tuple(eps.shape) != tuple(noise.shape):
+            raise ValueError(f"moments {tuple(src.shape)}, enc_noise {tuple(eps.shape)} and noise {tuple(noise.shape)} do not belong together")
+        mode = _lib.NR_IMG2IMG_MOMENTS
+    off = None
+    if offset is not None and offset_noise_level != 0.0:
+        off = _f32_cuda(offset, "offset").reshape(-1)
+        if off.numel() != n:
+            raise ValueError(f"offset holds one scalar per sample: expected {n}, got {off.numel()}")
+    if out is None:
+        out = torch.empty_like(noise)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != tuple(noise.shape):
+        raise ValueError("out must be a contiguous fp32 CUDA tensor of the noise's shape")
+    _lib.check(_lib.load().nr_edm_img2img_start(
+        torch.cuda.current_stream().cuda_stream, src.data_ptr() if mode == _lib.NR_IMG2IMG_LATENT else None,
+        src.data_ptr() if mode == _lib.NR_IMG2IMG_MOMENTS else None, eps.data_ptr() if eps is not None else None, noise.data_ptr(),
+        off.data_ptr() if off is not None else None, out.data_ptr(), n, nps, float(z_scale), float(sigma0), float(offset_noise_level), mode))
+    return out
+
+
+def _img2img_latents(img, model, sampler, denoiser, c, uc, noise, offset_noise_level, offset, skip_encode, enc_noise):
+    """helpers.py:272-296: the start (one HIP launch) and the sampler.  ``model`` is only needed to encode."""
+    if skip_encode:
+        start = dict(z=img)
+    else:
+        if not isinstance(model, NativeDiffusionEngine):
+            raise TypeError("img2img from an image needs a NativeDiffusionEngine to encode it (or pass a latent with skip_encode)")
+        moments = model.encode_first_stage_moments(img)
+        if enc_noise is None:           # the reference's draw: host, global generator, after the encoder ran (distributions.py:38-42)
+            n, c2, h, w = moments.shape
+            enc_noise = torch.randn((n, c2 // 2, h, w)).to(moments.device)
+        start = dict(moments=moments, enc_noise=enc_noise, z_scale=model.scale_factor)
+    sigmas = sampler.discretization(sampler.num_steps)
+    use_offset = offset_noise_level > 0.0 and offset is not None                                      # helpers.py:281
+    noised_z = edm_img2img_start(noise, float(sigmas[0]), offset=offset if use_offset else None,
+                                 offset_noise_level=offset_noise_level if use_offset else 0.0, **start)
+    return sampler(denoiser, noised_z, cond=c, uc=uc)
+
+
+@torch.no_grad()
+def do_img2img(img, model: NativeDiffusionEngine, sampler: EulerEDMSampler, c: Dict[str, torch.Tensor], uc: Dict[str, torch.Tensor],
+               noise: torch.Tensor, offset_noise_level: float = 0.0, offset: Optional[torch.Tensor] = None, skip_encode: bool = False,
+               return_latents: bool = False, enc_noise: Optional[torch.Tensor] = None, filter=None):
+    """``do_img2img`` (sgm/inference/helpers.py:243-305) on explicit conditioning and explicit draws.  The reference builds ``c`` / ``uc`` from
+    ``model.conditioner`` (:256-270); that stays PyTorch and the caller's, so the dicts (``crossattn`` / ``vector``, one row per sample) come in
+    as arguments.  ``img``: [n][3][H][W] in [-1, 1], or with ``skip_encode`` a latent [n][4][h][w].  ``noise`` [n][4][h][w] is the
+    ``randn_like(z)`` of :276, ``offset`` (n,) the per-sample draw of :282-284 (read when ``offset_noise_level > 0``), ``enc_noise`` the posterior
+    draw inside ``encode_first_stage`` (``None``: drawn as the reference draws it).  Strength is the sampler's: give it
+    ``Img2ImgDiscretizationWrapper(discretization, strength)`` as its discretization.  Returns images in [0, 1] (and the latents)."""
+    samples_z = _img2img_latents(img, model, sampler, model.native_denoiser(), c, uc, noise, offset_noise_level, offset, skip_encode, enc_noise)
+    samples_x = model.decode_first_stage(samples_z)
+    samples = torch.clamp((samples_x + 1.0) / 2.0, min=0.0, max=1.0)
+    if filter is not None:
+        samples = filter(samples)
+    if return_latents:
+        return samples, samples_z
+    return samples
+
 
 def unclip_sample(network, tokens, vector_suffix, z, noise, uc_tokens, sampler: EulerEDMSampler,
-                  offset_noise: Optional[torch.Tensor] = None, offset_noise_level: float = 0.04):
+                  offset_noise: Optional[torch.Tensor] = None, offset_noise_level: float = 0.04, init: Optional[torch.Tensor] = None,
+                  strength: float = 1.0, enc_noise: Optional[torch.Tensor] = None):
     """Sampling part of ``utils.unclip_recon`` (utils.py:308-340) on explicit tensors: ``tokens`` (1,256,1664) prior
     tokens x key-object mask, ``vector_suffix`` (1,1024), starting ``z`` and ``noise`` (n,4,h,w), ``uc_tokens`` the
     random unconditional tokens (:318), ``offset_noise`` (n,) the per-sample offset draw (:328-331).  ``network``: a NativeSGMUNet or
-    anything else ``EulerEDMSampler.__call__`` accepts as its denoiser."""
-    n = z.shape[0]
-    c = {"crossattn": tokens.repeat(n, 1, 1).to(z.device), "vector": vector_suffix.repeat(n, 1).to(z.device)}
-    uc = {"crossattn": uc_tokens.repeat(n, 1, 1).to(z.device), "vector": vector_suffix.repeat(n, 1).to(z.device)}
-    sigmas = sampler.discretization(sampler.num_steps)
-    sigma = sigmas[0].to(z.device)
-    if offset_noise_level > 0.0 and offset_noise is not None:
-        noise = noise + offset_noise_level * offset_noise.to(z.device).reshape(-1, 1, 1, 1)
-    noised_z = z + noise * sigma
-    noised_z = noised_z / torch.sqrt(1.0 + sigmas[0] ** 2.0).to(z.device)
-    return sampler(network, noised_z, cond=c, uc=uc)
+    anything else ``EulerEDMSampler.__call__`` accepts as its denoiser.
+
+    img2img ("can change to VAE outputs of initial image for img2img", utils.py:308): ``init`` replaces ``z`` (which may then be None), one per
+    sample: a latent (n,4,h,w), or an image (n,3,8h,8w) in [-1, 1], which ``network``, then a NativeDiffusionEngine, encodes (``enc_noise``: its
+    posterior draw).  ``strength`` prunes the sampler's sigma table for this call (Img2ImgDiscretizationWrapper).  Without ``init`` and at
+    ``strength == 1.0`` nothing of this is touched."""
+    if init is None and strength == 1.0:
+        n = z.shape[0]
+        c = {"crossattn": tokens.repeat(n, 1, 1).to(z.device), "vector": vector_suffix.repeat(n, 1).to(z.device)}
+        uc = {"crossattn": uc_tokens.repeat(n, 1, 1).to(z.device), "vector": vector_suffix.repeat(n, 1).to(z.device)}
+        sigmas = sampler.discretization(sampler.num_steps)
+        sigma = sigmas[0].to(z.device)
+        if offset_noise_level > 0.0 and offset_noise is not None:
+            noise = noise + offset_noise_level * offset_noise.to(z.device).reshape(-1, 1, 1, 1)
+        noised_z = z + noise * sigma
+        noised_z = noised_z / torch.sqrt(1.0 + sigmas[0] ** 2.0).to(z.device)
+        return sampler(network, noised_z, cond=c, uc=uc)
+    start = z if init is None else init
+    n, dev = noise.shape[0], noise.device
+    if start.shape[0] != n:
+        raise ValueError(f"one init per sample: noise has {n} samples, init {start.shape[0]}")
+    c = {"crossattn": tokens.repeat(n, 1, 1).to(dev), "vector": vector_suffix.repeat(n, 1).to(dev)}
+    uc = {"crossattn": uc_tokens.repeat(n, 1, 1).to(dev), "vector": vector_suffix.repeat(n, 1).to(dev)}
+    full = sampler.discretization
+    sampler.discretization = Img2ImgDiscretizationWrapper(full, strength)
+    try:
+        return _img2img_latents(start, network, sampler, network, c, uc, noise, offset_noise_level, offset_noise,
+                                tuple(start.shape) == tuple(noise.shape), enc_noise)
+    finally:
+        sampler.discretization = full
+
