@@ -277,6 +277,19 @@ nr_status nr_cfg_ddim_step_ex(nr_stream stream, const float* eps_dev, const floa
                               int32_t use_clipped_model_output, double alpha_prod_t, double alpha_prod_t_prev, double sigma, double dir_coeff,
                               const float* noise_dev);
 
+/* replaces the CFG combine + DPMSolverMultistepScheduler.step (diffusers 0.11.1: convert_model_output + the first / second order multistep
+ * update of algorithm_type "dpmsolver++"; Lu et al. 2022, DPM-Solver++ 2M).  Every such update is linear, so the caller forms the coefficients
+ * in double (neurons_amd/scheduler.py: DPMSolverMultistepScheduler.step_coefficients) and this entry knows nothing of schedules:
+ *   e = e_u + g (e_t - e_u) when do_cfg;   m0 = (x - sigma_s e) / alpha_s (EPSILON) | e (SAMPLE) | alpha_s x - sigma_s e (V_PREDICTION);
+ *   x_out = c_x x + c_m0 m0 + c_m1 m1,   m1 = the m0 of the previous step.
+ * out_dev fp32 [2B or B][...] (the network output, uncond half first), x_dev / m1_dev / x_out_dev / m0_out_dev fp32 [n].  m1_dev may be NULL
+ * (then c_m1 must be 0) and is not read when c_m1 == 0; m0_out_dev may be NULL.  x_out_dev may be x_dev and m0_out_dev may be m1_dev (one
+ * history buffer); m0_out_dev must not overlap x_dev / x_out_dev, and no two buffers may overlap partly.  alpha_s in (0, 1], sigma_s in
+ * [0, 1), every scalar finite, prediction_type one of NR_DDIM_*: NR_ERR_ARG otherwise, before any launch. */
+nr_status nr_cfg_dpmpp_step(nr_stream stream, const float* out_dev, const float* x_dev, const float* m1_dev, float* x_out_dev,
+                            float* m0_out_dev, int64_t n, double guidance_scale, int32_t do_cfg, int32_t prediction_type, double alpha_s,
+                            double sigma_s, double c_x, double c_m0, double c_m1);
+
 /* replaces the CFG combine alone (pipeline_neuroclips.py:478-480) for a caller that keeps its own scheduler object
  * (scripts/neuroclips_video.py:219) and calls its .step (pipeline_neuroclips.py:483) on the combined noise:
  *   eps_dev fp32 [2B][...] (uncond half first) -> eps_out_dev fp32 [B][...] = e_u + g (e_t - e_u); n = elements of the output */

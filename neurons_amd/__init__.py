@@ -7,10 +7,11 @@ Host side mirrors the reference's Python interface for this path (same names, ar
   NeuroclipsPipeline  ~ animatediff/pipelines/pipeline_neuroclips.py:43
   sgm.NativeSGMUNet   ~ generative_models/sgm/modules/diffusionmodules/openaimodel.py:472 (unCLIP keyframes)
   vae.NativeVAEDecoder ~ generative_models/sgm/modules/diffusionmodules/model.py:612 Decoder (= AutoencoderKL.decode)
+  DPMSolverMultistepScheduler ~ diffusers==0.11.1 DPMSolverMultistepScheduler (one of the six classes pipeline_neuroclips.py:20-25 accepts)
 All arithmetic of the two networks runs in libneurons_amd.so (hand-written HIP for gfx950) behind the
 C ABI in include/neurons_amd.h; PyTorch supplies device memory, streams and torch.distributed only.
 """
-from .scheduler import DDIMScheduler  # noqa: F401
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler  # noqa: F401
 from .unet3d import NativeUNet3D, UNet3DConfig  # noqa: F401
 from .sparsectrl import NativeSparseCtrl  # noqa: F401
 from .pipeline import NeuroclipsPipeline  # noqa: F401

@@ -101,6 +101,8 @@ SYMBOLS = {
     "nr_cfg_ddim_step": (_I32, [_VP, _VP, _VP, _VP, _I64, C.c_float, _I32, C.c_double, C.c_double]),
     "nr_cfg_ddim_step_ex": (_I32, [_VP, _VP, _VP, _VP, _VP, _I64, C.c_float, _I32, _I32, _I32, _I32, C.c_double, C.c_double, C.c_double,
                                    C.c_double, _VP]),
+    "nr_cfg_dpmpp_step": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I64, C.c_double, _I32, _I32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                 C.c_double]),
     "nr_cfg_combine": (_I32, [_VP, _VP, _VP, _I64, C.c_float]),
     "nr_net_export_manifest": (_I64, [_VP, _VP, _I64, C.POINTER(_I64)]),
     "nr_net_export_weights": (_I32, [_VP, _VP, _VP, _I64]),

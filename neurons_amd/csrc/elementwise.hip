@@ -336,6 +336,59 @@ __global__ __launch_bounds__(256) void cfg_ddim_full_kernel(const float* __restr
   }
 }
 
+// CFG + one DPM-Solver++ multistep update of order <= 2 (Lu et al. 2022, the 2M form): every such update is linear in (x, m0, m1), so the
+// host forms the coefficients in double and the kernel knows nothing of schedules.
+//   PRED as above gives the data prediction m0 (alpha_s, sigma_s of the current timestep);  x_out = c_x x + c_m0 m0 [+ c_m1 m1]  (HIST)
+// x / x_out and m1 / m0_out may be the same buffer (a thread reads its elements before it writes them): those four carry no __restrict__.
+struct DpmppCoef { float alpha_s, sigma_s, c_x, c_m0, c_m1, guidance; };
+
+template <int PRED>
+__device__ __forceinline__ float dpmpp_m0(float e, float xv, const DpmppCoef& c) {
+  if (PRED == 0) return (xv - c.sigma_s * e) / c.alpha_s;
+  if (PRED == 1) return e;
+  return c.alpha_s * xv - c.sigma_s * e;
+}
+
+// VEC as in cfg_ddim_full_kernel: 16-byte accesses with a scalar tail in the last thread, or one element per thread.
+template <int PRED, bool HIST, bool VEC>
+__global__ __launch_bounds__(256) void cfg_dpmpp_step_kernel(const float* __restrict__ out, const float* x, const float* m1, float* x_out,
+                                                             float* m0_out, long long total, long long half_off, int do_cfg, DpmppCoef c) {
+  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * (VEC ? 4 : 1);
+  if (i0 >= total) return;
+  if (VEC && i0 + 4 <= total) {
+    f32x4 e = *(const f32x4*)(out + i0);
+    if (do_cfg) {
+      const f32x4 et = *(const f32x4*)(out + i0 + half_off);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) e[k] = e[k] + c.guidance * (et[k] - e[k]);
+    }
+    const f32x4 xv = *(const f32x4*)(x + i0);
+    f32x4 h = {0.f, 0.f, 0.f, 0.f};
+    if (HIST) h = *(const f32x4*)(m1 + i0);
+    f32x4 o, p;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      p[k] = dpmpp_m0<PRED>(e[k], xv[k], c);
+      o[k] = c.c_x * xv[k] + c.c_m0 * p[k];
+      if (HIST) o[k] += c.c_m1 * h[k];
+    }
+    *(f32x4*)(x_out + i0) = o;
+    if (m0_out) *(f32x4*)(m0_out + i0) = p;
+    return;
+  }
+  const long long i1 = VEC ? total : i0 + 1;      // the ragged tail (VEC) or this thread's one element
+  for (long long i = i0; i < i1; ++i) {
+    float e = out[i];
+    if (do_cfg) e = e + c.guidance * (out[i + half_off] - e);
+    const float xv = x[i];
+    const float p = dpmpp_m0<PRED>(e, xv, c);
+    float o = c.c_x * xv + c.c_m0 * p;
+    if (HIST) o += c.c_m1 * m1[i];
+    x_out[i] = o;
+    if (m0_out) m0_out[i] = p;
+  }
+}
+
 // classifier-free guidance alone (pipeline_neuroclips.py:478-480): out = eps_uncond + g * (eps_text - eps_uncond).  For callers that keep a
 // scheduler of their own (the combined eps then goes to its .step); the pipeline's own scheduler uses the fused kernel above.
 __global__ void cfg_combine_kernel(const float* __restrict__ eps, float* __restrict__ out, long long total, float guidance) {
@@ -750,6 +803,39 @@ extern "C" int nr_launch_cfg_ddim_full(const float* eps, const float* x, const f
   else launch_cfg_ddim_full_clip<P, false>(clip, clipped_out, eps, x, nullptr, x_out, x0_out, total, do_cfg, c, stream);
   if (pred == 0) { NR_DDIM_PRED(0) } else if (pred == 1) { NR_DDIM_PRED(1) } else { NR_DDIM_PRED(2) }
 #undef NR_DDIM_PRED
+  return 0;
+}
+
+namespace {
+template <int PRED, bool HIST>
+void launch_cfg_dpmpp_step(const float* out, const float* x, const float* m1, float* x_out, float* m0_out, long long total, int do_cfg,
+                           const DpmppCoef& c, hipStream_t stream) {
+  // as launch_cfg_ddim_full: every base 16-byte aligned, and with guidance the text half of `out` (total floats in) too
+  const uintptr_t bases = (uintptr_t)out | (uintptr_t)x | (uintptr_t)m1 | (uintptr_t)x_out | (uintptr_t)m0_out;
+  const bool vec = (bases & 15) == 0 && (!do_cfg || total % 4 == 0);
+  if (vec) {
+    const long long threads = (total + 3) / 4;
+    hipLaunchKernelGGL((cfg_dpmpp_step_kernel<PRED, HIST, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, out, x, m1,
+                       x_out, m0_out, total, total, do_cfg, c);
+  } else {
+    hipLaunchKernelGGL((cfg_dpmpp_step_kernel<PRED, HIST, false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out, x, m1,
+                       x_out, m0_out, total, total, do_cfg, c);
+  }
+}
+}  // namespace
+
+// pred: 0 epsilon, 1 sample, 2 v_prediction.  m1 == nullptr selects the instantiations without the history read (c_m1 is then not used).
+extern "C" int nr_launch_cfg_dpmpp_step(const float* out, const float* x, const float* m1, float* x_out, float* m0_out, long long total,
+                                        float guidance, int do_cfg, int pred, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1,
+                                        hipStream_t stream) {
+  if (pred < 0 || pred > 2 || total <= 0) return 1;
+  if ((total + 255) / 256 > 0x7fffffffLL) return 2;
+  const DpmppCoef c = {alpha_s, sigma_s, c_x, c_m0, c_m1, guidance};
+#define NR_DPMPP_PRED(P)                                                                      \
+  if (m1) launch_cfg_dpmpp_step<P, true>(out, x, m1, x_out, m0_out, total, do_cfg, c, stream); \
+  else launch_cfg_dpmpp_step<P, false>(out, x, nullptr, x_out, m0_out, total, do_cfg, c, stream);
+  if (pred == 0) { NR_DPMPP_PRED(0) } else if (pred == 1) { NR_DPMPP_PRED(1) } else { NR_DPMPP_PRED(2) }
+#undef NR_DPMPP_PRED
   return 0;
 }
 

@@ -765,6 +765,31 @@ extern "C" nr_status nr_cfg_ddim_step_ex(nr_stream stream, const float* eps_dev,
   NR_CATCH
 }
 
+extern "C" nr_status nr_cfg_dpmpp_step(nr_stream stream, const float* out_dev, const float* x_dev, const float* m1_dev, float* x_out_dev,
+                                       float* m0_out_dev, int64_t n, double guidance_scale, int32_t do_cfg, int32_t prediction_type,
+                                       double alpha_s, double sigma_s, double c_x, double c_m0, double c_m1) {
+  NR_TRY
+  if (!out_dev || !x_dev || !x_out_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
+  if (n <= 0) throw NrError(NR_ERR_ARG, "n must be positive");
+  if (prediction_type < NR_DDIM_EPSILON || prediction_type > NR_DDIM_V_PREDICTION)
+    throw NrError(NR_ERR_ARG, "unknown prediction type (NR_DDIM_EPSILON / NR_DDIM_SAMPLE / NR_DDIM_V_PREDICTION)");
+  for (double v : {guidance_scale, alpha_s, sigma_s, c_x, c_m0, c_m1})
+    if (!std::isfinite(v)) throw NrError(NR_ERR_ARG, "non-finite coefficient");
+  if (!(alpha_s > 0.0 && alpha_s <= 1.0)) throw NrError(NR_ERR_ARG, "alpha_s out of range (0, 1]");
+  if (!(sigma_s >= 0.0 && sigma_s < 1.0)) throw NrError(NR_ERR_ARG, "sigma_s out of range [0, 1)");
+  if (c_m1 != 0.0 && !m1_dev) throw NrError(NR_ERR_ARG, "c_m1 != 0 needs the history tensor m1_dev");
+  // two [n] buffers that share elements without being the same buffer: a thread would read what another one wrote
+  const auto overlap = [n](const float* a, const float* b) { return a && b && a < b + n && b < a + n; };
+  if (overlap(m0_out_dev, x_dev) || overlap(m0_out_dev, x_out_dev)) throw NrError(NR_ERR_ARG, "m0_out_dev must not alias x_dev / x_out_dev");
+  if ((x_out_dev != x_dev && overlap(x_out_dev, x_dev)) || (m0_out_dev != m1_dev && overlap(m0_out_dev, m1_dev)))
+    throw NrError(NR_ERR_ARG, "x_out_dev / m0_out_dev may alias x_dev / m1_dev only as the same buffer, not partly");
+  // c_m1 == 0 (a first-order step): the history is not read even when the caller hands its buffer in
+  LAUNCH_OK(nr_launch_cfg_dpmpp_step(out_dev, x_dev, c_m1 != 0.0 ? m1_dev : nullptr, x_out_dev, m0_out_dev, n, (float)guidance_scale,
+                                     do_cfg ? 1 : 0, prediction_type, (float)alpha_s, (float)sigma_s, (float)c_x, (float)c_m0, (float)c_m1,
+                                     (hipStream_t)stream));
+  NR_CATCH
+}
+
 extern "C" nr_status nr_cfg_combine(nr_stream stream, const float* eps_dev, float* eps_out_dev, int64_t n, float guidance_scale) {
   NR_TRY
   if (!eps_dev || !eps_out_dev || n <= 0) throw NrError(NR_ERR_ARG, "bad argument");

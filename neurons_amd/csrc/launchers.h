@@ -71,6 +71,8 @@ int nr_launch_cfg_ddim_step(const float* eps, const float* x, float* x_out, long
 int nr_launch_cfg_ddim_full(const float* eps, const float* x, const float* noise, float* x_out, float* x0_out, long long total, float guidance,
                             int do_cfg, int pred, int clip, int clipped_out, float sqrt_at, float sqrt_1mat, float sqrt_ap, float dir, float sigma,
                             hipStream_t stream);
+int nr_launch_cfg_dpmpp_step(const float* out, const float* x, const float* m1, float* x_out, float* m0_out, long long total, float guidance,
+                             int do_cfg, int pred, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, hipStream_t stream);
 int nr_launch_add_bf16(const bf16* a, const bf16* b, bf16* out, long long n, hipStream_t stream);
 int nr_launch_prior_p_sample(const float* pred, const float* pred_null, const float* x, const float* noise, float* x_out, float* x_start_out,
                              long long total, float cond_scale, int mode, int clamp, float sqrt_ac, float sqrt_1mac, float sqrt_recip_ac,

@@ -330,6 +330,29 @@ def cfg_ddim_step(eps, x, guidance_scale, alpha_prod_t, alpha_prod_t_prev, do_cf
     return (out, x0) if return_pred_original else out
 
 
+def cfg_dpmpp_step(model_output, x, guidance_scale, alpha_s, sigma_s, c_x, c_m0, c_m1=0.0, m1=None, do_cfg=True, *, prediction_type="epsilon",
+                   x_out=None, m0_out=None, return_m0=False):
+    """CFG combine + one DPM-Solver++ multistep update (nr_cfg_dpmpp_step): m0 = the x0 prediction from (alpha_s, sigma_s) and
+    prediction_type, x_out = c_x x + c_m0 m0 + c_m1 m1 with the coefficients of DPMSolverMultistepScheduler.step_coefficients.  ``m1`` (fp32,
+    x's shape) is the previous step's m0, required when c_m1 != 0.  ``x_out`` / ``m0_out``: write into these tensors (x_out may be x, m0_out
+    may be m1).  return_m0 (or an m0_out) -> (x_out, m0)."""
+    _chk_f32(model_output, x, m1, x_out, m0_out)
+    from .scheduler import PREDICTION_TYPES
+    if prediction_type not in PREDICTION_TYPES:
+        raise ValueError(f"prediction_type given as {prediction_type} must be one of `epsilon`, `sample`, or `v_prediction`")
+    if model_output.numel() != x.numel() * (2 if do_cfg else 1):
+        raise ValueError(f"model_output: expected {x.numel() * (2 if do_cfg else 1)} elements, got {model_output.numel()}")
+    for name, t in (("m1", m1), ("x_out", x_out), ("m0_out", m0_out)):
+        if t is not None and t.numel() != x.numel():
+            raise ValueError(f"{name}: expected {x.numel()} elements (the latents' shape), got {t.numel()}")
+    out = torch.empty_like(x) if x_out is None else x_out
+    m0 = torch.empty_like(x) if (m0_out is None and return_m0) else m0_out
+    _lib.check(_lib.load().nr_cfg_dpmpp_step(_stream(), _ptr(model_output), _ptr(x), _ptr(m1), _ptr(out), _ptr(m0), x.numel(),
+                                             float(guidance_scale), 1 if do_cfg else 0, PREDICTION_TYPES[prediction_type], float(alpha_s),
+                                             float(sigma_s), float(c_x), float(c_m0), float(c_m1)))
+    return (out, m0) if m0 is not None else out
+
+
 def cfg_combine(eps, guidance_scale):
     """eps fp32 [2B, ...] (uncond half first) -> [B, ...] = e_u + g (e_t - e_u)  (pipeline_neuroclips.py:478-480), HIP nr_cfg_combine"""
     _chk_f32(eps)

@@ -281,8 +281,12 @@ class NeuroclipsPipeline:
         # Any other scheduler object (the diffusers surface the reference caller constructs, scripts/neuroclips_video.py:219) is driven exactly
         # as the reference drives it -- scale_model_input / step(...).prev_sample (pipeline_neuroclips.py:436,483) -- with the CFG combine in HIP.
         own_scheduler = hasattr(self.scheduler, "alpha_pair") and hasattr(self.scheduler, "timesteps_host")
-        timesteps_host = self.scheduler.timesteps_host if own_scheduler else [int(v) for v in torch.as_tensor(timesteps).tolist()]
-        extra_step_kwargs = {} if own_scheduler else self.prepare_extra_step_kwargs(generator, eta)
+        # This package's DPMSolverMultistepScheduler: CFG + x0 prediction + the multistep update as ONE nr_cfg_dpmpp_step per step.  eta and
+        # generator do not reach it (its step names neither: prepare_extra_step_kwargs would drop them)
+        dpmpp = getattr(self.scheduler, "native_rule", None) == "dpmsolver++" and hasattr(self.scheduler, "timesteps_host")
+        native_scheduler = own_scheduler or dpmpp
+        timesteps_host = self.scheduler.timesteps_host if native_scheduler else [int(v) for v in torch.as_tensor(timesteps).tolist()]
+        extra_step_kwargs = {} if native_scheduler else self.prepare_extra_step_kwargs(generator, eta)
 
         num_channels_latents = self.unet.in_channels
         latents = self.prepare_latents(batch_size * num_videos_per_prompt, num_channels_latents, video_length, height, width,
@@ -368,10 +372,12 @@ class NeuroclipsPipeline:
             # the loop below builds the U-Net input as cat([latents] * 2) with one timestep (:435): the native U-Net may evaluate what precedes
             # the first cross-attention once per pair (exact; nr_net_set_cfg_pair_identical).  Own scheduler only: its scale_model_input is the
             # identity, a foreign one is not known to treat the two halves alike
-            cfg_pair = bool(do_classifier_free_guidance and own_scheduler)
+            cfg_pair = bool(do_classifier_free_guidance and native_scheduler)
+            # DPM-Solver++: the previous step's x0 prediction, read and rewritten in place by each step's kernel
+            dpm_history = torch.empty_like(latents) if dpmpp else None
             for i, t in enumerate(timesteps_host):
                 latent_model_input = torch.cat([latents] * 2) if do_classifier_free_guidance else latents
-                latent_model_input = self.scheduler.scale_model_input(latent_model_input, t if own_scheduler else timesteps[i])
+                latent_model_input = self.scheduler.scale_model_input(latent_model_input, t if native_scheduler else timesteps[i])
                 down_res = mid_res = None
                 if G > 1:
                     launch, g, p_ = plan[i]
@@ -397,7 +403,19 @@ class NeuroclipsPipeline:
                     noise_pred = self.unet(latent_model_input, t, encoder_hidden_states=text_embeddings,
                                            down_block_additional_residuals=down_res,
                                            mid_block_additional_residual=mid_res).sample
-                if full_rule:
+                if dpmpp:
+                    # CFG + convert_model_output + the first / second order multistep update in one HIP kernel; the coefficients of the linear
+                    # form come from the host tables (step i of this walk has i steps of history)
+                    k = self.scheduler.step_coefficients(i, history=i)
+                    new_latents = torch.empty_like(latents)
+                    _lib.check(lib.nr_cfg_dpmpp_step(torch.cuda.current_stream().cuda_stream, noise_pred.data_ptr(), latents.data_ptr(),
+                                                     dpm_history.data_ptr() if k.order == 2 else None, new_latents.data_ptr(),
+                                                     dpm_history.data_ptr(), n_lat, float(guidance_scale),
+                                                     1 if do_classifier_free_guidance else 0,
+                                                     PREDICTION_TYPES[self.scheduler.config.prediction_type], k.alpha_s, k.sigma_s, k.c_x,
+                                                     k.c_m0, k.c_m1))
+                    latents = new_latents
+                elif full_rule:
                     # the same fusion for the rest of the step contract (eta, prediction_type): one HIP kernel, sigma and the direction
                     # coefficient from the host tables, this step's pre-drawn noise
                     a_t, a_prev, sigma, dir_coeff = self.scheduler.step_coefficients(t, eta)
