@@ -45,10 +45,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(NrGnParams p) {
     }
   }
   __syncthreads();
-  // group reduce (fixed order => deterministic): 8 threads per group
+  // group reduce (fixed order => deterministic): 8 threads per group, 32 groups per round (nr_gn_route admits up to 64 groups)
   const int cg = C / p.groups;
-  const int g = tid >> 3, sub = tid & 7;
-  if (g < p.groups) {
+  const int sub = tid & 7;
+  for (int g = tid >> 3; g < p.groups; g += 32) {
     float s = 0.f, q = 0.f;
     for (int i = sub; i < cg * PL; i += 8) {
       const int l = i / cg, ci = i - l * cg;

@@ -244,12 +244,13 @@ def condembed_in(cond, mask, w, bias, frames=None):
     return out
 
 
-def groupnorm(x0, gamma, beta, groups=32, eps=1e-5, silu=False, x1=None):
+def groupnorm(x0, gamma, beta, groups=32, eps=1e-5, silu=False, x1=None, out=None):
+    """GroupNorm [+ SiLU] over the channel concat of x0 [nimg, H, W, c0] and x1 [nimg, H, W, c1] (optional), per image.  out as in gemm."""
     _chk_bf16(x0, x1)
     _chk_f32(gamma, beta)
     nimg, H, W, c0 = x0.shape
     c1 = 0 if x1 is None else x1.shape[3]
-    out = torch.empty(nimg, H, W, c0 + c1, dtype=torch.bfloat16, device=x0.device)
+    out = _out_tensor(out, (nimg, H, W, c0 + c1), x0)
     ws = torch.empty(nimg * (H * W) * groups * 2 + 64, dtype=torch.float32, device=x0.device)
     lib = _lib.load()
     _lib.check(lib.nr_op_groupnorm(_stream(), _ptr(x0), c0, _ptr(x1), c1, nimg, H * W, groups, _ptr(gamma), _ptr(beta),
@@ -257,11 +258,12 @@ def groupnorm(x0, gamma, beta, groups=32, eps=1e-5, silu=False, x1=None):
     return out
 
 
-def layernorm(x, gamma, beta, eps=1e-5, pe=None, pe_hw=1, pe_F=1):
+def layernorm(x, gamma, beta, eps=1e-5, pe=None, pe_hw=1, pe_F=1, out=None):
+    """LayerNorm over the last dim of x [M, C] (+ pe[(row // pe_hw) % pe_F], an fp32 [>= pe_F, C] table, after the affine).  out as in gemm."""
     _chk_bf16(x)
     _chk_f32(gamma, beta, pe)
     M, Cc = x.shape
-    out = torch.empty_like(x)
+    out = _out_tensor(out, (M, Cc), x)
     lib = _lib.load()
     _lib.check(lib.nr_op_layernorm(_stream(), _ptr(x), _ptr(out), M, Cc, _ptr(gamma), _ptr(beta), eps, _ptr(pe), pe_hw, pe_F))
     return out

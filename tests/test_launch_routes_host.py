@@ -115,3 +115,53 @@ def test_groupnorm_route_agrees_with_its_launcher(stub_build, tmp_path):
             assert len(names) == (3 if "gn_finalize_kernel" in "".join(names) else 2)
     assert forms == {"slab", "small", "chunked2", "chunked3"}, forms
     assert len(launched["64 128 64 2"]) == 3 and len(launched["64 128 64 0"]) == 2, "plan_nimg must enter the chunking"
+
+
+def test_groupnorm_case_table_reaches_every_instantiation(stub_build, tmp_path):
+    """The GroupNorm cases of tests/test_norm_gpu.py (tests/norm_cases.py), routed and launched under the stub: each case takes the form its table
+    entry names, and together they launch every kernel nr_launch_groupnorm can launch at 512 threads: the slab at 2 .. 32 chunks per thread and
+    1 / 2 / 4 / 8 groups per workgroup, in both block orders; the three small-image kernels; the chunked form with and without gn_finalize, with
+    several pixel lanes and with one.  (The 1024-thread slab and the NR_GN_* bisect switches are read once per process from the environment: not here.)"""
+    import re
+    sys.path.insert(0, HERE)
+    from norm_cases import GN_CASES
+    trace = str(tmp_path / "trace.txt")
+    out = _run([os.path.join(stub_build, "gn_route"), "--c1-groups"] + [str(v) for c in GN_CASES for v in (c.nimg, c.hw, c.c0, 0, c.c1, c.groups)], trace)
+    launched = _sections(trace, "shape")
+    slab_nv, slab_gs, slab_order, small, chunked, lanes = set(), set(), set(), set(), set(), set()
+    for c in GN_CASES:
+        key = f"{c.nimg} {c.hw} {c.c0} 0 {c.c1} {c.groups}"
+        line = next(ln for ln in out.splitlines() if ln.startswith(f"shape {key}:")).split()
+        assert int(line[line.index("status") + 1]) == 0, key
+        C = c.c0 + c.c1
+        ls = [ln.split() for ln in launched[key]][:int(line[line.index("launches") + 1])]      # two cases share a shape: the first launch of each is the same
+        names = [f[1] for f in ls]
+        grid, block, lds = [int(v) for v in ls[0][2].split(",")], [int(v) for v in ls[0][3].split(",")], int(ls[0][4])
+        want = c.form
+        print(key, names, grid, block, lds, want)
+        if (m := re.search(r"gn_slab_kernelILi(\d+)ELi(\d+)EE", names[0])):
+            nv, threads = int(m.group(1)), int(m.group(2))
+            assert want["kind"] == "slab" and len(names) == 1 and threads == 512 and block == [512, 1, 1] and grid[1:] == [1, 1], key
+            assert (c.nimg * c.groups) % grid[0] == 0, key
+            gs = c.nimg * c.groups // grid[0]      # grid = nimg * (groups / GS)
+            cpp = gs * (C // c.groups) // 8
+            assert (gs * (C // c.groups)) % 8 == 0 and 1 <= cpp <= 64 and -(-c.hw // (512 // cpp)) <= nv, f"{key}: the slab must hold the image"
+            assert nv == want.get("nv", nv) and gs == want.get("gs", gs) and grid[0] == want.get("grid", grid[0]), (key, nv, gs, grid)
+            slab_nv.add(nv); slab_gs.add(gs); slab_order.add("remapped" if grid[0] % 8 == 0 else "plain")
+        elif (m := re.search(r"gn_fused_small_kernelILi(\d+)EE", names[0])):
+            maxp = int(m.group(1))
+            assert want["kind"] == "small" and len(names) == 1 and grid == [c.groups, c.nimg, 1] and block == [256, 1, 1], key
+            assert c.hw * (C // c.groups // 2) <= 256 * maxp and maxp == want.get("maxp", maxp), (key, maxp)
+            small.add(maxp)
+        else:
+            assert "gn_stats_kernel" in names[0] and "gn_apply_kernel" in names[-1] and block == [256, 1, 1], (key, names)
+            kind = "chunked3" if len(names) == 3 else "chunked2"
+            assert want["kind"] == kind and (len(names) == 2 or "gn_finalize_kernel" in names[1]), (key, names)
+            pl = lds // (2 * C * 4)                 # gn_stats_kernel's dynamic LDS: 2 * PL * C floats
+            assert lds == 2 * pl * C * 4 and pl == (256 // (C // 8) if C // 8 <= 256 else 1) and (pl == 1) == bool(want.get("pl1")), (key, lds)
+            chunked.add(kind); lanes.add("one" if pl == 1 else "many")
+    assert slab_nv == {2, 4, 8, 12, 16, 24, 32}, slab_nv
+    assert slab_gs == {1, 2, 4, 8}, slab_gs
+    assert slab_order == {"remapped", "plain"}, slab_order
+    assert small == {8, 16, 48}, small
+    assert chunked == {"chunked2", "chunked3"} and lanes == {"one", "many"}, (chunked, lanes)
