@@ -5,7 +5,6 @@
 //   timestep_sincos : diffusers Timesteps(320, flip_sin_to_cos=True, freq_shift=0)  (unet.py:101,386; in-repo
 //                     twin: generative_models/sgm/modules/diffusionmodules/util.py:207-231)
 //   linear_small    : y = W act(x) + b for the handful-of-rows time-embedding MLPs (unet.py:392; resnet.py:191)
-//   cfg_ddim_step   : classifier-free guidance + DDIM eta=0 update           (pipeline_neuroclips.py:478-483)
 //   add_bf16        : out = a + b (ControlNet residual adds, unet.py:425-428,436-439)
 //   condembed_*     : the SparseCtrl image-condition embedding (end of this file): a first conv from the fp32 condition planes, the
 //                     small-channel 3x3 convs on MFMA (implicit GEMM, K = 9 Cin <= 864) and the batch / frame broadcast
@@ -246,253 +245,6 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const float* __restri
   }
 }
 
-// eps: fp32 [2B][...] (uncond first, text second: pipeline_neuroclips.py:238,479); x: fp32 [B][...] updated in place
-// into x_out.  per = elements per batch entry.  DDIM eta=0 (diffusers 0.11.1 DDIMScheduler.step):
-//   x0 = (x - sqrt(1-a_t) * e) / sqrt(a_t);  x_prev = sqrt(a_prev) * x0 + sqrt(1-a_prev) * e
-__global__ void cfg_ddim_step_kernel(const float* __restrict__ eps, const float* __restrict__ x, float* __restrict__ x_out,
-                                     long long total, long long half_off, float guidance, int do_cfg, float sqrt_at,
-                                     float sqrt_1mat, float sqrt_ap, float sqrt_1map) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  float e;
-  if (do_cfg) {
-    const float eu = eps[i], et = eps[i + half_off];
-    e = eu + guidance * (et - eu);
-  } else {
-    e = eps[i];
-  }
-  const float xv = x[i];
-  const float x0 = (xv - sqrt_1mat * e) / sqrt_at;
-  x_out[i] = sqrt_ap * x0 + sqrt_1map * e;
-}
-
-// The full DDIM rule (Song et al. 2021 eq. 12 / 16 in the form of diffusers' DDIMScheduler.step) for everything the kernel above does not
-// cover; each variant is an instantiation of its own, the default (epsilon, no clipping, eta = 0, no x0 output) stays on the kernel above.
-//   PRED 0 epsilon: x0 = (x - sqrt(1-a_t) e) / sqrt(a_t)      1 sample: x0 = e      2 v: x0 = sqrt(a_t) x - sqrt(1-a_t) e
-//   PRED 1 / 2 then re-derive e: (x - sqrt(a_t) x0) / sqrt(1-a_t)  /  sqrt(a_t) v + sqrt(1-a_t) x
-//   CLIP: x0 clamped to [-1, 1];  CLIPPED_OUT: e re-derived from the (clamped) x0;  STOCH: + sigma * noise
-//   x_prev = sqrt(a_prev) x0 + dir e [+ sigma z],  dir = sqrt(1 - a_prev - sigma^2) formed on the host in double (0 at a_prev = 1: no sqrt
-//   of a rounded-negative number here).
-struct DdimCoef { float sqrt_at, sqrt_1mat, sqrt_ap, dir, sigma, guidance; };
-
-template <int PRED, bool CLIP, bool CLIPPED_OUT, bool STOCH>
-__device__ __forceinline__ float ddim_full_one(float e, float xv, float z, const DdimCoef& c, float& x0_out) {
-  float x0;
-  if (PRED == 0) {
-    x0 = (xv - c.sqrt_1mat * e) / c.sqrt_at;
-  } else if (PRED == 1) {
-    x0 = e;
-    e = (xv - c.sqrt_at * x0) / c.sqrt_1mat;
-  } else {
-    x0 = c.sqrt_at * xv - c.sqrt_1mat * e;
-    e = c.sqrt_at * e + c.sqrt_1mat * xv;
-  }
-  if (CLIP) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-  if (CLIPPED_OUT) e = (xv - c.sqrt_at * x0) / c.sqrt_1mat;
-  x0_out = x0;
-  float o = c.sqrt_ap * x0 + c.dir * e;
-  if (STOCH) o += c.sigma * z;
-  return o;
-}
-
-// VEC: thread i owns elements 4i .. 4i+3 with 16-byte loads / stores (every pointer, eps + half_off included, 16-byte aligned: checked by the
-// launcher); the last thread of a total that is no multiple of 4 walks its 1..3 elements one by one.  !VEC: one element per thread.
-template <int PRED, bool CLIP, bool CLIPPED_OUT, bool STOCH, bool VEC>
-__global__ __launch_bounds__(256) void cfg_ddim_full_kernel(const float* __restrict__ eps, const float* __restrict__ x,
-                                                            const float* __restrict__ noise, float* __restrict__ x_out,
-                                                            float* __restrict__ x0_out, long long total, long long half_off, int do_cfg,
-                                                            DdimCoef c) {
-  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * (VEC ? 4 : 1);
-  if (i0 >= total) return;
-  if (VEC && i0 + 4 <= total) {
-    f32x4 e = *(const f32x4*)(eps + i0);
-    if (do_cfg) {
-      const f32x4 et = *(const f32x4*)(eps + i0 + half_off);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) e[k] = e[k] + c.guidance * (et[k] - e[k]);
-    }
-    const f32x4 xv = *(const f32x4*)(x + i0);
-    f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    if (STOCH) z = *(const f32x4*)(noise + i0);
-    f32x4 o, p;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float x0;
-      o[k] = ddim_full_one<PRED, CLIP, CLIPPED_OUT, STOCH>(e[k], xv[k], z[k], c, x0);
-      p[k] = x0;
-    }
-    *(f32x4*)(x_out + i0) = o;
-    if (x0_out) *(f32x4*)(x0_out + i0) = p;
-    return;
-  }
-  const long long i1 = VEC ? total : i0 + 1;      // the ragged tail (VEC) or this thread's one element
-  for (long long i = i0; i < i1; ++i) {
-    float e = eps[i];
-    if (do_cfg) e = e + c.guidance * (eps[i + half_off] - e);
-    float x0;
-    const float o = ddim_full_one<PRED, CLIP, CLIPPED_OUT, STOCH>(e, x[i], STOCH ? noise[i] : 0.f, c, x0);
-    x_out[i] = o;
-    if (x0_out) x0_out[i] = x0;
-  }
-}
-
-// CFG + one DPM-Solver++ multistep update of order <= 2 (Lu et al. 2022, the 2M form): every such update is linear in (x, m0, m1), so the
-// host forms the coefficients in double and the kernel knows nothing of schedules.
-//   PRED as above gives the data prediction m0 (alpha_s, sigma_s of the current timestep);  x_out = c_x x + c_m0 m0 [+ c_m1 m1]  (HIST)
-// x / x_out and m1 / m0_out may be the same buffer (a thread reads its elements before it writes them): those four carry no __restrict__.
-struct DpmppCoef { float alpha_s, sigma_s, c_x, c_m0, c_m1, guidance; };
-
-template <int PRED>
-__device__ __forceinline__ float dpmpp_m0(float e, float xv, const DpmppCoef& c) {
-  if (PRED == 0) return (xv - c.sigma_s * e) / c.alpha_s;
-  if (PRED == 1) return e;
-  return c.alpha_s * xv - c.sigma_s * e;
-}
-
-// VEC as in cfg_ddim_full_kernel: 16-byte accesses with a scalar tail in the last thread, or one element per thread.
-template <int PRED, bool HIST, bool VEC>
-__global__ __launch_bounds__(256) void cfg_dpmpp_step_kernel(const float* __restrict__ out, const float* x, const float* m1, float* x_out,
-                                                             float* m0_out, long long total, long long half_off, int do_cfg, DpmppCoef c) {
-  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * (VEC ? 4 : 1);
-  if (i0 >= total) return;
-  if (VEC && i0 + 4 <= total) {
-    f32x4 e = *(const f32x4*)(out + i0);
-    if (do_cfg) {
-      const f32x4 et = *(const f32x4*)(out + i0 + half_off);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) e[k] = e[k] + c.guidance * (et[k] - e[k]);
-    }
-    const f32x4 xv = *(const f32x4*)(x + i0);
-    f32x4 h = {0.f, 0.f, 0.f, 0.f};
-    if (HIST) h = *(const f32x4*)(m1 + i0);
-    f32x4 o, p;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      p[k] = dpmpp_m0<PRED>(e[k], xv[k], c);
-      o[k] = c.c_x * xv[k] + c.c_m0 * p[k];
-      if (HIST) o[k] += c.c_m1 * h[k];
-    }
-    *(f32x4*)(x_out + i0) = o;
-    if (m0_out) *(f32x4*)(m0_out + i0) = p;
-    return;
-  }
-  const long long i1 = VEC ? total : i0 + 1;      // the ragged tail (VEC) or this thread's one element
-  for (long long i = i0; i < i1; ++i) {
-    float e = out[i];
-    if (do_cfg) e = e + c.guidance * (out[i + half_off] - e);
-    const float xv = x[i];
-    const float p = dpmpp_m0<PRED>(e, xv, c);
-    float o = c.c_x * xv + c.c_m0 * p;
-    if (HIST) o += c.c_m1 * m1[i];
-    x_out[i] = o;
-    if (m0_out) m0_out[i] = p;
-  }
-}
-
-// classifier-free guidance alone (pipeline_neuroclips.py:478-480): out = eps_uncond + g * (eps_text - eps_uncond).  For callers that keep a
-// scheduler of their own (the combined eps then goes to its .step); the pipeline's own scheduler uses the fused kernel above.
-__global__ void cfg_combine_kernel(const float* __restrict__ eps, float* __restrict__ out, long long total, float guidance) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const float eu = eps[i], et = eps[i + total];
-  out[i] = eu + guidance * (et - eu);
-}
-
-// One ancestral DDPM step of the diffusion prior (see nr_prior_p_sample_step in include/neurons_amd.h): network output -> x_start
-// (mode 0: the output IS x_start; 1: v-prediction; 2: noise prediction, clamped to [-1, 1] when `clamp`), classifier-free guidance
-// between the conditional and the null evaluation when pred_null != nullptr, posterior mean + sigma * noise.
-__global__ void prior_p_sample_kernel(const float* __restrict__ pred, const float* __restrict__ pred_null, const float* __restrict__ x,
-                                      const float* __restrict__ noise, float* __restrict__ x_out, float* __restrict__ x_start_out, long long total,
-                                      float cond_scale, int mode, int clamp, float sqrt_ac, float sqrt_1mac, float sqrt_recip_ac,
-                                      float sqrt_recipm1_ac, float coef1, float coef2, float sigma) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  float p = pred[i];
-  if (pred_null) { const float pn = pred_null[i]; p = pn + (p - pn) * cond_scale; }
-  const float xv = x[i];
-  float x0;
-  if (mode == 0) x0 = p;
-  else if (mode == 1) x0 = sqrt_ac * xv - sqrt_1mac * p;
-  else x0 = sqrt_recip_ac * xv - sqrt_recipm1_ac * p;
-  if (clamp) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-  if (x_start_out) x_start_out[i] = x0;
-  float o = coef1 * x0 + coef2 * xv;
-  if (noise) o += sigma * noise[i];
-  x_out[i] = o;
-}
-
-// EDM eps-scaling + vanilla CFG + Euler step (see nr_edm_cfg_euler_step in include/neurons_amd.h)
-__global__ void edm_cfg_euler_kernel(const float* __restrict__ net, const float* __restrict__ x, float* __restrict__ x_out,
-                                     long long total, float scale, float sigma_q, float sigma, float sigma_next) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const float xv = x[i];
-  const float du = net[i] * (-sigma_q) + xv;      // c_out = -quantised sigma, c_skip = 1 (denoiser_scaling.py:29-37)
-  const float dc = net[i + total] * (-sigma_q) + xv;
-  const float den = du + scale * (dc - du);
-  const float d = (xv - den) / sigma;
-  x_out[i] = xv + d * (sigma_next - sigma);
-}
-
-// sgm img2img start (see nr_edm_img2img_start in include/neurons_amd.h): one element of sample b.  `m` is the element's latent in mode 0 and
-// the posterior mean in mode 1 (then `lv` / `e` are its logvar and the encoder draw)
-template <int MODE>
-__device__ __forceinline__ float img2img_start_one(float m, float lv, float e, float nz, float off, float z_scale, float sigma0, float den) {
-  float z = m;
-  if (MODE == 1) z = (m + expf(0.5f * fminf(fmaxf(lv, -30.f), 20.f)) * e) * z_scale;
-  return (z + (nz + off) * sigma0) / den;
-}
-
-// src = z_in (mode 0, may alias out: every thread reads its own elements before it writes them) or the moments [batch][2][nps] (mode 1).
-// VEC: four consecutive elements of the flat [batch * nps] index per thread; such a group may straddle a sample boundary when nps % 4 != 0, so the
-// sample index (offset scalar o[b], moments row) is formed per element, and the moments are loaded as vectors only when nps % 4 == 0.
-template <int MODE, bool VEC>
-__global__ __launch_bounds__(256) void edm_img2img_start_kernel(const float* src, const float* __restrict__ eps_enc,
-                                                                const float* __restrict__ noise, const float* __restrict__ offset, float* out,
-                                                                long long total, long long nps, float z_scale, float sigma0, float den,
-                                                                float offset_level) {
-  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * (VEC ? 4 : 1);
-  if (i0 >= total) return;
-  if (VEC && i0 + 4 <= total) {
-    const f32x4 nz = *(const f32x4*)(noise + i0);
-    f32x4 m, lv = {0.f, 0.f, 0.f, 0.f}, e = {0.f, 0.f, 0.f, 0.f}, off = {0.f, 0.f, 0.f, 0.f};
-    const long long b0 = i0 / nps;
-    if (MODE == 0) {
-      m = *(const f32x4*)(src + i0);
-    } else {
-      e = *(const f32x4*)(eps_enc + i0);
-      if ((nps & 3) == 0) {
-        m = *(const f32x4*)(src + i0 + b0 * nps);
-        lv = *(const f32x4*)(src + i0 + b0 * nps + nps);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const long long b = (i0 + k) / nps;
-          m[k] = src[i0 + k + b * nps];
-          lv[k] = src[i0 + k + b * nps + nps];
-        }
-      }
-    }
-    if (offset) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) off[k] = offset_level * offset[(i0 + k) / nps];
-    }
-    f32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = img2img_start_one<MODE>(m[k], lv[k], e[k], nz[k], off[k], z_scale, sigma0, den);
-    *(f32x4*)(out + i0) = o;
-    return;
-  }
-  const long long i1 = VEC ? total : i0 + 1;      // the ragged tail (VEC) or this thread's one element
-  for (long long i = i0; i < i1; ++i) {
-    const long long b = i / nps;
-    const float off = offset ? offset_level * offset[b] : 0.f;
-    const float m = MODE == 0 ? src[i] : src[i + b * nps];
-    const float lv = MODE == 0 ? 0.f : src[i + b * nps + nps];
-    out[i] = img2img_start_one<MODE>(m, lv, MODE == 0 ? 0.f : eps_enc[i], noise[i], off, z_scale, sigma0, den);
-  }
-}
-
 __global__ void add_bf16_kernel(const bf16* __restrict__ a, const bf16* __restrict__ b, bf16* __restrict__ out,
                                 long long n8) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -722,136 +474,6 @@ extern "C" int nr_launch_linear_small(const float* x, int M, int K, const bf16* 
   return 0;
 }
 
-extern "C" int nr_launch_edm_cfg_euler(const float* net, const float* x, float* x_out, long long total, float scale,
-                                       float sigma_q, float sigma, float sigma_next, hipStream_t stream) {
-  hipLaunchKernelGGL(edm_cfg_euler_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, net, x, x_out, total,
-                     scale, sigma_q, sigma, sigma_next);
-  return 0;
-}
-
-namespace {
-template <int MODE>
-void launch_img2img_start(const float* src, const float* eps_enc, const float* noise, const float* offset, float* out, long long total,
-                          long long nps, float z_scale, float sigma0, float den, float offset_level, hipStream_t stream) {
-  // 16-byte accesses need every vector-loaded base 16-byte aligned (the per-sample offset scalars are read one at a time)
-  const uintptr_t bases = (uintptr_t)src | (uintptr_t)eps_enc | (uintptr_t)noise | (uintptr_t)out;
-  if ((bases & 15) == 0) {
-    const long long threads = (total + 3) / 4;
-    hipLaunchKernelGGL((edm_img2img_start_kernel<MODE, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, src, eps_enc, noise,
-                       offset, out, total, nps, z_scale, sigma0, den, offset_level);
-  } else {
-    hipLaunchKernelGGL((edm_img2img_start_kernel<MODE, false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, eps_enc, noise,
-                       offset, out, total, nps, z_scale, sigma0, den, offset_level);
-  }
-}
-}  // namespace
-
-// mode 0: src = z_in; mode 1: src = moments, eps_enc the encoder draw.  offset == nullptr: no offset noise.  den = sqrt(1 + sigma0^2).
-extern "C" int nr_launch_edm_img2img_start(const float* src, const float* eps_enc, const float* noise, const float* offset, float* out,
-                                           long long batch, long long nps, float z_scale, float sigma0, float den, float offset_level, int mode,
-                                           hipStream_t stream) {
-  if (mode < 0 || mode > 1 || batch <= 0 || nps <= 0) return 1;
-  const long long total = batch * nps;
-  if ((total + 255) / 256 > 0x7fffffffLL) return 2;
-  if (mode == 0) launch_img2img_start<0>(src, nullptr, noise, offset, out, total, nps, z_scale, sigma0, den, offset_level, stream);
-  else launch_img2img_start<1>(src, eps_enc, noise, offset, out, total, nps, z_scale, sigma0, den, offset_level, stream);
-  return 0;
-}
-
-extern "C" int nr_launch_cfg_ddim_step(const float* eps, const float* x, float* x_out, long long total, float guidance,
-                                       int do_cfg, float sqrt_at, float sqrt_1mat, float sqrt_ap, float sqrt_1map,
-                                       hipStream_t stream) {
-  hipLaunchKernelGGL(cfg_ddim_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, eps, x, x_out,
-                     total, total, guidance, do_cfg, sqrt_at, sqrt_1mat, sqrt_ap, sqrt_1map);
-  return 0;
-}
-
-namespace {
-template <int PRED, bool CLIP, bool CLIPPED_OUT, bool STOCH>
-void launch_cfg_ddim_full(const float* eps, const float* x, const float* noise, float* x_out, float* x0_out, long long total, int do_cfg,
-                          const DdimCoef& c, hipStream_t stream) {
-  // 16-byte accesses need every base 16-byte aligned; the text half of eps starts `total` floats in, so with guidance also total % 4 == 0
-  const uintptr_t bases = (uintptr_t)eps | (uintptr_t)x | (uintptr_t)noise | (uintptr_t)x_out | (uintptr_t)x0_out;
-  const bool vec = (bases & 15) == 0 && (!do_cfg || total % 4 == 0);
-  if (vec) {
-    const long long threads = (total + 3) / 4;
-    hipLaunchKernelGGL((cfg_ddim_full_kernel<PRED, CLIP, CLIPPED_OUT, STOCH, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream,
-                       eps, x, noise, x_out, x0_out, total, total, do_cfg, c);
-  } else {
-    hipLaunchKernelGGL((cfg_ddim_full_kernel<PRED, CLIP, CLIPPED_OUT, STOCH, false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       eps, x, noise, x_out, x0_out, total, total, do_cfg, c);
-  }
-}
-template <int PRED, bool STOCH>
-void launch_cfg_ddim_full_clip(int clip, int clipped_out, const float* eps, const float* x, const float* noise, float* x_out, float* x0_out,
-                               long long total, int do_cfg, const DdimCoef& c, hipStream_t stream) {
-  if (clip && clipped_out) launch_cfg_ddim_full<PRED, true, true, STOCH>(eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);
-  else if (clip) launch_cfg_ddim_full<PRED, true, false, STOCH>(eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);
-  else if (clipped_out) launch_cfg_ddim_full<PRED, false, true, STOCH>(eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);
-  else launch_cfg_ddim_full<PRED, false, false, STOCH>(eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);
-}
-}  // namespace
-
-// pred: 0 epsilon, 1 sample, 2 v_prediction.  noise == nullptr selects the deterministic instantiations (sigma is then not read).
-extern "C" int nr_launch_cfg_ddim_full(const float* eps, const float* x, const float* noise, float* x_out, float* x0_out, long long total,
-                                       float guidance, int do_cfg, int pred, int clip, int clipped_out, float sqrt_at, float sqrt_1mat,
-                                       float sqrt_ap, float dir, float sigma, hipStream_t stream) {
-  if (pred < 0 || pred > 2 || total <= 0) return 1;
-  const DdimCoef c = {sqrt_at, sqrt_1mat, sqrt_ap, dir, sigma, guidance};
-#define NR_DDIM_PRED(P)                                                                                                              \
-  if (noise) launch_cfg_ddim_full_clip<P, true>(clip, clipped_out, eps, x, noise, x_out, x0_out, total, do_cfg, c, stream);          \
-  else launch_cfg_ddim_full_clip<P, false>(clip, clipped_out, eps, x, nullptr, x_out, x0_out, total, do_cfg, c, stream);
-  if (pred == 0) { NR_DDIM_PRED(0) } else if (pred == 1) { NR_DDIM_PRED(1) } else { NR_DDIM_PRED(2) }
-#undef NR_DDIM_PRED
-  return 0;
-}
-
-namespace {
-template <int PRED, bool HIST>
-void launch_cfg_dpmpp_step(const float* out, const float* x, const float* m1, float* x_out, float* m0_out, long long total, int do_cfg,
-                           const DpmppCoef& c, hipStream_t stream) {
-  // as launch_cfg_ddim_full: every base 16-byte aligned, and with guidance the text half of `out` (total floats in) too
-  const uintptr_t bases = (uintptr_t)out | (uintptr_t)x | (uintptr_t)m1 | (uintptr_t)x_out | (uintptr_t)m0_out;
-  const bool vec = (bases & 15) == 0 && (!do_cfg || total % 4 == 0);
-  if (vec) {
-    const long long threads = (total + 3) / 4;
-    hipLaunchKernelGGL((cfg_dpmpp_step_kernel<PRED, HIST, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, out, x, m1,
-                       x_out, m0_out, total, total, do_cfg, c);
-  } else {
-    hipLaunchKernelGGL((cfg_dpmpp_step_kernel<PRED, HIST, false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out, x, m1,
-                       x_out, m0_out, total, total, do_cfg, c);
-  }
-}
-}  // namespace
-
-// pred: 0 epsilon, 1 sample, 2 v_prediction.  m1 == nullptr selects the instantiations without the history read (c_m1 is then not used).
-extern "C" int nr_launch_cfg_dpmpp_step(const float* out, const float* x, const float* m1, float* x_out, float* m0_out, long long total,
-                                        float guidance, int do_cfg, int pred, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1,
-                                        hipStream_t stream) {
-  if (pred < 0 || pred > 2 || total <= 0) return 1;
-  if ((total + 255) / 256 > 0x7fffffffLL) return 2;
-  const DpmppCoef c = {alpha_s, sigma_s, c_x, c_m0, c_m1, guidance};
-#define NR_DPMPP_PRED(P)                                                                      \
-  if (m1) launch_cfg_dpmpp_step<P, true>(out, x, m1, x_out, m0_out, total, do_cfg, c, stream); \
-  else launch_cfg_dpmpp_step<P, false>(out, x, nullptr, x_out, m0_out, total, do_cfg, c, stream);
-  if (pred == 0) { NR_DPMPP_PRED(0) } else if (pred == 1) { NR_DPMPP_PRED(1) } else { NR_DPMPP_PRED(2) }
-#undef NR_DPMPP_PRED
-  return 0;
-}
-
-extern "C" int nr_launch_cfg_combine(const float* eps, float* out, long long total, float guidance, hipStream_t stream) {
-  hipLaunchKernelGGL(cfg_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, eps, out, total, guidance);
-  return 0;
-}
-
-extern "C" int nr_launch_prior_p_sample(const float* pred, const float* pred_null, const float* x, const float* noise, float* x_out,
-                                        float* x_start_out, long long total, float cond_scale, int mode, int clamp, float sqrt_ac, float sqrt_1mac,
-                                        float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2, float sigma, hipStream_t stream) {
-  hipLaunchKernelGGL(prior_p_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, pred, pred_null, x, noise, x_out,
-                     x_start_out, total, cond_scale, mode, clamp, sqrt_ac, sqrt_1mac, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma);
-  return 0;
-}
-
 extern "C" int nr_launch_add_bf16(const bf16* a, const bf16* b, bf16* out, long long n, hipStream_t stream) {
   if (n % 8 != 0) return 1;
   const long long n8 = n / 8;
@@ -876,7 +498,7 @@ extern "C" int nr_launch_f32_to_bf16(const float* a, bf16* out, long long n, hip
 // eight 3x3 pad-1 convolutions from the RGB condition + mask at 8x the latent resolution down to the latent grid, SiLU after every
 // conv but the last.  Three kernels:
 //   condembed_in    : the first conv (Cin = conditioning_channels + 1 <= 8, Cout = 16 / 32) straight from the fp32 NCFHW condition and
-//                     mask planes (concatenated on the fly, as conv_in_small in elementwise.hip), plain FMA, one thread per output pixel.
+//                     mask planes (concatenated on the fly, as conv_in_small above), plain FMA, one thread per output pixel.
 //                     The frames it runs on come from a map: with the identical-frame evaluation only the conditioned frames + one
 //                     representative of the rest are embedded (the engine's n_cond_frames).
 //   condembed_conv  : the small-channel convs (Cin 16 .. 256, stride 1 / 2) as an implicit GEMM on v_mfma_f32_16x16x32_bf16.  K runs

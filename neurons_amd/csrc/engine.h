@@ -5,6 +5,7 @@
 //   engine_nets.hip     the network builders (U-Net / SparseCtrl, sgm U-Net, VAE decoder / encoder, CLIP, leaf modules) and plan()
 //   engine_ops.hip      the single-op test hooks (nr_op_*)
 //   engine.hip          graph-replay runtime, the C ABI, the engine's two small kernels
+//   sampler.hip         the per-step sampler arithmetic behind nr_cfg_* / nr_edm_* / nr_prior_p_sample_step: not the engine, shares its error type and macros
 // A plan idiom that is needed twice lives in ONE helper here (WeightStore::packed / convert / stacked / w_temb_projection, nr_net::begin_plan / stage_context /
 // context_kv / linear_wb / splitk_scratch / stem / head / downsample_conv / time_embedding / frame_gather, descf); a derived weight name is spelled in engine_weights.hip only; a host-side change of these files is accepted on tools/plan_equal.sh.
 #pragma once

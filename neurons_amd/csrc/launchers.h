@@ -61,22 +61,7 @@ int nr_launch_conv_out_small(const bf16* x, int Cin, int nimg, int F, int H, int
 int nr_launch_timestep_sincos(const float* t, int M, int dim, float* out, hipStream_t stream);
 int nr_launch_linear_small(const float* x, int M, int K, const bf16* W, const float* b, int N, int in_act, int out_act,
                            float* y, const float* addend, hipStream_t stream);
-int nr_launch_edm_cfg_euler(const float* net, const float* x, float* x_out, long long total, float scale, float sigma_q,
-                            float sigma, float sigma_next, hipStream_t stream);
-int nr_launch_edm_img2img_start(const float* src, const float* eps_enc, const float* noise, const float* offset, float* out, long long batch,
-                                long long nps, float z_scale, float sigma0, float den, float offset_level, int mode, hipStream_t stream);
-int nr_launch_cfg_combine(const float* eps, float* out, long long total, float guidance, hipStream_t stream);
-int nr_launch_cfg_ddim_step(const float* eps, const float* x, float* x_out, long long total, float guidance, int do_cfg,
-                            float sqrt_at, float sqrt_1mat, float sqrt_ap, float sqrt_1map, hipStream_t stream);
-int nr_launch_cfg_ddim_full(const float* eps, const float* x, const float* noise, float* x_out, float* x0_out, long long total, float guidance,
-                            int do_cfg, int pred, int clip, int clipped_out, float sqrt_at, float sqrt_1mat, float sqrt_ap, float dir, float sigma,
-                            hipStream_t stream);
-int nr_launch_cfg_dpmpp_step(const float* out, const float* x, const float* m1, float* x_out, float* m0_out, long long total, float guidance,
-                             int do_cfg, int pred, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, hipStream_t stream);
 int nr_launch_add_bf16(const bf16* a, const bf16* b, bf16* out, long long n, hipStream_t stream);
-int nr_launch_prior_p_sample(const float* pred, const float* pred_null, const float* x, const float* noise, float* x_out, float* x_start_out,
-                             long long total, float cond_scale, int mode, int clamp, float sqrt_ac, float sqrt_1mac, float sqrt_recip_ac,
-                             float sqrt_recipm1_ac, float coef1, float coef2, float sigma, hipStream_t stream);
 int nr_launch_f32_to_bf16(const float* a, bf16* out, long long n, hipStream_t stream);
 int nr_launch_add_bf16_multi(const NrAddMulti* p, hipStream_t stream);
 int nr_launch_frame_gather(const bf16* src, bf16* dst, int B, int Fs, int Fd, long long frame_elems, const int* map, hipStream_t stream);

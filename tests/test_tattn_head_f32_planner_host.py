@@ -19,7 +19,7 @@ sys.path.insert(0, HERE)
 SAN = os.path.join(HERE, "sanitize")
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 SAN_FLAGS = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
-SRCS = "gemm gemm8p smallm lin160 rowpanel ffpanel tattn tattnw xattn xattnw norm attention elementwise engine engine_weights engine_layers engine_nets engine_ops".split()    # tests/sanitize/Makefile
+SRCS = "gemm gemm8p smallm lin160 rowpanel ffpanel tattn tattnw xattn xattnw norm attention elementwise sampler engine engine_weights engine_layers engine_nets engine_ops".split()    # tests/sanitize/Makefile
 
 
 def _write_schema(path):

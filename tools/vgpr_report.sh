@@ -6,7 +6,7 @@
 set -e
 cd "$(dirname "$0")/../neurons_amd/csrc"
 T=$(mktemp -d)
-for f in gemm rowpanel norm attention elementwise; do
+for f in gemm rowpanel norm attention elementwise sampler; do
   extra=""
   [ $f = attention ] && extra="-fno-honor-nans -mllvm -amdgpu-mfma-vgpr-form"
   hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Xclang -target-feature -Xclang -packed-fp32-ops $extra -I../../include -c $f.hip -o $T/$f.o -save-temps=obj 2>/dev/null
