@@ -222,6 +222,22 @@ nr_status nr_gaussian_sample(nr_stream stream, const float* moments_dev, const f
 nr_status nr_edm_cfg_euler_step(nr_stream stream, const float* net_dev, const float* x_dev, float* x_out_dev, int64_t n,
                                 float cfg_scale, float sigma_quantized, float sigma, float sigma_next);
 
+/* replaces Denoiser.forward's output scaling + VanillaCFG + DPMPP2MSampler.sampler_step (denoiser.py:36-39, guiders.py:28-31, sampling.py:292-347;
+ * Lu et al. 2022, DPM-Solver++ 2M in sigma space) behind the network call:
+ *   den as in nr_edm_cfg_euler_step;   t = -log sigma, h = t_next - t, r = (t - t_prev) / h;
+ *   x_out = (sigma_next / sigma) x - expm1(-h) D,   D = den (first order) | (1 + 1/(2r)) den - 1/(2r) old_denoised (second order);
+ *   denoised_out = den.
+ * The coefficients are formed here in double.  First order when old_denoised_dev is NULL or sigma_next == 0 (sampling.py:335); sigma_prev is not
+ * read then.  At sigma_next == 0 the step returns den itself: x_out == denoised_out bit for bit.
+ *   net_dev fp32 [2][n] (uncond first), x_dev / old_denoised_dev / x_out_dev / denoised_out_dev fp32 [n], n = numel(x).
+ * x_out_dev may be x_dev and denoised_out_dev may be old_denoised_dev (one history buffer, rewritten in place); no other two buffers may share
+ * elements.  No allocation; 16-byte accesses when every base is 16-byte aligned and n % 4 == 0, scalar otherwise.  NR_ERR_ARG before any launch:
+ * a null net / x / x_out / denoised_out, n <= 0, sigma <= 0, sigma_next < 0 or >= sigma, sigma_prev <= sigma on a second-order step, a
+ * non-finite scalar, overlapping buffers; NR_ERR_UNSUPPORTED for an n whose grid does not fit one launch. */
+nr_status nr_edm_cfg_dpmpp2m_step(nr_stream stream, const float* net_dev, const float* x_dev, const float* old_denoised_dev, float* x_out_dev,
+                                  float* denoised_out_dev, int64_t n, float cfg_scale, float sigma_quantized, float sigma_prev, float sigma,
+                                  float sigma_next);
+
 /* replaces the start of sgm img2img, do_img2img between the encoder and the sampler (generative_models/sgm/inference/helpers.py:276-291; with
  * skip_encode it is the start utils.unclip_recon forms, utils.py:324-335), in one launch.  Per element of sample b:
  *   z      = z_in                                                         (NR_IMG2IMG_LATENT: skip_encode, the caller holds a latent)

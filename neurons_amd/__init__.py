@@ -6,6 +6,7 @@ Host side mirrors the reference's Python interface for this path (same names, ar
   DDIMScheduler       ~ diffusers==0.11.1 DDIMScheduler (call sites pipeline_neuroclips.py:378-483)
   NeuroclipsPipeline  ~ animatediff/pipelines/pipeline_neuroclips.py:43
   sgm.NativeSGMUNet   ~ generative_models/sgm/modules/diffusionmodules/openaimodel.py:472 (unCLIP keyframes)
+  sgm.EulerEDMSampler, sgm.DPMPP2MSampler ~ generative_models/sgm/modules/diffusionmodules/sampling.py:216-220, 292-367 (the keyframe loop)
   vae.NativeVAEDecoder ~ generative_models/sgm/modules/diffusionmodules/model.py:612 Decoder (= AutoencoderKL.decode)
   DPMSolverMultistepScheduler ~ diffusers==0.11.1 DPMSolverMultistepScheduler (one of the six classes pipeline_neuroclips.py:20-25 accepts)
 All arithmetic of the two networks runs in libneurons_amd.so (hand-written HIP for gfx950) behind the

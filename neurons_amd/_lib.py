@@ -96,6 +96,7 @@ SYMBOLS = {
     "nr_vae_encode": (_I32, [_VP, _VP, _VP, C.c_float, C.c_float, _VP]),
     "nr_gaussian_sample": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, C.c_float]),
     "nr_edm_cfg_euler_step": (_I32, [_VP, _VP, _VP, _VP, _I64, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "nr_edm_cfg_dpmpp2m_step": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "nr_edm_img2img_start": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I64, C.c_float, C.c_float, C.c_float, _I32]),
     "nr_prior_p_sample_step": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, C.c_float, _I32, _I32, C.c_double, C.c_double, C.c_double]),
     "nr_cfg_ddim_step": (_I32, [_VP, _VP, _VP, _VP, _I64, C.c_float, _I32, C.c_double, C.c_double]),

@@ -1,9 +1,10 @@
-// Everything between "the network has produced its output" and "the next latent": the per-step sampler arithmetic behind seven C ABI entry points
+// Everything between "the network has produced its output" and "the next latent": the per-step sampler arithmetic behind eight C ABI entry points
 // (include/neurons_amd.h), fp32 on flat arrays.
 //   nr_cfg_combine          classifier-free guidance alone
 //   nr_cfg_ddim_step[_ex]   guidance + one DDIM update (the default rule is the <epsilon, no clip, no re-derive, no noise> instantiation of the full one)
 //   nr_cfg_dpmpp_step       guidance + one DPM-Solver++ multistep update
 //   nr_edm_cfg_euler_step   EDM eps-scaling + guidance + Euler step
+//   nr_edm_cfg_dpmpp2m_step EDM eps-scaling + guidance + DPM-Solver++ 2M step in sigma space
 //   nr_edm_img2img_start    the noised start latent of sgm img2img
 //   nr_prior_p_sample_step  one ancestral DDPM step of the diffusion prior
 // A rule is a Step: a struct of pointers and coefficients with run<W>(i, n), its arithmetic on elements i .. i+W-1, written once for W = 4 and W = 1.
@@ -221,6 +222,30 @@ struct EdmEulerStep {
   }
 };
 
+// EDM eps-scaling + vanilla CFG + one DPM-Solver++ 2M update in sigma space (see nr_edm_cfg_dpmpp2m_step in include/neurons_amd.h): `den` as in
+// EdmEulerStep, then x_out = c_x x + c_d den [+ c_o old] (HIST) with the coefficients the entry point forms in double.  x / x_out and old / den_out
+// may be the same buffer (a thread reads its elements before it writes them): those four carry no __restrict__.
+template <bool HIST>
+struct EdmDpmpp2mStep {
+  const float* __restrict__ net; const float* x; const float* old; float* x_out; float* den_out;
+  float scale, sigma_q, c_x, c_d, c_o;
+  template <int W> __device__ __forceinline__ void run(long long i, long long n) const {
+    const Lanes<W> xv = ld<W>(x + i), nu = ld<W>(net + i), nc = ld<W>(net + i + n);
+    Lanes<W> h = {}, o, p;
+    if (HIST) h = ld<W>(old + i);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float du = nu[k] * (-sigma_q) + xv[k];
+      const float dc = nc[k] * (-sigma_q) + xv[k];
+      p[k] = du + scale * (dc - du);
+      o[k] = fmaf(c_x, xv[k], c_d * p[k]);      // the fma spelled out as in DpmppStep; c_x = 0, c_d = 1 (sigma_next = 0) gives den itself
+      if (HIST) o[k] += c_o * h[k];
+    }
+    st(x_out + i, o);
+    st(den_out + i, p);
+  }
+};
+
 // sgm img2img start (see nr_edm_img2img_start in include/neurons_amd.h): one element of sample b.  `m` is the element's latent in mode 0 and
 // the posterior mean in mode 1 (then `lv` / `e` are its logvar and the encoder draw)
 template <int MODE>
@@ -351,6 +376,51 @@ extern "C" nr_status nr_edm_cfg_euler_step(nr_stream stream, const float* net_de
   if (!net_dev || !x_dev || !x_out_dev || n <= 0 || sigma <= 0.f) throw NrError(NR_ERR_ARG, "bad argument");
   LAUNCH_OK(launch_step(EdmEulerStep{net_dev, x_dev, x_out_dev, cfg_scale, sigma_quantized, sigma, sigma_next}, n, {net_dev, x_dev, x_out_dev},
                         n % 4 == 0, (hipStream_t)stream));
+  NR_CATCH
+}
+
+extern "C" nr_status nr_edm_cfg_dpmpp2m_step(nr_stream stream, const float* net_dev, const float* x_dev, const float* old_denoised_dev,
+                                             float* x_out_dev, float* denoised_out_dev, int64_t n, float cfg_scale, float sigma_quantized,
+                                             float sigma_prev, float sigma, float sigma_next) {
+  NR_TRY
+  if (!net_dev || !x_dev || !x_out_dev || !denoised_out_dev) throw NrError(NR_ERR_ARG, "null tensor argument");
+  if (n <= 0) throw NrError(NR_ERR_ARG, "n must be positive");
+  // first order: no history yet, or the last step to sigma = 0 (sampling.py:335); sigma_prev is not read then
+  const bool hist = old_denoised_dev && sigma_next != 0.f;
+  for (float v : {cfg_scale, sigma_quantized, sigma, sigma_next, hist ? sigma_prev : 0.f})
+    if (!std::isfinite(v)) throw NrError(NR_ERR_ARG, "non-finite scalar argument");
+  if (!(sigma > 0.f)) throw NrError(NR_ERR_ARG, "sigma must be > 0");
+  if (!(sigma_next >= 0.f)) throw NrError(NR_ERR_ARG, "sigma_next must be >= 0");
+  if (!(sigma_next < sigma)) throw NrError(NR_ERR_ARG, "sigma_next must be below sigma");
+  if (hist && !(sigma_prev > sigma)) throw NrError(NR_ERR_ARG, "sigma_prev must be above sigma");
+  if ((n + 255) / 256 > 0x7fffffffLL) throw NrError(NR_ERR_UNSUPPORTED, "n too large for one launch");      // launch_step's limit, before 2 * n below
+  // two buffers that share elements without being the same buffer: a thread would read what another one wrote
+  const auto overlap = [](const float* a, long long na, const float* b, long long nb) { return a && b && a < b + nb && b < a + na; };
+  if (overlap(denoised_out_dev, n, x_dev, n) || overlap(denoised_out_dev, n, x_out_dev, n))
+    throw NrError(NR_ERR_ARG, "denoised_out_dev must not alias x_dev / x_out_dev");
+  if (overlap(net_dev, 2 * n, x_out_dev, n) || overlap(net_dev, 2 * n, denoised_out_dev, n))
+    throw NrError(NR_ERR_ARG, "net_dev must not alias an output");
+  if ((x_out_dev != x_dev && overlap(x_out_dev, n, x_dev, n)) ||
+      (denoised_out_dev != old_denoised_dev && overlap(denoised_out_dev, n, old_denoised_dev, n)) || overlap(x_out_dev, n, old_denoised_dev, n))
+    throw NrError(NR_ERR_ARG, "x_out_dev / denoised_out_dev may alias x_dev / old_denoised_dev only as the same buffer, not partly");
+  // t = -log sigma, h = t' - t;  x' = (sigma'/sigma) x - expm1(-h) D,  D = den (first order) | (1 + 1/(2r)) den - 1/(2r) old,  r = (t - t_prev) / h
+  double c_x = 0.0, c_d = 1.0, c_o = 0.0;      // sigma_next = 0: h = +inf, the step returns den
+  if (sigma_next > 0.f) {
+    const double h = std::log((double)sigma) - std::log((double)sigma_next);
+    const double em = std::expm1(-h);
+    c_x = (double)sigma_next / (double)sigma;
+    c_d = -em;
+    if (hist) {
+      const double r = (std::log((double)sigma_prev) - std::log((double)sigma)) / h;
+      c_d = -em * (1.0 + 1.0 / (2.0 * r));
+      c_o = em / (2.0 * r);
+    }
+  }
+  const float* old = hist ? old_denoised_dev : nullptr;
+  LAUNCH_OK(dispatch([&](auto H) {
+    return launch_step(EdmDpmpp2mStep<H() != 0>{net_dev, x_dev, old, x_out_dev, denoised_out_dev, cfg_scale, sigma_quantized, (float)c_x, (float)c_d,
+                                                (float)c_o}, n, {net_dev, x_dev, old, x_out_dev, denoised_out_dev}, n % 4 == 0, (hipStream_t)stream);
+  }, Choice<2>{hist}));
   NR_CATCH
 }
 

@@ -8,6 +8,8 @@
   EulerEDMSampler          ~ sampling.py:41-62,98-135,216-220 with VanillaCFG guiders.py:24-42: ``sampler(denoiser_fn, x, cond=, uc=)``;
                              on a native denoiser the per-element update (c_out/c_skip, CFG, to_d, Euler step) is the HIP kernel
                              nr_edm_cfg_euler_step; a foreign closure gets the reference's loop, statement for statement
+  DPMPP2MSampler           ~ sampling.py:292-367 with VanillaCFG: the second-order multistep sampler on the same loop and table, opt-in; its
+                             per-element update is the HIP kernel nr_edm_cfg_dpmpp2m_step (coefficients: dpmpp2m_coefficients)
   NativeDiffusionEngine    ~ sgm/models/diffusion.py DiffusionEngine, the attributes utils.unclip_recon (utils.py:302-350) and
                              recon_keyframe_neurons_enhance.py:300-324 touch: the drop-in boundary of the keyframe path
   unclip_sample            ~ the sampling part of utils.unclip_recon (:308-340), on explicit z / noise tensors; ``init`` / ``strength``
@@ -18,7 +20,7 @@
 """
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -433,31 +435,16 @@ def _closure_engine(fn):
         return None
 
 
-class EulerEDMSampler:
-    """``EulerEDMSampler`` (sampling.py:216-220; ``EDMSampler.__call__`` :114-135, ``sampler_step`` :98-112 with s_churn = 0 =>
-    gamma = 0; ``prepare_sampling_loop`` :41-57) + ``VanillaCFG``.  Call it as the reference does::
+class _GuidedSampler:
+    """``BaseDiffusionSampler`` (sampling.py:21-62) + ``VanillaCFG``, and what the native samplers share on top of it: the recognition of a native
+    denoiser and the entry of the fused path.  A subclass supplies ``_fused_loop`` (HIP) and ``_generic_loop`` (the reference's loop in torch)."""
 
-        samples = sampler(denoiser, x, cond=c, uc=uc)        # denoiser(x, sigma, c) -> denoised      (utils.py:337-340)
-
-    ``denoiser`` may be
-      * the closure utils.unclip_recon builds around a ``NativeDiffusionEngine`` (recognised by its code: exactly
-        ``engine.denoiser(engine.model, x, sigma, c)``, nothing more), ``engine.native_denoiser()`` (the explicit opt-in), a
-        ``NativeDiffusionEngine`` / ``NativeOpenAIWrapper`` / ``NativeSGMUNet``: the FUSED path — the network evaluation with ``c_in`` folded
-        into its boundary conv, then ONE HIP kernel (nr_edm_cfg_euler_step) for c_out / c_skip, CFG combine, to_d and the Euler update;
-      * any other callable ``denoiser(x, sigma, c)``: the generic path, statement for statement the reference's loop (guider.prepare_inputs
-        -> denoiser -> guider -> to_d -> euler_step) on torch tensors.  A foreign closure that routes into a native network still runs
-        every network FLOP in HIP; only the per-step scalars differ in where they are applied."""
-
-    def __init__(self, num_steps=38, scale=5.0, discretization: Optional[LegacyDDPMDiscretization] = None, s_churn=0.0, s_tmin=0.0,
-                 s_tmax=float("inf"), s_noise=1.0, verbose=False, device="cuda"):
-        if s_churn != 0.0:
-            raise NotImplementedError("s_churn != 0 (stochastic churn) is not on the NEURONS path (unclip6.yaml sampler_config)")
+    def __init__(self, num_steps, scale, discretization, verbose, device):
         self.num_steps = num_steps
         self.guider = VanillaCFG(scale)
         self.discretization = discretization or LegacyDDPMDiscretization()
         # host scalars of the fused path: the 1000-entry table the network is evaluated on, never an img2img-pruned one
         self.denoiser = DiscreteDenoiser(discretization=_unwrapped_discretization(self.discretization))
-        self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = s_churn, s_tmin, s_tmax, s_noise
         self.verbose = verbose
         self.device = device
         self._engine = None          # set by NativeDiffusionEngine: lets the sampler recognise the engine's own denoiser closure
@@ -498,17 +485,43 @@ class EulerEDMSampler:
         return None
 
     def __call__(self, denoiser, x, cond: Dict[str, torch.Tensor], uc: Optional[Dict[str, torch.Tensor]] = None,
-                 num_steps: Optional[int] = None):
+                 num_steps: Optional[int] = None, **loop_args):
         network = self._native_network(denoiser)
         if network is None:            # a foreign denoiser: the reference's loop around it, on whatever device its tensors live
-            return self._generic_loop(denoiser, x, cond, uc, num_steps)
+            return self._generic_loop(denoiser, x, cond, uc, num_steps, **loop_args)
         if not x.is_cuda:
-            raise RuntimeError("EulerEDMSampler runs the HIP kernels: CUDA (ROCm) tensors required; there is no CPU fallback")
+            raise RuntimeError(f"{type(self).__name__} runs the HIP kernels: CUDA (ROCm) tensors required; there is no CPU fallback")
         uc = cond if uc is None else uc
         sigmas = self.discretization(self.num_steps if num_steps is None else num_steps)
         x = (x * torch.sqrt(1.0 + sigmas[0] ** 2.0).to(x.device)).to(torch.float32).contiguous()       # sampling.py:52
         ctx = torch.cat((uc["crossattn"], cond["crossattn"]), 0)                                     # guiders.py:38 (uc first)
         vec = torch.cat((uc["vector"], cond["vector"]), 0)
+        return self._fused_loop(network, x, sigmas, ctx, vec, **loop_args)
+
+
+class EulerEDMSampler(_GuidedSampler):
+    """``EulerEDMSampler`` (sampling.py:216-220; ``EDMSampler.__call__`` :114-135, ``sampler_step`` :98-112 with s_churn = 0 =>
+    gamma = 0; ``prepare_sampling_loop`` :41-57) + ``VanillaCFG``.  Call it as the reference does::
+
+        samples = sampler(denoiser, x, cond=c, uc=uc)        # denoiser(x, sigma, c) -> denoised      (utils.py:337-340)
+
+    ``denoiser`` may be
+      * the closure utils.unclip_recon builds around a ``NativeDiffusionEngine`` (recognised by its code: exactly
+        ``engine.denoiser(engine.model, x, sigma, c)``, nothing more), ``engine.native_denoiser()`` (the explicit opt-in), a
+        ``NativeDiffusionEngine`` / ``NativeOpenAIWrapper`` / ``NativeSGMUNet``: the FUSED path — the network evaluation with ``c_in`` folded
+        into its boundary conv, then ONE HIP kernel (nr_edm_cfg_euler_step) for c_out / c_skip, CFG combine, to_d and the Euler update;
+      * any other callable ``denoiser(x, sigma, c)``: the generic path, statement for statement the reference's loop (guider.prepare_inputs
+        -> denoiser -> guider -> to_d -> euler_step) on torch tensors.  A foreign closure that routes into a native network still runs
+        every network FLOP in HIP; only the per-step scalars differ in where they are applied."""
+
+    def __init__(self, num_steps=38, scale=5.0, discretization: Optional[LegacyDDPMDiscretization] = None, s_churn=0.0, s_tmin=0.0,
+                 s_tmax=float("inf"), s_noise=1.0, verbose=False, device="cuda"):
+        if s_churn != 0.0:
+            raise NotImplementedError("s_churn != 0 (stochastic churn) is not on the NEURONS path (unclip6.yaml sampler_config)")
+        super().__init__(num_steps, scale, discretization, verbose, device)
+        self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = s_churn, s_tmin, s_tmax, s_noise
+
+    def _fused_loop(self, network, x, sigmas, ctx, vec):
         lib = _lib.load()
         n = x.numel()
         for i in range(len(sigmas) - 1):
@@ -533,6 +546,104 @@ class EulerEDMSampler:
         return x
 
 
+def dpmpp2m_coefficients(sigma_prev: Optional[float], sigma: float, sigma_next: float):
+    """The doubles ``nr_edm_cfg_dpmpp2m_step`` forms from its (fp32) sigmas: ``x_out = c_x x + c_d den + c_o old`` is one step of
+    ``DPMPP2MSampler`` (sampling.py:292-347).  With t = -log sigma, h = t_next - t, r = (t - t_prev) / h::
+
+        c_x = sigma_next / sigma        c_d = -expm1(-h) (1 + 1 / (2 r))        c_o = expm1(-h) / (2 r)
+
+    ``sigma_prev = None`` (the first step of a table) or ``sigma_next == 0`` (its last: sampling.py:335) is the first-order step: c_d = -expm1(-h),
+    c_o = None.  At ``sigma_next == 0`` h is +inf: (0, 1, None) exactly, the step returns the denoised estimate."""
+    import math
+    sigma, sigma_next = float(sigma), float(sigma_next)
+    if sigma_next == 0.0:
+        return 0.0, 1.0, None
+    h = math.log(sigma) - math.log(sigma_next)
+    em = math.expm1(-h)
+    c_x = sigma_next / sigma
+    if sigma_prev is None:
+        return c_x, -em, None
+    r = (math.log(float(sigma_prev)) - math.log(sigma)) / h
+    return c_x, -em * (1.0 + 1.0 / (2.0 * r)), em / (2.0 * r)
+
+
+class DPMPP2MSampler(_GuidedSampler):
+    """``DPMPP2MSampler`` (sampling.py:292-367; Lu et al. 2022, DPM-Solver++ 2M in sigma space) + ``VanillaCFG``: the second-order multistep
+    sampler of the keyframe loop.  One network evaluation per step, as Euler; the previous step's denoised estimate is the history.  Same sigma
+    table as ``EulerEDMSampler``, same call, same recognition of a native denoiser (see there):
+      * FUSED path: per step the network evaluation with ``c_in`` folded into its boundary conv, then ONE HIP kernel (nr_edm_cfg_dpmpp2m_step) for
+        c_out / c_skip, CFG combine and the multistep update.  The history is one fp32 buffer per call, rewritten in place; the first step of any
+        table (a pruned one included) and the step to sigma = 0 are first order;
+      * generic path: the reference's loop, statement for statement, its fp32 log / exp coefficient arithmetic included.
+    Opt-in (``NativeDiffusionEngine(sampler="dpmpp_2m")``): how few steps keep keyframe quality is a property of the checkpoint, see DESIGN section 7.
+    ``record``: a list that receives ``(x, denoised)`` clones after every step."""
+
+    def __init__(self, num_steps=38, scale=5.0, discretization: Optional[LegacyDDPMDiscretization] = None, verbose=False, device="cuda"):
+        super().__init__(num_steps, scale, discretization, verbose, device)
+
+    def _fused_loop(self, network, x, sigmas, ctx, vec, record: Optional[list] = None):
+        lib = _lib.load()
+        n = x.numel()
+        old = torch.empty_like(x)                     # the history: written by every step, read from the second on
+        for i in range(len(sigmas) - 1):
+            s_prev, s, s_next = (float(sigmas[i - 1]) if i else 0.0), float(sigmas[i]), float(sigmas[i + 1])
+            sq, c_in, idx = self.denoiser.scalars(s)
+            xin = torch.cat([x] * 2)                                                                  # guiders.py:42
+            net = network(xin, float(idx), context=ctx, y=vec, in_scale=c_in)
+            # x is this call's own tensor (the product with sqrt(1 + sigma0^2)): updated in place, as the history is
+            _lib.check(lib.nr_edm_cfg_dpmpp2m_step(torch.cuda.current_stream().cuda_stream, net.data_ptr(), x.data_ptr(),
+                                                   old.data_ptr() if i else None, x.data_ptr(), old.data_ptr(), n, float(self.guider.scale),
+                                                   sq, s_prev, s, s_next))
+            if record is not None:
+                record.append((x.clone(), old.clone()))
+        return x
+
+    # ---- the reference's statements (sampling.py:293-347), on torch tensors ----
+    def get_variables(self, sigma, next_sigma, previous_sigma=None):
+        t, t_next = [s.log().neg() for s in (sigma, next_sigma)]                                      # to_neg_log_sigma, sampling_utils.py:38-39
+        h = t_next - t
+        if previous_sigma is not None:
+            h_last = t - previous_sigma.log().neg()
+            r = h_last / h
+            return h, r, t, t_next
+        return h, None, t, t_next
+
+    def get_mult(self, h, r, t, t_next, previous_sigma):
+        mult1 = t_next.neg().exp() / t.neg().exp()                                                    # to_sigma, sampling_utils.py:42-43
+        mult2 = (-h).expm1()
+        if previous_sigma is not None:
+            mult3 = 1 + 1 / (2 * r)
+            mult4 = 1 / (2 * r)
+            return mult1, mult2, mult3, mult4
+        return mult1, mult2
+
+    def sampler_step(self, old_denoised, previous_sigma, sigma, next_sigma, denoiser, x, cond, uc=None):
+        denoised = denoiser(*self.guider.prepare_inputs(x, sigma, cond, uc))                          # sampling.py:59-62
+        denoised = self.guider(denoised, sigma)
+        h, r, t, t_next = self.get_variables(sigma, next_sigma, previous_sigma)
+        mult = [append_dims(m, x.ndim) for m in self.get_mult(h, r, t, t_next, previous_sigma)]
+        x_standard = mult[0] * x - mult[1] * denoised
+        if old_denoised is None or torch.sum(next_sigma) < 1e-14:
+            return x_standard, denoised                                                               # the first step, or all noise levels 0
+        denoised_d = mult[2] * denoised - mult[3] * old_denoised
+        x_advanced = mult[0] * x - mult[1] * denoised_d
+        x = torch.where(append_dims(next_sigma, x.ndim) > 0.0, x_advanced, x_standard)
+        return x, denoised
+
+    def _generic_loop(self, denoiser, x, cond, uc, num_steps, record: Optional[list] = None):
+        x, s_in, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x.to(torch.float32), cond, uc, num_steps)
+        old_denoised = None
+        for i in range(num_sigmas - 1):
+            x, old_denoised = self.sampler_step(old_denoised, None if i == 0 else s_in * sigmas[i - 1], s_in * sigmas[i], s_in * sigmas[i + 1],
+                                                denoiser, x, cond, uc=uc)
+            if record is not None:
+                record.append((x.clone(), old_denoised.clone()))
+        return x
+
+
+_SAMPLERS = {"euler_edm": EulerEDMSampler, "dpmpp_2m": DPMPP2MSampler}      # NativeDiffusionEngine(sampler=)
+
+
 class NativeDiffusionEngine:
     """The surface of ``sgm.models.diffusion.DiffusionEngine`` that the keyframe script and ``utils.unclip_recon`` touch
     (recon_keyframe_neurons_enhance.py:300-324,458-462; utils.py:302-350), backed by libneurons_amd.so:
@@ -540,6 +651,7 @@ class NativeDiffusionEngine:
         .model                 NativeOpenAIWrapper(NativeSGMUNet)        model(x, t, c_dict)                        wrappers.py:23-34
         .denoiser              DiscreteDenoiser (EpsScaling)             denoiser(model, x, sigma, c)               denoiser.py:23-75
         .sampler               EulerEDMSampler + VanillaCFG              sampler(denoiser_fn, x, cond=, uc=); .discretization(n); .num_steps
+                               (``sampler="dpmpp_2m"``: DPMPP2MSampler, opt-in; a sampler object may also be assigned to ``.sampler``)
         .first_stage_model     NativeVAEDecoder                          decode_first_stage(z)                      diffusion.py:118-135
         .first_stage_encoder   NativeVAEEncoder (same ddconfig)          encode_first_stage(x[, noise])             diffusion.py:137-150
         .ema_scope()           no-op context (use_ema is False in unclip6.yaml; diffusion.py:198-210)
@@ -551,8 +663,11 @@ class NativeDiffusionEngine:
     ``denoiser.sigmas`` (regenerated), ``first_stage_model.loss.*`` and ``model_ema.*`` are ignored."""
 
     def __init__(self, network_config: Optional[SGMUNetConfig] = None, first_stage_config=None, num_steps: int = 38, scale: float = 5.0,
-                 scale_factor: float = 0.18215, disable_first_stage_autocast: bool = True, use_ema: bool = False, **ignored):
+                 scale_factor: float = 0.18215, disable_first_stage_autocast: bool = True, use_ema: bool = False, sampler: str = "euler_edm",
+                 **ignored):
         from .vae import NativeVAEDecoder, NativeVAEEncoder, VAEDecoderConfig
+        if sampler not in _SAMPLERS:
+            raise ValueError(f"sampler must be one of {sorted(_SAMPLERS)}, got {sampler!r}")
         if use_ema:
             raise NotImplementedError("use_ema: inference checkpoints carry the EMA weights already (unclip6.yaml has no EMA)")
         self.model = NativeOpenAIWrapper(NativeSGMUNet(network_config or SGMUNetConfig()))
@@ -560,7 +675,7 @@ class NativeDiffusionEngine:
         self.first_stage_encoder = NativeVAEEncoder(self.first_stage_model.config)       # same ddconfig as the decoder
         disc = LegacyDDPMDiscretization()
         self.denoiser = DiscreteDenoiser(discretization=disc)
-        self.sampler = EulerEDMSampler(num_steps=num_steps, scale=scale, discretization=disc)
+        self.sampler = _SAMPLERS[sampler](num_steps=num_steps, scale=scale, discretization=disc)
         self.sampler._engine = self
         self.scale_factor = scale_factor
         self.disable_first_stage_autocast = disable_first_stage_autocast
@@ -709,7 +824,8 @@ def edm_img2img_start(noise, sigma0: float, z: Optional[torch.Tensor] = None, mo
 
 
 def _img2img_latents(img, model, sampler, denoiser, c, uc, noise, offset_noise_level, offset, skip_encode, enc_noise):
-    """helpers.py:272-296: the start (one HIP launch) and the sampler.  ``model`` is only needed to encode."""
+    """helpers.py:272-296: the start (one HIP launch) and the sampler (either class: only .discretization, .num_steps and the call are touched).
+    ``model`` is only needed to encode."""
     if skip_encode:
         start = dict(z=img)
     else:
@@ -728,13 +844,13 @@ def _img2img_latents(img, model, sampler, denoiser, c, uc, noise, offset_noise_l
 
 
 @torch.no_grad()
-def do_img2img(img, model: NativeDiffusionEngine, sampler: EulerEDMSampler, c: Dict[str, torch.Tensor], uc: Dict[str, torch.Tensor],
+def do_img2img(img, model: NativeDiffusionEngine, sampler: Union[EulerEDMSampler, DPMPP2MSampler], c: Dict[str, torch.Tensor], uc: Dict[str, torch.Tensor],
                noise: torch.Tensor, offset_noise_level: float = 0.0, offset: Optional[torch.Tensor] = None, skip_encode: bool = False,
                return_latents: bool = False, enc_noise: Optional[torch.Tensor] = None, filter=None):
     """``do_img2img`` (sgm/inference/helpers.py:243-305) on explicit conditioning and explicit draws.  The reference builds ``c`` / ``uc`` from
     ``model.conditioner`` (:256-270); that stays PyTorch and the caller's, so the dicts (``crossattn`` / ``vector``, one row per sample) come in
     as arguments.  ``img``: [n][3][H][W] in [-1, 1], or with ``skip_encode`` a latent [n][4][h][w].  ``noise`` [n][4][h][w] is the
-    ``randn_like(z)`` of :276, ``offset`` (n,) the per-sample draw of :282-284 (read when ``offset_noise_level > 0``), ``enc_noise`` the posterior
+    ``randn_like(z)`` of :276, ``sampler`` an EulerEDMSampler or a DPMPP2MSampler, ``offset`` (n,) the per-sample draw of :282-284 (read when ``offset_noise_level > 0``), ``enc_noise`` the posterior
     draw inside ``encode_first_stage`` (``None``: drawn as the reference draws it).  Strength is the sampler's: give it
     ``Img2ImgDiscretizationWrapper(discretization, strength)`` as its discretization.  Returns images in [0, 1] (and the latents)."""
     samples_z = _img2img_latents(img, model, sampler, model.native_denoiser(), c, uc, noise, offset_noise_level, offset, skip_encode, enc_noise)
@@ -747,13 +863,13 @@ def do_img2img(img, model: NativeDiffusionEngine, sampler: EulerEDMSampler, c: D
     return samples
 
 
-def unclip_sample(network, tokens, vector_suffix, z, noise, uc_tokens, sampler: EulerEDMSampler,
+def unclip_sample(network, tokens, vector_suffix, z, noise, uc_tokens, sampler: Union[EulerEDMSampler, DPMPP2MSampler],
                   offset_noise: Optional[torch.Tensor] = None, offset_noise_level: float = 0.04, init: Optional[torch.Tensor] = None,
                   strength: float = 1.0, enc_noise: Optional[torch.Tensor] = None):
     """Sampling part of ``utils.unclip_recon`` (utils.py:308-340) on explicit tensors: ``tokens`` (1,256,1664) prior
     tokens x key-object mask, ``vector_suffix`` (1,1024), starting ``z`` and ``noise`` (n,4,h,w), ``uc_tokens`` the
     random unconditional tokens (:318), ``offset_noise`` (n,) the per-sample offset draw (:328-331).  ``network``: a NativeSGMUNet or
-    anything else ``EulerEDMSampler.__call__`` accepts as its denoiser.
+    anything else ``EulerEDMSampler.__call__`` accepts as its denoiser; ``sampler``: an EulerEDMSampler or a DPMPP2MSampler.
 
     img2img ("can change to VAE outputs of initial image for img2img", utils.py:308): ``init`` replaces ``z`` (which may then be None), one per
     sample: a latent (n,4,h,w), or an image (n,3,8h,8w) in [-1, 1], which ``network``, then a NativeDiffusionEngine, encodes (``enc_noise``: its
