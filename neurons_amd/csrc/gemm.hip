@@ -21,7 +21,7 @@
 //     each slice writes an fp32 slab, a second kernel sums the slabs in fixed order (deterministic, no
 //     atomics) and applies the epilogue.
 #include "launchers.h"
-#include "device_prims.h"
+#include "igemm_blocks.h"
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
@@ -80,34 +80,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   int bid = nr_xcd_bid();                         // the n-tiles that share one A row-panel share an L2
   const int slice = splitk > 1 ? nr_fdiv_small(bid, ntn * ntm) : 0;
   bid -= slice * ntn * ntm;
-  // tile order inside an XCD's range: the operand that is re-used by neighbouring tiles should be the BIG
-  // one.  m_fast: neighbours share a weight panel (weight-heavy 4x4 / 8x8 levels); else an activation panel.
   int bm, bn;
-  if (m_fast >= 2) {
-    // grouped order (m_fast = G >= 2): bands of G m-tiles, inside a band the m index runs fastest, then n.  The tiles that are in
-    // flight together on an XCD (2 per CU) then form a G x (64 / G) block: both operand panels of the block fit its 4 MiB L2, where
-    // a plain n-fastest walk streams the whole weight matrix past the L2 once per m-tile row (W > L2: GEGLU / q|k|v at 16x16, 8x8)
-    const int G = m_fast;
-    const int band = nr_fdiv_small(bid, G * ntn);
-    const int first = band * G;
-    const int gsz = min(G, ntm - first);
-    const int r = bid - band * G * ntn;
-    bn = nr_fdiv_small(r, gsz);
-    bm = first + r - bn * gsz;
-  } else if (m_fast) { bn = nr_fdiv_small(bid, ntm); bm = bid - bn * ntm; } else { bm = nr_fdiv_small(bid, ntn); bn = bid - bm * ntn; }
+  igemm_tile_order(bid, m_fast, ntm, ntn, bm, bn);
   // PH: row tiles [phase * ntmp, (phase + 1) * ntmp) are one phase's, so in every tile order the tiles that share a weight matrix stay neighbours
   const int phase = PH ? nr_fdiv_small(bm, ntmp) : 0;
   if constexpr (PH) bm -= phase * ntmp;
   const int ph_py = phase >> 1, ph_px = phase & 1;
   const int m0 = bm * BM, n0 = bn * BN;
-  // PH: output row (pixel index) of row r of this tile's phase
-  auto ph_out_row = [&](int r) {
-    const int hw = p.H * p.W;
-    const int n = nr_fdiv_small(r, hw);
-    const int q = r - n * hw;
-    const int y = nr_fdiv_small(q, p.W), x = q - y * p.W;
-    return (n * p.OH + 2 * y + ph_py) * p.OW + 2 * x + ph_px;
-  };
   NR_STAMP_AT(40);
   const int lr = lane >> 3;                 // row within the 8-row group
   const int lp = lane & 7;                  // physical 16-B chunk
@@ -125,16 +104,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
     const int mm = a_ok[j] ? m : 0;
     if constexpr (PH) {      // (image, y, x) of the SOURCE pixel
       const int hw = p.H * p.W;
-      const int n = nr_fdiv_small(mm, hw);
-      const int r = mm - n * hw;
-      a_pix[j] = n; a_oy[j] = nr_fdiv_small(r, p.W); a_ox[j] = r - a_oy[j] * p.W;
+      igemm_pixel_decode(mm, hw, p.W, a_pix[j], a_oy[j], a_ox[j]);
     } else if (p.ksize == 1) {
       a_pix[j] = mm; a_oy[j] = 0; a_ox[j] = 0;
     } else {
       const int ohw = p.OH * p.OW;
-      const int n = nr_fdiv_small(mm, ohw);
-      const int r = mm - n * ohw;
-      a_pix[j] = n; a_oy[j] = nr_fdiv_small(r, p.OW); a_ox[j] = r - a_oy[j] * p.OW;
+      igemm_pixel_decode(mm, ohw, p.OW, a_pix[j], a_oy[j], a_ox[j]);
     }
   }
   const bf16* zsrc = (const bf16*)nr_zero16;
@@ -147,7 +122,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   if (tap_inner) {
 #pragma unroll
     for (int j = 0; j < GA; ++j) {
-      a_cbyte[j] = (((long long)a_pix[j] * p.H + a_oy[j]) * p.W + a_ox[j]) * p.lda0 * (long long)sizeof(bf16);
+      a_cbyte[j] = igemm_pixel_byte(a_pix[j], a_oy[j], a_ox[j], p.H, p.W, p.lda0);
       unsigned msk = 0;
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
@@ -187,8 +162,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   }
   // tap-inner: every k-tile is another tap of the same 64 channels: pointer = centre + (wave-uniform) tap offset, or the zero word
   auto setup_rows_tap_inner = [&]() {
-    const int ky = st_tap / 3, kx = st_tap - ky * 3;
-    const long long delta = ((long long)(ky - 1) * p.W + (kx - 1)) * p.lda0 * (long long)sizeof(bf16);
+    const long long delta = igemm_tap_delta(st_tap, p.W, p.lda0);
     const char* base = reinterpret_cast<const char*>(p.a0 + st_c + lchunk) + delta;
 #pragma unroll
     for (int j = 0; j < GA; ++j) {
@@ -255,8 +229,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
 #pragma unroll
     for (int j = 0; j < GB; ++j) wp[j] += winc[j];
     if (tap_inner) {
-      st_tap += 1;
-      if (st_tap == 9) { st_tap = 0; st_c += BK; }
+      igemm_k_next_tap_inner(st_tap, st_c);
       setup_rows_tap_inner();
       return;
     }
@@ -306,12 +279,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       const int row = wn * WN + i * 16 + fr;
-      wf[0][i] = *(const bf16x8*)(sB + row * BK + ((fg ^ (row & 7)) << 3));
+      wf[0][i] = igemm_frag(sB, row, fg);
     }
 #pragma unroll
     for (int j = 0; j < MT; ++j) {
       const int row = wm * WM + j * 16 + fr;
-      xf[0][j] = *(const bf16x8*)(sA + row * BK + ((fg ^ (row & 7)) << 3));
+      xf[0][j] = igemm_frag(sA, row, fg);
     }
     __builtin_amdgcn_sched_barrier(0);
     {
@@ -323,12 +296,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       const int row = wn * WN + i * 16 + fr;
-      wf[1][i] = *(const bf16x8*)(sB + row * BK + (((4 + fg) ^ (row & 7)) << 3));
+      wf[1][i] = igemm_frag(sB, row, 4 + fg);
     }
 #pragma unroll
     for (int j = 0; j < MT; ++j) {
       const int row = wm * WM + j * 16 + fr;
-      xf[1][j] = *(const bf16x8*)(sA + row * BK + (((4 + fg) ^ (row & 7)) << 3));
+      xf[1][j] = igemm_frag(sA, row, 4 + fg);
     }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -453,29 +426,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
       const int row = idx / c8n, c8 = idx - row * c8n;
       const int m = m0 + row, n = nb0 + c8 * 8;
       if (m >= Mrows || n >= nout) continue;
-      f32x4 va = *(const f32x4*)(sC + row * BN + (((2 * c8) ^ (row & 7)) << 2));
-      f32x4 vb = *(const f32x4*)(sC + row * BN + (((2 * c8 + 1) ^ (row & 7)) << 2));
-      if (!p.geglu) {
-        if (p.bias) { va += *(const f32x4*)(p.bias + n); vb += *(const f32x4*)(p.bias + n + 4); }
-        if (p.rowvec) {
-          const float* rv = p.rowvec + nr_rowvec_row(p, m) + n;
-          va += *(const f32x4*)rv; vb += *(const f32x4*)(rv + 4);
-        }
-        va *= p.out_scale; vb *= p.out_scale;
-        if (p.act == 1) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { va[e] = quick_gelu_f(va[e]); vb[e] = quick_gelu_f(vb[e]); }
-        }
-        if (p.res) {
-          const bf16x8 r = *(const bf16x8*)(p.res + (size_t)m * p.ldr + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { va[e] += (float)r[e]; vb[e] += (float)r[4 + e]; }
-        }
-      }
-      bf16x8 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { o[e] = (bf16)va[e]; o[4 + e] = (bf16)vb[e]; }
-      nr_store16(p.out + (size_t)(PH ? ph_out_row(m) : m) * p.ldo + n, o);
+      const bf16x8 o = igemm_finish8<BN>(sC, row, c8, &p, m, n);
+      nr_store16(p.out + (size_t)(PH ? igemm_phase_out_row(&p, phase, m) : m) * p.ldo + n, o);
     }
 #ifdef NR_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -488,29 +440,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, (LNF && WGM * WGN == 8) ? 4 : 1) vo
   for (int j = 0; j < MT; ++j) {
     const int m = m0 + wm * WM + j * 16 + fr;
     if (m >= Mrows) continue;
-    const size_t mo = PH ? ph_out_row(m) : m;
+    const size_t mo = PH ? igemm_phase_out_row(&p, phase, m) : m;
     const float* rv = p.rowvec ? p.rowvec + nr_rowvec_row(p, m) : nullptr;
     if (!p.geglu) {
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
         const int n = n0 + wn * WN + i * 16 + 4 * fg;
         if (n >= p.N) continue;
-        f32x4 v = acc[i][j];
-        if (p.bias) { const f32x4 b = *(const f32x4*)(p.bias + n); v += b; }
-        if (rv) { const f32x4 t = *(const f32x4*)(rv + n); v += t; }
-        v *= p.out_scale;
-        if (p.act == 1) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
-        }
-        if (p.res) {
-          const bf16x4 r = *(const bf16x4*)(p.res + (size_t)m * p.ldr + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += (float)r[e];
-        }
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
+        const bf16x4 o = igemm_finish4(&p, acc[i][j], rv, m, n);
         nr_store8(p.out + mo * p.ldo + n, o);
       }
     } else {
@@ -576,16 +513,8 @@ __global__ __launch_bounds__(512, 1) void igemm_kpair_kernel(NrGemmParams p_arg,
   int bid = nr_xcd_bid();
   const int pair = nslab > 1 ? nr_fdiv_small(bid, ntn * ntm) : 0;
   bid -= pair * ntn * ntm;
-  int bm, bn;      // the tile orders of igemm_bf16_kernel
-  if (m_fast >= 2) {
-    const int G = m_fast;
-    const int band = nr_fdiv_small(bid, G * ntn);
-    const int first = band * G;
-    const int gsz = min(G, ntm - first);
-    const int r = bid - band * G * ntn;
-    bn = nr_fdiv_small(r, gsz);
-    bm = first + r - bn * gsz;
-  } else if (m_fast) { bn = nr_fdiv_small(bid, ntm); bm = bid - bn * ntm; } else { bm = nr_fdiv_small(bid, ntn); bn = bid - bm * ntn; }
+  int bm, bn;
+  igemm_tile_order(bid, m_fast, ntm, ntn, bm, bn);
   const int m0 = bm * BM, n0 = bn * BN;
   const int lr = lane >> 3;                 // row within the 8-row group
   const int lp = lane & 7;                  // physical 16-B chunk
@@ -604,9 +533,7 @@ __global__ __launch_bounds__(512, 1) void igemm_kpair_kernel(NrGemmParams p_arg,
       a_pix[j] = mm; a_oy[j] = 0; a_ox[j] = 0;
     } else {
       const int ohw = p.OH * p.OW;
-      const int n = nr_fdiv_small(mm, ohw);
-      const int r = mm - n * ohw;
-      a_pix[j] = n; a_oy[j] = nr_fdiv_small(r, p.OW); a_ox[j] = r - a_oy[j] * p.OW;
+      igemm_pixel_decode(mm, ohw, p.OW, a_pix[j], a_oy[j], a_ox[j]);
     }
   }
   const bf16* zsrc = (const bf16*)nr_zero16;
@@ -616,7 +543,7 @@ __global__ __launch_bounds__(512, 1) void igemm_kpair_kernel(NrGemmParams p_arg,
   if constexpr (tap_inner) {
 #pragma unroll
     for (int j = 0; j < GA; ++j) {
-      a_cbyte[j] = (((long long)a_pix[j] * p.H + a_oy[j]) * p.W + a_ox[j]) * p.lda0 * (long long)sizeof(bf16);
+      a_cbyte[j] = igemm_pixel_byte(a_pix[j], a_oy[j], a_ox[j], p.H, p.W, p.lda0);
       unsigned msk = 0;
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
@@ -651,8 +578,7 @@ __global__ __launch_bounds__(512, 1) void igemm_kpair_kernel(NrGemmParams p_arg,
     }
   }
   auto setup_rows_tap_inner = [&]() {
-    const int ky = st_tap / 3, kx = st_tap - ky * 3;
-    const long long delta = ((long long)(ky - 1) * p.W + (kx - 1)) * p.lda0 * (long long)sizeof(bf16);
+    const long long delta = igemm_tap_delta(st_tap, p.W, p.lda0);
     const char* base = reinterpret_cast<const char*>(p.a0 + st_c + lchunk) + delta;
 #pragma unroll
     for (int j = 0; j < GA; ++j) {
@@ -697,8 +623,7 @@ __global__ __launch_bounds__(512, 1) void igemm_kpair_kernel(NrGemmParams p_arg,
 #pragma unroll
     for (int j = 0; j < GB; ++j) wp[j] += BK;
     if constexpr (tap_inner) {
-      st_tap += 1;
-      if (st_tap == 9) { st_tap = 0; st_c += BK; }
+      igemm_k_next_tap_inner(st_tap, st_c);
       setup_rows_tap_inner();
       return;
     }
@@ -729,12 +654,12 @@ __global__ __launch_bounds__(512, 1) void igemm_kpair_kernel(NrGemmParams p_arg,
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       const int row = wn * WN + i * 16 + fr;
-      wf[ks][i] = *(const bf16x8*)(sB + row * BK + (((4 * ks + fg) ^ (row & 7)) << 3));
+      wf[ks][i] = igemm_frag(sB, row, 4 * ks + fg);
     }
 #pragma unroll
     for (int j = 0; j < MT; ++j) {
       const int row = wm * WM + j * 16 + fr;
-      xf[ks][j] = *(const bf16x8*)(sA + row * BK + (((4 * ks + fg) ^ (row & 7)) << 3));
+      xf[ks][j] = igemm_frag(sA, row, 4 * ks + fg);
     }
   };
   auto multiply = [&]() {
@@ -831,22 +756,7 @@ __global__ __launch_bounds__(512, 1) void igemm_kpair_kernel(NrGemmParams p_arg,
     for (int i = 0; i < NT; ++i) {
       const int n = n0 + wn * WN + i * 16 + 4 * fg;
       if (n >= p.N) continue;
-      f32x4 v = acc[i][j];
-      if (p.bias) { const f32x4 b = *(const f32x4*)(p.bias + n); v += b; }
-      if (rv) { const f32x4 t = *(const f32x4*)(rv + n); v += t; }
-      v *= p.out_scale;
-      if (p.act == 1) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
-      }
-      if (p.res) {
-        const bf16x4 r = *(const bf16x4*)(p.res + (size_t)m * p.ldr + n);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += (float)r[e];
-      }
-      bf16x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
+      const bf16x4 o = igemm_finish4(&p, acc[i][j], rv, m, n);
       nr_store8(p.out + (size_t)m * p.ldo + n, o);
     }
   }
@@ -871,28 +781,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(NrGemmParams p_arg, 
   const float* src = partial + (size_t)m * p.N + n;
   f32x4 v = *(const f32x4*)src;
   for (int s = 1; s < splitk; ++s) v += *(const f32x4*)(src + s * slab);
-  if (p.bias) v += *(const f32x4*)(p.bias + n);
-  if (p.rowvec) v += *(const f32x4*)(p.rowvec + nr_rowvec_row(p, m) + n);
-  v *= p.out_scale;
-  if (p.act == 1) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
-  }
-  if (p.res) {
-    const bf16x4 r = *(const bf16x4*)(p.res + (size_t)m * p.ldr + n);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] += (float)r[e];
-  }
-  bf16x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
+  const bf16x4 o = igemm_finish4(&p, v, p.rowvec ? p.rowvec + nr_rowvec_row(p, m) : nullptr, m, n);
   size_t mo = (size_t)m;
   if constexpr (PH) {
-    const int Mp = p.M >> 2, hw = p.H * p.W;
-    const int phase = m / Mp, r = m - phase * Mp;
-    const int img = r / hw, q = r - img * hw;
-    const int y = q / p.W, x = q - y * p.W;
-    mo = (size_t)(img * p.OH + 2 * y + (phase >> 1)) * p.OW + 2 * x + (phase & 1);
+    const int Mp = p.M >> 2, phase = m / Mp;
+    mo = igemm_phase_out_row(&p, phase, m - phase * Mp);
   }
   nr_store8(p.out + mo * p.ldo + n, o);
 }
@@ -949,6 +842,8 @@ constexpr const TileRow* find_row(int bm, int bn, int waves, bool phase = false)
 // tiles gain 1.3-1.7x from split-K; 128x160 only pays for N = 320.
 // row tiles of a launch: the phase form tiles each of its four phases (M / 4 source pixels) on its own
 inline long long row_tiles(const NrGemmParams& p, int bm) { return p.ups == 2 ? 4ll * ((p.M / 4 + bm - 1) / bm) : (p.M + bm - 1) / bm; }
+// tiles of a launch on bm x bn tiles
+inline long long tile_count(const NrGemmParams& p, int bm, int bn) { return row_tiles(p, bm) * ((p.N + bn - 1) / bn); }
 
 // Phase-form upsample convs: four GEMMs of M / 4 rows and K = 4 Cin that share one launch, so the rules of choose_plan keyed on nk >= 128 (K = 9 Cin)
 // do not fire.  Per shape by NR_IGEMM_FORCE sweeps of the op (HBM-cold weights, profiles/ups_phase_ab.txt; us per launch, the 3x3 form beside it):
@@ -958,7 +853,6 @@ inline long long row_tiles(const NrGemmParams& p, int bm) { return p.ups == 2 ? 
 //   N = 512 / 256 (the VAE: no 160-column tiling)  128x128 8 waves: 140 / 551 / 640 against 256x128: 156 / 610 / 774 (3x3: 292 / 1153 / 1241)
 // The split-K rule for under-filled grids below is choose_plan's reasoning, not a measurement of this form.
 Plan choose_plan_phase(const NrGemmParams& p) {
-  auto nblk = [&](int bm, int bn) { return row_tiles(p, bm) * ((p.N + bn - 1) / bn); };
   const int nk = p.K / 64;
   Plan pl{};
   pl.splitk = 1; pl.stages = 2; pl.waves = 4;
@@ -968,12 +862,12 @@ Plan choose_plan_phase(const NrGemmParams& p) {
     if (p.M <= 2048 && nk >= 64) { pl.splitk = 4; return pl; }
   } else {
     const bool n128 = p.N % 128 == 0 || p.N >= 960;
-    if (n128 && nblk(128, 128) >= 400) { pl.bm = 128; pl.bn = 128; pl.waves = 8; }
-    else if (nblk(128, 64) >= 256) { pl.bm = 128; pl.bn = 64; }
+    if (n128 && tile_count(p, 128, 128) >= 400) { pl.bm = 128; pl.bn = 128; pl.waves = 8; }
+    else if (tile_count(p, 128, 64) >= 256) { pl.bm = 128; pl.bn = 64; }
     else { pl.bm = 64; pl.bn = 64; }
   }
   // under-filled grids with a K worth cutting: deterministic split-K as in choose_plan (every slice keeps >= 16 k-tiles, <= 4 slabs)
-  const long long tiles = nblk(pl.bm, pl.bn);
+  const long long tiles = tile_count(p, pl.bm, pl.bn);
   if (tiles < 512 && nk >= 64) {
     int s_ = (int)((1024 + tiles - 1) / tiles);
     if (s_ > nk / 16) s_ = nk / 16;
@@ -983,7 +877,6 @@ Plan choose_plan_phase(const NrGemmParams& p) {
   return pl;
 }
 Plan choose_plan_slices(const NrGemmParams& p) {
-  auto nblk = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
   const int nk = p.K / 64;
   Plan pl{};
   pl.splitk = 1; pl.stages = 2; pl.waves = 4;
@@ -1001,7 +894,7 @@ Plan choose_plan_slices(const NrGemmParams& p) {
   }
   // 16x16-level convs (M = 8192, N = 640, K >= 5760): 128x160 with two K slices instead of 128x64 (per-shape in-situ A/B,
   // tools/igemm_ab_shapes.py: -0.06 / -0.09 ms per DDIM step)
-  if (!p.geglu && p.ksize == 3 && p.M <= 8192 && p.N % 160 == 0 && p.N < 960 && nk >= 64 && nblk(128, 160) >= 128 && nblk(128, 160) < 512) {
+  if (!p.geglu && p.ksize == 3 && p.M <= 8192 && p.N % 160 == 0 && p.N < 960 && nk >= 64 && tile_count(p, 128, 160) >= 128 && tile_count(p, 128, 160) < 512) {
     pl.bm = 128; pl.bn = 160; pl.splitk = 2;
     return pl;
   }
@@ -1015,16 +908,16 @@ Plan choose_plan_slices(const NrGemmParams& p) {
   // workgroup per CU with a 3-deep ring instead of 320-640 smaller tiles two per CU: 16.2 vs 19.2 us at M = 2048, N = K = 1280, 26.5 vs 36.3 at
   // K = 2560, 17.1 vs 20.1 LayerNorm-folded (2-deep ring there) (profiles/r05_sweep_64x160.txt, HBM-cold weights)
   static const bool t64x160_rule = env_not_0("NR_IGEMM_T64X160");   // A/B switch
-  if (t64x160_rule && p.ksize == 1 && !p.geglu && p.N % 160 == 0 && p.M > 512 && nk >= 16 && nk <= 48 && nblk(64, 160) >= 128 && nblk(64, 160) <= 256) {
+  if (t64x160_rule && p.ksize == 1 && !p.geglu && p.N % 160 == 0 && p.M > 512 && nk >= 16 && nk <= 48 && tile_count(p, 64, 160) >= 128 && tile_count(p, 64, 160) <= 256) {
     pl.bm = 64; pl.bn = 160; pl.stages = 3;
     return pl;
   }
   const bool n128 = p.N % 128 == 0 || p.N >= 960;          // <= 6 % padded columns otherwise
-  if (!p.geglu && p.N % 160 == 0 && p.N < 960 && p.N % 128 != 0 && nk >= 20 && nblk(128, 160) >= 256) { pl.bm = 128; pl.bn = 160; }
-  else if (n128 && nblk(128, 128) >= 400) { pl.bm = 128; pl.bn = 128; pl.waves = 8; }
-  else if (nblk(128, 64) >= 512 || (nblk(128, 64) >= 256 && nk > 32)) { pl.bm = 128; pl.bn = 64; pl.waves = nk <= 32 ? 8 : 4; }
-  else if (nblk(64, 64) >= 256 && nk <= 96) { pl.bm = 64; pl.bn = 64; }
-  else if (p.M >= 1024 && nblk(128, 64) >= 64) { pl.bm = 128; pl.bn = 64; }
+  if (!p.geglu && p.N % 160 == 0 && p.N < 960 && p.N % 128 != 0 && nk >= 20 && tile_count(p, 128, 160) >= 256) { pl.bm = 128; pl.bn = 160; }
+  else if (n128 && tile_count(p, 128, 128) >= 400) { pl.bm = 128; pl.bn = 128; pl.waves = 8; }
+  else if (tile_count(p, 128, 64) >= 512 || (tile_count(p, 128, 64) >= 256 && nk > 32)) { pl.bm = 128; pl.bn = 64; pl.waves = nk <= 32 ? 8 : 4; }
+  else if (tile_count(p, 64, 64) >= 256 && nk <= 96) { pl.bm = 64; pl.bn = 64; }
+  else if (p.M >= 1024 && tile_count(p, 128, 64) >= 64) { pl.bm = 128; pl.bn = 64; }
   else { pl.bm = 64; pl.bn = 64; }
   // 4x4-level / sgm 16x16-level Linears (M <= 512): fewer blocks than CUs, every k-step waits for cold weights from HBM.
   // A 4-deep ring (3 tiles in flight) and, where the epilogue allows, 64x32 tiles (twice the blocks) measured -10 % on the
@@ -1040,16 +933,16 @@ Plan choose_plan_slices(const NrGemmParams& p) {
     // ... and exactly 256 tiles of 128 x 160 at M = 512 (one round, one workgroup per CU, ring 3-4 deep: the 320 tiles of 128 x 128 wait for
     // HBM-cold k-tiles with one in flight): 4 x 1 waves of 32 x 160 so that a wave holds whole (value, gate) pairs; 23.1 vs 28.9 us plain,
     // 27.0 vs 31.7 us LayerNorm-folded (profiles/r05_sweep_rowwave.txt)
-    if (rowwave_rule && p.geglu && p.N >= 8192 && p.N % 160 == 0 && p.M > 256 && nblk(128, 160) <= 256) {
+    if (rowwave_rule && p.geglu && p.N >= 8192 && p.N % 160 == 0 && p.M > 256 && tile_count(p, 128, 160) <= 256) {
       pl.bm = 128; pl.bn = 160; pl.waves = 41; pl.stages = p.ln_c ? 3 : 4;
     }
     else if (!p.geglu && nk >= 96 && !p.ln_c) { pl.bm = 64; pl.bn = 64; pl.stages = 2; pl.splitk = 4; return pl; }
     // wide projections (q|k|v, N = 3840): 960 tiles of 64 x 32 re-read A 120 times; 240 tiles of 128 x 64 with the same 4-deep ring:
     // 13.3 vs 19.8 us plain, 15.2 vs 17.5 us LayerNorm-folded (profiles/r05_sweep_ln_ns4.txt, HBM-cold weights)
-    else if (wide_rule && !p.geglu && nblk(64, 32) > 640 && nblk(128, 64) >= 192) { pl.bm = 128; pl.bn = 64; pl.waves = 8; pl.stages = 4; }
+    else if (wide_rule && !p.geglu && tile_count(p, 64, 32) > 640 && tile_count(p, 128, 64) >= 192) { pl.bm = 128; pl.bn = 64; pl.waves = 8; pl.stages = 4; }
   }
   if (!p.geglu) {
-    const long long tiles = nblk(pl.bm, pl.bn);
+    const long long tiles = tile_count(p, pl.bm, pl.bn);
     const int cap_m = p.M >= 8192 ? 2 : (p.M >= 2048 ? 4 : 8);      // bounds the fp32 slab traffic (8*M*N*split bytes)
     const int min_tiles = p.M <= 1024 ? 8 : 16;                      // k-tiles each slice keeps
     if (tiles < 512 && nk >= 4 * min_tiles) {
@@ -1086,7 +979,7 @@ Plan choose_plan(const NrGemmParams& p) {
   const Plan pl = choose_plan_slices(p);
   static const bool kpair_rule = env_not_0("NR_IGEMM_KPAIR");      // A/B switch
   if (!kpair_rule) return pl;
-  const long long tiles = (long long)((p.M + 127) / 128) * ((p.N + 159) / 160);
+  const long long tiles = tile_count(p, 128, 160);      // (a K-pair plan is never a phase form's: kpair_ok)
   Plan kp = pl;
   kp.waves = KPAIR_WAVES;
   if (pl.bm == 128 && pl.bn == 160 && pl.waves == 4 && pl.stages == 2 && pl.splitk >= 2 && pl.splitk % 2 == 0) {
@@ -1147,7 +1040,7 @@ int launch_exact(std::index_sequence<J...>, const NrGemmParams& p, unsigned grid
 // igemm_kpair_kernel: the K pairs of a 128 x 160 plan (waves == 82), pl.splitk slabs.  Returns 0; 2 when the runtime refuses the LDS opt-in
 int launch_kpair(const NrGemmParams& p, unsigned grid, const Plan& pl, float* partial, int m_fast, hipStream_t stream) {
   const igemm_kern_t k = pl.lin ? igemm_kpair_kernel<true, false> : (p.tap_inner ? igemm_kpair_kernel<false, true> : igemm_kpair_kernel<false, false>);
-  const size_t shm = (size_t)2 * 2 * (128 + 160) * 64 * sizeof(bf16);      // two groups x two stages
+  constexpr size_t shm = 2 * find_row(128, 160, 4)->lds_bytes(2, false);      // two K groups, each the two-stage ring of the tile's 2 x 2 row
   static unsigned long long attr_done[3] = {};          // per instantiation
   if (const int rc = nr_lds_opt_in(attr_done[pl.lin ? 0 : (p.tap_inner ? 1 : 2)], {(const void*)k}, shm)) return rc;
   hipLaunchKernelGGL(k, dim3(grid), dim3(512), shm, stream, p, pl.splitk, partial, m_fast);
@@ -1297,7 +1190,7 @@ int launch_tiled(const NrGemmParams& p, const Plan& pl, int m_fast, float* works
   if (kpair && !(kpair_ok(p, pl) && pl.stages == 2)) return 9;
   if (pl.splitk > 1 && !workspace) return 6;
   float* partial = p.out_f32 ? p.out_f32 : (pl.splitk > 1 ? workspace : nullptr);
-  const unsigned grid = (unsigned)(row_tiles(p, pl.bm) * ((p.N + pl.bn - 1) / pl.bn) * pl.splitk);
+  const unsigned grid = (unsigned)(tile_count(p, pl.bm, pl.bn) * pl.splitk);
   // no such instantiation (9) or no LDS opt-in (2): fail loudly, never launch a neighbour on a grid computed for this tile
   if (const int rc = kpair ? launch_kpair(p, grid, pl, partial, m_fast, stream)
                            : launch_exact(std::make_index_sequence<NTILES * NRINGS>{}, p, grid, pl, partial, m_fast, stream)) return rc;

@@ -26,7 +26,7 @@
 // Not here (the launcher falls back to gemm.hip): split-K, the LayerNorm-folded variant, raw fp32 output, strided / upsampling /
 // tap-major 3x3 convs, grids that would leave the chip under-filled.
 #include "launchers.h"
-#include "device_prims.h"
+#include "igemm_blocks.h"
 #include <cstdlib>
 
 namespace {
@@ -52,15 +52,7 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
   const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + G8_BM - 1) / G8_BM;
   const int bid = nr_xcd_bid();                        // the tiles of one operand panel share an L2, as gemm.hip
   int bm, bn;
-  if (m_fast >= 2) {
-    const int G = m_fast;
-    const int band = nr_fdiv_small(bid, G * ntn);
-    const int first = band * G;
-    const int gsz = min(G, ntm - first);
-    const int r = bid - band * G * ntn;
-    bn = nr_fdiv_small(r, gsz);
-    bm = first + r - bn * gsz;
-  } else if (m_fast) { bn = nr_fdiv_small(bid, ntm); bm = bid - bn * ntm; } else { bm = nr_fdiv_small(bid, ntn); bn = bid - bm * ntn; }
+  igemm_tile_order(bid, m_fast, ntm, ntn, bm, bn);
   const int m0 = bm * G8_BM, n0 = bn * BN;
 
   const int lr = lane >> 3, lp = lane & 7;
@@ -79,9 +71,8 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
     a_m[j] = ok ? m : 0;
     if constexpr (TAPI) {
       const int ohw = p.OH * p.OW;
-      const int n = nr_fdiv_small(a_m[j], ohw);
-      const int r = a_m[j] - n * ohw;
-      const int oy = nr_fdiv_small(r, p.OW), ox = r - oy * p.OW;
+      int n, oy, ox;
+      igemm_pixel_decode(a_m[j], ohw, p.OW, n, oy, ox);
       a_off[j] = (unsigned)((((size_t)n * p.H + oy) * p.W + ox) * (size_t)p.lda0 * sizeof(bf16)) + lchunk_b;
       unsigned msk = 0;
 #pragma unroll
@@ -117,8 +108,7 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
     if constexpr (TAPI) {
       const int c64 = kt / 9;
       tap = kt - 9 * c64;
-      const int ky = tap / 3, kx = tap - 3 * ky;
-      const long long delta = ((long long)(ky - 1) * p.W + (kx - 1)) * p.lda0 * (long long)sizeof(bf16);
+      const long long delta = igemm_tap_delta(tap, p.W, p.lda0);
       return reinterpret_cast<const char*>(p.a0 + c64 * G8_BK) + delta;
     } else {
       tap = 0;
@@ -292,28 +282,7 @@ __global__ __launch_bounds__(512, 2) void g8p_kernel(NrGemmParams p_arg, int m_f
       const int gg = row / (RT * 16), lrow = row - gg * (RT * 16);
       const int m = m0 + gg * 128 + r * (RT * 16) + lrow, n = nb0 + c8 * 8;
       if (m >= p.M || n >= nout) continue;
-      f32x4 va = *(const f32x4*)(sC + row * BN + (((2 * c8) ^ (row & 7)) << 2));
-      f32x4 vb = *(const f32x4*)(sC + row * BN + (((2 * c8 + 1) ^ (row & 7)) << 2));
-      if (!p.geglu) {
-        if (p.bias) { va += *(const f32x4*)(p.bias + n); vb += *(const f32x4*)(p.bias + n + 4); }
-        if (p.rowvec) {
-          const float* rv = p.rowvec + nr_rowvec_row(p, m) + n;
-          va += *(const f32x4*)rv; vb += *(const f32x4*)(rv + 4);
-        }
-        va *= p.out_scale; vb *= p.out_scale;
-        if (p.act == 1) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { va[e] = quick_gelu_f(va[e]); vb[e] = quick_gelu_f(vb[e]); }
-        }
-        if (p.res) {
-          const bf16x8 rr = *(const bf16x8*)(p.res + (size_t)m * p.ldr + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { va[e] += (float)rr[e]; vb[e] += (float)rr[4 + e]; }
-        }
-      }
-      bf16x8 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { o[e] = (bf16)va[e]; o[4 + e] = (bf16)vb[e]; }
+      const bf16x8 o = igemm_finish8<BN>(sC, row, c8, &p, m, n);
       nr_store16(p.out + (size_t)m * p.ldo + n, o);
     }
   }
